@@ -630,6 +630,16 @@ def cpu_baseline(state_dict, kpts: int, seconds_budget: float = 20.0):
     return res
 
 
+def dump_outputs(path: str, out: dict, rank: int) -> None:
+    """--dump-outputs: the arrays PoseEngine.estimate returned in the last timed step, gathered over the ranks (contiguous shards: rank order is
+    pair order) and written by rank 0 as <path>/<name>.npy in float64 (the integer outputs are exact in it).  Every rank must call it."""
+    arrays = {k: gdist.gather_records(v.to(torch.float64)).cpu().numpy() for k, v in out.items()}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -666,6 +676,8 @@ def main() -> None:
                                                                      "fused-projection self-check are set-up work that a rocprofv3 pass over few steps would count as steps)")
     ap.add_argument("--sync-certify", action="store_true", help="certificate resolved inside every call (one host synchronisation per step) instead of one call later")
     ap.add_argument("--share-gpu", action="store_true", help="dry-run aid: every rank uses cuda:0 (with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step returned (R, t, n_match, n_inliers, "
+                                                                      "ok of every pair, all ranks' shards in pair order) as DIR/<name>.npy in float64")
     args = ap.parse_args()
 
     if args.only_loftr:
@@ -775,6 +787,8 @@ def main() -> None:
             eng.set_certify("rerun")
     else:
         elapsed, mine = elapsed1, _
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
     tripped, trips = eng.guard_status()
     fused_status = eng.fused_projection_status()
     cert_main = certificate_block(eng, cert_cal)
