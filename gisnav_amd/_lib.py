@@ -53,6 +53,8 @@ SIGNATURES = {
     "gn_device_numa_node": (C.c_int, [C.c_int]),
     "gn_get_certify_stats": (C.c_int, [VP, c_i64p]),
     "gn_reset_certify_stats": (C.c_int, [VP]),
+    "gn_set_certify_ladder": (C.c_int, [VP, C.c_int, C.c_float]),
+    "gn_get_certify_ladder_stats": (C.c_int, [VP, c_i64p]),
     "gn_calibrate_certify": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, VP]),
     "gn_get_uncertain": (C.c_int, [VP, C.c_int, c_i32p, VP]),
     "gn_source_digest": (C.c_char_p, []),
@@ -102,6 +104,7 @@ GN_PREC_BF16_ATTN = 1
 GN_PREC_F32X3_BF16_ATTN = 2
 GN_PREC_F16X2_BF16_ATTN = 3
 GN_PREC_F16X2_F16_ATTN = 4
+GN_PREC_F16X2_F16X2_ATTN = 5
 GN_FEATURE_SIFT = 0
 GN_FEATURE_SUPERPOINT = 1
 GN_KPT_LAF = 0

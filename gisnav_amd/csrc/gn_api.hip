@@ -84,7 +84,14 @@ struct gn_ctx {
   } cert_pend[2];
   int cert_slot = 0;
   long long cert_calls = 0, cert_pairs = 0, cert_flag_margin = 0, cert_flag_range = 0, cert_rerun = 0, cert_f32_marginal = 0;
-  int attn_f16 = 0;        // GN_PREC_F16X2_F16_ATTN: q | k rows, V^T panels and the probabilities are fp16 instead of bf16 (precision itself reads F16X2_BF16_ATTN)
+  int attn_f16 = 0;        // GN_PREC_F16X2_F16_ATTN: q | k rows, V^T panels and the probabilities are fp16 instead of bf16 (precision itself reads F16X2_BF16_ATTN);
+                           // 2 = split: f32 q | k | v rows from the f16x2 projection GEMMs, k_attn_f16x2 (GN_PREC_F16X2_F16X2_ATTN, and the ladder's middle level)
+  // the certificate's re-run ladder (gn_set_certify_ladder): flagged pairs are re-run first in mode-5 arithmetic (MidScope) and certified there against
+  // cert_eps_mid (< 0 = not calibrated: straight to exact f32); only the pairs still flagged go on to exact f32
+  int ladder = 0; float cert_eps_mid = -1.f, cert_mid_measured = -1.f;
+  long long mid_rerun = 0, mid_certified = 0, mid_passed = 0;
+  float *colbest = nullptr, *col2 = nullptr;   // [B][npad] best score / runner-up of every column (written by the fused head while cal_cols is set)
+  bool cal_cols = false;
   int precision_api = 0;   // the gn_precision value gn_create was called with
   int feature = 0;         // GN_FEATURE_SIFT / GN_FEATURE_SUPERPOINT (gn_create_ex)
   float size_q[2] = {0.f, 0.f}, size_r[2] = {0.f, 0.f};   // gn_set_image_size: (w, h) per side for the keypoint normalisation, 0 = keypoint extent
@@ -404,7 +411,8 @@ static void attn_split(gn_ctx* c, AttnArgs& a) {
 }
 
 void attention(gn_ctx* c, const AttnArgs& a, hipStream_t s) {
-  if (c->precision != GN_PREC_F32) launch_attention_bf16(a, s); else launch_attention_f32(a, s);
+  if (c->precision != GN_PREC_F32 && c->attn_f16 == 2) launch_attention_f16x2(a, s);
+  else if (c->precision != GN_PREC_F32) launch_attention_bf16(a, s); else launch_attention_f32(a, s);
 }
 
 // one attention launch of the matcher schedule, optionally bracketed by HIP events (kernel class 1);
@@ -553,7 +561,7 @@ template <typename F> bool timed_launch(gn_ctx* c, hipStream_t s, double flops, 
 }
 
 inline bool ffn_auto(const gn_ctx* c) { return c->ffn_products == 0 && c->cert_eps_lvl[0] >= 0.f && c->cert_eps_lvl[1] >= 0.f && c->certify >= 2; }
-inline int ffn_level(const gn_ctx* c) { return c->ffn_products == 0 ? (ffn_auto(c) ? c->auto_level : 3) : c->ffn_products; }
+inline int ffn_level(const gn_ctx* c) { return c->attn_f16 == 2 ? 3 : c->ffn_products == 0 ? (ffn_auto(c) ? c->auto_level : 3) : c->ffn_products; }
 inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? c->cert_eps_lvl[c->auto_level - 2] : c->cert_eps; }
 
 bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
@@ -639,11 +647,11 @@ int run_matcher(gn_ctx* c, int B, int kpt_format,
                 const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
                 int64_t* idx, float* score, int32_t* n_match, hipStream_t s) {
   const int np = c->npad_run, T = B * 2 * np, BS = B * 2;
-  const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1;
+  const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
   gn::g_attn_variant = c->attn_variant;
   gn::g_attn_stamps = ((c->attn_variant == 73 || c->attn_variant >= 1000) && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;
   const int vt_perm = (bf16v2 ? 1 : 0) | (c->dbg_vt_skip ? 2 : 0);   // k_attn_bf16_v5 reads V^T with keys permuted inside 16-groups   // k_attn_bf16_v4 reads permuted V^T
-  const bool attn_planes = c->planes_mode && bf16v2;   // k_attn_bf16_v5 writes the hm16 rows itself
+  const bool attn_planes = c->planes_mode && (bf16v2 || c->attn_f16 == 2);   // k_attn_bf16_v5 / k_attn_f16x2 write the hm16 rows themselves
   c->launch_count = 0;
   if (c->planes_mode && c->guard) hipMemsetAsync(c->ovf, (c->dbg_trip_group && c->ovf == c->ovf_base + (c->dbg_trip_group - 1)) ? 1 : 0, sizeof(unsigned int), s);
   {
@@ -761,6 +769,7 @@ int run_matcher(gn_ctx* c, int B, int kpt_format,
     hd.md = c->planes_mode ? (const void*)c->md_p : (const void*)c->md; hd.md_f32 = c->planes_mode ? 0 : 1;
     hd.cpart_m = c->cpart_m; hd.cpart_s = c->cpart_s; hd.cpart_i = c->cpart_i; hd.rpart_a = c->rpart_a; hd.rpart_b = c->rpart_b; hd.tickets = c->tickets;
     hd.dbg_ts = (c->head_stamps && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer knob 17
+    if (c->cal_cols) { hd.colbest = c->colbest; hd.col2 = c->col2; }
     if (c->head_fused || !c->sim) {
       ++c->launch_count;
       if (c->stop_after && c->launch_count > c->stop_after) return GN_OK;
@@ -808,6 +817,7 @@ int alloc_workspace(gn_ctx* ctx, int max_kpts) {
   if (ctx->precision != GN_PREC_F32) { GN_ALLOC(qkb, T * 2 * kDim); GN_ALLOC(vtb, T * kDim); GN_ALLOC(attn_part, (size_t)256 * 4 * 34 * 64); GN_ALLOC(attn_tickets, 256); }
   GN_ALLOC(rowmax, B * np); GN_ALLOC(rowlog, B * np); GN_ALLOC(colmax, B * np); GN_ALLOC(collog, B * np);
   GN_ALLOC(max0, B * np); GN_ALLOC(m0, B * np); GN_ALLOC(m1, B * np); GN_ALLOC(max0b, B * np); GN_ALLOC(rpart_c, B * 8 * np); GN_ALLOC(uncert, B); GN_ALLOC(uncert_alt, B);
+  GN_ALLOC(colbest, B * np); GN_ALLOC(col2, B * np);
   GN_ALLOC(cpart_m, B * (np / 32) * np); GN_ALLOC(cpart_s, B * (np / 32) * np); GN_ALLOC(cpart_i, B * (np / 32) * np); GN_ALLOC(rpart_a, B * 8 * np); GN_ALLOC(rpart_b, B * 8 * np); GN_ALLOC(tickets, B * 2);
   GN_ALLOC(e_idx, B * np * 2); GN_ALLOC(e_score, B * np); GN_ALLOC(e_mkp, B * np * 2); GN_ALLOC(e_obj, B * np * 3);
   GN_ALLOC(vo_norm2, T); GN_ALLOC(vo_nn_idx, B * np * 2); GN_ALLOC(vo_nn_dist, B * np * 2); GN_ALLOC(vo_good, B * np);
@@ -846,7 +856,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
   c->fused_proj_status = -1;
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
-  if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
+  if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
       !c->qkv_fused || !c->rot4 || !c->lists || !c->msg_p || !c->h_p || c->feature < 0 || gn::g_ffn_ablate != 0 || gn::g_ffn_shape != 0) return GN_OK;
   int B = (256 * 128 + 2 * np - 1) / (2 * np);          // the smallest batch whose grid selects k_ffn128 (>= 256 tiles of 128 tokens)
   if (B > c->max_batch) return GN_OK;                   // this context never runs the bulk kernels
@@ -968,23 +978,10 @@ CertView cert_view_at(const CertView& v, const CertShape& h, size_t b) {
 // block first (device-to-device copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a
 // batched f32 call costs ~0.8 ms per pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
 // Counts what it saw (gn_get_certify_stats).
-template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const CertShape& h, const CertView& v, F&& run, const int32_t* flags_ready = nullptr, int flags_level = 0) {
-  if (!flags_ready) {
-    GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    GN_HIP(hipStreamSynchronize(s));
-    flags_ready = ctx->uncert_host;
-  }
-  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_level ? flags_level : ctx->auto_level);     // (both callers lay the other level's flags max_batch entries behind)
-  ++ctx->cert_calls; ctx->cert_pairs += B;
-  std::vector<int> flagged;
-  for (int b = 0; b < B; ++b) {
-    const int f = flags_ready[b];
-    if (f == 1) ++ctx->cert_flag_margin; else if (f == 2) ++ctx->cert_flag_range;
-    if (f != 0) flagged.push_back(b);
-  }
-  if (flagged.empty()) return GN_OK;
-  if (ctx->precision == GN_PREC_F32) { ctx->cert_f32_marginal += (long long)flagged.size(); return GN_OK; }   // already the exact arithmetic: counted, nothing better to run
+// The flagged pairs `flagged` (ascending) of a call again, in whatever arithmetic the caller has switched the context to; rflags[k] = the re-run's
+// own certificate flag of flagged[k].
+template <typename F> int rerun_pairs(gn_ctx* ctx, int B, hipStream_t s, const CertShape& h, const CertView& v, F& run, const std::vector<int>& flagged,
+                                      std::vector<int32_t>& rflags) {
   const int nf = (int)flagged.size();
   const bool contiguous = flagged.back() - flagged.front() + 1 == nf;
   int rc = GN_OK;
@@ -1024,7 +1021,6 @@ template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const
     }
   }
   {
-    F32Scope f32(ctx);
     const bool ig = ctx->in_group; unsigned int* const ovf = ctx->ovf;
     ctx->cert_inner = true; ctx->in_group = true; ctx->ovf = ctx->ovf_base;
     if (contiguous) {
@@ -1035,7 +1031,6 @@ template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const
     } else {
       rc = run(st, nf);
     }
-    ctx->cert_rerun += nf;
     ctx->cert_inner = false; ctx->in_group = ig; ctx->ovf = ovf;
   }
   if (rc != GN_OK) return rc;
@@ -1052,10 +1047,72 @@ template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const
       if (v.score) GN_HIP(cp(dst.score, src.score, h.km * 4));
     }
   }
-  // the re-run's own flags (stated for cert_eps_f32): how many of the pairs are marginal even in exact f32 -- counted, reported, not acted upon
   GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   GN_HIP(hipStreamSynchronize(s));
-  for (int k = 0; k < nf; ++k) if (ctx->uncert_host[contiguous ? flagged[k] : k] != 0) ++ctx->cert_f32_marginal;
+  rflags.resize(nf);
+  for (int k = 0; k < nf; ++k) rflags[k] = ctx->uncert_host[contiguous ? flagged[k] : k];
+  return GN_OK;
+}
+
+// The middle level of the re-run ladder for the duration of a scope: GN_PREC_F16X2_F16X2_ATTN's arithmetic (f32 projection rows, k_attn_f16x2, three-product
+// block tail) on this context's planes and split weights, certified against eps_mid.
+struct MidScope {
+  gn_ctx* c; int attn_f16, ffn_products, dbg_trip_group; float cert_eps;
+  explicit MidScope(gn_ctx* c_) : c(c_), attn_f16(c_->attn_f16), ffn_products(c_->ffn_products), dbg_trip_group(c_->dbg_trip_group), cert_eps(c_->cert_eps) {
+    c->attn_f16 = 2; c->ffn_products = 3; c->dbg_trip_group = 0; c->cert_eps = c->cert_eps_mid;
+  }
+  ~MidScope() { c->attn_f16 = attn_f16; c->ffn_products = ffn_products; c->dbg_trip_group = dbg_trip_group; c->cert_eps = cert_eps; }
+};
+inline bool ladder_active(const gn_ctx* c) { return c->ladder && c->cert_eps_mid >= 0.f && c->precision != GN_PREC_F32 && c->planes_mode && c->attn_f16 != 2; }
+
+// gn_set_certify(2 / 3): the per-pair flags of a call (read here from the device -- synchronises s -- or handed in), then the flagged pairs again with
+// the context switched to the exact-f32 arithmetic, through `run(view, n)` = matcher (+ gather + PnP) of n consecutive pairs.  One contiguous run of
+// flagged pairs is re-run IN PLACE (pointers and per-pair workspaces moved to its first pair).  Scattered flagged pairs are GATHERED into a staging
+// block first (device-to-device copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a
+// batched f32 call costs ~0.8 ms per pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
+// With the ladder on (gn_set_certify_ladder, eps_mid calibrated) the pairs flagged for margin go through the middle level first (MidScope, the same
+// gather / run / scatter); those it certifies keep its results, the rest -- and every pair flagged for range -- go on to exact f32.
+// Counts what it saw (gn_get_certify_stats, gn_get_certify_ladder_stats).
+template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const CertShape& h, const CertView& v, F&& run, const int32_t* flags_ready = nullptr, int flags_level = 0) {
+  if (!flags_ready) {
+    GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
+    flags_ready = ctx->uncert_host;
+  }
+  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_level ? flags_level : ctx->auto_level);     // (both callers lay the other level's flags max_batch entries behind)
+  ++ctx->cert_calls; ctx->cert_pairs += B;
+  std::vector<int> flagged, margin;
+  for (int b = 0; b < B; ++b) {
+    const int f = flags_ready[b];
+    if (f == 1) ++ctx->cert_flag_margin; else if (f == 2) ++ctx->cert_flag_range;
+    if (f != 0) flagged.push_back(b);
+    if (f == 1) margin.push_back(b);
+  }
+  if (flagged.empty()) return GN_OK;
+  if (ctx->precision == GN_PREC_F32) { ctx->cert_f32_marginal += (long long)flagged.size(); return GN_OK; }   // already the exact arithmetic: counted, nothing better to run
+  std::vector<int32_t> rflags;
+  if (ladder_active(ctx) && !margin.empty()) {
+    std::vector<int> still(flagged.size() - margin.size());     // the pairs flagged for range first ...
+    std::copy_if(flagged.begin(), flagged.end(), still.begin(), [&](int b) { return flags_ready[b] != 1; });
+    int rc = GN_OK;
+    { MidScope mid(ctx); rc = rerun_pairs(ctx, B, s, h, v, run, margin, rflags); }
+    if (rc != GN_OK) return rc;
+    ctx->mid_rerun += (long long)margin.size();
+    for (size_t k = 0; k < margin.size(); ++k) {
+      if (rflags[k] == 0) ++ctx->mid_certified;
+      else { ++ctx->mid_passed; still.push_back(margin[k]); }   // ... then those the middle level leaves flagged (or whose middle pass left the fp16 range)
+    }
+    std::sort(still.begin(), still.end());
+    flagged.swap(still);
+    if (flagged.empty()) return GN_OK;
+  }
+  int rc = GN_OK;
+  { F32Scope f32(ctx); rc = rerun_pairs(ctx, B, s, h, v, run, flagged, rflags); }
+  ctx->cert_rerun += (long long)flagged.size();
+  if (rc != GN_OK) return rc;
+  // the re-run's own flags (stated for cert_eps_f32): how many of the pairs are marginal even in exact f32 -- counted, reported, not acted upon
+  for (int32_t f : rflags) if (f != 0) ++ctx->cert_f32_marginal;
   return GN_OK;
 }
 
@@ -1094,10 +1151,12 @@ int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int fea
   gn_ctx* ctx = nullptr;
   if (!out || max_batch < 1 || max_kpts < 2) return fail(nullptr, GN_ERR_ARG, "bad gn_create argument");
   if (precision != GN_PREC_F32 && precision != GN_PREC_BF16_ATTN && precision != GN_PREC_F32X3_BF16_ATTN &&
-      precision != GN_PREC_F16X2_BF16_ATTN && precision != GN_PREC_F16X2_F16_ATTN)
+      precision != GN_PREC_F16X2_BF16_ATTN && precision != GN_PREC_F16X2_F16_ATTN && precision != GN_PREC_F16X2_F16X2_ATTN)
     return fail(nullptr, GN_ERR_ARG, "bad precision");
+  if (precision == GN_PREC_F16X2_F16X2_ATTN && feature != GN_FEATURE_SIFT)
+    return fail(nullptr, GN_ERR_ARG, "GN_PREC_F16X2_F16X2_ATTN: SIFT-LightGlue contexts only (the SuperPoint extractor has no split-attention schedule)");
   const int precision_api = precision;
-  if (precision == GN_PREC_F16X2_F16_ATTN) precision = GN_PREC_F16X2_BF16_ATTN;   // the same projections / FFN / head; only the attention operand format differs (ctx->attn_f16)
+  if (precision == GN_PREC_F16X2_F16_ATTN || precision == GN_PREC_F16X2_F16X2_ATTN) precision = GN_PREC_F16X2_BF16_ATTN;   // the same projections / FFN / head; only the attention operand format differs (ctx->attn_f16)
   GN_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   GN_HIP(hipGetDeviceProperties(&prop, device));
@@ -1106,7 +1165,7 @@ int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int fea
   ctx = new gn_ctx();
   if (feature != GN_FEATURE_SIFT && feature != GN_FEATURE_SUPERPOINT) { delete ctx; return fail(nullptr, GN_ERR_ARG, "bad feature type"); }
   ctx->device = device; ctx->max_batch = max_batch; ctx->precision = precision; ctx->feature = feature;
-  ctx->precision_api = precision_api; ctx->attn_f16 = precision_api == GN_PREC_F16X2_F16_ATTN ? 1 : 0;
+  ctx->precision_api = precision_api; ctx->attn_f16 = precision_api == GN_PREC_F16X2_F16_ATTN ? 1 : precision_api == GN_PREC_F16X2_F16X2_ATTN ? 2 : 0;
   ctx->gemm_variant = precision == GN_PREC_F16X2_BF16_ATTN ? 6 : precision == GN_PREC_F32X3_BF16_ATTN ? 5 : 3;
   { const int rc_ws = alloc_workspace(ctx, max_kpts); if (rc_ws != GN_OK) { gn_destroy(ctx); return rc_ws; } }
   // pinned host words: [0, 16) guard words, [16, 16 + 4096) the per-image counters the SIFT / SuperPoint calls read back (up to 1024 images per call)
@@ -1317,6 +1376,7 @@ int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int
     ctx->loaded[name] = true; ctx->fused_proj_pending = true;
     // a calibration belongs to the weights it was measured on: the automatic block-tail level goes back to "not calibrated" (three products, cert_eps)
     ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = -1.f; ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+    ctx->cert_eps_mid = -1.f;   // (the ladder sends flagged pairs straight to exact f32 until the next calibration)
   }
   return rc;
 }
@@ -1466,12 +1526,14 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   std::vector<float> best[3], second[3];
   std::vector<int32_t> nv(2 * (size_t)B);
   unsigned int tripped = 0u;
+  const bool lad = ctx->ladder && ctx->planes_mode && ctx->attn_f16 != 2;   // (gn_set_certify_ladder refuses every other context)
+  std::vector<float> cb_f32, c2_f32;                 // the exact pass's column best / runner-up (ladder only)
   for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
     std::unique_ptr<F32Scope> f32;
-    if (pass == n_lv) f32.reset(new F32Scope(ctx)); else ctx->ffn_products = lv[pass];
+    if (pass == n_lv) { f32.reset(new F32Scope(ctx)); ctx->cal_cols = lad; } else ctx->ffn_products = lv[pass];
     const bool ig = ctx->in_group; ctx->in_group = true;       // (no nested certification, ovf_groups_last untouched)
     rc = run_matcher(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, ctx->e_idx, ctx->e_score, nm, s);
-    ctx->in_group = ig; ctx->ffn_products = setting;
+    ctx->in_group = ig; ctx->ffn_products = setting; ctx->cal_cols = false;
     if (rc != GN_OK) break;
     best[pass].resize(n); second[pass].resize(n);
     unsigned int trip = 0u;
@@ -1479,7 +1541,47 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
         hipMemcpy(second[pass].data(), ctx->max0b, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(nv.data(), ctx->nvalid, nv.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (pass < n_lv && ctx->planes_mode && ctx->guard && hipMemcpy(&trip, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = GN_ERR_HIP;
+    if (rc == GN_OK && lad && pass == n_lv) {
+      cb_f32.resize(n); c2_f32.resize(n);
+      if (hipMemcpy(cb_f32.data(), ctx->colbest, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c2_f32.data(), ctx->col2, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = GN_ERR_HIP;
+    }
     tripped |= trip;
+  }
+  // the ladder's middle level: mode-5 arithmetic on the whole sample and on its first pair alone (the ladder mostly runs small grids, whose kernels
+  // differ), against the exact pass above, over every valid row's AND column's best score and runner-up
+  double mid_mx = -1.0;
+  for (int mp = 0; lad && mp < 2 && rc == GN_OK && !tripped; ++mp) {
+    const int Bm = mp == 0 ? B : 1;
+    std::vector<float> rb(n), r2(n), cb(n), c2(n);
+    unsigned int trip = 0u;
+    {
+      MidScope mid(ctx);
+      const bool ig = ctx->in_group; ctx->in_group = true; ctx->cal_cols = true;
+      rc = run_matcher(ctx, Bm, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, ctx->e_idx, ctx->e_score, nm, s);
+      ctx->in_group = ig; ctx->cal_cols = false;
+    }
+    if (rc != GN_OK) break;
+    const size_t nb = (size_t)Bm * np;
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(rb.data(), ctx->max0, nb * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(r2.data(), ctx->max0b, nb * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cb.data(), ctx->colbest, nb * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(c2.data(), ctx->col2, nb * 4, hipMemcpyDeviceToHost) != hipSuccess || (ctx->guard && hipMemcpy(&trip, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) { rc = GN_ERR_HIP; break; }
+    tripped |= trip;
+    const float Lm = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
+    double mx = 0.0, mx_all = 0.0; long long cnt = 0;
+    auto take = [&](float bm, float be, float sm, float se) {
+      const double d1 = std::fabs((double)bm - be), d2 = std::fabs((double)sm - se);
+      const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
+      mx_all = std::max(mx_all, d);
+      if (std::max(bm, be) >= Lm - 1.f) { ++cnt; mx = std::max(mx, d); }
+    };
+    for (int b = 0; b < Bm; ++b) {
+      const int n0 = nv[2 * b], n1 = nv[2 * b + 1];
+      if (n0 < 2 || n1 < 2) continue;
+      for (int i = 0; i < n0; ++i) { const size_t o = (size_t)b * np + i; take(rb[o], best[n_lv][o], r2[o], second[n_lv][o]); }
+      for (int j = 0; j < n1; ++j) { const size_t o = (size_t)b * np + j; take(cb[o], cb_f32[o], c2[o], c2_f32[o]); }
+    }
+    if (cnt == 0) mx = mx_all;
+    mid_mx = std::max(mid_mx, mx);
   }
   hipFree(nm);
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
@@ -1514,6 +1616,11 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     ctx->cert_eps_lvl[1] = eps_of[1]; ctx->cert_eps_lvl[0] = std::max(eps_of[0], eps_of[1]);
     ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
   }
+  if (lad && mid_mx >= 0.0) {
+    if (!std::isfinite(mid_mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the middle level's pass");
+    ctx->cert_eps_mid = std::max(floor_eps, safety * (float)mid_mx);
+    ctx->cert_mid_measured = (float)mid_mx;
+  }
   const int rep = n_lv - 1;       // reported: the three-product level's values under the automatic setting (gn_get_ffn_level returns both eps)
   ctx->cert_eps = eps_of[rep];
   if (measured_host) *measured_host = mx_of[rep];
@@ -1528,9 +1635,28 @@ int gn_get_certify_stats(gn_ctx* ctx, int64_t* out8) {
   return GN_OK;
 }
 
+int gn_set_certify_ladder(gn_ctx* ctx, int enable, float eps_mid) {
+  if (!ctx) return GN_ERR_ARG;
+  if (enable && (!ctx->planes_mode || ctx->attn_f16 == 2 || ctx->feature != GN_FEATURE_SIFT))
+    return fail(ctx, GN_ERR_ARG, "gn_set_certify_ladder: the ladder needs a SIFT context of GN_PREC_F16X2_BF16_ATTN or GN_PREC_F16X2_F16_ATTN "
+                                 "(its middle level is GN_PREC_F16X2_F16X2_ATTN's arithmetic on the same planes; exact f32 has nothing to ladder)");
+  ctx->ladder = enable ? 1 : 0;
+  if (eps_mid >= 0.f) ctx->cert_eps_mid = eps_mid;
+  return GN_OK;
+}
+
+int gn_get_certify_ladder_stats(gn_ctx* ctx, int64_t* out4) {
+  if (!ctx || !out4) return GN_ERR_ARG;
+  uint32_t bits = 0;
+  memcpy(&bits, &ctx->cert_eps_mid, sizeof bits);
+  out4[0] = ctx->mid_rerun; out4[1] = ctx->mid_certified; out4[2] = ctx->mid_passed; out4[3] = ctx->cert_eps_mid >= 0.f ? (int64_t)bits : -1;
+  return GN_OK;
+}
+
 int gn_reset_certify_stats(gn_ctx* ctx) {
   if (!ctx) return GN_ERR_ARG;
   ctx->cert_calls = ctx->cert_pairs = ctx->cert_flag_margin = ctx->cert_flag_range = ctx->cert_rerun = ctx->cert_f32_marginal = 0;
+  ctx->mid_rerun = ctx->mid_certified = ctx->mid_passed = 0;
   ctx->auto_calls_lvl[0] = ctx->auto_calls_lvl[1] = ctx->auto_switches = 0;
   return GN_OK;
 }
@@ -1595,7 +1721,7 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   mv(c->qkb, T2 * 2 * kDim); mv(c->vtb, T2 * kDim);
   mv(c->rowmax, np); mv(c->rowlog, np); mv(c->colmax, np); mv(c->collog, np); mv(c->max0, np); mv(c->m0, np); mv(c->m1, np);
   mv(c->cpart_m, (np / 32) * np); mv(c->cpart_s, (np / 32) * np); mv(c->cpart_i, (np / 32) * np); mv(c->rpart_a, 8 * np); mv(c->rpart_b, 8 * np); mv(c->tickets, 2);
-  mv(c->max0b, np); mv(c->rpart_c, 8 * np); mv(c->uncert, 1); mv(c->uncert_alt, 1);
+  mv(c->max0b, np); mv(c->rpart_c, 8 * np); mv(c->uncert, 1); mv(c->uncert_alt, 1); mv(c->colbest, np); mv(c->col2, np);
   // match lists and the PnP masks are strided by the context's padded maximum (gn_kmax), whatever the active size
   const long long km = c->npad;
   mv(c->e_idx, km * 2); mv(c->e_score, km); mv(c->e_mkp, km * 2); mv(c->e_obj, km * 3);
@@ -2328,7 +2454,7 @@ int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale, c
   a.nvalid = nkv; a.npad = npad; a.cross = cross; a.qscale = qscale; a.BS = BS;
   a.qb = a.kb = a.vt = nullptr; a.ldqb = a.ldkb = 0; a.outp = nullptr; a.half_fmt = ctx->attn_f16; a.ncu = ctx->ncu;
   const long long cap = (long long)ctx->max_batch * 2 * ctx->npad;
-  if (ctx->precision != GN_PREC_F32 && ctx->attn_variant >= 1 && ctx->qkb && ctx->vtb && (long long)BS * npad <= cap) {
+  if (ctx->precision != GN_PREC_F32 && ctx->attn_f16 != 2 && ctx->attn_variant >= 1 && ctx->qkb && ctx->vtb && (long long)BS * npad <= cap) {
     // the production kernel (k_attn_bf16_v5) on the layouts the projection epilogues would have written
     launch_pack_attn_bf16(a, ctx->qkb, ctx->vtb, (hipStream_t)stream);
     a.qb = ctx->qkb; a.kb = ctx->qkb + kDim; a.ldqb = a.ldkb = 2 * kDim; a.vt = ctx->vtb;

@@ -231,6 +231,7 @@ constexpr int kTileListBase = 16;
 void launch_tile_lists(const int32_t* nvalid, int BS, int npad, int* lists, unsigned long long* feedback /* pinned host word or nullptr */, hipStream_t s);
 void launch_attention_f32(const AttnArgs& a, hipStream_t s);
 void launch_attention_bf16(const AttnArgs& a, hipStream_t s);
+void launch_attention_f16x2(const AttnArgs& a, hipStream_t s);   // k_attn_f16x2 (gn_attention_f16x2.hip): f32 rows in, split-fp16 operands, f32-accurate
 void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s);
 bool launch_attention_pw(const AttnArgs& a, int ablate, hipStream_t s);   // k_attn_pw (gn_attention_pw.hip): bulk grids, npad % 256 == 0; false = not applicable
 void launch_pack_attn_bf16(const AttnArgs& a, uint16_t* qkb, uint16_t* vtb, hipStream_t s);   // (a.half_fmt selects bf16 / fp16)   // f32 rows -> the bf16 layouts k_attn_bf16_v5 reads (test entry)
@@ -281,6 +282,8 @@ struct HeadArgs {
   float cert_eps;           // bound on |P_this mode - P_exact| the certificate is stated for
   int32_t* uncert_alt = nullptr;   // [B] out (optional): the same test for cert_eps_alt -- what the OTHER block-tail level's certificate would say about these
   float cert_eps_alt = -1.f;       // scores (gn_set_ffn_products(0): the context weighs the two levels' re-run fractions against each other); 0 / 1
+  float* colbest = nullptr;        // [B][npad] out (optional, fused head): best score and runner-up of every column (gn_calibrate_certify's middle
+  float* col2 = nullptr;           // level measures its eps over row AND column decisions)
 };
 void launch_match_head(const HeadArgs& a, hipStream_t s);
 void launch_match_head_fused(const HeadArgs& a, hipStream_t s);

@@ -566,6 +566,7 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
     if (SWEEP == 1) { a.colmax[ro + j] = m; a.collog[ro + j] = logf(sm); }
     else {
       a.m1[ro + j] = bi; m1s[j] = bi;
+      if (a.colbest != nullptr) { a.colbest[ro + j] = m; a.col2[ro + j] = m2; }
       if (cert && m >= Lth - a.cert_eps && !(m - m2 > 2.f * a.cert_eps)) unc = 1;     // (b)
       if (cert2 && m >= Lth - a.cert_eps_alt && !(m - m2 > 2.f * a.cert_eps_alt)) unc2 = 1;
     }

@@ -10,6 +10,7 @@ core/_shared.py:109-116.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -25,7 +26,8 @@ RANSAC_REPROJ_PX = 8.0    # cv2.solvePnPRansac default
 RANSAC_CONFIDENCE = 0.99  # cv2.solvePnPRansac default
 
 _PRECISIONS = {"f32": _lib.GN_PREC_F32, "bf16_attn": _lib.GN_PREC_BF16_ATTN, "f32x3_bf16_attn": _lib.GN_PREC_F32X3_BF16_ATTN,
-               "f16x2_bf16_attn": _lib.GN_PREC_F16X2_BF16_ATTN, "f16x2_f16_attn": _lib.GN_PREC_F16X2_F16_ATTN}
+               "f16x2_bf16_attn": _lib.GN_PREC_F16X2_BF16_ATTN, "f16x2_f16_attn": _lib.GN_PREC_F16X2_F16_ATTN,
+               "f16x2_f16x2_attn": _lib.GN_PREC_F16X2_F16X2_ATTN}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -263,9 +265,27 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_calibrate_certify")
         lv = self.ffn_level()
         d = {"measured": float(m.value), "eps": float(e.value), "safety": float(safety)}
+        if getattr(self, "_certify_ladder", False):      # set_certify_ladder(True): the middle level was measured too
+            d["eps_mid"] = self.certify_ladder_stats()["eps_mid"]
         if getattr(self, "_ffn_auto", False):      # set_ffn_products("auto"): both levels were measured; measured / eps are the three-product level's
             d["eps_two_products"], d["eps_three_products"] = lv["eps_two_products"], lv["eps_three_products"]
         return d
+
+    def set_certify_ladder(self, enable: bool, eps_mid: Optional[float] = None) -> None:
+        """gn_set_certify_ladder: with the ladder on, set_certify("rerun" / "deferred") re-runs the pairs flagged for margin first in the
+        "f16x2_f16x2_attn" arithmetic, certified there against eps_mid (measured by calibrate_certify while the ladder is on), and only the pairs still
+        flagged in exact f32.  Contexts of "f16x2_bf16_attn" / "f16x2_f16_attn" only.  eps_mid=None keeps the current value."""
+        _lib.check(self.ctx, self.lib.gn_set_certify_ladder(self.ctx, int(bool(enable)), -1.0 if eps_mid is None else float(eps_mid)),
+                   "gn_set_certify_ladder")
+        self._certify_ladder = bool(enable)
+
+    def certify_ladder_stats(self) -> Dict[str, float]:
+        """gn_get_certify_ladder_stats: pairs re-run on the middle level, of those certified there, of those passed on to exact f32 (since the last
+        certify_stats(reset=True)), and eps_mid (None when not calibrated)."""
+        buf = (C.c_int64 * 4)()
+        _lib.check(self.ctx, self.lib.gn_get_certify_ladder_stats(self.ctx, buf), "gn_get_certify_ladder_stats")
+        eps = None if buf[3] < 0 else struct.unpack("<f", struct.pack("<I", int(buf[3])))[0]
+        return {"mid_rerun": int(buf[0]), "mid_certified": int(buf[1]), "passed_to_f32": int(buf[2]), "eps_mid": eps}
 
     def certify_stats(self, reset: bool = False) -> Dict[str, int]:
         buf = (C.c_int64 * 8)()

@@ -20,9 +20,24 @@ from .weights import N_LAYERS
 _DEFAULTS = {"n_layers": N_LAYERS, "filter_threshold": 0.1, "depth_confidence": 0.95, "width_confidence": 0.99}
 
 
+_LADDER_PRECISIONS = ("f16x2_bf16_attn", "f16x2_f16_attn")
+
+
+def _check_ladder(certify_ladder: bool, precision: str, feature_name: str, certify: bool) -> bool:
+    """The ladder keyword of LightGlueMatcher / PoseNode: False, or a certified SIFT matcher in one of the fast f16x2 modes (its middle level is
+    "f16x2_f16x2_attn" arithmetic on the same weight planes; "f32" -- and mode 5 itself -- have nothing to ladder)."""
+    if not certify_ladder:
+        return False
+    if precision not in _LADDER_PRECISIONS or feature_name != "sift" or not certify:
+        raise ValueError(f"certify_ladder=True needs certify=True, feature 'sift' and precision in {_LADDER_PRECISIONS} (got precision={precision!r}, "
+                         f"feature={feature_name!r}, certify={certify})")
+    return True
+
+
 class LightGlueMatcher:
     def __init__(self, feature_name: str = "sift", params: Optional[Dict] = None, *,
-                 state_dict=None, max_kpts: int = 4096, precision: str = "f32", certify: bool = True, certify_calibration_calls: int = 8):
+                 state_dict=None, max_kpts: int = 4096, precision: str = "f32", certify: bool = True, certify_calibration_calls: int = 8,
+                 certify_ladder: bool = False):
         if feature_name not in ("sift", "superpoint"):
             raise NotImplementedError("LightGlue('sift') is what PoseNode uses (pose_node.py:110); 'superpoint' (256-d descriptors, BASELINE configs[4]) "
                                       "is the other variant built here")
@@ -43,6 +58,9 @@ class LightGlueMatcher:
         # is matched a second time in f32: 4 x the largest difference seen), then frozen.
         self._certify = bool(certify) and precision != "f32"
         self._cal_left, self._cal_eps = int(certify_calibration_calls), 0.0
+        # the certificate's re-run ladder (off by default): flagged pairs go through the "f16x2_f16x2_attn" arithmetic before exact f32; eps_mid is
+        # calibrated with eps on the same calls and forwarded to the engine with it
+        self._ladder, self._cal_eps_mid = _check_ladder(certify_ladder, precision, feature_name, self._certify), 0.0
         self._engine: Optional[PoseEngine] = None
 
     @staticmethod
@@ -74,6 +92,8 @@ class LightGlueMatcher:
         self._engine = PoseEngine(device.index or 0, max_batch=1, max_kpts=self._max_kpts, precision=self._precision,
                                   state_dict=self._state_dict, n_layers=self.params["n_layers"],
                                   filter_threshold=self.params["filter_threshold"], guard="sync", feature=self.feature_name)
+        if self._ladder:
+            self._engine.set_certify_ladder(True)
         return self
 
     def eval(self):
@@ -110,6 +130,9 @@ class LightGlueMatcher:
                 self._cal_eps = max(self._cal_eps, cal["eps"])
                 self._cal_left -= 1
                 self._engine.set_certify("rerun", eps=self._cal_eps)
+                if self._ladder and cal.get("eps_mid") is not None:
+                    self._cal_eps_mid = max(self._cal_eps_mid, cal["eps_mid"])
+                    self._engine.set_certify_ladder(True, eps_mid=self._cal_eps_mid)
             except _lib.GnError:          # (a sample that cannot calibrate -- it left the fp16 range -- : the next call tries again)
                 pass
         idx, score, n_match = self._engine.match(d1, l1, n1, d2, l2, n2, fmt)

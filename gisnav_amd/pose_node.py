@@ -28,7 +28,9 @@ class PoseNode:
     MIN_MATCHES = MIN_MATCHES    # pose_node.py:63
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
-                 certify: bool = True, certify_calibration_calls: int = 8):
+                 certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False):
+        from .matcher import _check_ladder
+        ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
         self._engine = PoseEngine(device, max_batch=1, max_kpts=max_kpts, precision=precision, state_dict=state_dict,
                                   n_layers=9, filter_threshold=self.CONFIDENCE_THRESHOLD, guard="sync")
         if extractor is None:
@@ -39,6 +41,10 @@ class PoseNode:
         # the first messages' own inputs (each is matched a second time in f32), 4 x the largest difference seen, then frozen
         self._certify = bool(certify) and precision != "f32"
         self._cal_left, self._cal_eps = int(certify_calibration_calls), 0.0
+        # the certificate's re-run ladder (off by default): eps_mid calibrated with eps on the same messages, forwarded with it
+        self._ladder, self._cal_eps_mid = ladder, 0.0
+        if ladder:
+            self._engine.set_certify_ladder(True)
         self._cached_stamp_kps_desc = None
         self._cached_n_r = 0
         self.camera_info: Optional[CameraInfo] = None
@@ -105,9 +111,13 @@ class PoseNode:
         try:
             if self._certify and self._cal_left > 0 and n >= 2 and self._cached_n_r >= 2:
                 try:
-                    self._cal_eps = max(self._cal_eps, eng.calibrate_certify(inputs)["eps"])
+                    cal = eng.calibrate_certify(inputs)
+                    self._cal_eps = max(self._cal_eps, cal["eps"])
                     self._cal_left -= 1
                     eng.set_certify("rerun", eps=self._cal_eps)
+                    if self._ladder and cal.get("eps_mid") is not None:
+                        self._cal_eps_mid = max(self._cal_eps_mid, cal["eps_mid"])
+                        eng.set_certify_ladder(True, eps_mid=self._cal_eps_mid)
                 except _lib.GnError:      # (a sample that cannot calibrate -- it left the fp16 range -- : the next message tries again)
                     pass
             eng.estimate(inputs, np.asarray(camera_info.k, np.float64).reshape(3, 3), self.MIN_MATCHES, out=self._out)

@@ -79,7 +79,14 @@ enum gn_precision {
                             q, k, v to half for F.scaled_dot_product_attention when flash=True; pose_node.py:285-287 via
                             SURVEY.md:314), at the same matrix-pipe rate as bf16.  q / k / v share the guarded fp16 domain
                             of the activations (|value| < 65504, else the guard word is raised; the guard-2 re-run uses bf16
-                            attention operands, which have f32's range) */
+                            attention operands, which have f32's range) */,
+  GN_PREC_F16X2_F16X2_ATTN = 5 /* as 3 with an f32-accurate attention on the FP16 matrix instruction: the q | k | v projections leave f32 rows
+                            (the f16x2 GEMMs, three products), and k_attn_f16x2 splits q, k, v and the probabilities into two fp16 terms
+                            each under power-of-two scales (S = qh kh + qh kl + ql kh, O = ph vh + ph vl + pl vh, f32 softmax with the
+                            exact running maximum, f32 accumulation); the block tail on three products.  Every contraction is
+                            f32-accurate and all of them run on the 16-bit matrix pipe.  Guarded like 3 (a high term or an hm16 output
+                            that leaves the fp16 range raises the guard word).  SIFT contexts only (GN_FEATURE_SUPERPOINT: GN_ERR_ARG).
+                            Also the middle level of the certificate's re-run ladder (gn_set_certify_ladder). */
 };
 
 enum gn_kpt_format {
@@ -170,6 +177,19 @@ int gn_device_numa_node(int device);
  * re-run (or, in an f32 context, original) pairs that are marginal even for eps_f32, current mode, reserved. */
 int gn_get_certify_stats(gn_ctx* ctx, int64_t* out8);
 int gn_reset_certify_stats(gn_ctx* ctx);
+/* The certificate's re-run ladder (off by default; contexts of GN_PREC_F16X2_BF16_ATTN / GN_PREC_F16X2_F16_ATTN with SIFT features only, else
+ * GN_ERR_ARG when enabling).  With it on and eps_mid calibrated, gn_set_certify(2 / 3) re-runs the pairs flagged for margin (flag 1) first in
+ * GN_PREC_F16X2_F16X2_ATTN's arithmetic on this context's weights and workspaces, and the match head certifies them there against eps_mid; only
+ * the pairs still flagged -- together with every pair flagged for range (flag 2) and every pair whose middle pass left the fp16 range -- go on to
+ * the exact-f32 re-run.  eps_mid < 0 keeps the current value.  gn_calibrate_certify, with the ladder on, adds a mode-5 pass (on the sample and on
+ * its first pair alone) and sets eps_mid = max(floor_eps, safety * max |P_mid - P_f32|) over the best score and runner-up of every row AND column
+ * that come within 1 of log(filter_threshold); gn_load_tensor discards eps_mid (flagged pairs then go straight to exact f32 until the next
+ * calibration).  With the ladder off nothing of the certified path changes. */
+int gn_set_certify_ladder(gn_ctx* ctx, int enable, float eps_mid);
+/* out4: pairs re-run on the middle level, of those certified there, of those passed on to exact f32 (since gn_reset_certify_stats), and eps_mid
+ * as the IEEE-754 bits of the float (an unsigned 32-bit value), or -1 when eps_mid is not calibrated.  gn_get_certify_stats' re-run count stays
+ * "re-run in exact f32". */
+int gn_get_certify_ladder_stats(gn_ctx* ctx, int64_t* out4);
 /* Measure eps for THIS context's weights and precision mode on a sample batch (arguments as gn_match): the batch is matched twice -- in the
  * context's arithmetic and on the exact-f32 kernels -- and eps = max(floor_eps, safety * max |P_mode - P_f32|) over the best score and the
  * runner-up of every valid row that comes within 1 of log(filter_threshold) in either arithmetic (all rows when the threshold is 0, or when no row
