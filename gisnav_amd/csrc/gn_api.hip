@@ -70,6 +70,8 @@ struct gn_ctx {
   // exact-f32 arithmetic (GN_PREC_F32's kernels on this context's f32 weights and f32 workspaces), which also takes over the fp16-range fallback
   int certify = 0;             // 0 off, 1 flags only (gn_get_uncertain), 2 flags + f32 re-run of the flagged pairs
   float cert_eps = 4.0e-3f;    // stated bound on |P_mode - P_exact| for this context's arithmetic (tools/certify_eps.py measures it)
+  int cert_eps_src = 0;        // where cert_eps comes from: 0 the built-in default, 1 stated (gn_set_certify), 2 measured (gn_calibrate_certify),
+                               // 3 measured on weights since replaced (gn_load_tensor; cert_eps is then +inf: every pair goes to exact f32)
   float cert_eps_f32 = 1.0e-4f;   // the same for the exact-f32 kernels (GPU f32 against the torch-CPU f32 oracle: summation order only)
   float* max0b = nullptr; float* rpart_c = nullptr; int32_t* uncert = nullptr; int32_t* uncert_alt = nullptr; int32_t* uncert_host = nullptr;   // uncert_host: pinned [2 * max_batch] (flags | the other level's flags)
   bool cert_inner = false;     // a certificate re-run is being enqueued (no nested certification)
@@ -151,8 +153,9 @@ struct gn_ctx {
                            // padding, 20 % faster on a ragged one; identical bits).  2: always walk.  3: never walk.
   int ncu = 256;           // compute units of ctx->device (grids of the walking kernels)
   int fused_proj_status = -1;   // self-check of the projection fused behind the block tail (selfcheck_fused_projection): -1 not run / not applicable to this
-                                // context, 1 bitwise equal to the separate k_qkv launches, 0 differed -> qkv_in_tail switched off for this context
-  bool fused_proj_pending = true;   // run the self-check at the next forward call (set by every weight (re)load)
+                                // context, 1 bitwise equal to the separate k_qkv launches, 0 differed -> fused_proj_off for this context
+  bool fused_proj_pending = true;   // run the self-check at the next forward call (set by every weight (re)load and block-tail level change)
+  int fused_proj_off = 0;  // the self-check saw a difference: the fusion stays off until the next check passes (knob 32 keeps the caller's setting)
   int qkv_in_tail = 1;     // knob 32.  1 (default): on bulk grids the block tail k_ffn128 also computes the NEXT block's attention input projection from the rows
                            // it has just produced (k_ffn128<., ., ., 1 / 2>: no k_qkv launch, no read-back of the residual stream); 0: separate k_qkv launches
   int skinny = 1;          // knob 33.  1 (default): calls of one or two pairs run the attention input projections and the block
@@ -590,7 +593,7 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     f.ncu = c->ncu;
     f.composed = comp ? 1 : 0;
     f.products = (comp && ffn_level(c) == 2) ? 2 : 3;
-    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && comp && ffn_selects_128(f) && gn::g_ffn_ablate == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
+    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_ablate == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
                           c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
       f.qkv = next_cross ? 2 : 1;
@@ -850,10 +853,13 @@ __global__ void k_count_diff(const uint4* a, const uint4* b, size_t n, unsigned 
 // k_qkv launches on ITS weights before it is used: the first forward call after a weight (re)load runs, on pseudo-random token rows in the context's own
 // workspaces, the block tail with the projection fused (self and cross form, one-tile and walking form) and tail + k_qkv separately, and compares the
 // q | k rows and V^T panels bit for bit.  Any difference switches the fusion off for this context (gn_fused_projection_status).  ~60 ms, once.
+// Every block-tail level the context can select is proved: three products, and two when gn_set_ffn_products is 2 or 0 (automatic).  The check runs
+// at the full padded size (the smallest bulk grid there) whatever gn_set_active_kpts has set: ffn() lays the rows out at npad_run.
 int selfcheck_fused_projection(gn_ctx* c) {
   gn_ctx* ctx = c;
   c->fused_proj_pending = false;
   c->fused_proj_status = -1;
+  c->fused_proj_off = 0;
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
   if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
@@ -887,11 +893,15 @@ int selfcheck_fused_projection(gn_ctx* c) {
   unsigned int* cnt = c->ovf_base + 12;                                 // (words 9..15 of the guard block are unused)
   GN_HIP(hipMemset(cnt, 0, sizeof(unsigned int)));
   const int lists0 = c->use_lists, fused0 = c->qkv_in_tail, guard0 = c->guard; const bool kt0 = c->ktiming; const int lc0 = c->launch_count, sa0 = c->stop_after;
-  c->ktiming = false; c->stop_after = 0; c->guard = 0;
+  const int np_run0 = c->npad_run, prod0 = c->ffn_products;
+  c->ktiming = false; c->stop_after = 0; c->guard = 0; c->npad_run = np;
   bool applicable = true;
   const int nblk = c->n_layers > 1 ? 1 : 0;
+  const int n_lv = (prod0 == 0 || prod0 == 2) ? 2 : 1;     // levels: 3, then 2 when the context can select it
+  for (int lv = 0; lv < n_lv && applicable; ++lv)
   for (int cross = 0; cross < 2 && applicable; ++cross)
     for (int walk = 0; walk < 2 && applicable; ++walk) {
+      c->ffn_products = lv == 0 ? 3 : 2;
       const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
       const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
       c->use_lists = walk ? 2 : 3;
@@ -910,6 +920,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
       hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_v), reinterpret_cast<const uint4*>(c->vtb), vbytes / 16, cnt);
     }
   c->use_lists = lists0; c->qkv_in_tail = fused0; c->guard = guard0; c->ktiming = kt0; c->launch_count = lc0; c->stop_after = sa0;
+  c->npad_run = np_run0; c->ffn_products = prod0;
   unsigned int diffs = 0;
   GN_HIP(hipStreamSynchronize(0));
   GN_HIP(hipMemcpy(&diffs, cnt, sizeof diffs, hipMemcpyDeviceToHost));
@@ -920,7 +931,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
   if (!applicable) return GN_OK;
   c->fused_proj_status = diffs == 0 ? 1 : 0;
   if (diffs != 0) {
-    c->qkv_in_tail = 0;
+    c->fused_proj_off = 1;
     fprintf(stderr, "[gisnav_amd] the projection fused behind the block tail differs from the separate k_qkv launches in %u 16-byte words on this context's weights: "
                     "fusion switched off for this context (results stay correct, ~4 %% slower)\n", diffs);
   }
@@ -1377,6 +1388,9 @@ int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int
     // a calibration belongs to the weights it was measured on: the automatic block-tail level goes back to "not calibrated" (three products, cert_eps)
     ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = -1.f; ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
     ctx->cert_eps_mid = -1.f;   // (the ladder sends flagged pairs straight to exact f32 until the next calibration)
+    // and so does the single eps when it was measured (a stated one is the caller's to keep): every pair is flagged -- exact f32 -- until
+    // gn_calibrate_certify runs again or gn_set_certify states an eps
+    if (ctx->cert_eps_src >= 2) { ctx->cert_eps = INFINITY; ctx->cert_eps_src = 3; }
   }
   return rc;
 }
@@ -1474,7 +1488,10 @@ int gn_fused_projection_status(const gn_ctx* ctx) { return ctx ? ctx->fused_proj
 
 int gn_set_ffn_products(gn_ctx* ctx, int products) {
   if (!ctx || (products != 0 && products != 2 && products != 3)) return GN_ERR_ARG;
-  if (products != ctx->ffn_products) { ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0; }
+  if (products != ctx->ffn_products) {
+    ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+    ctx->fused_proj_pending = true;        // the fused projection is proved on every level the new setting can select
+  }
   ctx->ffn_products = products;
   return GN_OK;
 }
@@ -1500,7 +1517,7 @@ int gn_set_certify(gn_ctx* ctx, int mode, float eps, float eps_f32) {
   if (ctx->certify == 3 && mode != 3 && (ctx->cert_pend[0].active || ctx->cert_pend[1].active))
     return fail(ctx, GN_ERR_ARG, "gn_set_certify: deferred certificates are still open -- gn_flush first");
   ctx->certify = mode;
-  if (eps >= 0.f) ctx->cert_eps = eps;
+  if (eps >= 0.f) { ctx->cert_eps = eps; ctx->cert_eps_src = 1; }
   if (eps_f32 >= 0.f) ctx->cert_eps_f32 = eps_f32;
   return GN_OK;
 }
@@ -1583,6 +1600,45 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     if (cnt == 0) mx = mx_all;
     mid_mx = std::max(mid_mx, mx);
   }
+  // the sample's first pair alone, and with its reference side cut to 128 and to 2 keypoints: the one-pair grid of bucket remainders, and the
+  // few-keypoint sides of a ragged stream, where the fp16 attention's rounding averages over few keys (measured against fp64 on a ragged bulk
+  // batch: 1.7x the eps of a 16 x 1024 sample alone, tests/test_gpu_fp64_parity.py).  Each level's eps is taken over these passes too.
+  double var_mx[2] = {0.0, 0.0};
+  int32_t* nr1 = nullptr;
+  if (rc == GN_OK && !tripped && nv[0] >= 2 && nv[1] >= 2 && hipMalloc((void**)&nr1, sizeof(int32_t)) != hipSuccess) rc = GN_ERR_HIP;
+  for (int var = 0; nr1 && rc == GN_OK && var < 3; ++var) {
+    const int32_t nr_cut = var == 0 ? nv[1] : std::min(nv[1], var == 1 ? 128 : 2);
+    if (hipMemcpy(nr1, &nr_cut, sizeof nr_cut, hipMemcpyHostToDevice) != hipSuccess) { rc = GN_ERR_HIP; break; }
+    std::vector<float> vb[3], vs[3];
+    unsigned int trip = 0u;
+    for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
+      std::unique_ptr<F32Scope> f32;
+      if (pass == n_lv) f32.reset(new F32Scope(ctx)); else ctx->ffn_products = lv[pass];
+      const bool ig = ctx->in_group; ctx->in_group = true;
+      rc = run_matcher(ctx, 1, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, nr1, stride_r, ctx->e_idx, ctx->e_score, nm, s);
+      ctx->in_group = ig; ctx->ffn_products = setting;
+      if (rc != GN_OK) break;
+      vb[pass].resize(np); vs[pass].resize(np);
+      unsigned int t = 0u;
+      if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(vb[pass].data(), ctx->max0, np * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(vs[pass].data(), ctx->max0b, np * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+          (pass < n_lv && ctx->planes_mode && ctx->guard && hipMemcpy(&t, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = GN_ERR_HIP;
+      trip |= t;
+    }
+    if (rc != GN_OK || trip) continue;          // (a pass that left the fp16 range is re-run as a whole by the certificate: nothing to measure)
+    const float Lv = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
+    for (int k = 0; k < n_lv; ++k) {
+      double mx = 0.0, mx_all = 0.0; long long rows = 0;
+      for (int i = 0; i < nv[0]; ++i) {
+        const double d1 = std::fabs((double)vb[k][i] - vb[n_lv][i]), d2 = std::fabs((double)vs[k][i] - vs[n_lv][i]);
+        const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
+        mx_all = std::max(mx_all, d);
+        if (std::max(vb[k][i], vb[n_lv][i]) >= Lv - 1.f) { ++rows; mx = std::max(mx, d); }
+      }
+      var_mx[k] = std::max(var_mx[k], rows ? mx : mx_all);
+    }
+  }
+  if (nr1) hipFree(nr1);
   hipFree(nm);
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
   if (tripped) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample left the fp16 range of this precision mode (nothing to calibrate: such calls are re-run as a whole)");
@@ -1609,6 +1665,8 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     if (rows == 0) { mx = mx_all; rows = rows_all; }
     if (!std::isfinite(mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the sample");
     if (rows == 0) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample holds no pair with at least two keypoints per side (nothing to measure)");
+    if (!std::isfinite(var_mx[k])) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the one-pair passes");
+    mx = std::max(mx, var_mx[k]);
     mx_of[k] = (float)mx; eps_of[k] = std::max(floor_eps, safety * (float)mx);
   }
   if (setting == 0) {
@@ -1622,7 +1680,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     ctx->cert_mid_measured = (float)mid_mx;
   }
   const int rep = n_lv - 1;       // reported: the three-product level's values under the automatic setting (gn_get_ffn_level returns both eps)
-  ctx->cert_eps = eps_of[rep];
+  ctx->cert_eps = eps_of[rep]; ctx->cert_eps_src = 2;
   if (measured_host) *measured_host = mx_of[rep];
   if (eps_host) *eps_host = eps_of[rep];
   return GN_OK;
@@ -1631,7 +1689,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
 int gn_get_certify_stats(gn_ctx* ctx, int64_t* out8) {
   if (!ctx || !out8) return GN_ERR_ARG;
   out8[0] = ctx->cert_calls; out8[1] = ctx->cert_pairs; out8[2] = ctx->cert_flag_margin; out8[3] = ctx->cert_flag_range;
-  out8[4] = ctx->cert_rerun; out8[5] = ctx->cert_f32_marginal; out8[6] = ctx->certify; out8[7] = 0;
+  out8[4] = ctx->cert_rerun; out8[5] = ctx->cert_f32_marginal; out8[6] = ctx->certify; out8[7] = ctx->cert_eps_src;
   return GN_OK;
 }
 

@@ -294,6 +294,8 @@ class PoseEngine:
             _lib.check(self.ctx, self.lib.gn_reset_certify_stats(self.ctx), "gn_reset_certify_stats")
         keys = ("calls", "pairs", "flagged_margin", "flagged_fp16_range", "rerun_pairs", "f32_marginal_pairs", "mode")
         d = {k: int(buf[i]) for i, k in enumerate(keys)}
+        # where the eps in effect comes from; "discarded": measured on weights a load has since replaced (every pair goes to exact f32)
+        d["eps_source"] = {0: "default", 1: "stated", 2: "calibrated", 3: "discarded"}.get(int(buf[7]), str(int(buf[7])))
         d["rerun_fraction"] = (d["rerun_pairs"] / d["pairs"]) if d["pairs"] else 0.0
         return d
 

@@ -57,7 +57,8 @@ class LightGlueMatcher:
         # the calibrated error margin are re-run in f32 before the call returns).  eps is calibrated on the first calls' own inputs (each of them
         # is matched a second time in f32: 4 x the largest difference seen), then frozen.
         self._certify = bool(certify) and precision != "f32"
-        self._cal_left, self._cal_eps = int(certify_calibration_calls), 0.0
+        self._cal_calls = int(certify_calibration_calls)
+        self._cal_left, self._cal_eps = self._cal_calls, 0.0
         # the certificate's re-run ladder (off by default): flagged pairs go through the "f16x2_f16x2_attn" arithmetic before exact f32; eps_mid is
         # calibrated with eps on the same calls and forwarded to the engine with it
         self._ladder, self._cal_eps_mid = _check_ladder(certify_ladder, precision, feature_name, self._certify), 0.0
@@ -103,6 +104,11 @@ class LightGlueMatcher:
         self._state_dict = sd
         if self._engine is not None:
             self._engine.load_state_dict(sd)
+            # eps was measured on the old weights: calibrate again on the next calls, and until then certify nothing (every pair in exact f32)
+            self._cal_left, self._cal_eps = self._cal_calls, 0.0
+            self._cal_eps_mid = 0.0
+            if self._certify:
+                self._engine.set_certify("rerun", eps=float("inf"))
 
     @torch.inference_mode()
     def __call__(self, desc1: torch.Tensor, desc2: torch.Tensor, lafs1: torch.Tensor, lafs2: torch.Tensor,

@@ -143,7 +143,10 @@ int gn_get_guard_status(gn_ctx* ctx, void* stream, int32_t* last_call_tripped, i
  *           again -- matcher, and for gn_estimate also gather + PnP -- on GN_PREC_F32's kernels (the context keeps f32 weights and f32
  *           workspaces in every mode).  A call whose activations left the fp16 range is flagged as a whole (flag value 2), so this mode
  *           also takes over gn_set_guard(2)'s fallback.  In a GN_PREC_F32 context nothing is re-run: the flags (for eps_f32) are counted.
- * Results of a pair do not depend on which other pairs were re-run. */
+ * Results of a pair do not depend on which other pairs were re-run.
+ * A calibration belongs to the weights it was measured on: gn_load_tensor marks an eps measured by gn_calibrate_certify as discarded, and
+ * until gn_calibrate_certify runs again or an eps is stated here, modes 2 and 3 send every pair to exact f32.  An eps stated here (or the
+ * built-in default) is the caller's and survives a load. */
 int gn_set_certify(gn_ctx* ctx, int mode, float eps, float eps_f32);
 /* Arithmetic of the block tail (ffn.0 -> LayerNorm -> GELU -> ffn.3 with out_proj folded in; kornia `x + ffn(cat[x, msg])`) on bulk grids in the f16x2
  * modes: 3 (default) = every operand as two fp16 terms, three partial products, f32-accurate; 2 = the activations' fp16 HIGH term only (22-bit weights x
@@ -166,15 +169,17 @@ int gn_get_ffn_level(gn_ctx* ctx, int32_t* level, float* eps2, float* eps3, int6
 int gn_set_ffn_level_eps(gn_ctx* ctx, float eps2, float eps3, int level);
 /* On bulk grids the block-tail kernel also computes the next block's attention input projection (one launch and one pass over the residual rows
  * less).  Every context proves that fused form against the separate launches on its own weights before using it: at the first forward call after
- * a weight (re)load both forms run on pseudo-random rows and their outputs are compared bit for bit (~60 ms, once); a difference switches the
- * fusion off for the context.  Returns 1 = checked equal, 0 = differed (fusion off), -1 = not run yet / not applicable (small contexts, other modes). */
+ * a weight (re)load or a change of gn_set_ffn_products both forms run on pseudo-random rows, at the full padded size whatever gn_set_active_kpts
+ * has set, on every block-tail level the setting can select (three products; also two under 2 or 0), and their outputs are compared bit for bit
+ * (~60 ms per level, once); a difference switches the fusion off for the context until the next check passes.  Returns 1 = checked equal, 0 = differed (fusion off), -1 = not run yet / not applicable (small contexts, other modes). */
 int gn_fused_projection_status(const gn_ctx* ctx);
 /* NUMA node of HIP device `device` (its PCI function's /sys/bus/pci/devices/<bus id>/numa_node), or -1 when the platform does not say.  The host side pins
  * the staging threads of a rank to that node's cores (gisnav_amd.engine.RecordStager): with one rank per GPU, eight staging pools otherwise share whatever
  * cores the scheduler picks. */
 int gn_device_numa_node(int device);
 /* out8: calls certified, pairs certified, pairs flagged for margin, pairs flagged for fp16 range, pairs re-run in exact f32,
- * re-run (or, in an f32 context, original) pairs that are marginal even for eps_f32, current mode, reserved. */
+ * re-run (or, in an f32 context, original) pairs that are marginal even for eps_f32, current mode, and where eps comes from: 0 the built-in
+ * default, 1 stated through gn_set_certify, 2 measured by gn_calibrate_certify, 3 measured on weights that gn_load_tensor has since replaced. */
 int gn_get_certify_stats(gn_ctx* ctx, int64_t* out8);
 int gn_reset_certify_stats(gn_ctx* ctx);
 /* The certificate's re-run ladder (off by default; contexts of GN_PREC_F16X2_BF16_ATTN / GN_PREC_F16X2_F16_ATTN with SIFT features only, else
@@ -193,7 +198,8 @@ int gn_get_certify_ladder_stats(gn_ctx* ctx, int64_t* out4);
 /* Measure eps for THIS context's weights and precision mode on a sample batch (arguments as gn_match): the batch is matched twice -- in the
  * context's arithmetic and on the exact-f32 kernels -- and eps = max(floor_eps, safety * max |P_mode - P_f32|) over the best score and the
  * runner-up of every valid row that comes within 1 of log(filter_threshold) in either arithmetic (all rows when the threshold is 0, or when no row
- * of the sample comes that close).
+ * of the sample comes that close) -- over the batch, and over three one-pair passes on its first pair: as it is, and with its reference side
+ * cut to 128 and to 2 keypoints (the one-pair grid of bucket remainders; few-keypoint sides, where the fp16 attention's error is larger).
  * Synchronises; sets the context's eps and returns the measured maximum and eps through the two host pointers (either may be NULL).  Call
  * it once after loading a checkpoint, on representative pairs, IN A BATCH OF THE SIZE THE REAL CALLS HAVE (the kernel family -- and with it the arithmetic
  * whose error is being measured -- follows the grid size); safety >= 1 is the stated safety factor (the Python mirror uses 4). */

@@ -325,12 +325,18 @@ def pose_node_match(
     sd: Dict[str, Tensor],
     kp_q: Tensor, desc_q: Tensor, size_q: Tensor, angle_q: Tensor,
     kp_r: Tensor, desc_r: Tensor, size_r: Tensor, angle_r: Tensor,
-    taps: Optional[dict] = None, filter_threshold: float = FILTER_THRESHOLD,
+    taps: Optional[dict] = None, filter_threshold: float = FILTER_THRESHOLD, dtype: torch.dtype = torch.float32,
 ):
     """pose_node.py:246-297 with torch-CPU tensors: LAF build, RootSIFT, matcher, gather.
 
-    Returns (mkp_q (K,2) f32, mkp_r (K,2) f32, scores (K,1), idx (K,2) int64).
+    dtype=torch.float64 runs the same code on float64 weights and inputs: the high-precision reference the GPU kernels' errors are
+    measured against (the taps, the log-assignment and the match list then come out in float64).
+
+    Returns (mkp_q (K,2) f32, mkp_r (K,2) f32, scores (K,1), idx (K,2) int64) -- in `dtype`.
     """
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) for k, v in canonical_state_dict(sd).items()}
+        kp_q, desc_q, size_q, angle_q, kp_r, desc_r, size_r, angle_r = (t.to(dtype) for t in (kp_q, desc_q, size_q, angle_q, kp_r, desc_r, size_r, angle_r))
     with torch.inference_mode():
         laf_q = laf_from_center_scale_ori(kp_q.unsqueeze(0), size_q[None, :, None, None], angle_q[None, :, None])
         laf_r = laf_from_center_scale_ori(kp_r.unsqueeze(0), size_r[None, :, None, None], angle_r[None, :, None])

@@ -248,18 +248,21 @@ def test_estimate_bucketed_with_overlapped_pose_stage_and_deferred_joins(state_d
     del eng
 
 
-def test_projection_fused_into_the_block_tail_gives_the_bits_of_the_separate_launches(state_dict_np, state_dict_t):
+@pytest.mark.parametrize("products", [3, 2])
+def test_projection_fused_into_the_block_tail_gives_the_bits_of_the_separate_launches(state_dict_np, state_dict_t, products):
     """Round 5: on bulk grids k_ffn128 computes the NEXT block's attention input projection from the rows its epilogue has just produced
     (k_ffn128<0, true, ., 1 / 2>; knob 32).  Same partial products in the same order and the same epilogue expressions as k_qkv<., true, 2>:
     everything downstream -- match descriptors, scores, correspondence indices, poses -- is BITWISE what the separate launches give; the launch
     table shows 17 fused tails + 1 plain one and ONE k_qkv launch (the first block's) instead of 18.  Checked on a full batch (16 x 1024), on a
-    ragged one (work lists; the walking and the one-tile form of the tail), and the full batch against the oracle."""
+    ragged one (work lists; the walking and the one-tile form of the tail), and the full batch against the oracle.  On both block-tail levels
+    (gn_set_ffn_products 3 and 2: k_ffn128<., ., ., 1 / 2, PROD>)."""
     from gisnav_amd.engine import PoseEngine
     _threads()
     rs = np.random.default_rng(3)
     full = [make_pair(8800 + i, n_q=1024, n_r=1024 - 7 * (i % 4)) for i in range(16)]
     rag = [make_pair(8900 + i, n_q=int(rs.integers(60, 1025)), n_r=int(rs.integers(60, 1025))) for i in range(16)]
     eng = PoseEngine(0, max_batch=16, max_kpts=1024, precision=HEADLINE, state_dict=state_dict_np)
+    eng.set_ffn_products(products)
     for label, pairs, forms in (("full", full, (1,)), ("ragged", rag, (2, 3))):
         inp = eng.stage_inputs(pairs)
         for lists in forms:
@@ -281,6 +284,7 @@ def test_projection_fused_into_the_block_tail_gives_the_bits_of_the_separate_lau
             fused_tail = lambda k: k.startswith("k_ffn128") and k.rstrip(">").split(", ")[3] in ("1", "2")      # noqa: E731  (k_ffn128<ABL, COMP, LOOP, QKV, PROD>)
             nf = sum(v for k, v in a[5].items() if fused_tail(k))
             assert nf == 17 and sum(v for k, v in a[5].items() if k.startswith("k_qkv")) == 1, a[5]
+            assert all(k.rstrip(">").split(", ")[4] == str(products) for k in list(a[5]) + list(b[5]) if k.startswith("k_ffn128")), (a[5], b[5])
             assert sum(v for k, v in b[5].items() if k.startswith("k_qkv")) == 18 and not any(fused_tail(k) for k in b[5]), b[5]
             assert np.array_equal(a[2], b[2]) and a[2].max() > 300, (label, lists)
             for p in range(16):
@@ -295,7 +299,7 @@ def test_projection_fused_into_the_block_tail_gives_the_bits_of_the_separate_lau
             ref = [oracle_match(state_dict_t, p) for p in pairs]
             m, t, fam, _ = _match_counted(eng, pairs, ref)
             assert fam["k_ffn128"] and fam["k_attn_pw"] and m == 0 and t > 8000, (m, t, fam)
-            _report("fused_tail_projection_16x1024_margin_built", {"index_mismatches": m, "cpu_matches": t})
+            _report(f"fused_tail_projection_16x1024_margin_built{'' if products == 3 else '_two_products'}", {"index_mismatches": m, "cpu_matches": t})
     del eng
 
 

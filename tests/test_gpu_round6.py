@@ -325,7 +325,8 @@ def test_two_product_block_tail_is_repeatable_and_close_to_the_three_product_for
 def test_every_bulk_context_proves_the_fused_projection_on_its_own_weights(state_dict_np):
     """the projection fused behind k_ffn128 is checked bitwise against the separate k_qkv launches at the first forward call after a
     weight load, on the context's own weights (self / cross form x one-tile / walking form): status 1 on bulk-sized contexts of every weight family
-    tested here, -1 (never selected, never checked) on a small context; the call that triggered the check returns the same results as the next one."""
+    tested here, -1 (never selected, never checked) on a small context; the call that triggered the check returns the same results as the next one.
+    A context set to two products (and one on the automatic level) proves the two-product instantiation too, on its first call."""
     from gisnav_amd.engine import PoseEngine
     small = PoseEngine(0, max_batch=2, max_kpts=512, precision=HEADLINE, state_dict=state_dict_np)
     inp = small.stage_inputs([make_pair(9300 + i, n_q=500, n_r=512) for i in range(2)])
@@ -334,9 +335,10 @@ def test_every_bulk_context_proves_the_fused_projection_on_its_own_weights(state
     assert small.fused_projection_status() == -1
     del small
     pairs = [make_pair(9310 + i, n_q=1024, n_r=1000) for i in range(16)]
-    for name in ("margin_built", "low_margin", "default_init"):
+    for name, products in (("margin_built", 3), ("low_margin", 3), ("default_init", 3), ("margin_built", 2), ("low_margin", "auto")):
         sd, _, th = _family(name)
         eng = PoseEngine(0, max_batch=16, max_kpts=1024, precision=HEADLINE, state_dict=sd, filter_threshold=th)
+        eng.set_ffn_products(products)
         inp = eng.stage_inputs(pairs)
         assert eng.fused_projection_status() == -1
         a = _match(eng, inp)                       # runs the self-check first
