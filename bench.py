@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X PoseNode hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--kpts 1024] [--precision f16x2_bf16_attn]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--kpts 1024] [--precision f16x2_bf16_attn] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,17 +11,25 @@ matched-point gather + DEM lift, PnP-RANSAC + refinement -- over one batch of `-
 contiguous shard of N*batch pairs (weak scaling, no data-path collective); value = pairs all ranks processed / max-over-ranks time.
 Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: it sets up (weights, certificate calibration, staged batches), warms up, times the
+K steps, writes --dump-outputs and prints the line.  Everything marked [full] below takes runs of its own and is measured only
+with --full (the --no-* options still skip single parts of it); without --full those fields are empty (null, [] or absent).
+
 What the line reports, and where each number comes from:
   value / ms_per_step   host clock around K steps, barrier + synchronize on both sides, max over ranks
   end_to_end            value x 80.7 GFLOP (algorithmic work per pair, formula of SURVEY.md:405-408) against the 2.5 PF dense 16-bit MFMA peak
-  roofline              the DOMINANT kernel (largest share of the HIP-event time measured in this run, on the launch stream), by the
+  roofline       [full] the DOMINANT kernel (largest share of the HIP-event time measured in this run, on the launch stream), by the
                         name rocprofv3 prints for it: algorithmic flops per launch / average launch duration, against the same peak
-  kernels               the same for every timed kernel (joins row by row with profiles/*kernel_stats*.csv)
-  traffic               HBM bytes per step from rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md), collected by
+  kernels        [full] the same for every timed kernel (joins row by row with profiles/*kernel_stats*.csv).  Both come from a
+                        single-stream pass of K steps of their own; when the headline itself runs on one stream (--substreams 1, or
+                        batches under 16 pairs) it is that pass, and a plain run reports them too
+  traffic        [full] HBM bytes per step from rocprofv3 PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md), collected by
                         re-running this script under the profiler (N = 1 only; --no-traffic skips it), next to the compulsory bytes
-  extra_configs         further BASELINE configurations timed in the same process (batch-1 f32 = configs[1] as the survey reads it;
+  pcie_inclusive [full] a stream of new pairs from host bytes (--no-stream skips it); the synchronous staging figures are measured in every run
+  extra_configs  [full] further BASELINE configurations timed in the same process (batch-1 f32 = configs[1] as the survey reads it;
                         batch-32 with exact-f32 MFMA GEMMs + bf16 attention = configs[2] without the split-fp16 GEMMs)
-  cpu_baseline          the CPU restatement of the reference on this box's host cores, bounded sample
+  cpu_baseline   [full] the CPU restatement of the reference on this box's host cores, bounded sample
+  multi_gpu.rccl_selfcheck_world1 [full] the world-1 RCCL self-check of an N = 1 run, in a child process
 """
 from __future__ import annotations
 
@@ -678,6 +686,8 @@ def main() -> None:
     ap.add_argument("--share-gpu", action="store_true", help="dry-run aid: every rank uses cuda:0 (with --backend gloo)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step returned (R, t, n_match, n_inliers, "
                                                                       "ok of every pair, all ranks' shards in pair order) as DIR/<name>.npy in float64")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the single-stream per-kernel pass (kernels, roofline), "
+                                                        "HBM traffic, the stream of new pairs, extra_configs, cpu_baseline and the world-1 RCCL self-check")
     args = ap.parse_args()
 
     if args.only_loftr:
@@ -697,7 +707,7 @@ def main() -> None:
         print(f"[bench] --gpus {args.gpus} asked for, but only {torch.cuda.device_count()} GPU(s) are visible on this box", file=sys.stderr)
         sys.exit(2)
     rccl_check = None
-    if args.gpus == 1 and args.backend == "nccl" and not args.debug_variant and not args.no_rccl_check and "WORLD_SIZE" not in os.environ:
+    if args.full and args.gpus == 1 and args.backend == "nccl" and not args.debug_variant and not args.no_rccl_check and "WORLD_SIZE" not in os.environ:
         # (under a launcher -- WORLD_SIZE set, even to 1 -- the run below IS an nccl process group: its broadcast / gathers are the proof, and a
         #  child that inherits the launcher's rendezvous variables was seen to hang on a 1-GPU box)
         try:   # the collectives of the N > 1 path on a world-1 RCCL group: what a 1-GPU lease can prove.  In a child process: RCCL writes a
@@ -767,11 +777,13 @@ def main() -> None:
     nsub = args.substreams if args.substreams > 0 else (2 if args.batch >= 16 else 1)
     # Per-kernel figures (roofline, kernel table) come from a pass with ONE stream: with sub-batch streams the launches of two groups
     # run concurrently and a launch's HIP-event duration stops being that kernel's own time.  `value` is timed afterwards, in its own
-    # K steps, with the sub-batch streams on.
+    # K steps, with the sub-batch streams on; a plain run skips the per-kernel pass unless it is the headline's own (one stream).
     eng.set_substreams(1)
-    elapsed1, _ = timed_steps(eng, inps, out, args.steps, args.warmup, dev, kernel_timing=True)   # (_ = this rank's own seconds)
-    table = eng.kernel_table()
-    eng.set_kernel_timing(0)
+    elapsed1, table = None, []
+    if args.full or nsub == 1:
+        elapsed1, _ = timed_steps(eng, inps, out, args.steps, args.warmup, dev, kernel_timing=True)   # (_ = this rank's own seconds)
+        table = eng.kernel_table()
+        eng.set_kernel_timing(0)
     if nsub > 1:
         eng.set_substreams(nsub, deferred_join=args.deferred_join)
         outs = out
@@ -820,7 +832,7 @@ def main() -> None:
     rec_sha = hashlib.sha256(rec.cpu().numpy().tobytes()).hexdigest()
     per_rank_ms = gdist.gather_records(torch.tensor([[mine / args.steps * 1e3] + [0.0] * 15], dtype=torch.float64, device=dev))[:, 0].cpu().tolist()
     stream = None
-    if not args.no_stream and not args.debug_variant and world == 1:
+    if args.full and not args.no_stream and not args.debug_variant and world == 1:
         from gisnav_amd import wire
         msgs = [[(wire.pack_keypoints(p.kp_q, p.size_q, p.angle_q, p.desc_q), wire.pack_keypoints(p.kp_r, p.size_r, p.angle_r, p.desc_r), p.dem)
                  for p in ps] for ps in pair_sets]
@@ -829,7 +841,7 @@ def main() -> None:
     torch.cuda.empty_cache()
 
     extras = []
-    if not args.no_extras and not args.debug_variant and world == 1:   # per-GPU side configurations: reported by the N = 1 line; an N > 1 run times the sharded headline only
+    if args.full and not args.no_extras and not args.debug_variant and world == 1:   # per-GPU side configurations: reported by the N = 1 line; an N > 1 run times the sharded headline only
         extras.append(run_extra(local_rank, sd, "BASELINE configs[1] as SURVEY.md reads it: batch-1 640x480 pair, f32 everywhere (exact-f32 MFMA GEMMs and attention)",
                                 1, args.kpts, "f32", 30, 5, dev))
         extras.append(run_extra(local_rank, sd, "BASELINE configs[2] with exact-f32 MFMA projections/FFN (no fp16 split) + bf16 MFMA attention (a tolerance mode: no certificate)",
@@ -897,8 +909,8 @@ def main() -> None:
             fam.setdefault(r_["name"].split("<")[0], []).append(r_)
         dom_family = max(fam.values(), key=lambda ms: sum(m["share_of_timed_kernel_time"] for m in ms)) if fam else []
         dom = max(dom_family, key=lambda m: m["share_of_timed_kernel_time"]) if dom_family else None
-        traffic, traffic_err = (None, "skipped")
-        if not args.no_traffic and world == 1:
+        traffic, traffic_err = (None, "skipped" if args.full else "plain run (measured with --full)")
+        if args.full and not args.no_traffic and world == 1:
             traffic, traffic_err = measure_traffic(args, certify_eps=(cert_main or {}).get("profile_eps_arg", ""))
         comp_mb = compulsory_mb_per_pair(args.kpts, args.kpts) * args.batch + 47.5   # + the f32 weights once per step (cache-resident in practice)
         line = {
@@ -929,6 +941,7 @@ def main() -> None:
             "data": "synthetic",
             "inputs_resident": True,
             "debug_variant": list(args.debug_variant),
+            "full": bool(args.full),
             "config": {
                 "workload": f"BASELINE {'configs[1] (batch-1' if args.batch == 1 else 'configs[2]/[3] (batch-' + str(args.batch)} per GPU): "
                             f"640x480 pairs, {args.kpts} SIFT kpts/side, "
@@ -940,7 +953,7 @@ def main() -> None:
                 "parallelism": f"pair-sharded x{world} (no data-path collective)",
                 "pose_stage_overlap": bool(args.overlap),
                 "sub_batch_streams": nsub,
-                "single_stream_ms_per_step": round(elapsed1 / args.steps * 1e3, 4),
+                "single_stream_ms_per_step": round(elapsed1 / args.steps * 1e3, 4) if elapsed1 is not None else None,
                 "weights": "seeded synthetic, kornia sift_lightglue state-dict layout",
                 "same_staged_batch_every_step": nres == 1,
                 "distinct_resident_batches_rotated": nres,
@@ -1018,7 +1031,7 @@ def main() -> None:
                            "per_kernel": traffic["kernels"] if traffic else None,
                            "method": traffic["method"] if traffic else f"not measured: {traffic_err}"}
         line["extra_configs"] = extras
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(sd, args.kpts)
         try:   # anything libraries left in the C-level stdout buffer (RCCL's banner) goes out BEFORE the line: the JSON line is the last line
             import ctypes

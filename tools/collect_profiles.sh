@@ -1,16 +1,16 @@
 #!/bin/bash
 # Collect the judged artefacts of one round on the GPU box (run through gpurun):
 #   bash tools/collect_profiles.sh <tag>        e.g. r02d
-# -> gpurun_out/<tag>_bench_n1.json          the default `python bench.py` line (HIP-event per-kernel table, live PMC traffic, extra_configs, cpu_baseline)
-#    gpurun_out/<tag>_kernel_stats.csv       rocprofv3 --kernel-trace --stats summary of `bench.py --steps 5 --warmup 2` (same workload)
-#    gpurun_out/<tag>_pmc_mfma_busy.json     SQ_VALU_MFMA_BUSY_CYCLES / (128 x GRBM_GUI_ACTIVE) per kernel (own pass, --kernel-trace only)
+# -> $O/<tag>_bench_n1.json          the `python bench.py --full` line (HIP-event per-kernel table, live PMC traffic, extra_configs, cpu_baseline)
+#    $O/<tag>_kernel_stats.csv       rocprofv3 --kernel-trace --stats summary of `bench.py --steps 5 --warmup 2` (same workload)
+#    $O/<tag>_pmc_mfma_busy.json     SQ_VALU_MFMA_BUSY_CYCLES / (128 x GRBM_GUI_ACTIVE) per kernel (own pass, --kernel-trace only)
 # (copy them into profiles/ afterwards).
 TAG=${1:-rXX}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py 2> $O/${TAG}_bench.err | grep '^{"metric' | tail -1 > $O/${TAG}_bench_n1.json
+python $R/bench.py --full 2> $O/${TAG}_bench.err | grep '^{"metric' | tail -1 > $O/${TAG}_bench_n1.json
 # the profiling passes run the same certified configuration with the eps (both block-tail levels' and the level the run settled on) the full run calibrated (--certify-eps: no calibration pass, no self-check launches among the steps)
 EPS=$(python -c "import json;print(json.load(open('$O/${TAG}_bench_n1.json'))['precision_guarantee']['certificate']['profile_eps_arg'])")
 rm -rf $O/${TAG}_prof && rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-traffic --no-extras --no-stream --substreams 1 --certify-eps $EPS > /dev/null 2>&1
