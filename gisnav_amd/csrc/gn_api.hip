@@ -121,7 +121,7 @@ struct gn_ctx {
   float* attn_part = nullptr; unsigned int* attn_tickets = nullptr;   // split-keys attention of small batches: <= 256 partial results, their tickets
   int attn_split = 1;      // developer knob 23: largest number of key ranges the attention of a small batch is split into (default 1 = never: the
                            // split changes the rounding of the probabilities, and results would then depend on batch size / padding / sub-streams)
-  int attn_variant = 4;    // 0: k_attn_bf16 (f32 inputs, in-kernel conversion), otherwise k_attn_bf16_v5 (4; 41 / 42 = timing ablations)
+  int attn_variant = 4;    // developer knob 1: 0 = k_attn_bf16 (f32 inputs, in-kernel conversion), otherwise the k_attn_bf16_v5 family (4 = automatic choice)
   int stop_after = 0;      // developer knob: return from run_matcher after this many GEMM/attention launches
   int launch_count = 0;
   int no_planes = 0;       // developer knob: ignore the pre-split weight planes (f32x3 splits B on the fly)
@@ -569,7 +569,7 @@ inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? c->cert_eps_lv
 
 bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
   if (skinny_applies(c, T, np) && !(c->skinny & 8) && c->ffn_fused == 3 && c->ffn_compose && tail_folds_out_proj(c, blk, T) && blk.wfc && blk.b1c && !blk.comp_dirty && blk.ffn3.wfn &&
-      c->h && c->ctx_p && gn::g_ffn_ablate == 0 && gn::g_ffn_shape == 0) {
+      c->h && c->ctx_p && gn::g_ffn_stamps == 0 && gn::g_ffn_shape == 0) {
     // small grid: the weight stream split across CUs -- two launches (gn_skinny.hip)
     SkinnyTailArgs a;
     a.xp = c->x_p; a.cp = c->ctx_p; a.w1 = blk.wfc; a.w1_scale = blk.wfc_scale; a.b1 = blk.b1c; a.h = c->h; a.ln_g = blk.ln_g; a.ln_b = blk.ln_b;
@@ -588,12 +588,12 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     const bool comp = fold && c->ffn_compose && blk.wfc && blk.b1c && !blk.comp_dirty;
     if (comp) { f.composed = 1; f.w1s = blk.wfc; f.w1_scale = blk.wfc_scale; f.b1 = blk.b1c; }
     f.ovf = c->guard ? c->ovf : nullptr;
-    f.tiles = (c->use_lists && c->lists && !(gn::g_ffn_ablate & 8)) ? c->lists : nullptr;
+    f.tiles = (c->use_lists && c->lists && gn::g_ffn_stamps == 0) ? c->lists : nullptr;
     f.walk = c->use_lists == 2 || (c->use_lists == 1 && tail_should_walk(c));
     f.ncu = c->ncu;
     f.composed = comp ? 1 : 0;
     f.products = (comp && ffn_level(c) == 2) ? 2 : 3;
-    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_ablate == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
+    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_stamps == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
                           c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
       f.qkv = next_cross ? 2 : 1;
@@ -603,7 +603,7 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
       f.npad = np;
     }
     if (c->use_lists) { f.nvalid = c->nvalid; f.npad = c->npad_run; }
-    f.dbg_ts = (gn::g_ffn_ablate & 8) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
+    f.dbg_ts = gn::g_ffn_stamps ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
     ++c->launch_count;
     if (c->stop_after && c->launch_count > c->stop_after) return false;
     const bool rec = c->ktiming && c->kused < c->kflops.size();
@@ -652,7 +652,7 @@ int run_matcher(gn_ctx* c, int B, int kpt_format,
   const int np = c->npad_run, T = B * 2 * np, BS = B * 2;
   const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
   gn::g_attn_variant = c->attn_variant;
-  gn::g_attn_stamps = ((c->attn_variant == 73 || c->attn_variant >= 1000) && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;
+  gn::g_attn_stamps = (c->attn_variant == 73 && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;
   const int vt_perm = (bf16v2 ? 1 : 0) | (c->dbg_vt_skip ? 2 : 0);   // k_attn_bf16_v5 reads V^T with keys permuted inside 16-groups   // k_attn_bf16_v4 reads permuted V^T
   const bool attn_planes = c->planes_mode && (bf16v2 || c->attn_f16 == 2);   // k_attn_bf16_v5 / k_attn_f16x2 write the hm16 rows themselves
   c->launch_count = 0;
@@ -863,7 +863,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
   if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
-      !c->qkv_fused || !c->rot4 || !c->lists || !c->msg_p || !c->h_p || c->feature < 0 || gn::g_ffn_ablate != 0 || gn::g_ffn_shape != 0) return GN_OK;
+      !c->qkv_fused || !c->rot4 || !c->lists || !c->msg_p || !c->h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || gn::g_ffn_shape != 0) return GN_OK;
   int B = (256 * 128 + 2 * np - 1) / (2 * np);          // the smallest batch whose grid selects k_ffn128 (>= 256 tiles of 128 tokens)
   if (B > c->max_batch) return GN_OK;                   // this context never runs the bulk kernels
   const int T = B * 2 * np;
@@ -2517,7 +2517,7 @@ int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale, c
     launch_pack_attn_bf16(a, ctx->qkb, ctx->vtb, (hipStream_t)stream);
     a.qb = ctx->qkb; a.kb = ctx->qkb + kDim; a.ldqb = a.ldkb = 2 * kDim; a.vt = ctx->vtb;
     gn::g_attn_variant = ctx->attn_variant;
-    gn::g_attn_stamps = ((ctx->attn_variant == 73 || ctx->attn_variant >= 1000) && ctx->sim) ? reinterpret_cast<long long*>(ctx->sim) : nullptr;
+    gn::g_attn_stamps = (ctx->attn_variant == 73 && ctx->sim) ? reinterpret_cast<long long*>(ctx->sim) : nullptr;
     attn_split(ctx, a);
     launch_attention_bf16_v2(a, (hipStream_t)stream);
   } else {
@@ -2534,9 +2534,22 @@ int gn_sp_set_arithmetic(gn_ctx* ctx, int mode) {
   return GN_OK;
 }
 
+// knob values of timing-only ablations and rejected experiments that have been retired: refused, so that a stale script fails
+// instead of timing the default kernel under their label
+static bool retired_variant(int which, int value) {
+  switch (which) {
+    case 0: return (value >= 51 && value <= 57) || (value >= 61 && value <= 67);
+    case 1: return (value >= 41 && value <= 46) || value == 48 || (value >= 51 && value <= 55) || value == 57 || value == 58 ||
+                   value == 71 || value == 72 || value >= 1000;
+    case 8: return value != 0 && value != 1;
+    case 12: return value != 0 && value != 8 && value != 136;
+    default: return false;
+  }
+}
+
 int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
-  if (!ctx) return GN_ERR_ARG;
-  if ((which == 1 && (value == 73 || value >= 1000)) || (which == 12 && (value & 8)) || (which == 15 && value) || (which == 16 && !value) || (which == 17 && value) || (which == 20 && value)) {   // these developer paths use the similarity buffer
+  if (!ctx || retired_variant(which, value)) return GN_ERR_ARG;
+  if ((which == 1 && value == 73) || (which == 12 && (value & 8)) || (which == 15 && value) || (which == 16 && !value) || (which == 17 && value) || (which == 20 && value)) {   // these developer paths use the similarity buffer
     GN_HIP(hipSetDevice(ctx->device));
     const int rc = ensure_sim(ctx); if (rc != GN_OK) return rc;
   }
@@ -2552,13 +2565,12 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 11) ctx->x_planes_only = value;
   else if (which == 8) gn::g_p2_wide = value;
   else if (which == 9) ctx->dbg_vt_skip = value;
-  else if (which == 12) gn::g_ffn_ablate = value;
+  else if (which == 12) gn::g_ffn_stamps = value;
   else if (which == 13) ctx->ffn_fold = value;
   else if (which == 14) gn::g_ffn_shape = value;
   else if (which == 15) ctx->pnp_stamps = value;
   else if (which == 16) ctx->head_fused = value;
   else if (which == 17) ctx->head_stamps = value;
-  else if (which == 18) gn::g_head_ablate = value;
   else if (which == 19) ctx->qkv_fused = value;
   else if (which == 20) ctx->qkv_stamps = value;
   else if (which == 21) ctx->sp_split = value;

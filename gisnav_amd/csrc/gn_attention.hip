@@ -491,11 +491,14 @@ template <typename T> __device__ __forceinline__ T ld_dev(const T* p) { return _
 // probabilities above 65504 become inf, so the optimistic reference falls back to the exact running maximum (whose lazy update keeps every
 // probability <= 2^8) as soon as a score exceeds the reference by ~16 in log2 units (bf16: ~100); probabilities below 2^-24 flush to zero (they
 // are below 2^-16 of the row's largest even under the lazy maximum), subnormals are honoured by the matrix pipe.
-template <int ABL, int NW, int ND = 3, int NQ = 1, bool SPLIT = false, bool F16 = false>   // NW waves share one K / V^T tile stream; ND = ring depth (3 or 4 tiles; 4 measured no faster);
-                                                     // NQ = query tiles of 32 per wave (2: every K / V^T fragment read from LDS feeds two MFMAs)
-__global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs a) {   // NQ = 1: two waves per SIMD (two workgroups per CU at NW = 4): at most 256 registers; NQ = 2: one wave per SIMD with the whole register file
+// ABL = 128: the maximum searched in every tile (the exact path a workgroup otherwise falls back to).  NW waves share one K / V^T tile stream,
+// ND = ring depth in tiles, NQ = query tiles of 32 per wave: only NW = 4, ND = 3, NQ = 1 is built (an eight-wave form, 4-deep rings and two query
+// tiles per wave were measured slower).  Two workgroups per CU: at most 256 registers per wave.
+template <int ABL, int NW, int ND = 3, int NQ = 1, bool SPLIT = false, bool F16 = false>
+__global__ __launch_bounds__(64 * NW, 2) void k_attn16_v5(AttnArgs a) {
+  static_assert((ABL == 0 || ABL == 128) && NW == 4 && ND == 3 && NQ == 1, "k_attn16_v5: the built forms only");
   constexpr int IPW = 8 / NW;                 // LDS-DMA instructions per wave per 8 KB tile
-  __shared__ __attribute__((aligned(1024))) unsigned short smem[2 * ND * kRing + 8 + ((ABL & 512) ? 24576 : 0)];   // ABL 512 (experiment): +48 KB so that only one workgroup fits a CU   // K ring [ND][64 keys][64], V^T ring [ND][64 dims][64 keys], overflow flag
+  __shared__ __attribute__((aligned(1024))) unsigned short smem[2 * ND * kRing + 8];   // K ring [ND][64 keys][64], V^T ring [ND][64 dims][64 keys], overflow flag
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, ql = lane & 31;
@@ -552,13 +555,9 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
     const int c = (lane & 7) ^ ((r ^ (r >> 3)) & 7);
     ksrc[j] = a.kb + ((size_t)kvs * a.npad + key_off + r) * a.ldkb + h * 64 + c * 8;
     vsrc[j] = a.vt + (((size_t)kvs * kHeads + h) * kHeadDim + r) * a.npad + key_off + c * 8;
-    if (ABL & 2) {   // timing probe: the same bytes fetched as contiguous 8 KB tiles (wrong data)
-      ksrc[j] = a.kb + ((size_t)kvs * kHeads + h) * a.npad * 64 + (IPW * wave + j) * 512 + lane * 8;
-      vsrc[j] = a.vt + ((size_t)kvs * kHeads + h) * a.npad * 64 + (IPW * wave + j) * 512 + lane * 8;
-    }
   }
-  const size_t kstep = (ABL & 2) ? (size_t)KT * 64 : (size_t)KT * a.ldkb;
-  const int vstep = (ABL & 2) ? KT * 64 : KT;
+  const size_t kstep = (size_t)KT * a.ldkb;
+  const int vstep = KT;
 #define GN_DMA_K(stage, t)                                                                                              \
   _Pragma("unroll") for (int j = 0; j < IPW; ++j)                                                                       \
     __builtin_amdgcn_global_load_lds((gptr_t)(ksrc[j] + (size_t)(t) * kstep),                                           \
@@ -606,7 +605,7 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
 #pragma unroll 1
   for (int attempt = 0; attempt < 2; ++attempt) {
   const bool safe = attempt != 0 || (ABL & 128);
-  int s0 = 0, s1 = 1, s2 = 2, s3 = 3;  // ring stages of tiles t, t+1, t+2 (, t+3) modulo ND
+  int s0 = 0, s1 = 1, s2 = 2;  // ring stages of tiles t, t+1, t+2 modulo ND
   if (ntiles > 0) {
     GN_DMA_K(0, 0);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -614,33 +613,19 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
     GN_DMA_V(0, 0);
     if (ntiles > 2) GN_DMA_K(2, 2);
     if (ntiles > 1) GN_DMA_V(1, 1);
-    if (ND == 4) { if (ntiles > 3) GN_DMA_K(3, 3); if (ntiles > 2) GN_DMA_V(2, 2); }
     qk_tile(sa, 0);
   }
 
-  // FAST: a tile in the steady state of the optimistic pass -- both rings are refilled unconditionally, no key of the tile is masked and
-  // the reference is not searched: the body has no scalar branch in it (the generic body tests six conditions per tile)
-  auto tile = [&](f32x16 (&ST)[NQ][2], f32x16 (&SN)[NQ][2], int t, auto fast_tag) __attribute__((always_inline)) {
-    constexpr bool FAST = decltype(fast_tag)::value;
-    // K(t+1) and V^T(t) have landed once everything but the ND - 2 newest DMA groups ({K(t+2), V^T(t+1)}, ...) is complete;
+  auto tile = [&](f32x16 (&ST)[NQ][2], f32x16 (&SN)[NQ][2], int t) __attribute__((always_inline)) {
+    // K(t+1) and V^T(t) have landed once everything but the newest DMA group ({K(t+2), V^T(t+1)}: 2 x IPW = 4 instructions) is complete;
     // lgkmcnt(0): this wave's fragment reads of the stages refilled below (issued just in front of the barrier, consumed by MFMAs behind
     // it) have RETURNED before any wave may start the refill -- without it an LDS-DMA that hits in cache can overtake such a read
     // the barrier publishes all waves' shares and proves the stages refilled below are no longer being read
-    constexpr int G = 2 * (8 / NW);                       // DMA instructions per wave per group (K tile + V^T tile)
-    if (ABL & 32) {
-      // timing probe: no workgroup barrier per tile (races on the ring: wrong data)
-    } else if (FAST || t + ND - 1 < ntiles) {
-      if (G * (ND - 2) == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else if (G * (ND - 2) == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-    if (!(ABL & 1)) {
-      if (FAST || t + ND < ntiles) GN_DMA_K(s0, t + ND);                          // K(t) was consumed one iteration ago
-      if (FAST || t + ND - 1 < ntiles) GN_DMA_V(ND == 4 ? s3 : s2, t + ND - 1);   // the stage V^T(t-1) was read from
-    }
-    if (!FAST && t * KT + KT > nkv) {
+    if (t + ND - 1 < ntiles) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (t + ND < ntiles) GN_DMA_K(s0, t + ND);              // K(t) was consumed one iteration ago
+    if (t + ND - 1 < ntiles) GN_DMA_V(s2, t + ND - 1);      // the stage V^T(t-1) was read from
+    if (t * KT + KT > nkv) {
 #pragma unroll
       for (int qi = 0; qi < NQ; ++qi)
 #pragma unroll
@@ -651,12 +636,11 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
             if (key >= nkv) ST[qi][kt][r] = -INFINITY;
           }
     }
-    if (!FAST && (safe || t < kSearchTiles)) {   // wave-uniform
+    if (safe || t < kSearchTiles) {   // wave-uniform
       float mloc[NQ];
       bool grow = false;
 #pragma unroll
       for (int qi = 0; qi < NQ; ++qi) {
-        if (ABL & 64) { mloc[qi] = 0.f; if (t == 0) m_run[qi] = 0.f; continue; }   // timing probe: no maximum search (wrong for large scores)
         float m = fmaxf(ST[qi][0][0], ST[qi][1][0]);
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
@@ -683,9 +667,7 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
     for (int qi = 0; qi < NQ; ++qi) mneg[qi] = -m_run[qi] * kLog2e;
 
     // scores of the next tile on the matrix pipe while this tile's probabilities are computed on the VALU
-    if (ABL & 4) __builtin_amdgcn_s_setprio(1);
     qk_tile(SN, s1);
-    if (ABL & 4) __builtin_amdgcn_s_setprio(0);
 
     bf16x8 pf[NQ][2][2];
 #pragma unroll
@@ -697,26 +679,17 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
           u32x4 pw;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            f32x2 x2;
-            if (ABL & 8) {   // developer variant 46: one v_pk_fma_f32 for the pair -- measured 5 % SLOWER (114.3 vs 109.1 us on one box)
-              x2 = __builtin_elementwise_fma((f32x2){ST[qi][kt][8 * u + 2 * e], ST[qi][kt][8 * u + 2 * e + 1]}, (f32x2){kLog2e, kLog2e}, (f32x2){mneg[qi], mneg[qi]});
-            } else {
-              x2[0] = __builtin_fmaf(ST[qi][kt][8 * u + 2 * e], kLog2e, mneg[qi]);
-              x2[1] = __builtin_fmaf(ST[qi][kt][8 * u + 2 * e + 1], kLog2e, mneg[qi]);
-            }
+            f32x2 x2;   // (one v_pk_fma_f32 for the pair measured 5 % slower)
+            x2[0] = __builtin_fmaf(ST[qi][kt][8 * u + 2 * e], kLog2e, mneg[qi]);
+            x2[1] = __builtin_fmaf(ST[qi][kt][8 * u + 2 * e + 1], kLog2e, mneg[qi]);
             f32x2 p;
-            if (ABL & 16) {   // timing probe: no transcendental (wrong data)
-              p = x2;
-            } else {
-              p[0] = __builtin_amdgcn_exp2f(x2[0]);
-              p[1] = __builtin_amdgcn_exp2f(x2[1]);
-            }
+            p[0] = __builtin_amdgcn_exp2f(x2[0]);
+            p[1] = __builtin_amdgcn_exp2f(x2[1]);
             pw[e] = pack16<F16>(p[0], p[1]);   // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE)
           }
           pf[qi][kt][u] = __builtin_bit_cast(bf16x8, pw);
         }
     const unsigned short* Vs = smem + (ND + s0) * kRing;
-    if (ABL & 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -730,28 +703,21 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
           for (int qi = 0; qi < NQ; ++qi) o[qi][d] = mfma16<F16>(vf, pf[qi][kt][u], o[qi][d]);
         }
       }
-    if (ABL & 4) __builtin_amdgcn_s_setprio(0);
-    const int s_ = s0; s0 = s1; s1 = s2;
-    if (ND == 4) { s2 = s3; s3 = s_; } else { s2 = s_; }
+    const int s_ = s0; s0 = s1; s1 = s2; s2 = s_;
   };
 
   {
     int t = 0;
     if (!safe) {
       for (; t < kSearchTiles && t < ntiles; t += 2) {
-        tile(sa, sb, t, std::false_type{});
-        if (t + 1 < ntiles) tile(sb, sa, t + 1, std::false_type{});
-      }
-#pragma unroll 1
-      for (; (ABL & 256) && t + 1 + ND < ntiles; t += 2) {   // tiles t and t + 1 are both in the steady state
-        tile(sa, sb, t, std::true_type{});
-        tile(sb, sa, t + 1, std::true_type{});
+        tile(sa, sb, t);
+        if (t + 1 < ntiles) tile(sb, sa, t + 1);
       }
     }
 #pragma unroll 1
     for (; t < ntiles; t += 2) {
-      tile(sa, sb, t, std::false_type{});
-      if (t + 1 < ntiles) tile(sb, sa, t + 1, std::false_type{});
+      tile(sa, sb, t);
+      if (t + 1 < ntiles) tile(sb, sa, t + 1);
     }
   }
   if (safe) break;
@@ -773,7 +739,6 @@ __global__ __launch_bounds__(64 * NW, NQ == 1 ? 2 : 1) void k_attn16_v5(AttnArgs
 #undef GN_DMA_V
 
   if (SPLIT) {
-    static_assert(!SPLIT || NQ == 1, "split keys: one query tile per wave");
     // partial result of this wave: [34][64] floats = registers o[0][0..15], o[1][0..15], reference, denominator of lane l at [.][l]
     const int S = a.nsplit;
     const size_t entry = (((size_t)bs * kHeads + h) * nqb + qblk) * S;
@@ -1080,14 +1045,14 @@ void launch_pack_attn_bf16(const AttnArgs& a, uint16_t* qkb, uint16_t* vtb, hipS
                      qkb, qkb + kDim, 2 * kDim, vtb, ntok, a.npad, a.half_fmt);
 }
 thread_local long long* g_attn_stamps = nullptr;
-thread_local int g_attn_variant = 4;  // developer knob: 4 = k_attn_bf16_v5 (4 waves per block, default), 48 = 8 waves per block, 43 = 4-deep rings, 41 / 42 = timing-only ablations
+thread_local int g_attn_variant = 4;  // developer knob 1 (include/gisnav_amd.h): 4 = the automatic choice below
 void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s) {
   // fp16 mode, grids of at least one 256-query workgroup per CU: k_attn_pw (one wave per SIMD, pinned instruction stream; 31 vs 36 us at 8 pairs x
   // 1024 keypoints, 112 vs 125 us at 32, 224 vs 244 us at 64; below that k_attn16_v5's two workgroups per CU and its key splits win: 27 vs 24 us at 4
-  // pairs).  Knob 1: 4 = this choice, 5 = k_attn16_v5 always, 70 = k_attn_pw whenever npad % 256 == 0, 71.. / 1000.. = its timing variants.
+  // pairs).  Knob 1: 4 = this choice, 5 = k_attn16_v5 always, 70 = k_attn_pw whenever npad % 256 == 0, 73 = the same with phase stamps.
   const bool pw_auto = g_attn_variant == 4 && a.half_fmt && a.npad % 256 == 0 && (long long)(a.npad / 256) * kHeads * a.BS >= 256;
-  if ((pw_auto || (g_attn_variant >= 70 && g_attn_variant <= 73) || g_attn_variant >= 1000) && !(a.nsplit > 1 && a.part != nullptr) &&
-      launch_attention_pw(a, pw_auto ? 0 : g_attn_variant >= 1000 ? g_attn_variant - 900 : g_attn_variant - 70, s)) return;
+  if ((pw_auto || g_attn_variant == 70 || g_attn_variant == 73) && !(a.nsplit > 1 && a.part != nullptr) &&
+      launch_attention_pw(a, g_attn_variant == 73, s)) return;
   // ONE pair (k_attn16_v5's grid leaves three quarters of the CUs idle; measured 14.4 vs 21.1 us per launch at 1024 keypoints; at two pairs the
   // two kernels tie): the four waves of a workgroup split the KEYS of 32 queries (k_attn_ks).  The choice depends on the number of pairs only,
   // never on the padded length: gn_set_active_kpts must not change a result bit (test_active_kpts_padding_does_not_change_results).
@@ -1121,36 +1086,13 @@ void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s) {
     else { hipLaunchKernelGGL((k_attn16_v5<128, 4, 3, 1, false, true>), dim3(a.npad / 128, kHeads, a.BS), dim3(256), 0, s, a); g_last_kernel = "k_attn16_v5<128, 4, 3, 1, false, true>"; }
     return;
   }
-  if (g_attn_variant == 48 && a.npad % 256 == 0) {   // experiment: 8 waves share each K / V^T tile (half the L2 -> LDS traffic per query); measured 6 % SLOWER
-    dim3 grid(a.npad / 256, kHeads, a.BS), block(512);
-    switch (g_attn_variant) {
-      default: hipLaunchKernelGGL((k_attn16_v5<0, 8>), grid, block, 0, s, a); break;
-    }
-    return;
-  }
   if (a.nsplit > 1 && a.part != nullptr && a.tickets != nullptr && (g_attn_variant == 4 || g_attn_variant == 59)) {
     hipLaunchKernelGGL((k_attn16_v5<0, 4, 3, 1, true>), dim3(a.npad / 128 * a.nsplit, kHeads, a.BS), dim3(256), 0, s, a);
     g_last_kernel = "k_attn16_v5<0, 4, 3, 1, true, false>";
     return;
   }
   dim3 grid(a.npad / 128, kHeads, a.BS), block(256);
-  switch (g_attn_variant) {
-    case 43: hipLaunchKernelGGL((k_attn16_v5<0, 4, 4>), grid, block, 0, s, a); break;  // 4-deep rings
-    case 41: hipLaunchKernelGGL((k_attn16_v5<1, 4>), grid, block, 0, s, a); break;   // timing-only ablations
-    case 42: hipLaunchKernelGGL((k_attn16_v5<2, 4>), grid, block, 0, s, a); break;
-    case 44: hipLaunchKernelGGL((k_attn16_v5<4, 4>), grid, block, 0, s, a); break;
-    case 46: hipLaunchKernelGGL((k_attn16_v5<8, 4>), grid, block, 0, s, a); break;    // experiment: packed fma in front of the exponentials (5 % slower)
-    case 51: hipLaunchKernelGGL((k_attn16_v5<16, 4>), grid, block, 0, s, a); break;    // timing probes (wrong results): no exponentials
-    case 52: hipLaunchKernelGGL((k_attn16_v5<32, 4>), grid, block, 0, s, a); break;    //   no per-tile barrier
-    case 53: hipLaunchKernelGGL((k_attn16_v5<64, 4>), grid, block, 0, s, a); break;    //   no maximum search
-    case 54: hipLaunchKernelGGL((k_attn16_v5<112, 4>), grid, block, 0, s, a); break;   //   none of the three
-    case 55: hipLaunchKernelGGL((k_attn16_v5<33, 4>), grid, block, 0, s, a); break;    //   no barrier, no DMA
-    case 58: hipLaunchKernelGGL((k_attn16_v5<512, 4>), grid, block, 0, s, a); break;   // experiment: one workgroup (one wave per SIMD) per CU
-    case 57: hipLaunchKernelGGL((k_attn16_v5<256, 4>), grid, block, 0, s, a); break;   // steady-state tiles through a branch-free body in a loop of their own: <= 1 % faster, not the default (it is what exposed the ring race fixed by lgkmcnt(0) in front of the barriers)
-    case 56: hipLaunchKernelGGL((k_attn16_v5<128, 4>), grid, block, 0, s, a); break;   // the maximum searched in every tile (the exact path a workgroup falls back to)
-    case 45: if (a.npad % 256 == 0) { hipLaunchKernelGGL((k_attn16_v5<0, 4, 3, 2>), dim3(a.npad / 256, kHeads, a.BS), block, 0, s, a); break; }   // experiment: two query tiles per wave (every K / V^T fragment feeds two MFMAs, one wave per SIMD): bit-identical output, 27 % SLOWER (144 vs 113 us)
-             hipLaunchKernelGGL((k_attn16_v5<0, 4>), grid, block, 0, s, a); break;   // experiment: s_setprio(1) around the MFMA clusters (measured 3 % SLOWER: 107 vs 104 us)
-    default: hipLaunchKernelGGL((k_attn16_v5<0, 4>), grid, block, 0, s, a); break;
-  }
+  if (g_attn_variant == 56) hipLaunchKernelGGL((k_attn16_v5<128, 4>), grid, block, 0, s, a);   // the maximum searched in every tile (the exact path a workgroup falls back to)
+  else hipLaunchKernelGGL((k_attn16_v5<0, 4>), grid, block, 0, s, a);
 }
 }  // namespace gn

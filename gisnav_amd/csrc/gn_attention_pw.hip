@@ -50,9 +50,7 @@ template <bool F16> __device__ __forceinline__ void mfma_v(f32x16& s, const bf16
   else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(s) : "v"(x), "v"(y));
 }
 
-// ABL (timing only, wrong results): 1 no exponentials, 2 no LDS-DMA in the loop, 4 no barrier in the loop, 16 no maximum search, 32 no probability steps,
-// 64 no score MFMAs, 256 no fragment reads, 524288 the rescale test without its branch; 8 = s_memtime stamps into a.part (results stay valid).
-// (Removing the V^T P^T MFMAs is not a usable probe: the probabilities become dead code and the compiler deletes their steps.)
+// ABL = 8: s_memtime stamps per phase into a.part (results stay valid; tools/attn_pw_ab.py); 0 otherwise
 template <bool F16, int ABL>
 __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   constexpr int NDK = 4, NDV = 3, NW = 4, NQ = 2, IPW = 8 / NW;
@@ -186,8 +184,7 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   };
   // lazy maximum: keep the stale reference unless some query's maximum grew by more than 2^8 (probabilities stay <= 256)
   auto rescale = [&]() __attribute__((always_inline)) {
-    if (ABL & 524288) { asm volatile("" ::"v"(grow ? 1 : 0)); }     // timing: the test without the branch
-    else if (__builtin_amdgcn_ballot_w64(grow) != 0) {
+    if (__builtin_amdgcn_ballot_w64(grow) != 0) {
 #pragma unroll
       for (int qi = 0; qi < NQ; ++qi) {
         const unsigned mu = __float_as_uint(mloc[qi]);
@@ -213,7 +210,7 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
       for (int e = 4 * st; e < 4 * st + 4; ++e) xe[e] = __builtin_fmaf(S[qi][8 * u + e], kLog2e, mneg[qi]);
     } else if (st < 4) {
 #pragma unroll
-      for (int e = 4 * (st - 2); e < 4 * (st - 2) + 4; ++e) xe[e] = (ABL & 1) ? xe[e] : __builtin_amdgcn_exp2f(xe[e]);
+      for (int e = 4 * (st - 2); e < 4 * (st - 2) + 4; ++e) xe[e] = __builtin_amdgcn_exp2f(xe[e]);
     } else {
       u32x4 pw;
 #pragma unroll
@@ -229,7 +226,6 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   stamp(1);
 
   bf16x8 kf[3];     // K fragments in flight: the one being multiplied and two prefetched
-  if (ABL & (32 | 256)) { kf[0] = kf[1] = kf[2] = ones; pf[0][0] = pf[0][1] = pf[1][0] = pf[1][1] = ones; }
   if (ntiles > 0) {
     // scores of sub-tile 0 (not pipelined: once per workgroup)
 #pragma unroll
@@ -257,18 +253,17 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   auto subtile = [&](const f32x16 (&SC)[NQ], f32x16 (&SN)[NQ], unsigned kst, int ktn, unsigned kst2, int kt2, unsigned vst, int kt, int next_key0,
                      auto mask, bool live) __attribute__((always_inline)) {
     bf16x8 vf[2][2];
-    if (ABL & 256) vf[0][0] = vf[0][1] = vf[1][0] = vf[1][1] = ones;
     // ---- slots 0..7: scores of the next sub-tile
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
 #pragma unroll
       for (int qi = 0; qi < NQ; ++qi) {
         const int m = 2 * c + qi;
-        if (!(ABL & 64)) { if (c == 0) mfma_v0<F16>(SN[qi], kf[c % 3], qf[qi][c]); else mfma_v<F16>(SN[qi], kf[c % 3], qf[qi][c]); }
+        if (c == 0) mfma_v0<F16>(SN[qi], kf[c % 3], qf[qi][c]); else mfma_v<F16>(SN[qi], kf[c % 3], qf[qi][c]);
         // steps [10 m / 8, 10 (m + 1) / 8) of the 10 steps of fragments (qi = 0, u = 0), (1, 0)
 #pragma unroll
-        for (int st = (10 * m) / 8; st < (10 * (m + 1)) / 8; ++st) if (!(ABL & 32)) e_step(SC, st / 5, st % 5);
-        if (qi == 0 && !(ABL & 256)) {   // fragment reads behind the first MFMA of the pair (in front of it, the wait for kf[c] would also wait for them)
+        for (int st = (10 * m) / 8; st < (10 * (m + 1)) / 8; ++st) e_step(SC, st / 5, st % 5);
+        if (qi == 0) {   // fragment reads behind the first MFMA of the pair (in front of it, the wait for kf[c] would also wait for them)
           __builtin_amdgcn_sched_barrier(0);
           if (c < 2) kf[(c + 2) % 3] = k_frag(kst, ktn, c + 2);
           vf[c & 1][c >> 1] = v_frag(vst, c & 1, kt, c >> 1);
@@ -282,20 +277,19 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) {        // ol[0], ol[1], o[0][0], o[1][0], o[0][1], o[1][1]
         const int qi = i & 1, m = 6 * u + i;
-        if (u == 1 && i == 0 && !(ABL & 256)) kf[0] = k_frag(kst2, kt2, 0);      // fragments of the sub-tile after the next one
-        if (u == 1 && i == 2 && !(ABL & 256)) kf[1] = k_frag(kst2, kt2, 1);
+        if (u == 1 && i == 0) kf[0] = k_frag(kst2, kt2, 0);      // fragments of the sub-tile after the next one
+        if (u == 1 && i == 2) kf[1] = k_frag(kst2, kt2, 1);
         if (i < 2) ol[qi] = mfma16<F16>(ones, pf[qi][u], ol[qi]);
         else o[qi][(i - 2) >> 1] = mfma16<F16>(vf[(i - 2) >> 1][u], pf[qi][u], o[qi][(i - 2) >> 1]);
         if (m < 6) {
           // probabilities of the second 16 keys: 10 steps over 6 slots
 #pragma unroll
-          for (int st = (10 * m) / 6; st < (10 * (m + 1)) / 6; ++st) if (!(ABL & 32)) e_step(SC, 2 + st / 5, st % 5);
+          for (int st = (10 * m) / 6; st < (10 * (m + 1)) / 6; ++st) e_step(SC, 2 + st / 5, st % 5);
         } else {
           // maximum search of the next sub-tile: 2 x 3 steps over the first four slots -- the test's compare is two MFMAs old when the
           // branch behind the sub-tile reads it
           const int mm = m - 6;
-          if (ABL & 16) { }
-          else if (mm < 2) m_step(SN, mm, 0, next_key0, mask);
+          if (mm < 2) m_step(SN, mm, 0, next_key0, mask);
           else if (mm == 2) { m_step(SN, 0, 1, next_key0, mask); m_step(SN, 1, 1, next_key0, mask); }
           else if (mm == 3) { m_step(SN, 0, 2, next_key0, mask); m_step(SN, 1, 2, next_key0, mask); }
         }
@@ -316,13 +310,10 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   auto tile = [&](int t, auto mask_a, auto mask_b) __attribute__((always_inline)) {
     // K(t+1) and V^T(t) have landed once everything but the newest DMA group ({K(t+2), V^T(t+1)}) is complete; lgkmcnt(0): this wave's fragment
     // reads of the stages refilled below have returned; the barrier publishes all waves' shares and proves those stages are no longer being read
-    if (ABL & 4) { }
-    else if (t + 2 < ntiles) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (t + 2 < ntiles) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (!(ABL & 2)) {
-      if (t + 3 < ntiles) GN_DMA_K(k3, t + 3);        // the stage K(t-1) was read from (its second half one sub-tile ago)
-      if (t + 2 < ntiles) GN_DMA_V(v2, t + 2);        // the stage V^T(t-1) was read from
-    }
+    if (t + 3 < ntiles) GN_DMA_K(k3, t + 3);        // the stage K(t-1) was read from (its second half one sub-tile ago)
+    if (t + 2 < ntiles) GN_DMA_V(v2, t + 2);        // the stage V^T(t-1) was read from
     const unsigned ks0 = 2 * kRing * k0, ks1 = 2 * kRing * k1, vs0 = 2 * kRing * (NDK + v0);
     GN_PIN();
     // sub-tile 2 t: scores of keys 32..63 of tile t; prefetch the first fragments of keys 0..31 of tile t + 1
@@ -399,7 +390,6 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
   }
   // the rings and the slab are free for the next item once every wave is here (and its LDS reads have returned)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  if (!(ABL & 8)) continue;
   if (ABL & 8) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stamp(5);
@@ -414,28 +404,20 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
 #undef GN_PIN
 }  // namespace
 
-// grids of whole 256-query blocks; false = not applicable, the caller launches k_attn16_v5
-bool launch_attention_pw(const AttnArgs& a, int ablate, hipStream_t s) {
+// grids of whole 256-query blocks; false = not applicable, the caller launches k_attn16_v5.  stamps: the phase-stamp form (developer knob 1 = 73)
+bool launch_attention_pw(const AttnArgs& a, bool stamps, hipStream_t s) {
   if (a.npad % 256 != 0 || a.qb == nullptr) return false;
   const int nitems = a.npad / 256 * kHeads * a.BS;
   if (nitems < 8) return false;
   const int ncu = a.ncu >= 8 ? a.ncu : std::max(device_cu_count(), 8);
   // one workgroup per CU (LDS and registers leave room for one) walks the work list; a multiple of the 8 XCDs.  The phase-stamp variants keep one
   // workgroup per item (tools/attn_pw_ab.py reads one record per item).
-  const bool stamps = ablate == 3 || ablate >= 100;
   const dim3 grid((unsigned)((stamps || nitems < ncu) ? (nitems & ~7) : (ncu & ~7))), block(256);
   if (a.half_fmt) {
-    if (ablate == 1) hipLaunchKernelGGL((k_attn_pw<true, 1>), grid, block, 0, s, a, nitems);
-    else if (ablate == 2) hipLaunchKernelGGL((k_attn_pw<true, 2>), grid, block, 0, s, a, nitems);
-    else if (stamps) {
+    if (stamps) {
       if (g_attn_stamps == nullptr) return false;
       AttnArgs b = a; b.part = reinterpret_cast<float*>(g_attn_stamps); b.tiles = nullptr;
-#define GN_PW_ABL(x) case x: hipLaunchKernelGGL((k_attn_pw<true, (x) | 8>), grid, block, 0, s, b, nitems); break;
-      switch (ablate >= 100 ? ablate - 100 : 0) {
-        GN_PW_ABL(0) GN_PW_ABL(1) GN_PW_ABL(2) GN_PW_ABL(4) GN_PW_ABL(6) GN_PW_ABL(16) GN_PW_ABL(32) GN_PW_ABL(48) GN_PW_ABL(64) GN_PW_ABL(256) GN_PW_ABL(524288) GN_PW_ABL(524320)
-        default: return false;
-      }
-#undef GN_PW_ABL
+      hipLaunchKernelGGL((k_attn_pw<true, 8>), grid, block, 0, s, b, nitems);
     }
     else hipLaunchKernelGGL((k_attn_pw<true, 0>), grid, block, 0, s, a, nitems);
     g_last_kernel = "k_attn_pw<true, 0>";

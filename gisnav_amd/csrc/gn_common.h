@@ -135,7 +135,7 @@ struct FfnArgs {
   float* y;                                // optional f32 copy of the output, or nullptr
   int T;                                   // tokens, a multiple of 64 (of 32 for the 4-wave shape)
   unsigned int* ovf;                       // f16x2 domain guard word, or nullptr
-  long long* dbg_ts;                       // developer: [blocks][8 waves][8] s_memtime stamps (ablation 8), or nullptr
+  long long* dbg_ts;                       // developer: [blocks][8 waves][8] s_memtime stamps (knob 12 = 8), or nullptr
   const int* tiles = nullptr;              // k_ffn128: work list of the call (launch_tile_lists), or nullptr = every 128-token tile of T
   int walk = 0;                            // 1: one workgroup per CU walks `tiles`; 0: one workgroup per tile of T, which leaves at once when `tiles` says (through
                                            // nvalid / npad) that its tile holds only padding
@@ -153,11 +153,10 @@ struct FfnArgs {
 };
 void launch_ffn_fused(const FfnArgs& a, hipStream_t s);
 bool ffn_selects_128(const FfnArgs& a);   // true when launch_ffn_fused(a) dispatches k_ffn128 (the caller may then ask for the fused projection: a.qkv)
-void launch_ffn128(const FfnArgs& a, int ablate, hipStream_t s);   // gn_ffn128.hip: 128 tokens per workgroup (a.cp set, a.T % 128 == 0); ablate: developer knob 12
-extern int g_ffn_ablate;
+void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s);   // gn_ffn128.hip: 128 tokens per workgroup (a.cp set, a.T % 128 == 0); stamps: developer knob 12
+extern int g_ffn_stamps;
 extern int g_ffn_shape;
 extern int g_sp_conv_h;
-extern int g_head_ablate;
 void build_weight_fragments(const float* w, int N, int K, float scale, int permute_k, uint16_t* out);   // host arrays; out: 2 * N * K halfs
 
 // ---- attention input projections of the f16x2 mode (gn_qkv.hip): hm16 rows in, bf16 q | k rows and bf16 V^T panels out -------
@@ -233,10 +232,10 @@ void launch_attention_f32(const AttnArgs& a, hipStream_t s);
 void launch_attention_bf16(const AttnArgs& a, hipStream_t s);
 void launch_attention_f16x2(const AttnArgs& a, hipStream_t s);   // k_attn_f16x2 (gn_attention_f16x2.hip): f32 rows in, split-fp16 operands, f32-accurate
 void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s);
-bool launch_attention_pw(const AttnArgs& a, int ablate, hipStream_t s);   // k_attn_pw (gn_attention_pw.hip): bulk grids, npad % 256 == 0; false = not applicable
+bool launch_attention_pw(const AttnArgs& a, bool stamps, hipStream_t s);   // k_attn_pw (gn_attention_pw.hip): bulk grids, npad % 256 == 0; false = not applicable
 void launch_pack_attn_bf16(const AttnArgs& a, uint16_t* qkb, uint16_t* vtb, hipStream_t s);   // (a.half_fmt selects bf16 / fp16)   // f32 rows -> the bf16 layouts k_attn_bf16_v5 reads (test entry)
 extern thread_local long long* g_attn_stamps;   // developer (knob 1 = 73): k_attn_pw writes s_memtime phase stamps here (the idle sim buffer)
-extern thread_local int g_attn_variant;  // developer knob: 4 = k_attn_bf16_v5 (default), 41 / 42 = its timing-only ablations
+extern thread_local int g_attn_variant;  // developer knob 1: 4 = the automatic attention kernel choice (default)
 
 // ---- elementwise / small kernels ----------------------------------------------------------------
 struct PrepArgs {

@@ -37,7 +37,7 @@ namespace {
 // twice the weight bytes with the same number of loads in flight) and is not instantiated.
 //   NJ            token tiles of 32 per workgroup (every wave covers all of them)
 //   NI = 16 / NW  hidden tiles of 32 per wave in GEMM 1;   NO = 8 / NW  output tiles of 32 per wave in GEMM 0 and GEMM 2
-template <int ABL = 0, bool FOLD = true, int NW = 8, int NJ = 2>   // ABL, timing-only ablations: 1 no weight loads inside the loops, 2 no second GEMM, 4 no GELU; 8 = s_memtime stamps per phase into a.dbg_ts
+template <int ABL = 0, bool FOLD = true, int NW = 8, int NJ = 2>   // ABL = 8: s_memtime stamps per phase into a.dbg_ts (results stay valid); 0 otherwise
 __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
   constexpr int NI = 16 / NW, NO = 8 / NW;
   constexpr int TM = 32 * NJ;             // tokens per workgroup
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
 #pragma unroll
           for (int j = 0; j < NJ; ++j)
             acc0[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(go[kk % RO][o][p == 0 ? 1 : 0], fb[cb][j][p == 1 ? 1 : 0], acc0[o][j], 0, 0, 0);
-      if (!(ABL & 1) && kk + RO < 16) {
+      if (kk + RO < 16) {
 #pragma unroll
         for (int o = 0; o < NO; ++o)
 #pragma unroll
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
 #pragma unroll
           for (int j = 0; j < NJ; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[slot][i][p == 0 ? 1 : 0], fb[cb][j][p == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
-      if (!(ABL & 1) && n2 + RA < 32) load_a(slot, n2 + RA);
+      if (n2 + RA < 32) load_a(slot, n2 + RA);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (n == 7) { __syncthreads(); read_b(0, smem, 0); }     // x tile complete (n2 + 1 == 16 is the one fragment set that could not be prefetched)
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; c += 2) {
           const f32x2v yn = pair(acc[i][j], 4 * g + c) * splat2(rstd[j]) * (f32x2v){gm[c], gm[c + 1]} + (f32x2v){bt[c], bt[c + 1]};
-          set_pair(acc[i][j], 4 * g + c, (ABL & 4) ? yn : gelu_erf2(yn));
+          set_pair(acc[i][j], 4 * g + c, gelu_erf2(yn));
         }
     }
   stamp(3);
@@ -328,27 +328,25 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc2[o][j][r] = 0.f;
-  if (!(ABL & 2)) {
-    read_b(0, smem, 0);
+  read_b(0, smem, 0);
 #pragma unroll
-    for (int kk = 0; kk < 32; ++kk) {
-      const int cb = kk & 1;
-      if (kk + 1 < 32) read_b(cb ^ 1, smem + ((kk + 1) >> 1) * KT, (kk + 1) & 1);
+  for (int kk = 0; kk < 32; ++kk) {
+    const int cb = kk & 1;
+    if (kk + 1 < 32) read_b(cb ^ 1, smem + ((kk + 1) >> 1) * KT, (kk + 1) & 1);
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
+    for (int p = 0; p < 3; ++p)
 #pragma unroll
-        for (int o = 0; o < NO; ++o)
+      for (int o = 0; o < NO; ++o)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc2[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[kk % RG][o][p == 0 ? 1 : 0], fb[cb][j][p == 1 ? 1 : 0], acc2[o][j], 0, 0, 0);
-      if (!(ABL & 1) && kk + RG < 32) {
+        for (int j = 0; j < NJ; ++j)
+          acc2[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[kk % RG][o][p == 0 ? 1 : 0], fb[cb][j][p == 1 ? 1 : 0], acc2[o][j], 0, 0, 0);
+    if (kk + RG < 32) {
 #pragma unroll
-        for (int o = 0; o < NO; ++o)
+      for (int o = 0; o < NO; ++o)
 #pragma unroll
-          for (int pl = 0; pl < 2; ++pl) ga[kk % RG][o][pl] = __builtin_bit_cast(f16x8, w2f[((o * 32 + kk + RG) * 2 + pl) * 64]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
+        for (int pl = 0; pl < 2; ++pl) ga[kk % RG][o][pl] = __builtin_bit_cast(f16x8, w2f[((o * 32 + kk + RG) * 2 + pl) * 64]);
     }
+    __builtin_amdgcn_sched_barrier(0);
   }
   stamp(5);
   __syncthreads();   // the hidden tile is dead: its space becomes the [TM tokens][256 features] f32 tile of the row-wise epilogue
@@ -400,7 +398,7 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
 }
 }  // namespace
 
-int g_ffn_ablate = 0;   // developer knob 12: timing-only ablations of k_ffn_fused (wrong results)
+int g_ffn_stamps = 0;   // developer knob 12: 8 = phase stamps into FfnArgs::dbg_ts (k_ffn_fused; k_ffn128 also 136), 0 otherwise
 int g_ffn_shape = 0;    // developer knob 14: 0 = automatic, 64 / 32 = force the 64-token / 32-token workgroup shape
 bool ffn_selects_128(const FfnArgs& a) {
   return a.cp != nullptr && a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256));
@@ -419,23 +417,16 @@ void launch_ffn_fused(const FfnArgs& a_in, hipStream_t s) {
     return;
   }
   // bulk grids: 128 tokens per workgroup, one wave per SIMD (gn_ffn128.hip); developer knob 14 = 128 / 64 / 32 forces a shape
-  if (a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256))) { launch_ffn128(a, g_ffn_ablate, s); return; }
+  if (a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256))) { launch_ffn128(a, g_ffn_stamps, s); return; }
   if (small) {
-    if (g_ffn_ablate == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
+    if (g_ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((k_ffn_fused<0, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
     g_last_kernel = "k_ffn_fused<0, true, 8, 1>";
     return;
   }
   const dim3 grid(a.T / 64), block(512);
-  switch (g_ffn_ablate) {
-    case 1: hipLaunchKernelGGL((k_ffn_fused<1, true, 8, 2>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_ffn_fused<2, true, 8, 2>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_ffn_fused<3, true, 8, 2>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((k_ffn_fused<4, true, 8, 2>), grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL((k_ffn_fused<7, true, 8, 2>), grid, block, 0, s, a); break;
-    case 8: hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 2>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((k_ffn_fused<0, true, 8, 2>), grid, block, 0, s, a); break;
-  }
+  if (g_ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 2>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((k_ffn_fused<0, true, 8, 2>), grid, block, 0, s, a);
   g_last_kernel = "k_ffn_fused<0, true, 8, 2>";
 }
 

@@ -55,7 +55,7 @@ __device__ __forceinline__ float resid_hi(unsigned int h, float y) { float r; as
 // projections since round 4, one rounding of the GEMM inputs to fp16, which the fp16 attention beside it applies to q, k, v and the probabilities anyway.
 // A third of the matrix-pipe work of both GEMMs, half of the token-fragment reads, no residual split of the hidden tile.  Meant to run under the margin
 // certificate (gn_set_certify), which makes the correspondence indices independent of the fast pass's arithmetic; composed form only.
-template <int ABL, bool COMP, bool LOOP = false, int QKV = 0, int PROD = 3>   // LOOP: the workgroup walks the work list (one workgroup per CU); timing-only ablations (bits): 1 no weight loads inside the loops, 2 no token-row loads inside the loops, 4 no GELU polynomial, 16 no barriers inside the k-loops; 8 = s_memtime stamps per phase into a.dbg_ts (results stay valid)
+template <int ABL, bool COMP, bool LOOP = false, int QKV = 0, int PROD = 3>   // LOOP: the workgroup walks the work list (one workgroup per CU); ABL: 0, or 8 = s_memtime stamps per phase into a.dbg_ts, + 128 = per k-tile stamps too (results stay valid)
 __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
   static_assert(PROD == 3 || (PROD == 2 && COMP), "two partial products: composed form only");
   constexpr int NJ = 4, NI = 4, NO = 2, NW = 4, TM = 128;
@@ -282,11 +282,11 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
           const int m = 6 * j + 2 * p + o;
           acc0[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(go[kk % RO][o][p == 0 ? 1 : 0], bq[g % 3][p == 1 ? 1 : 0], acc0[o][j], 0, 0, 0);
           if (ks == 0 && m % 6 == 1) stage_write(s + 1, m / 6);          // tile 8 = the first x k-tile
-          if (!(ABL & 1) && m % 6 == 3 && kk >= 1 && kk + RO - 1 < 16) {
+          if (m % 6 == 3 && kk >= 1 && kk + RO - 1 < 16) {
             const int lo = (m / 6) >> 1, lpl = (m / 6) & 1;
             go[(kk - 1) % RO][lo][lpl] = ldw(wob, ((lo * 16 + kk + RO - 1) * 2 + lpl) * 1024);
           }
-          if (!(ABL & 2) && ks == 0 && m % 6 == 5 && s + 3 <= 8) stage_load(s + 3, m / 6);
+          if (ks == 0 && m % 6 == 5 && s + 3 <= 8) stage_load(s + 3, m / 6);
           if (kk == 12 && m % 6 == 5)
 #pragma unroll
             for (int g4 = 0; g4 < 2; ++g4) {
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
           GN_PIN();
         }
     }
-    if (!(ABL & 16)) __syncthreads();     // after k-step 0: tile s + 1 is visible; after k-step 1: tile s's slot may be overwritten
+    __syncthreads();     // after k-step 0: tile s + 1 is visible; after k-step 1: tile s's slot may be overwritten
     GN_PIN();
   }
   stamp(2);
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int g = 4 * n2 + j, g1 = g + 1, m2 = g1 >> 2, nn = m2 >> 1;
-      if (m2 < 32 && !((ABL & 64) && n2 > 0)) read_b(g1, (!COMP && nn < 8) ? nn * KT : RING + (nn & 1) * KT, m2 & 1, g1 & 3);
+      if (m2 < 32) read_b(g1, (!COMP && nn < 8) ? nn * KT : RING + (nn & 1) * KT, m2 & 1, g1 & 3);
       // products: W_m X_h, W_h X_m, W_h X_h (small terms first), the four hidden tiles round-robin
 #pragma unroll
       for (int p = 0; p < 3; ++p)
@@ -385,16 +385,16 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
           // the memory instructions of the k-step, one per MFMA gap: three products: gaps 2 | 5, 10 | 7 of the j-step's 12; two products: 2 | 1, 9 | 3 of its 8 (mj 4..7 do not exist)
           constexpr int kLa0 = PROD == 3 ? 5 : 1, kLa1 = PROD == 3 ? 10 : 9, kSl = PROD == 3 ? 7 : 3;
           if ((COMP || n >= 8) && ks == 0 && n + 1 < 16 && mj == 2) stage_write(n + 1, j);
-          if (!(ABL & 1) && (mj == kLa0 || mj == kLa1) && n2 >= 1 && n2 + RA - 1 < 32) {
+          if ((mj == kLa0 || mj == kLa1) && n2 >= 1 && n2 + RA - 1 < 32) {
             const int u = 2 * j + (mj == kLa1 ? 1 : 0);   // 0..7 -> (i, term)
             load_a((n2 - 1) % RA, n2 + RA - 1, u >> 1, u & 1);
           }
-          if (!(ABL & 2) && ks == 0 && (COMP || n + 3 >= 9) && n + 3 < 16 && mj == kSl) stage_load(n + 3, j);     // (x tiles 9, 10 are requested during the last message k-tiles)
+          if (ks == 0 && (COMP || n + 3 >= 9) && n + 3 < 16 && mj == kSl) stage_load(n + 3, j);     // (x tiles 9, 10 are requested during the last message k-tiles)
           if (n2 == 29 && mj == kSl && j == 0) cst_a = *reinterpret_cast<const uint4*>((tid < 128 ? a.ln_g : a.ln_b - 512) + 4 * tid);
           GN_PIN();
         }
     }
-    if ((COMP || n >= 8) && !(ABL & 16)) __syncthreads();
+    if (COMP || n >= 8) __syncthreads();
     if (n2 == 15) stamp(10);
     if ((ABL & 128) && ks == 1) ts2[n] = (long long)__builtin_amdgcn_s_memtime();
     GN_PIN();
@@ -498,8 +498,6 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     } else if (st == 2) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) gy[e] = gy[e] * c2[e >> 2][e & 3] + c3[e >> 2][e & 3];
-    } else if (ABL & 4) {
-      if (st >= 18) tail_stage(st, 0, j, ksp);
     } else if (st == 3) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) gt[e] = gy[e] * 0.70710678118654752440f;
@@ -560,33 +558,31 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     for (int k = 0; k < 8; ++k) y[k] = pair(acc[q][j], 2 * k) * splat2(rs[j]) + splat2(nmr[j]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) y[k] = y[k] * (f32x2v){w4[k >> 1][2 * (k & 1)], w4[k >> 1][2 * (k & 1) + 1]} + (f32x2v){b4[k >> 1][2 * (k & 1)], b4[k >> 1][2 * (k & 1) + 1]};
-    if (!(ABL & 4)) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) t[k] = y[k] * splat2(0.70710678118654752440f);
+    for (int k = 0; k < 8; ++k) t[k] = y[k] * splat2(0.70710678118654752440f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) t[k] = (f32x2v){fminf(fabsf(t[k][0]), 4.0f), fminf(fabsf(t[k][1]), 4.0f)};
+    for (int k = 0; k < 8; ++k) t[k] = (f32x2v){fminf(fabsf(t[k][0]), 4.0f), fminf(fabsf(t[k][1]), 4.0f)};
 #pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = splat2(4.6081331674940884e-05f) * t[k] + splat2(-0.00045161080197431147f);
+    for (int k = 0; k < 8; ++k) u[k] = splat2(4.6081331674940884e-05f) * t[k] + splat2(-0.00045161080197431147f);
 #pragma unroll
-      for (int st = 0; st < 6; ++st) {
-        const float cf = st == 0 ? 0.0015096671413630247f : st == 1 ? 0.0007409505778923631f : st == 2 ? -0.028223754838109016f
-                       : st == 3 ? 0.1484677642583847f : st == 4 ? 0.918419361114502f : 1.6279083490371704f;
+    for (int st = 0; st < 6; ++st) {
+      const float cf = st == 0 ? 0.0015096671413630247f : st == 1 ? 0.0007409505778923631f : st == 2 ? -0.028223754838109016f
+                     : st == 3 ? 0.1484677642583847f : st == 4 ? 0.918419361114502f : 1.6279083490371704f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) u[k] = u[k] * t[k] + splat2(cf);
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = u[k] * t[k];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = (f32x2v){__builtin_amdgcn_exp2f(-u[k][0]), __builtin_amdgcn_exp2f(-u[k][1])};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = splat2(1.0f) - u[k];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = (f32x2v){copysignf(u[k][0], y[k][0]), copysignf(u[k][1], y[k][1])};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t[k] = splat2(0.5f) * y[k];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) y[k] = t[k] * u[k] + t[k];
+      for (int k = 0; k < 8; ++k) u[k] = u[k] * t[k] + splat2(cf);
     }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = u[k] * t[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = (f32x2v){__builtin_amdgcn_exp2f(-u[k][0]), __builtin_amdgcn_exp2f(-u[k][1])};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = splat2(1.0f) - u[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = (f32x2v){copysignf(u[k][0], y[k][0]), copysignf(u[k][1], y[k][1])};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t[k] = splat2(0.5f) * y[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) y[k] = t[k] * u[k] + t[k];
     // maximum, fp16 split, publish: registers 0..7 -> the fragment of k-step 0, 8..15 -> k-step 1
     unsigned int hw[8], mw[8];
 #pragma unroll
@@ -658,7 +654,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
               // the VALU stage of the next quarter's fragment (token tile w4, k-step ks) that shares this MFMA's gap
               if (fill && m < 22) gelu_stage(m, q + 1, w4, ks);
               if (q == 3 && m == 2 && !LOOP) res_load(cc);      // (walking form: the registers are not there, all residual rows are requested in the epilogue)
-              if (!(ABL & 1) && m % 6 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, (m / 6) >> 1, (m / 6) & 1);
+              if (m % 6 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, (m / 6) >> 1, (m / 6) & 1);
             } else {
               // sixteen MFMA gaps per (quarter, k-step) for the fragment's twenty stages (no residual split): the light neighbours share a gap
               const int m = 4 * j + (p == 2 ? 2 : 0) + o;
@@ -669,7 +665,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
                 if (second[m] >= 0) gelu_stage(second[m], q + 1, w4, ks);
               }
               if (q == 3 && m == 2 && !LOOP) res_load(cc);
-              if (!(ABL & 1) && m % 4 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, (m / 4) >> 1, (m / 4) & 1);
+              if (m % 4 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, (m / 4) >> 1, (m / 4) & 1);
             }
             GN_PIN();
           }
@@ -931,25 +927,25 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #undef GN_PIN
 }  // namespace
 
-void launch_ffn128(const FfnArgs& a, int ablate, hipStream_t s) {
+void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s) {
   const int ncu = a.ncu > 0 ? a.ncu : device_cu_count();
-  const bool walk = a.tiles != nullptr && a.walk && ablate == 0;
+  const bool walk = a.tiles != nullptr && a.walk && stamps == 0;
   const dim3 grid(walk ? std::min(a.T / 128, ncu) : a.T / 128), block(256);     // walking form: one workgroup per CU
   FfnArgs b = a;
   if (!walk) b.tiles = nullptr;
-  if (walk || ablate != 0) b.nvalid = nullptr;
-  if (a.composed && a.products == 2 && (ablate == 0 || ablate == 8)) {      // two partial products (round 6): composed form only
-#define GN_F2(Q) do { if (ablate == 8) hipLaunchKernelGGL((k_ffn128<8, true, false, Q, 2>), grid, block, 0, s, b); \
+  if (walk || stamps != 0) b.nvalid = nullptr;
+  if (a.composed && a.products == 2 && (stamps == 0 || stamps == 8)) {      // two partial products (round 6): composed form only
+#define GN_F2(Q) do { if (stamps == 8) hipLaunchKernelGGL((k_ffn128<8, true, false, Q, 2>), grid, block, 0, s, b); \
                       else if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true, Q, 2>), grid, block, 0, s, b); \
                       else hipLaunchKernelGGL((k_ffn128<0, true, false, Q, 2>), grid, block, 0, s, b); } while (0)
-    const int qv = ablate == 0 ? a.qkv : 0;
+    const int qv = stamps == 0 ? a.qkv : 0;
     if (qv == 1) { GN_F2(1); g_last_kernel = walk ? "k_ffn128<0, true, true, 1, 2>" : "k_ffn128<0, true, false, 1, 2>"; }
     else if (qv == 2) { GN_F2(2); g_last_kernel = walk ? "k_ffn128<0, true, true, 2, 2>" : "k_ffn128<0, true, false, 2, 2>"; }
     else { GN_F2(0); g_last_kernel = walk ? "k_ffn128<0, true, true, 0, 2>" : "k_ffn128<0, true, false, 0, 2>"; }
 #undef GN_F2
     return;
   }
-  if (a.composed && a.qkv != 0 && ablate == 0) {      // the next block's attention input projection behind the tail (a.qkv: 1 self, 2 cross)
+  if (a.composed && a.qkv != 0 && stamps == 0) {      // the next block's attention input projection behind the tail (a.qkv: 1 self, 2 cross)
     if (a.qkv == 1) {
       if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true, 1>), grid, block, 0, s, b); else hipLaunchKernelGGL((k_ffn128<0, true, false, 1>), grid, block, 0, s, b);
       g_last_kernel = walk ? "k_ffn128<0, true, true, 1, 3>" : "k_ffn128<0, true, false, 1, 3>";
@@ -960,7 +956,7 @@ void launch_ffn128(const FfnArgs& a, int ablate, hipStream_t s) {
     return;
   }
   if (a.composed) {
-    switch (ablate) {
+    switch (stamps) {
       case 8: hipLaunchKernelGGL((k_ffn128<8, true>), grid, block, 0, s, b); break;
       case 136: hipLaunchKernelGGL((k_ffn128<136, true>), grid, block, 0, s, b); break;
       default: if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true>), grid, block, 0, s, b); else hipLaunchKernelGGL((k_ffn128<0, true>), grid, block, 0, s, b); break;
@@ -968,7 +964,7 @@ void launch_ffn128(const FfnArgs& a, int ablate, hipStream_t s) {
     g_last_kernel = walk ? "k_ffn128<0, true, true, 0, 3>" : "k_ffn128<0, true, false, 0, 3>";
     return;
   }
-  switch (ablate) {
+  switch (stamps) {
     case 8: hipLaunchKernelGGL((k_ffn128<8, false>), grid, block, 0, s, b); break;
     case 136: hipLaunchKernelGGL((k_ffn128<136, false>), grid, block, 0, s, b); break;
     default: if (walk) hipLaunchKernelGGL((k_ffn128<0, false, true>), grid, block, 0, s, b); else hipLaunchKernelGGL((k_ffn128<0, false>), grid, block, 0, s, b); break;

@@ -635,7 +635,7 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
 // so only the A fragments are split in registers.  B plane tiles are [plane][128 rows][32 k] bf16 (64-byte
 // rows); 16-byte chunk c of row r sits at position c ^ ((r >> 2) & 3), which makes every ds_read_b128 lane
 // group hit 16 distinct bank slots.
-template <int EPI, bool WP, int ABL = 0>   // ABL: timing-only ablations (1: no operand split, 2: no DMA in the loop, 4: no barrier)
+template <int EPI, bool WP>
 __global__ __launch_bounds__(256) void k_gemm_f32x3(GemmArgs a) {
   constexpr int TILE = WP ? (BM * BK + 3 * BN * BK / 2) : (BM + BN) * BK;  // floats per buffer: f32 A tile + (f32 | 3 bf16-plane) B tile
   constexpr int SLAB = 4 * 64 * ES;
@@ -737,8 +737,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32x3(GemmArgs a) {
 #define GN_SPLIT(ra_, rb_, A_, B_)                                                                \
   {                                                                                               \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                               \
-      if (ABL & 1) { A_[i][0] = __builtin_bit_cast(bf16x8, ra_[i][0]); A_[i][1] = __builtin_bit_cast(bf16x8, ra_[i][1]); A_[i][2] = A_[i][0]; } \
-      else split8(ra_[i][0], ra_[i][1], A_[i][0], A_[i][1], A_[i][2]);                            \
+      split8(ra_[i][0], ra_[i][1], A_[i][0], A_[i][1], A_[i][2]);                                 \
       if (!WP) split8(rb_[i][0], rb_[i][1], B_[i][0], B_[i][1], B_[i][2]);                        \
     }                                                                                             \
   }
@@ -788,8 +787,8 @@ __global__ __launch_bounds__(256) void k_gemm_f32x3(GemmArgs a) {
     if (WP) GN_BPLANE_READ(B1, cur, 1);
     GN_MFMA24(A0, B0)
     GN_SPLIT(rawa, rawb, A1, B1);
-    if (!(ABL & 4)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-    if (!(ABL & 2) && t + 2 < nt) GN_DMA_TILE(cur, (t + 2) * BK);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
+    if (t + 2 < nt) GN_DMA_TILE(cur, (t + 2) * BK);
     if (t + 1 < nt) {
       GN_RAW_READ(rawa, rawb, cur ^ 1, 0);
       if (WP) GN_BPLANE_READ(B0, cur ^ 1, 0);
@@ -953,7 +952,7 @@ __device__ __forceinline__ void split8h(const f32x4& a, const f32x4& b, f16x8& h
 // subnormal range; the epilogue multiplies the accumulator by the exact inverse, GemmArgs::acc_scale).
 // Domain: |activation| < 65504 (fp16 range) -- LightGlue's activations are O(1..100).
 // Tiles, DMA, swizzles and epilogues are those of k_gemm_f32x3.
-template <int EPI, bool WP, int ABL = 0>   // ABL: timing-only ablations (1: no operand split, 2: no DMA in the loop, 4: no barrier)
+template <int EPI, bool WP>
 __global__ __launch_bounds__(256) void k_gemm_f16x2(GemmArgs a) {
   constexpr int TILE = (BM + BN) * BK;  // floats per buffer: f32 A tile + (f32 | 2 fp16-plane) B tile, 16 KB each
   constexpr int SLAB = 4 * 64 * ES;
@@ -1056,8 +1055,7 @@ __global__ __launch_bounds__(256) void k_gemm_f16x2(GemmArgs a) {
 #define GN_SPLIT(ra_, rb_, A_, B_)                                                                \
   {                                                                                               \
     _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                               \
-      if (ABL & 1) { A_[i][0] = __builtin_bit_cast(f16x8, ra_[i][0]); A_[i][1] = __builtin_bit_cast(f16x8, ra_[i][1]); } \
-      else split8h(ra_[i][0], ra_[i][1], A_[i][0], A_[i][1]);                                     \
+      split8h(ra_[i][0], ra_[i][1], A_[i][0], A_[i][1]);                                          \
       if (!WP) split8h(rb_[i][0], rb_[i][1], B_[i][0], B_[i][1]);                                 \
     }                                                                                             \
   }
@@ -1106,8 +1104,8 @@ __global__ __launch_bounds__(256) void k_gemm_f16x2(GemmArgs a) {
     if (WP) GN_BPLANE_READ(B1, cur, 1);
     GN_MFMA24(A0, B0)
     GN_SPLIT(rawa, rawb, A1, B1);
-    if (!(ABL & 4)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-    if (!(ABL & 2) && t + 2 < nt) GN_DMA_TILE(cur, (t + 2) * BK);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
+    if (t + 2 < nt) GN_DMA_TILE(cur, (t + 2) * BK);
     if (t + 1 < nt) {
       GN_RAW_READ(rawa, rawb, cur ^ 1, 0);
       if (WP) GN_BPLANE_READ(B0, cur ^ 1, 0);
@@ -1319,26 +1317,9 @@ void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s) {
     hipLaunchKernelGGL((k_gemm_f32_v3<EPI_BIAS, false>), grid, block, 0, s, a);
     return;
   }
-  if (g_gemm_variant >= 60 && epi == EPI_BIAS && a.Wp) {   // f16x2 ablation builds (timing only, wrong numbers)
-    switch (g_gemm_variant) {
-      case 61: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 1>), grid, block, 0, s, a); break;
-      case 62: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 2>), grid, block, 0, s, a); break;
-      case 63: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 3>), grid, block, 0, s, a); break;
-      case 64: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 4>), grid, block, 0, s, a); break;
-      case 67: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 7>), grid, block, 0, s, a); break;
-      default: hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true, 0>), grid, block, 0, s, a); break;
-    }
-    return;
-  }
-  if (g_gemm_variant >= 50 && epi == EPI_BIAS && a.Wp) {   // ablation builds (timing only, wrong numbers)
-    switch (g_gemm_variant) {
-      case 51: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 1>), grid, block, 0, s, a); break;
-      case 52: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 2>), grid, block, 0, s, a); break;
-      case 53: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 3>), grid, block, 0, s, a); break;
-      case 54: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 4>), grid, block, 0, s, a); break;
-      case 57: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 7>), grid, block, 0, s, a); break;
-      default: hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true, 0>), grid, block, 0, s, a); break;
-    }
+  if (g_gemm_variant >= 50 && epi == EPI_BIAS && a.Wp) {   // 50 / 60: k_gemm_f32x3 / k_gemm_f16x2 on the bias epilogue alone (tools/gemm_bench.py)
+    if (g_gemm_variant >= 60) hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true>), grid, block, 0, s, a);
     return;
   }
   if (g_gemm_variant == 6) {

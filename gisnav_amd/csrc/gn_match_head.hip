@@ -253,7 +253,7 @@ __device__ __forceinline__ void head_mma(const uint4& a0, const uint4& a1, const
   }
 }
 
-template <bool F32, int SWEEP, int ABL = 0>   // ABL, timing-only ablations (wrong results): 1 no DMA in the loop, 2 no VALU work, 4 no MFMA, 8 no LDS fragment reads
+template <bool F32, int SWEEP>
 __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * kHeadTile];
   __shared__ int s_last;
@@ -347,12 +347,11 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   Acc2 acc;
   // the MFMAs of tile t
   auto mma_tile = [&](int t) __attribute__((always_inline)) {
-    if (ABL & 4) return;
     const unsigned char* const cur = smem + (t & 1) * kHeadTile;
     read_b(0, cur, 0);
 #pragma unroll
     for (int st = 0; st < 16; ++st) {
-      if (st + 1 < 16 && !(ABL & 8)) read_b((st + 1) & 1, cur, st + 1);
+      if (st + 1 < 16) read_b((st + 1) & 1, cur, st + 1);
       if (st == 0) head_mma<F32, true, 0>(af[0], af[1], fb[0][0], fb[0][1], acc);
       else head_mma<F32, false, 0>(af[2 * st], af[2 * st + 1], fb[st & 1][0], fb[st & 1][1], acc);
       head_mma<F32, false, 1>(af[2 * st], af[2 * st + 1], fb[st & 1][0], fb[st & 1][1], acc);
@@ -360,7 +359,6 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   };
   // the VALU work of tile t on the accumulators: row statistics / arg-max in registers, the column's over this lane's 16 rows
   auto epi_tile = [&](int t) __attribute__((always_inline)) {
-    if (ABL & 2) return;
     const int j = 64 * (tbeg + t) + 32 * wc + ql;        // this lane's column
     const bool cvalid = j < n1;
     float cm = 0.f, cl = 0.f, lj = 0.f;
@@ -433,7 +431,7 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   // that an MFMA wave and a VALU wave sharing a SIMD take LONGER than one after the other (500 vs 317 cycles per probe body), while
   // two MFMA waves or two VALU waves share it well -- the opposite-phase arrangement tried first was the worst choice available.
   for (int t = 0; t < ntile; ++t) {
-    if (t + 1 < ntile && !(ABL & 1)) stage_tile(t + 1);
+    if (t + 1 < ntile) stage_tile(t + 1);
     flush_cols(t - 1);                // complete since the barrier that ended iteration t - 1
     mma_tile(t);
     epi_tile(t);
@@ -648,7 +646,6 @@ __global__ __launch_bounds__(256) void k_gather(GatherArgs a) {
 }
 }  // namespace
 
-int g_head_ablate = 0;   // developer knob 18: timing-only ablations of the first sweep (wrong results)
 void launch_match_head_fused(const HeadArgs& a, hipStream_t s) {
   // small batches: split the column tiles of a pair over S workgroups per row block until the grid covers the chip
   const int nrb = a.npad / kHeadRows, ntile = a.npad / 64;
@@ -659,16 +656,6 @@ void launch_match_head_fused(const HeadArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((k_head_fused<true, 1>), grid, block, 0, s, a);
     hipLaunchKernelGGL((k_head_fused<true, 2>), grid, block, 0, s, a);
     g_last_kernel = "k_head_fused<true, 2>";
-  } else if (g_head_ablate) {
-    switch (g_head_ablate) {
-      case 1: hipLaunchKernelGGL((k_head_fused<false, 1, 1>), grid, block, 0, s, a); break;
-      case 2: hipLaunchKernelGGL((k_head_fused<false, 1, 2>), grid, block, 0, s, a); break;
-      case 4: hipLaunchKernelGGL((k_head_fused<false, 1, 4>), grid, block, 0, s, a); break;
-      case 8: hipLaunchKernelGGL((k_head_fused<false, 1, 8>), grid, block, 0, s, a); break;
-      case 6: hipLaunchKernelGGL((k_head_fused<false, 1, 6>), grid, block, 0, s, a); break;
-      default: hipLaunchKernelGGL((k_head_fused<false, 1, 14>), grid, block, 0, s, a); break;
-    }
-    hipLaunchKernelGGL((k_head_fused<false, 2>), grid, block, 0, s, a);
   } else {
     hipLaunchKernelGGL((k_head_fused<false, 1>), grid, block, 0, s, a);
     hipLaunchKernelGGL((k_head_fused<false, 2>), grid, block, 0, s, a);

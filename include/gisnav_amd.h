@@ -462,13 +462,15 @@ int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);
  * out3 = {launches recorded, total milliseconds, total algorithmic flops (2 M N K)}. */
 /* Developer knobs: select a kernel variant (which = 0: GEMM) for A/B benchmarking; run a pure
  * v_mfma_f32_32x32x2_f32 issue-rate probe (blocks x 256 threads x iters x 8 MFMAs per wave).
- * Knobs added in round 2 (value 0 restores the round-1 path unless noted): 10 block-tail fusion level, 12 k_ffn_fused ablations /
- * phase stamps, 13 out_proj folded into the tail, 14 k_ffn_fused workgroup shape (64 / 32 tokens), 15 PnP phase stamps,
- * 16 fused match head (0 = similarity GEMM + five passes), 17 / 18 k_head_fused phase stamps / ablations, 19 k_qkv projections
+ * Knobs added in round 2 (value 0 restores the round-1 path unless noted): 10 block-tail fusion level, 12 block-tail phase stamps
+ * (8; k_ffn128 also 136), 13 out_proj folded into the tail, 14 k_ffn_fused workgroup shape (64 / 32 tokens), 15 PnP phase stamps,
+ * 16 fused match head (0 = similarity GEMM + five passes), 17 k_head_fused phase stamps, 19 k_qkv projections
  * (0 = tiled GEMM, 2 = force at any batch size), 20 k_qkv phase stamps, 21 SuperPoint split-fp16 convolutions, 23 largest number of key ranges the
  * attention of a small batch is split into (default 1 = never; 4 gives -5 % latency at batch 1 but rounds the probabilities per split), 25 start the guard word of sub-batch group value - 1 raised (tests).  Knob 1 (attention) values: 4 default,
- * 43 / 44 / 45 / 46 / 48 rejected variants kept for A/B timing, 51-55 timing probes with WRONG results, 56 the exact running maximum in every key
- * tile (the path a workgroup of the default kernel falls back to).  A bench line run with any knob set records it in `debug_variant`.
+ * 5 k_attn16_v5 always, 56 the exact running maximum in every key tile (the path a workgroup of the default kernel falls back to), 60 the
+ * optimistic fp16 form, 70 / 73 k_attn_pw whenever it applies (73 with phase stamps), 80 / 81 k_attn_ks always (eight / four waves).  Knob 8: 0 / 1
+ * (the 256 x 256 GEMM k_gemm_p2w off / automatic).  Retired timing ablations and rejected experiments (knob 0 = 51-57, 61-67; knob 1 = 41-46,
+ * 48, 51-55, 57, 58, 71, 72, >= 1000; knob 8 >= 2; knob 12 other than 0 / 8 / 136; knob 18) return GN_ERR_ARG.  A bench line run with any knob set records it in `debug_variant`.
  * Process-wide knobs of late round 5 (every context; the shipped value is 0 unless noted): 41 largest 128 x 128 grid the exact-f32 GEMM leaves to 64-row
  * tiles (320; 0 = never), 42 LoFTR forms of rounds 3-4 (bit 0 staging without the register prefetch, bit 1 fine level over all max_matches windows
  * with interleaved sides, bit 2 the stem with [channel][tap] weights, bit 3 multiply the zero-padding channel steps, bit 4 no branch-free MFMA stream for the 128- / 256-channel layers; bits 8.. the overhead term of the

@@ -334,6 +334,19 @@ def test_c_abi_rejects_bad_arguments(eng256, dev):
         e.load_state_dict({"input_proj.weight": np.zeros((256, 64), np.float32)})
 
 
+def test_retired_developer_knob_values_are_refused(eng256_h2, state_dict_t, dev):
+    """Knob values of retired timing ablations and rejected experiments return an error instead of timing the default kernel under
+    their label; the context still matches the oracle afterwards."""
+    for which, value in ((1, 41), (1, 48), (1, 1000), (0, 51), (8, 2), (12, 1), (18, 1)):
+        assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, which, value) != 0, (which, value)
+    p = make_pair(63, n_q=129, n_r=128)
+    inp = eng256_h2.stage_inputs([p])
+    idx, score, n_match = eng256_h2.match(inp["desc_q"], inp["kpt_q"], inp["n_q"], inp["desc_r"], inp["kpt_r"], inp["n_r"])
+    _, _, _, oidx = oracle_match(state_dict_t, p)
+    k = int(n_match[0])
+    assert k == len(oidx) and np.array_equal(idx[0, :k].cpu().numpy(), oidx.numpy())
+
+
 # ------------------------------------------------------------------ the three seams
 def test_seam_b1_lightglue_matcher_drop_in(state_dict_np, state_dict_t, dev):
     from gisnav_amd.matcher import LightGlueMatcher

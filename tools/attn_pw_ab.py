@@ -1,6 +1,7 @@
 """Developer tool: k_attn_pw (knob 1 = 70: one wave per SIMD, 64 queries per wave, pinned order) against k_attn16_v5 (knob 1 = 4) in one
 process: (a) the attention op alone on random q / k / v with ragged key counts -- outputs compared with each other and with fp64 on the
-fp16-rounded operands; (b) a bench-sized matcher call -- correspondences, final features, per-kernel HIP-event times.
+fp16-rounded operands; (b) a bench-sized matcher call -- correspondences, final features, per-kernel HIP-event times; (c) with GN_AB_STAMPS=1,
+the phase stamps of k_attn_pw (knob 1 = 73).
 usage: attn_pw_ab.py [batch]"""
 import os
 import sys
@@ -77,15 +78,15 @@ for var in VARS[1:]:
     i1, s1, n1, x1 = res[var]
     same = all(np.array_equal(i0[b, : n0[b]], i1[b, : n1[b]]) for b in range(B)) and np.array_equal(n0, n1)
     print(f"variant {var} vs {VARS[0]}: final features max rel diff {np.abs(x1 - x0).max() / np.abs(x0).max():.3e}; finite {np.isfinite(x1).all()}; matches {n0[:4]} / {n1[:4]}; indices identical: {same}")
-for abl in [int(v) for v in os.environ.get("GN_AB_STAMPS", "").split(",") if v]:
-    eng.lib.gn_debug_set_variant(eng.ctx, 1, 1000 + abl)
+if os.environ.get("GN_AB_STAMPS"):
+    assert eng.lib.gn_debug_set_variant(eng.ctx, 1, 73) == 0
     eng.lib.gn_debug_set_variant(eng.ctx, 4, 3)       # stop after the first attention launch (input projection, k_qkv, attention)
     eng.match(*args)
     torch.cuda.synchronize()
     nwg = (N // 256) * 4 * 2 * B
     ts = eng.debug_read("sim", nwg * 4 * 8 * 2, np.uint32).view(np.int64).reshape(nwg, 4, 8)
     d = np.diff(ts[:, :, :6], axis=2).astype(np.float64)
-    print(f"k_attn_pw<{abl} | 8>: " + ", ".join(f"{nm} {np.median(d[:, 0, k]):.0f}" for k, nm in enumerate(["prologue", "sub-tile 0", "tile loop", "-", "rows out"]) if nm != "-")
+    print("k_attn_pw<true, 8>: " + ", ".join(f"{nm} {np.median(d[:, 0, k]):.0f}" for k, nm in enumerate(["prologue", "sub-tile 0", "tile loop", "-", "rows out"]) if nm != "-")
           + f"; per 64 keys {np.median(d[:, 0, 2] / np.maximum(ts[:, 0, 6], 1)):.0f}; workgroup {np.median(ts[:, 0, 5] - ts[:, 0, 0]):.0f} cycles", flush=True)
 eng.lib.gn_debug_set_variant(eng.ctx, 4, 0)
 eng.lib.gn_debug_set_variant(eng.ctx, 1, 4)

@@ -1,6 +1,6 @@
 """Developer tool: k_ffn128 (128 tokens per workgroup, knob 14 = 128) against k_ffn_fused (knob 14 = 64) in one process:
 final features / correspondences of a bench-sized call, per-kernel HIP-event times, and (optionally) the phase stamps of k_ffn128.
-usage: ffn128_ab.py [batch] [stamps]"""
+usage: ffn128_ab.py [batch] [stamps ...]   (stamps: 8 = per phase, 136 = also per k-tile of GEMM 1 and per quarter of GEMM 2)"""
 import os
 import sys
 
@@ -44,23 +44,23 @@ same = all(np.array_equal(i0[b, : n0[b]], i1[b, : n1[b]]) for b in range(B)) and
 print(f"final features: max rel diff {rel:.3e}; finite {np.isfinite(x1).all()}; matches per pair {n0[:4]} / {n1[:4]}; indices identical: {same}")
 names = ["prologue", "gemm0", "publish msg", "gemm1 msg", "gemm1 x", "ln stats", "gelu q0", "gemm2+gelu", "yt store", "epilogue"]
 order = [0, 1, 2, 3, 10, 4, 5, 6, 7, 8, 9]      # stamp 10 sits between the two halves of GEMM 1
-for abl in ([int(v) for v in sys.argv[2:]] if len(sys.argv) > 2 else []):
+for stamps in ([int(v) for v in sys.argv[2:]] if len(sys.argv) > 2 else []):
     eng.lib.gn_debug_set_variant(eng.ctx, 14, 128)
     eng.lib.gn_debug_set_variant(eng.ctx, 28, 1)
-    eng.lib.gn_debug_set_variant(eng.ctx, 12, abl)
+    assert eng.lib.gn_debug_set_variant(eng.ctx, 12, stamps) == 0, "knob 12: 8 or 136"
     eng.lib.gn_debug_set_variant(eng.ctx, 4, 5)       # stop after the first FFN launch: the stamps in `sim` are not overwritten by the head
     eng.match(*args)
     torch.cuda.synchronize()
     nb = T // 128
     ts = eng.debug_read("sim", nb * 4 * 12 * 2, np.uint32).view(np.int64).reshape(nb, 4, 12)[:, :, order]
     d = np.diff(ts, axis=2).astype(np.float64)
-    print(f"k_ffn128<{abl}> phase cycles, median over blocks (wave 0) / median of max over waves:")
+    print(f"k_ffn128<{stamps}> phase cycles, median over blocks (wave 0) / median of max over waves:")
     for k, nm in enumerate(names):
         print(f"  {nm:12s} {np.median(d[:, 0, k]):9.0f}   {np.median(d[:, :, k].max(axis=1)):9.0f}")
     tot = ts[:, 0, -1] - ts[:, 0, 0]
     raw = eng.debug_read("sim", nb * 4 * 12 * 2, np.uint32).view(np.int64).reshape(nb, 4, 12)
     print("  stamp 11 - stamp 5 (first pass of the exposed GELU quarters):", np.median(raw[:, 0, 11] - raw[:, 0, 5]))
-    if abl & 128:
+    if stamps & 128:
         t2 = eng.debug_read("sim", (nb * 4 * 12 + nb * 4 * 16) * 2, np.uint32).view(np.int64)[nb * 4 * 12:].reshape(nb, 4, 16)
         full = np.concatenate([raw[:, :, 3:4], t2], axis=2)
         print("  GEMM 1 per k-tile 4.. (wave 0, median):", " ".join(f"{v:.0f}" for v in np.median(np.diff(t2[:, 0, 4:], axis=1), axis=0)))

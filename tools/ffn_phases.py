@@ -1,4 +1,4 @@
-"""Developer tool: per-phase shader-clock stamps of k_ffn_fused (ablation 8), from the last FFN launch of one bench-sized call."""
+"""Developer tool: per-phase shader-clock stamps of k_ffn_fused (knob 12 = 8), from the last FFN launch of one bench-sized call."""
 import os
 import sys
 

@@ -16,8 +16,6 @@ inp = eng.stage_inputs([make_pair(i) for i in range(B)])
 args = (inp["desc_q"], inp["kpt_q"], inp["n_q"], inp["desc_r"], inp["kpt_r"], inp["n_r"])
 eng.match(*args)
 eng.lib.gn_debug_set_variant(eng.ctx, 17, 1)
-if len(sys.argv) > 2:
-    eng.lib.gn_debug_set_variant(eng.ctx, 18, int(sys.argv[2]))
 eng.match(*args)
 torch.cuda.synchronize()
 nrb = 1024 // 128
