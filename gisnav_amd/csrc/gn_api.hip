@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cctype>
 #include <algorithm>
-#include <memory>
+#include <tuple>
 
 using namespace gn;
 
@@ -34,6 +34,51 @@ struct Block {       // one SelfBlock or CrossBlock
 };
 
 enum Stage { ST_PREP = 0, ST_PROJ, ST_ATTN, ST_FFN, ST_HEAD, ST_GATHER, ST_PNP, ST_COUNT };
+
+// One matcher / estimate call: its per-pair arrays as pointers to the first pair, the strides that step from pair to pair, and the estimate's
+// call-wide inputs.  A per-pair array the call does not own stays null (the estimate path's idx / score live in the e_idx / e_score workspaces).
+struct Call {
+  int B = 0, kpt_format = 0, stride_q = 0, stride_r = 0;
+  const float *desc_q = nullptr, *kpt_q = nullptr, *desc_r = nullptr, *kpt_r = nullptr; const int32_t *n_q = nullptr, *n_r = nullptr;
+  const uint8_t* dem = nullptr; int H = 0, W = 0;
+  double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr; int64_t* idx = nullptr; float* score = nullptr;
+  const double* K9 = nullptr; int min_matches = 0;
+  int kw = 0, in_dim = 0; size_t km = 0;   // floats per keypoint, per descriptor; match-list stride (gn_kmax)
+  Call() = default;
+  Call(int feature, int npad, int B_, int kpt_format_, const float* desc_q_, const float* kpt_q_, const int32_t* n_q_, int stride_q_,
+       const float* desc_r_, const float* kpt_r_, const int32_t* n_r_, int stride_r_)
+      : B(B_), kpt_format(kpt_format_), stride_q(stride_q_), stride_r(stride_r_), desc_q(desc_q_), kpt_q(kpt_q_), desc_r(desc_r_), kpt_r(kpt_r_),
+        n_q(n_q_), n_r(n_r_), kw((kpt_format_ & 0xff) == GN_KPT_LAF ? 6 : (kpt_format_ & 0xff) == GN_KPT_RECORD ? kRecordFloats : 4),
+        in_dim(feature == GN_FEATURE_SIFT ? kInDim : kDim), km((size_t)npad) {}
+};
+
+// Every per-pair array of the calls `c...` (all of one shape, that of h), in one fixed order -- inputs, then outputs -- as f(bytes per pair, is output,
+// c.array...).  Slicing, the re-run's staging layout, its gather and its scatter all walk this list.
+template <typename F, typename... C> void pair_arrays(const Call& h, F&& f, C&... c) {
+  f((size_t)h.stride_q * h.in_dim * 4, false, c.desc_q...); f((size_t)h.stride_r * h.in_dim * 4, false, c.desc_r...);
+  f((size_t)h.stride_q * h.kw * 4, false, c.kpt_q...); f((size_t)h.stride_r * h.kw * 4, false, c.kpt_r...);
+  f((size_t)4, false, c.n_q...); f((size_t)4, false, c.n_r...); f((size_t)h.H * h.W, false, c.dem...);
+  f((size_t)72, true, c.R...); f((size_t)24, true, c.t...); f((size_t)4, true, c.n_match...); f((size_t)4, true, c.n_inliers...); f((size_t)1, true, c.ok...);
+  f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...);
+}
+template <typename T> T* byte_offset(T* p, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes); }
+
+// pairs [b0, b0 + n) of a call
+Call slice(const Call& v, size_t b0, int n) {
+  Call o = v;
+  o.B = n;
+  pair_arrays(o, [&](size_t bytes, bool, auto*& p) { if (p) p = byte_offset(p, b0 * bytes); }, o);
+  return o;
+}
+
+// Fields (of the context) restored to their values at construction when the scope ends: the one way this file overrides context state for a while
+template <typename... T> struct Restore {
+  std::tuple<T&...> ref; std::tuple<T...> val;
+  explicit Restore(T&... r) : ref(r...), val(r...) {}
+  ~Restore() { ref = val; }
+  Restore(const Restore&) = delete;
+  Restore& operator=(const Restore&) = delete;
+};
 
 }  // namespace
 
@@ -80,15 +125,14 @@ struct gn_ctx {
   // pairs from the SAVED arguments -- after call n + 1 has been enqueued (or in gn_flush), so the host never waits for an idle GPU
   struct CertPending {
     bool active = false; hipEvent_t ev = nullptr; int32_t* flags = nullptr;   // flags: pinned [max_batch]
-    int B = 0, kpt_format = 0, stride_q = 0, stride_r = 0, H = 0, W = 0, min_matches = 0, npad_run = 0, level = 0;
-    const float *desc_q = nullptr, *kpt_q = nullptr, *desc_r = nullptr, *kpt_r = nullptr; const int32_t *n_q = nullptr, *n_r = nullptr; const uint8_t* dem = nullptr;
-    double K9[9] = {0}; double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr;
+    int npad_run = 0, level = 0;
+    Call call; double K9[9] = {0};      // call.K9 points at K9, the saved copy of the caller's matrix
   } cert_pend[2];
   int cert_slot = 0;
   long long cert_calls = 0, cert_pairs = 0, cert_flag_margin = 0, cert_flag_range = 0, cert_rerun = 0, cert_f32_marginal = 0;
   int attn_f16 = 0;        // GN_PREC_F16X2_F16_ATTN: q | k rows, V^T panels and the probabilities are fp16 instead of bf16 (precision itself reads F16X2_BF16_ATTN);
                            // 2 = split: f32 q | k | v rows from the f16x2 projection GEMMs, k_attn_f16x2 (GN_PREC_F16X2_F16X2_ATTN, and the ladder's middle level)
-  // the certificate's re-run ladder (gn_set_certify_ladder): flagged pairs are re-run first in mode-5 arithmetic (MidScope) and certified there against
+  // the certificate's re-run ladder (gn_set_certify_ladder): flagged pairs are re-run first in mode-5 arithmetic (MidLevel) and certified there against
   // cert_eps_mid (< 0 = not calibrated: straight to exact f32); only the pairs still flagged go on to exact f32
   int ladder = 0; float cert_eps_mid = -1.f, cert_mid_measured = -1.f;
   long long mid_rerun = 0, mid_certified = 0, mid_passed = 0;
@@ -296,6 +340,23 @@ bool planes_of(gn_ctx* c, const float* p, uint16_t** planes) {
   return false;
 }
 
+// One recorded launch of the matcher schedule: stop_after bookkeeping, optional HIP events around it, and its row of the launch table (kernel
+// class 0 = projection / FFN / similarity GEMM, 1 = attention; algorithmic flops and bytes; the kernel's own name unless `name` is given).
+// Returns false when stop_after cut the launch.
+template <typename F> bool timed_launch(gn_ctx* c, hipStream_t s, int kclass, double flops, double bytes, const char* name, F&& launch) {
+  ++c->launch_count;
+  if (c->stop_after && c->launch_count > c->stop_after) return false;
+  const bool rec = c->ktiming && c->kused < c->kflops.size();
+  if (rec) hipEventRecord(c->kev[2 * c->kused], s);
+  launch();
+  if (rec) {
+    hipEventRecord(c->kev[2 * c->kused + 1], s);
+    c->kflops[c->kused] = flops; c->kbytes[c->kused] = bytes; c->kclass[c->kused] = kclass; c->kname[c->kused] = name ? name : gn::g_last_kernel;
+    ++c->kused;
+  }
+  return true;
+}
+
 void timed_gemm(gn_ctx* c, int epi, const GemmArgs& g_in, int batch, hipStream_t s) {
   if (c->gemm_variant >= 0) gn::g_gemm_variant = c->gemm_variant;
   GemmArgs g = g_in;
@@ -321,29 +382,15 @@ void timed_gemm(gn_ctx* c, int epi, const GemmArgs& g_in, int batch, hipStream_t
       else if (epi == EPI_LN_GELU && g.Y == c->h) { planes_of(c, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; g.Y = nullptr; }
     }
   }
-  ++c->launch_count;
-  if (c->stop_after && c->launch_count > c->stop_after) return;
-  const bool rec = c->ktiming && c->kused < c->kflops.size();
-  if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-  if (p2) launch_gemm_p2(epi, g, batch, s); else launch_gemm_f32(epi, g, batch, s);
-  if (rec) {
-    hipEventRecord(c->kev[2 * c->kused + 1], s);
-    c->kflops[c->kused] = 2.0 * g.M * (double)g.N * g.K * batch;
-    {   // compulsory bytes: A and W once (4 B per element as f32 or as an hm16 pair), every output array once, residual rows and
-        // rotary tables once
-      const double mn = (double)g.M * g.N * batch;
-      double by = 4.0 * ((double)g.M * g.K * batch + (double)g.N * g.K * (g.strideW ? batch : 1));
-      if (epi == EPI_ROTARY_BF16 || epi == EPI_SCALE_BF16) by += 2.0 * mn;
-      else if (epi == EPI_LN_GELU) by += 4.0 * mn;
-      else if (epi != EPI_LN_GELU) by += (g.Y ? 4.0 * mn : 0.0) + (g.Yp ? 4.0 * mn : 0.0);
-      if (epi == EPI_RESIDUAL) by += 4.0 * mn;
-      if (epi == EPI_ROTARY || epi == EPI_ROTARY_BF16) by += 2.0 * 4.0 * (double)g.M * kFreq;
-      c->kbytes[c->kused] = by;
-    }
-    c->kclass[c->kused] = 0;
-    c->kname[c->kused] = gn::g_last_kernel;
-    ++c->kused;
-  }
+  // compulsory bytes: A and W once (4 B per element as f32 or as an hm16 pair), every output array once, residual rows and rotary tables once
+  const double mn = (double)g.M * g.N * batch;
+  double by = 4.0 * ((double)g.M * g.K * batch + (double)g.N * g.K * (g.strideW ? batch : 1));
+  if (epi == EPI_ROTARY_BF16 || epi == EPI_SCALE_BF16) by += 2.0 * mn;
+  else if (epi == EPI_LN_GELU) by += 4.0 * mn;
+  else if (epi != EPI_LN_GELU) by += (g.Y ? 4.0 * mn : 0.0) + (g.Yp ? 4.0 * mn : 0.0);
+  if (epi == EPI_RESIDUAL) by += 4.0 * mn;
+  if (epi == EPI_ROTARY || epi == EPI_ROTARY_BF16) by += 2.0 * 4.0 * (double)g.M * kFreq;
+  timed_launch(c, s, 0, 2.0 * g.M * (double)g.N * g.K * batch, by, nullptr, [&] { if (p2) launch_gemm_p2(epi, g, batch, s); else launch_gemm_f32(epi, g, batch, s); });
 }
 
 void gemm(gn_ctx* c, int epi, GemmArgs& g, hipStream_t s) {
@@ -421,19 +468,9 @@ void attention(gn_ctx* c, const AttnArgs& a, hipStream_t s) {
 // one attention launch of the matcher schedule, optionally bracketed by HIP events (kernel class 1);
 // flops = QK^T + PV over full npad x npad score panels (the bench fills every slot)
 void timed_attention(gn_ctx* c, const AttnArgs& a, bool bf16v2, hipStream_t s) {
-  ++c->launch_count;
-  if (c->stop_after && c->launch_count > c->stop_after) return;
-  const bool rec = c->ktiming && c->kused < c->kflops.size();
-  if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-  if (bf16v2) launch_attention_bf16_v2(a, s); else attention(c, a, s);
-  if (rec) {
-    hipEventRecord(c->kev[2 * c->kused + 1], s);
-    c->kflops[c->kused] = 4.0 * a.BS * kHeads * (double)a.npad * a.npad * kHeadDim;
-    c->kbytes[c->kused] = (double)a.BS * a.npad * kDim * (a.qb ? 2.0 + 2.0 + 2.0 : 12.0) + (double)a.BS * a.npad * kDim * 4.0;   // q, k, v in; context rows out
-    c->kclass[c->kused] = 1;
-    c->kname[c->kused] = gn::g_last_kernel;
-    ++c->kused;
-  }
+  timed_launch(c, s, 1, 4.0 * a.BS * kHeads * (double)a.npad * a.npad * kHeadDim,
+               (double)a.BS * a.npad * kDim * (a.qb ? 2.0 + 2.0 + 2.0 : 12.0) + (double)a.BS * a.npad * kDim * 4.0,   // q, k, v in; context rows out
+               nullptr, [&] { if (bf16v2) launch_attention_bf16_v2(a, s); else attention(c, a, s); });
 }
 
 // q | k | v (or qk | v) projection of one block straight into the attention kernel's bf16 layouts; false when the shape / mode
@@ -459,20 +496,9 @@ bool qkv_projection(gn_ctx* c, const Block& blk, bool cross, int T, int np, int 
   q.tiles = (c->use_lists && c->lists && !c->qkv_stamps) ? c->lists : nullptr;
   q.products = c->qkv_products == 3 ? 3 : 2; q.ncu = c->ncu;
   q.dbg_ts = (c->qkv_stamps && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer knob 20
-  ++c->launch_count;
-  if (c->stop_after && c->launch_count > c->stop_after) return true;
-  const bool rec = c->ktiming && c->kused < c->kflops.size();
-  if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-  if (skinny) launch_skinny_qkv(q, cross, s); else launch_qkv(q, cross, s);
-  if (rec) {
-    const double N = cross ? 2.0 * kDim : 3.0 * kDim;
-    hipEventRecord(c->kev[2 * c->kused + 1], s);
-    c->kflops[c->kused] = 2.0 * T * N * kDim;
-    c->kbytes[c->kused] = 4.0 * T * kDim + 2.0 * T * N + 4.0 * N * kDim + (cross ? 0.0 : 2.0 * 4.0 * T * kFreq);   // x in (hm16), bf16 out, weights once, rotary tables
-    c->kclass[c->kused] = 0;
-    c->kname[c->kused] = gn::g_last_kernel;
-    ++c->kused;
-  }
+  const double N = cross ? 2.0 * kDim : 3.0 * kDim;
+  timed_launch(c, s, 0, 2.0 * T * N * kDim, 4.0 * T * kDim + 2.0 * T * N + 4.0 * N * kDim + (cross ? 0.0 : 2.0 * 4.0 * T * kFreq),   // x in (hm16), bf16 out, weights once, rotary tables
+               nullptr, [&] { if (skinny) launch_skinny_qkv(q, cross, s); else launch_qkv(q, cross, s); });
   return true;
 }
 
@@ -545,28 +571,13 @@ bool tail_should_walk(const gn_ctx* c) {
   return all > 0 && (unsigned long long)valid * 10u < (unsigned long long)all * 9u;
 }
 
-// x += ffn3(gelu(ln(ffn0([x | msg]))))
-// next / next_cross: the block whose attention input projection follows this tail (nullptr: none) -- when the tail runs as the composed k_ffn128 and that
-// projection is a k_qkv<., true, 2> launch, it is computed inside the tail instead; returns true when it was (the caller then skips the projection)
-// one recorded launch of the matcher schedule (kernel class 0): stop_after bookkeeping + optional HIP events around it
-template <typename F> bool timed_launch(gn_ctx* c, hipStream_t s, double flops, double bytes, F&& launch) {
-  ++c->launch_count;
-  if (c->stop_after && c->launch_count > c->stop_after) return false;
-  const bool rec = c->ktiming && c->kused < c->kflops.size();
-  if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-  launch();
-  if (rec) {
-    hipEventRecord(c->kev[2 * c->kused + 1], s);
-    c->kflops[c->kused] = flops; c->kbytes[c->kused] = bytes; c->kclass[c->kused] = 0; c->kname[c->kused] = gn::g_last_kernel;
-    ++c->kused;
-  }
-  return true;
-}
-
 inline bool ffn_auto(const gn_ctx* c) { return c->ffn_products == 0 && c->cert_eps_lvl[0] >= 0.f && c->cert_eps_lvl[1] >= 0.f && c->certify >= 2; }
 inline int ffn_level(const gn_ctx* c) { return c->attn_f16 == 2 ? 3 : c->ffn_products == 0 ? (ffn_auto(c) ? c->auto_level : 3) : c->ffn_products; }
 inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? c->cert_eps_lvl[c->auto_level - 2] : c->cert_eps; }
 
+// x += ffn3(gelu(ln(ffn0([x | msg]))))
+// next / next_cross: the block whose attention input projection follows this tail (nullptr: none) -- when the tail runs as the composed k_ffn128 and that
+// projection is a k_qkv<., true, 2> launch, it is computed inside the tail instead; returns true when it was (the caller then skips the projection)
 bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
   if (skinny_applies(c, T, np) && !(c->skinny & 8) && c->ffn_fused == 3 && c->ffn_compose && tail_folds_out_proj(c, blk, T) && blk.wfc && blk.b1c && !blk.comp_dirty && blk.ffn3.wfn &&
       c->h && c->ctx_p && gn::g_ffn_stamps == 0 && gn::g_ffn_shape == 0) {
@@ -575,8 +586,8 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     a.xp = c->x_p; a.cp = c->ctx_p; a.w1 = blk.wfc; a.w1_scale = blk.wfc_scale; a.b1 = blk.b1c; a.h = c->h; a.ln_g = blk.ln_g; a.ln_b = blk.ln_b;
     a.w2 = blk.ffn3.wfn; a.w2_scale = blk.ffn3.acc_scale; a.b2 = blk.ffn3.b; a.xp_out = c->x_p; a.y = keep_f32 ? c->x : nullptr;
     a.ovf = c->guard ? c->ovf : nullptr; a.T = T;
-    if (!timed_launch(c, s, 2.0 * T * 512.0 * 512.0, 4.0 * T * (256.0 + 256.0 + 512.0) + 4.0 * 512.0 * 512.0, [&] { launch_skinny_h(a, s, c->skinny >> 4); })) return false;
-    timed_launch(c, s, 2.0 * T * 256.0 * 512.0, 4.0 * T * (512.0 + 256.0 + 256.0) + 4.0 * 256.0 * 512.0, [&] { launch_skinny_out(a, s, c->skinny >> 4); });
+    if (!timed_launch(c, s, 0, 2.0 * T * 512.0 * 512.0, 4.0 * T * (256.0 + 256.0 + 512.0) + 4.0 * 512.0 * 512.0, nullptr, [&] { launch_skinny_h(a, s, c->skinny >> 4); })) return false;
+    timed_launch(c, s, 0, 2.0 * T * 256.0 * 512.0, 4.0 * T * (512.0 + 256.0 + 256.0) + 4.0 * 256.0 * 512.0, nullptr, [&] { launch_skinny_out(a, s, c->skinny >> 4); });
     return false;
   }
   if (c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && blk.ffn0.wf && blk.ffn3.wf && T % 64 == 0) {   // the whole tail in one launch
@@ -604,25 +615,14 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     }
     if (c->use_lists) { f.nvalid = c->nvalid; f.npad = c->npad_run; }
     f.dbg_ts = gn::g_ffn_stamps ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
-    ++c->launch_count;
-    if (c->stop_after && c->launch_count > c->stop_after) return false;
-    const bool rec = c->ktiming && c->kused < c->kflops.size();
-    if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-    launch_ffn_fused(f, s);
-    if (rec) {
-      hipEventRecord(c->kev[2 * c->kused + 1], s);
-      c->kflops[c->kused] = 2.0 * T * (512.0 * 512.0 + 256.0 * 512.0 + ((fold && !comp) ? 256.0 * 256.0 : 0.0));   // composed: the flops the kernel's own formulation needs (algorithmic: whatever the number of partial products)
-      c->kbytes[c->kused] = 4.0 * T * (256.0 + 256.0 + 256.0 + 256.0) + 4.0 * (512.0 * 512.0 + 256.0 * 512.0);   // x, msg, residual rows in; x out; weights once
-      if (fuse_qkv) {     // + the projection (k_qkv's figures without its read of the rows)
-        const double N = next_cross ? 2.0 * kDim : 3.0 * kDim;
-        c->kflops[c->kused] += 2.0 * T * N * kDim;
-        c->kbytes[c->kused] += 2.0 * T * N + 4.0 * N * kDim + (next_cross ? 0.0 : 2.0 * 4.0 * T * kFreq);
-      }
-      c->kclass[c->kused] = 0;
-      c->kname[c->kused] = gn::g_last_kernel;
-      ++c->kused;
+    double flops = 2.0 * T * (512.0 * 512.0 + 256.0 * 512.0 + ((fold && !comp) ? 256.0 * 256.0 : 0.0));   // composed: the flops the kernel's own formulation needs (algorithmic: whatever the number of partial products)
+    double bytes = 4.0 * T * (256.0 + 256.0 + 256.0 + 256.0) + 4.0 * (512.0 * 512.0 + 256.0 * 512.0);   // x, msg, residual rows in; x out; weights once
+    if (fuse_qkv) {     // + the projection (k_qkv's figures without its read of the rows)
+      const double N = next_cross ? 2.0 * kDim : 3.0 * kDim;
+      flops += 2.0 * T * N * kDim;
+      bytes += 2.0 * T * N + 4.0 * N * kDim + (next_cross ? 0.0 : 2.0 * 4.0 * T * kFreq);
     }
-    return fuse_qkv;
+    return timed_launch(c, s, 0, flops, bytes, nullptr, [&] { launch_ffn_fused(f, s); }) && fuse_qkv;
   }
   GemmArgs g = gemm_args(c->x, kDim, blk.ffn0, c->h, 2 * kDim, T);
   g.A2 = c->msg; g.lda2 = kDim; g.K1 = kDim;
@@ -645,11 +645,8 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
   return false;
 }
 
-int run_matcher(gn_ctx* c, int B, int kpt_format,
-                const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-                const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-                int64_t* idx, float* score, int32_t* n_match, hipStream_t s) {
-  const int np = c->npad_run, T = B * 2 * np, BS = B * 2;
+int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
+  const int B = v.B, np = c->npad_run, T = B * 2 * np, BS = B * 2;
   const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
   gn::g_attn_variant = c->attn_variant;
   gn::g_attn_stamps = (c->attn_variant == 73 && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;
@@ -660,9 +657,9 @@ int run_matcher(gn_ctx* c, int B, int kpt_format,
   {
     StageTimer tm(c, s, ST_PREP);
     PrepArgs p;
-    p.desc_q = desc_q; p.kpt_q = kpt_q; p.n_q = n_q; p.stride_q = stride_q;
-    p.desc_r = desc_r; p.kpt_r = kpt_r; p.n_r = n_r; p.stride_r = stride_r;
-    p.kpt_format = kpt_format; p.B = B; p.npad = np; p.wr = c->wr;
+    p.desc_q = v.desc_q; p.kpt_q = v.kpt_q; p.n_q = v.n_q; p.stride_q = v.stride_q;
+    p.desc_r = v.desc_r; p.kpt_r = v.kpt_r; p.n_r = v.n_r; p.stride_r = v.stride_r;
+    p.kpt_format = v.kpt_format; p.B = B; p.npad = np; p.wr = c->wr;
     p.desc = c->desc; p.kxy = nullptr; p.cos_t = c->cos_t; p.sin_t = c->sin_t; p.nvalid = c->nvalid; p.extent = c->extent;
     p.size_q[0] = c->size_q[0]; p.size_q[1] = c->size_q[1]; p.size_r[0] = c->size_r[0]; p.size_r[1] = c->size_r[1];
     p.feature = c->feature; p.x = nullptr; p.xp = nullptr;
@@ -768,25 +765,15 @@ int run_matcher(gn_ctx* c, int B, int kpt_format,
     hd.max0b = c->max0b; hd.rpart_c = c->rpart_c; hd.uncert = c->certify ? c->uncert : nullptr;
     hd.cert_eps = (c->precision == GN_PREC_F32) ? c->cert_eps_f32 : cert_eps_now(c);
     if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) { hd.uncert_alt = c->uncert_alt; hd.cert_eps_alt = c->cert_eps_lvl[3 - c->auto_level]; }
-    hd.idx = idx; hd.score = score; hd.n_match = n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
+    hd.idx = v.idx; hd.score = v.score; hd.n_match = v.n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
     hd.md = c->planes_mode ? (const void*)c->md_p : (const void*)c->md; hd.md_f32 = c->planes_mode ? 0 : 1;
     hd.cpart_m = c->cpart_m; hd.cpart_s = c->cpart_s; hd.cpart_i = c->cpart_i; hd.rpart_a = c->rpart_a; hd.rpart_b = c->rpart_b; hd.tickets = c->tickets;
     hd.dbg_ts = (c->head_stamps && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer knob 17
     if (c->cal_cols) { hd.colbest = c->colbest; hd.col2 = c->col2; }
-    if (c->head_fused || !c->sim) {
-      ++c->launch_count;
-      if (c->stop_after && c->launch_count > c->stop_after) return GN_OK;
-      const bool rec = c->ktiming && c->kused < c->kflops.size();
-      if (rec) hipEventRecord(c->kev[2 * c->kused], s);
-      launch_match_head_fused(hd, s);
-      if (rec) {   // both sweeps as one entry
-        hipEventRecord(c->kev[2 * c->kused + 1], s);
-        c->kflops[c->kused] = 2.0 * 2.0 * B * (double)np * np * kDim;                                   // the similarity tiles are computed twice
-        c->kbytes[c->kused] = 2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0;               // descriptors once per sweep, per-row / per-column statistics, matches
-        c->kclass[c->kused] = 0;
-        c->kname[c->kused] = "k_head_fused (2 sweeps)";
-        ++c->kused;
-      }
+    if (c->head_fused || !c->sim) {   // both sweeps as one entry
+      timed_launch(c, s, 0, 2.0 * 2.0 * B * (double)np * np * kDim,                         // the similarity tiles are computed twice
+                   2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0,            // descriptors once per sweep, per-row / per-column statistics, matches
+                   "k_head_fused (2 sweeps)", [&] { launch_match_head_fused(hd, s); });
       return GN_OK;
     }
     GemmArgs gs;
@@ -892,35 +879,35 @@ int selfcheck_fused_projection(gn_ctx* c) {
   GN_HIP(hipMemcpy(c->msg_p, c->x_p, xbytes, hipMemcpyDeviceToDevice));  // the rows every run starts from (the tail updates x_p in place)
   unsigned int* cnt = c->ovf_base + 12;                                 // (words 9..15 of the guard block are unused)
   GN_HIP(hipMemset(cnt, 0, sizeof(unsigned int)));
-  const int lists0 = c->use_lists, fused0 = c->qkv_in_tail, guard0 = c->guard; const bool kt0 = c->ktiming; const int lc0 = c->launch_count, sa0 = c->stop_after;
-  const int np_run0 = c->npad_run, prod0 = c->ffn_products;
-  c->ktiming = false; c->stop_after = 0; c->guard = 0; c->npad_run = np;
   bool applicable = true;
-  const int nblk = c->n_layers > 1 ? 1 : 0;
-  const int n_lv = (prod0 == 0 || prod0 == 2) ? 2 : 1;     // levels: 3, then 2 when the context can select it
-  for (int lv = 0; lv < n_lv && applicable; ++lv)
-  for (int cross = 0; cross < 2 && applicable; ++cross)
-    for (int walk = 0; walk < 2 && applicable; ++walk) {
-      c->ffn_products = lv == 0 ? 3 : 2;
-      const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
-      const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
-      c->use_lists = walk ? 2 : 3;
-      GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
-      GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
-      c->qkv_in_tail = 1;
-      if (!ffn(c, tail, T, 0, false, next, cross != 0, np, 1)) { applicable = false; break; }
-      GN_HIP(hipMemcpyAsync(keep_q, c->qkb, qbytes, hipMemcpyDeviceToDevice, 0));
-      GN_HIP(hipMemcpyAsync(keep_v, c->vtb, vbytes, hipMemcpyDeviceToDevice, 0));
-      GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
-      GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
-      c->qkv_in_tail = 0;
-      ffn(c, tail, T, 0, false, next, cross != 0, np, 1);
-      if (!qkv_projection(c, *next, cross != 0, T, np, 1, 0)) { applicable = false; break; }
-      hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_q), reinterpret_cast<const uint4*>(c->qkb), (cross ? qbytes / 2 : qbytes) / 16, cnt);
-      hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_v), reinterpret_cast<const uint4*>(c->vtb), vbytes / 16, cnt);
-    }
-  c->use_lists = lists0; c->qkv_in_tail = fused0; c->guard = guard0; c->ktiming = kt0; c->launch_count = lc0; c->stop_after = sa0;
-  c->npad_run = np_run0; c->ffn_products = prod0;
+  {
+    const Restore keep(c->use_lists, c->qkv_in_tail, c->guard, c->ktiming, c->launch_count, c->stop_after, c->npad_run, c->ffn_products);
+    const int prod0 = c->ffn_products;
+    c->ktiming = false; c->stop_after = 0; c->guard = 0; c->npad_run = np;
+    const int nblk = c->n_layers > 1 ? 1 : 0;
+    const int n_lv = (prod0 == 0 || prod0 == 2) ? 2 : 1;     // levels: 3, then 2 when the context can select it
+    for (int lv = 0; lv < n_lv && applicable; ++lv)
+    for (int cross = 0; cross < 2 && applicable; ++cross)
+      for (int walk = 0; walk < 2 && applicable; ++walk) {
+        c->ffn_products = lv == 0 ? 3 : 2;
+        const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
+        const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
+        c->use_lists = walk ? 2 : 3;
+        GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
+        c->qkv_in_tail = 1;
+        if (!ffn(c, tail, T, 0, false, next, cross != 0, np, 1)) { applicable = false; break; }
+        GN_HIP(hipMemcpyAsync(keep_q, c->qkb, qbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemcpyAsync(keep_v, c->vtb, vbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
+        c->qkv_in_tail = 0;
+        ffn(c, tail, T, 0, false, next, cross != 0, np, 1);
+        if (!qkv_projection(c, *next, cross != 0, T, np, 1, 0)) { applicable = false; break; }
+        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_q), reinterpret_cast<const uint4*>(c->qkb), (cross ? qbytes / 2 : qbytes) / 16, cnt);
+        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_v), reinterpret_cast<const uint4*>(c->vtb), vbytes / 16, cnt);
+      }
+  }
   unsigned int diffs = 0;
   GN_HIP(hipStreamSynchronize(0));
   GN_HIP(hipMemcpy(&diffs, cnt, sizeof diffs, hipMemcpyDeviceToHost));
@@ -938,9 +925,6 @@ int selfcheck_fused_projection(gn_ctx* c) {
   return GN_OK;
 }
 
-// The exact-f32 arithmetic inside a context of another precision, for the duration of a scope: GN_PREC_F32's kernels read the f32 weights (kept in
-// every mode) and the f32 workspaces (allocated in every mode); nothing of the hm16 / 16-bit state is touched.
-
 // gn_set_ffn_products(0): one certified call's flags (those of the level it ran on, and the other level's from the same scores) into the window
 void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt, int lvl) {      // lvl: the level the call ran on (a deferred call's: saved with it)
   if (!ffn_auto(c) || c->precision == GN_PREC_F32 || lvl < 2 || lvl > 3) return;
@@ -955,136 +939,99 @@ void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt
   c->auto_pairs = c->auto_wide = c->auto_narrow = 0;
 }
 
-struct F32Scope {
-  gn_ctx* c; int precision, planes_mode, gemm_variant, no_planes, attn_f16;
-  explicit F32Scope(gn_ctx* c_) : c(c_), precision(c_->precision), planes_mode(c_->planes_mode), gemm_variant(c_->gemm_variant), no_planes(c_->no_planes), attn_f16(c_->attn_f16) {
+// The arithmetics a call is run again in, each for the duration of a scope (counters and statistics are never part of one):
+// ExactF32 -- the certificate's re-run: GN_PREC_F32's kernels inside a context of another precision.  They read the f32 weights (kept in every mode) and
+//   the f32 workspaces (allocated in every mode); nothing of the hm16 / 16-bit state is touched.
+// MidLevel -- the ladder's middle level: GN_PREC_F16X2_F16X2_ATTN's arithmetic (f32 projection rows, k_attn_f16x2, three-product block tail) on this
+//   context's planes and split weights, certified against eps_mid.
+// F32x3 -- gn_set_guard(2)'s fallback when an activation left the fp16 range: every operand split exactly into three bf16 terms (f32 range, f32
+//   accuracy) on the f32 workspaces.  The weights stay as hm16 planes: f32x3 splits the f32 weights on the fly; the attention operands go back to
+//   bf16 (f32's exponent range).
+struct ExactF32 : Restore<int, int, int, int, int> {
+  explicit ExactF32(gn_ctx* c) : Restore(c->precision, c->planes_mode, c->gemm_variant, c->no_planes, c->attn_f16) {
     c->precision = GN_PREC_F32; c->planes_mode = 0; c->gemm_variant = 3; c->no_planes = 1; c->attn_f16 = 0;
   }
-  ~F32Scope() { c->precision = precision; c->planes_mode = planes_mode; c->gemm_variant = gemm_variant; c->no_planes = no_planes; c->attn_f16 = attn_f16; }
 };
+struct MidLevel : Restore<int, int, int, float> {
+  explicit MidLevel(gn_ctx* c) : Restore(c->attn_f16, c->ffn_products, c->dbg_trip_group, c->cert_eps) {
+    c->attn_f16 = 2; c->ffn_products = 3; c->dbg_trip_group = 0; c->cert_eps = c->cert_eps_mid;
+  }
+};
+struct F32x3 : Restore<int, int, int, int> {
+  explicit F32x3(gn_ctx* c) : Restore(c->planes_mode, c->gemm_variant, c->no_planes, c->attn_f16) {
+    c->planes_mode = 0; c->gemm_variant = 5; c->no_planes = 1; c->attn_f16 = 0;
+  }
+};
+inline bool ladder_active(const gn_ctx* c) { return c->ladder && c->cert_eps_mid >= 0.f && c->precision != GN_PREC_F32 && c->planes_mode && c->attn_f16 != 2; }
 
-// The per-pair arrays of a call (inputs, outputs), as pointers to its first pair, and what is needed to step from pair to pair
-struct CertView { const float *desc_q, *kpt_q, *desc_r, *kpt_r; const int32_t *n_q, *n_r; const uint8_t* dem;
-                  double *R, *t; int32_t *n_match, *n_inliers; uint8_t* ok; int64_t* idx; float* score; };
-struct CertShape { int stride_q, stride_r, H, W, kw, in_dim; size_t km; };
-CertView cert_view_at(const CertView& v, const CertShape& h, size_t b) {
-  CertView o = v;
-  if (v.desc_q) o.desc_q = v.desc_q + b * h.stride_q * h.in_dim;
-  if (v.desc_r) o.desc_r = v.desc_r + b * h.stride_r * h.in_dim;
-  o.kpt_q = v.kpt_q + b * h.stride_q * h.kw; o.kpt_r = v.kpt_r + b * h.stride_r * h.kw; o.n_q = v.n_q + b; o.n_r = v.n_r + b;
-  if (v.dem) o.dem = v.dem + b * (size_t)h.H * h.W;
-  if (v.R) o.R = v.R + b * 9;
-  if (v.t) o.t = v.t + b * 3;
-  o.n_match = v.n_match + b;
-  if (v.n_inliers) o.n_inliers = v.n_inliers + b;
-  if (v.ok) o.ok = v.ok + b;
-  if (v.idx) o.idx = v.idx + b * h.km * 2;
-  if (v.score) o.score = v.score + b * h.km;
-  return o;
-}
-
-// gn_set_certify(2 / 3): the per-pair flags of a call (read here from the device -- synchronises s -- or handed in), then the flagged pairs again with
-// the context switched to the exact-f32 arithmetic, through `run(view, n)` = matcher (+ gather + PnP) of n consecutive pairs.  One contiguous run of
-// flagged pairs is re-run IN PLACE (pointers and per-pair workspaces moved to its first pair).  Scattered flagged pairs are GATHERED into a staging
-// block first (device-to-device copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a
-// batched f32 call costs ~0.8 ms per pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
-// Counts what it saw (gn_get_certify_stats).
-// The flagged pairs `flagged` (ascending) of a call again, in whatever arithmetic the caller has switched the context to; rflags[k] = the re-run's
-// own certificate flag of flagged[k].
-template <typename F> int rerun_pairs(gn_ctx* ctx, int B, hipStream_t s, const CertShape& h, const CertView& v, F& run, const std::vector<int>& flagged,
-                                      std::vector<int32_t>& rflags) {
+// The flagged pairs `flagged` (ascending) of call v again, through `run(call)` = matcher (+ gather + PnP), in whatever arithmetic the caller has
+// switched the context to; rflags[k] = the re-run's own certificate flag of flagged[k].  One contiguous run of flagged pairs is re-run IN PLACE
+// (pointers and per-pair workspaces moved to its first pair).  Scattered flagged pairs are GATHERED into a staging block first (device-to-device
+// copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a batched f32 call costs ~0.8 ms per
+// pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
+template <typename F> int rerun_pairs(gn_ctx* ctx, hipStream_t s, const Call& v, F& run, const std::vector<int>& flagged, std::vector<int32_t>& rflags) {
   const int nf = (int)flagged.size();
   const bool contiguous = flagged.back() - flagged.front() + 1 == nf;
   int rc = GN_OK;
-  CertView st = v;          // staged view (compact form)
+  Call st = slice(v, 0, nf);      // staged call (compact form)
   if (!contiguous) {
     // staging block: [inputs of nf pairs | outputs of nf pairs], 256-byte aligned pieces; grown on demand, owned by the context
-    const size_t a256 = 255;
-    size_t off = 0;
-    auto piece = [&](size_t bytes) { const size_t o = off; off = (off + bytes + a256) & ~a256; return o; };
-    const size_t o_dq = v.desc_q ? piece((size_t)nf * h.stride_q * h.in_dim * 4) : 0, o_dr = v.desc_r ? piece((size_t)nf * h.stride_r * h.in_dim * 4) : 0;
-    const size_t o_kq = piece((size_t)nf * h.stride_q * h.kw * 4), o_kr = piece((size_t)nf * h.stride_r * h.kw * 4), o_nq = piece((size_t)nf * 4), o_nr = piece((size_t)nf * 4);
-    const size_t o_dem = v.dem ? piece((size_t)nf * h.H * h.W) : 0;
-    const size_t o_R = v.R ? piece((size_t)nf * 72) : 0, o_t = v.t ? piece((size_t)nf * 24) : 0, o_nm = piece((size_t)nf * 4), o_ni = v.n_inliers ? piece((size_t)nf * 4) : 0, o_ok = v.ok ? piece((size_t)nf) : 0;
-    const size_t o_idx = v.idx ? piece((size_t)nf * h.km * 16) : 0, o_sc = v.score ? piece((size_t)nf * h.km * 4) : 0;
-    if (off > ctx->cert_stage_bytes) {
+    auto place = [&](char* base) {
+      size_t off = 0;
+      pair_arrays(st, [&](size_t bytes, bool, auto*& p) {
+        if (!p) return;
+        if (base) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+        off = (off + nf * bytes + 255) & ~(size_t)255;
+      }, st);
+      return off;
+    };
+    const size_t need = place(nullptr);
+    if (need > ctx->cert_stage_bytes) {
       if (ctx->cert_stage) { GN_HIP(hipStreamSynchronize(s)); GN_HIP(hipFree(ctx->cert_stage)); ctx->cert_stage = nullptr; ctx->cert_stage_bytes = 0; }
-      GN_HIP(hipMalloc(&ctx->cert_stage, off));
-      ctx->cert_stage_bytes = off;
+      GN_HIP(hipMalloc(&ctx->cert_stage, need));
+      ctx->cert_stage_bytes = need;
     }
-    char* const base = static_cast<char*>(ctx->cert_stage);
-    st.desc_q = v.desc_q ? reinterpret_cast<const float*>(base + o_dq) : nullptr; st.desc_r = v.desc_r ? reinterpret_cast<const float*>(base + o_dr) : nullptr;
-    st.kpt_q = reinterpret_cast<const float*>(base + o_kq); st.kpt_r = reinterpret_cast<const float*>(base + o_kr);
-    st.n_q = reinterpret_cast<const int32_t*>(base + o_nq); st.n_r = reinterpret_cast<const int32_t*>(base + o_nr);
-    st.dem = v.dem ? reinterpret_cast<const uint8_t*>(base + o_dem) : nullptr;
-    st.R = v.R ? reinterpret_cast<double*>(base + o_R) : nullptr; st.t = v.t ? reinterpret_cast<double*>(base + o_t) : nullptr;
-    st.n_match = reinterpret_cast<int32_t*>(base + o_nm); st.n_inliers = v.n_inliers ? reinterpret_cast<int32_t*>(base + o_ni) : nullptr;
-    st.ok = v.ok ? reinterpret_cast<uint8_t*>(base + o_ok) : nullptr;
-    st.idx = v.idx ? reinterpret_cast<int64_t*>(base + o_idx) : nullptr; st.score = v.score ? reinterpret_cast<float*>(base + o_sc) : nullptr;
-    for (int k = 0; k < nf; ++k) {       // gather the inputs of flagged pair k into slot k
-      const CertView src = cert_view_at(v, h, (size_t)flagged[k]), dst = cert_view_at(st, h, (size_t)k);
-      auto cp = [&](const void* d, const void* q, size_t bytes) { return hipMemcpyAsync(const_cast<void*>(d), q, bytes, hipMemcpyDeviceToDevice, s); };
-      if (v.desc_q) GN_HIP(cp(dst.desc_q, src.desc_q, (size_t)h.stride_q * h.in_dim * 4));
-      if (v.desc_r) GN_HIP(cp(dst.desc_r, src.desc_r, (size_t)h.stride_r * h.in_dim * 4));
-      GN_HIP(cp(dst.kpt_q, src.kpt_q, (size_t)h.stride_q * h.kw * 4)); GN_HIP(cp(dst.kpt_r, src.kpt_r, (size_t)h.stride_r * h.kw * 4));
-      GN_HIP(cp(dst.n_q, src.n_q, 4)); GN_HIP(cp(dst.n_r, src.n_r, 4));
-      if (v.dem) GN_HIP(cp(dst.dem, src.dem, (size_t)h.H * h.W));
-    }
+    place(static_cast<char*>(ctx->cert_stage));
   }
+  // copies of one pair's inputs (gather) or outputs (scatter), in list order
+  auto copy_pair = [&](const Call& dst, size_t bd, const Call& src, size_t bs, bool outputs) {
+    hipError_t e = hipSuccess;
+    pair_arrays(v, [&](size_t bytes, bool out, auto* d, auto* q) {
+      if (d && out == outputs && e == hipSuccess)
+        e = hipMemcpyAsync(const_cast<void*>(static_cast<const void*>(byte_offset(d, bd * bytes))), byte_offset(q, bs * bytes), bytes, hipMemcpyDeviceToDevice, s);
+    }, dst, src);
+    return e;
+  };
+  if (!contiguous)
+    for (int k = 0; k < nf; ++k) GN_HIP(copy_pair(st, k, v, flagged[k], false));      // gather the inputs of flagged pair k into slot k
   {
-    const bool ig = ctx->in_group; unsigned int* const ovf = ctx->ovf;
+    const Restore keep(ctx->cert_inner, ctx->in_group, ctx->ovf);
     ctx->cert_inner = true; ctx->in_group = true; ctx->ovf = ctx->ovf_base;
     if (contiguous) {
       const int b0 = flagged.front();
       shift_workspaces(ctx, b0, +1);
-      rc = run(cert_view_at(v, h, (size_t)b0), nf);
+      rc = run(slice(v, b0, nf));
       shift_workspaces(ctx, b0, -1);
     } else {
-      rc = run(st, nf);
+      rc = run(st);
     }
-    ctx->cert_inner = false; ctx->in_group = ig; ctx->ovf = ovf;
   }
   if (rc != GN_OK) return rc;
-  if (!contiguous) {
-    for (int k = 0; k < nf; ++k) {       // scatter the outputs of slot k to flagged pair k
-      const CertView dst = cert_view_at(v, h, (size_t)flagged[k]), src = cert_view_at(st, h, (size_t)k);
-      auto cp = [&](void* d, const void* q, size_t bytes) { return hipMemcpyAsync(d, q, bytes, hipMemcpyDeviceToDevice, s); };
-      if (v.R) GN_HIP(cp(dst.R, src.R, 72));
-      if (v.t) GN_HIP(cp(dst.t, src.t, 24));
-      GN_HIP(cp(dst.n_match, src.n_match, 4));
-      if (v.n_inliers) GN_HIP(cp(dst.n_inliers, src.n_inliers, 4));
-      if (v.ok) GN_HIP(cp(dst.ok, src.ok, 1));
-      if (v.idx) GN_HIP(cp(dst.idx, src.idx, h.km * 16));
-      if (v.score) GN_HIP(cp(dst.score, src.score, h.km * 4));
-    }
-  }
-  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (!contiguous)
+    for (int k = 0; k < nf; ++k) GN_HIP(copy_pair(v, flagged[k], st, k, true));       // scatter the outputs of slot k to flagged pair k
+  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   GN_HIP(hipStreamSynchronize(s));
   rflags.resize(nf);
   for (int k = 0; k < nf; ++k) rflags[k] = ctx->uncert_host[contiguous ? flagged[k] : k];
   return GN_OK;
 }
 
-// The middle level of the re-run ladder for the duration of a scope: GN_PREC_F16X2_F16X2_ATTN's arithmetic (f32 projection rows, k_attn_f16x2, three-product
-// block tail) on this context's planes and split weights, certified against eps_mid.
-struct MidScope {
-  gn_ctx* c; int attn_f16, ffn_products, dbg_trip_group; float cert_eps;
-  explicit MidScope(gn_ctx* c_) : c(c_), attn_f16(c_->attn_f16), ffn_products(c_->ffn_products), dbg_trip_group(c_->dbg_trip_group), cert_eps(c_->cert_eps) {
-    c->attn_f16 = 2; c->ffn_products = 3; c->dbg_trip_group = 0; c->cert_eps = c->cert_eps_mid;
-  }
-  ~MidScope() { c->attn_f16 = attn_f16; c->ffn_products = ffn_products; c->dbg_trip_group = dbg_trip_group; c->cert_eps = cert_eps; }
-};
-inline bool ladder_active(const gn_ctx* c) { return c->ladder && c->cert_eps_mid >= 0.f && c->precision != GN_PREC_F32 && c->planes_mode && c->attn_f16 != 2; }
-
-// gn_set_certify(2 / 3): the per-pair flags of a call (read here from the device -- synchronises s -- or handed in), then the flagged pairs again with
-// the context switched to the exact-f32 arithmetic, through `run(view, n)` = matcher (+ gather + PnP) of n consecutive pairs.  One contiguous run of
-// flagged pairs is re-run IN PLACE (pointers and per-pair workspaces moved to its first pair).  Scattered flagged pairs are GATHERED into a staging
-// block first (device-to-device copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a
-// batched f32 call costs ~0.8 ms per pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
-// With the ladder on (gn_set_certify_ladder, eps_mid calibrated) the pairs flagged for margin go through the middle level first (MidScope, the same
-// gather / run / scatter); those it certifies keep its results, the rest -- and every pair flagged for range -- go on to exact f32.
+// gn_set_certify(2 / 3): the per-pair flags of call v (read here from the device -- synchronises s -- or handed in), then the flagged pairs again in
+// exact f32 (rerun_pairs).  With the ladder on (gn_set_certify_ladder, eps_mid calibrated) the pairs flagged for margin go through the middle level
+// first (the same gather / run / scatter); those it certifies keep its results, the rest -- and every pair flagged for range -- go on to exact f32.
 // Counts what it saw (gn_get_certify_stats, gn_get_certify_ladder_stats).
-template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const CertShape& h, const CertView& v, F&& run, const int32_t* flags_ready = nullptr, int flags_level = 0) {
+template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& v, F&& run, const int32_t* flags_ready = nullptr, int flags_level = 0) {
+  const int B = v.B;
   if (!flags_ready) {
     GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1107,7 +1054,7 @@ template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const
     std::vector<int> still(flagged.size() - margin.size());     // the pairs flagged for range first ...
     std::copy_if(flagged.begin(), flagged.end(), still.begin(), [&](int b) { return flags_ready[b] != 1; });
     int rc = GN_OK;
-    { MidScope mid(ctx); rc = rerun_pairs(ctx, B, s, h, v, run, margin, rflags); }
+    { const MidLevel mid(ctx); rc = rerun_pairs(ctx, s, v, run, margin, rflags); }
     if (rc != GN_OK) return rc;
     ctx->mid_rerun += (long long)margin.size();
     for (size_t k = 0; k < margin.size(); ++k) {
@@ -1119,12 +1066,61 @@ template <typename F> int certify_rerun(gn_ctx* ctx, int B, hipStream_t s, const
     if (flagged.empty()) return GN_OK;
   }
   int rc = GN_OK;
-  { F32Scope f32(ctx); rc = rerun_pairs(ctx, B, s, h, v, run, flagged, rflags); }
+  { const ExactF32 f32(ctx); rc = rerun_pairs(ctx, s, v, run, flagged, rflags); }
   ctx->cert_rerun += (long long)flagged.size();
   if (rc != GN_OK) return rc;
   // the re-run's own flags (stated for cert_eps_f32): how many of the pairs are marginal even in exact f32 -- counted, reported, not acted upon
   for (int32_t f : rflags) if (f != 0) ++ctx->cert_f32_marginal;
   return GN_OK;
+}
+
+// gn_calibrate_certify: one pass of the sample w (the whole sample, its first pair, or its first pair with the reference side cut) in arithmetic
+// `arith` -- 2 / 3 = the context's own on that block-tail level, kCalExactF32, kCalMid = the ladder's middle level -- and the host copies of every row's
+// best score and runner-up, of every column's when `cols`, of the per-slot counts when `nv`, and the guard word's trip bit (not read in exact f32)
+enum { kCalExactF32 = 0, kCalMid = 1 };
+struct CalPass { std::vector<float> best, second, colbest, col2; unsigned int trip = 0u; };
+int cal_pass(gn_ctx* ctx, const Call& w, int arith, bool cols, std::vector<int32_t>* nv, CalPass& out, hipStream_t s) {
+  int rc = GN_OK;
+  {
+    const Restore keep(ctx->in_group, ctx->cal_cols, ctx->ffn_products);
+    ctx->in_group = true;       // (no nested certification, ovf_groups_last untouched)
+    ctx->cal_cols = cols;
+    if (arith == kCalExactF32) { const ExactF32 f32(ctx); rc = run_matcher(ctx, w, s); }
+    else if (arith == kCalMid) { const MidLevel mid(ctx); rc = run_matcher(ctx, w, s); }
+    else { ctx->ffn_products = arith; rc = run_matcher(ctx, w, s); }
+  }
+  if (rc != GN_OK) return rc;
+  const size_t n = (size_t)w.B * ctx->npad_run;
+  out.best.resize(n); out.second.resize(n);
+  if (cols) { out.colbest.resize(n); out.col2.resize(n); }
+  auto get = [&](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+  const bool ok = hipStreamSynchronize(s) == hipSuccess && get(out.best.data(), ctx->max0, n * 4) && get(out.second.data(), ctx->max0b, n * 4) &&
+                  (!nv || get(nv->data(), ctx->nvalid, nv->size() * 4)) &&
+                  (!cols || (get(out.colbest.data(), ctx->colbest, n * 4) && get(out.col2.data(), ctx->col2, n * 4))) &&
+                  (arith == kCalExactF32 || !ctx->planes_mode || !ctx->guard || get(&out.trip, ctx->ovf, 4));
+  return ok ? GN_OK : GN_ERR_HIP;
+}
+
+// The largest difference between two passes (a: the arithmetic measured, e: exact f32) over the entries a decision looks at: the best score and
+// runner-up of every valid row -- and column when `cols` -- of pairs [0, Bp) with at least two keypoints per side, restricted to the entries that come
+// within 1 (in log units) of L in either arithmetic; over all of them when none does (a sample whose every decision is far away still calibrates,
+// which only makes eps larger).  *entries: how many the maximum was taken over.
+double max_diff(const CalPass& a, const CalPass& e, const std::vector<int32_t>& nv, int Bp, size_t np, bool cols, float L, long long* entries = nullptr) {
+  double mx = 0.0, mx_all = 0.0; long long n_near = 0, n_all = 0;
+  auto take = [&](float bm, float be, float sm, float se) {
+    const double d1 = std::fabs((double)bm - be), d2 = std::fabs((double)sm - se);
+    const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
+    ++n_all; mx_all = std::max(mx_all, d);
+    if (std::max(bm, be) >= L - 1.f) { ++n_near; mx = std::max(mx, d); }
+  };
+  for (int b = 0; b < Bp; ++b) {
+    const int n0 = nv[2 * b], n1 = nv[2 * b + 1];
+    if (n0 < 2 || n1 < 2) continue;
+    for (int i = 0; i < n0; ++i) { const size_t o = (size_t)b * np + i; take(a.best[o], e.best[o], a.second[o], e.second[o]); }
+    for (int j = 0; cols && j < n1; ++j) { const size_t o = (size_t)b * np + j; take(a.colbest[o], e.colbest[o], a.col2[o], e.col2[o]); }
+  }
+  if (entries) *entries = n_near ? n_near : n_all;
+  return n_near ? mx : mx_all;
 }
 
 int check_fwd(gn_ctx* ctx, int B, int stride_q, int stride_r) {
@@ -1134,6 +1130,7 @@ int check_fwd(gn_ctx* ctx, int B, int stride_q, int stride_r) {
   if (stride_q < 1 || stride_r < 1 || stride_q > ctx->npad || stride_r > ctx->npad)
     return fail(ctx, GN_ERR_ARG, "keypoint stride exceeds max_kpts of this context");
   if (gn_missing_tensors(ctx) != 0) return fail(ctx, GN_ERR_WEIGHTS, "weights not fully loaded");
+  GN_HIP(hipSetDevice(ctx->device));          // (before anything below touches the GPU: the caller's current device need not be the context's)
   const int rc_c = ensure_composed(ctx);      // (host work on the first call after a (re)load only)
   if (rc_c != GN_OK) return rc_c;
   if (ctx->fused_proj_pending && !ctx->in_group && !ctx->cert_inner) return selfcheck_fused_projection(ctx);
@@ -1406,38 +1403,27 @@ int gn_match(gn_ctx* ctx, int B, int kpt_format,
   if (kfmt == GN_KPT_RECORD && ctx->feature != GN_FEATURE_SIFT) return fail(ctx, GN_ERR_ARG, "GN_KPT_RECORD (KEYPOINT_DTYPE wire records) needs a SIFT context");
   if (((!desc_q || !desc_r) && kfmt != GN_KPT_RECORD) || !kpt_q || !n_q || !kpt_r || !n_r || !idx || !score || !n_match)
     return fail(ctx, GN_ERR_ARG, "null pointer passed to gn_match");
-  GN_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
   ctx->n_ev = 0;
   if (!ctx->in_group) ctx->ovf_groups_last = 1;
-  rc = run_matcher(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, idx, score, n_match,
-                   (hipStream_t)stream);
+  Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
+  v.idx = idx; v.score = score; v.n_match = n_match;
+  rc = run_matcher(ctx, v, s);
   if (rc != GN_OK) return rc;
   if (ctx->certify >= 2 && !ctx->in_group && !ctx->cert_inner) {
     // certified mode (3 = deferred exists for gn_estimate's sub-batch-stream path only; everywhere else it is 2): read this call's per-pair flags (one stream synchronisation -- the reference's call site synchronises right after the
     // matcher anyway, pose_node.py:296-297) and run the flagged pairs again on the exact-f32 kernels; covers the fp16-range fallback too
-    const int kw = kfmt == GN_KPT_LAF ? 6 : kfmt == GN_KPT_RECORD ? kRecordFloats : 4;
-    const int in_dim = ctx->feature == GN_FEATURE_SIFT ? kInDim : kDim;
-    const size_t km = (size_t)ctx->npad;
-    const CertShape shp{stride_q, stride_r, 0, 0, kw, in_dim, km};
-    const CertView view{desc_q, kpt_q, desc_r, kpt_r, n_q, n_r, nullptr, nullptr, nullptr, n_match, nullptr, nullptr, idx, score};
-    rc = certify_rerun(ctx, B, (hipStream_t)stream, shp, view, [&](const CertView& w, int n) {
-      return run_matcher(ctx, n, kpt_format, w.desc_q, w.kpt_q, w.n_q, stride_q, w.desc_r, w.kpt_r, w.n_r, stride_r, w.idx, w.score, w.n_match, (hipStream_t)stream);
-    });
+    rc = certify_rerun(ctx, s, v, [&](const Call& w) { return run_matcher(ctx, w, s); });
     if (rc != GN_OK) return rc;
   } else if (ctx->planes_mode && ctx->guard == 2 && ctx->certify < 2) {
     // guarded mode: observe the domain word of THIS call (one stream synchronisation -- the reference's call site synchronises
-    // right after the matcher anyway, pose_node.py:296-297) and, if an activation left the fp16 range, run the call again with
-    // every operand split exactly into three bf16 terms (the f32x3 mode: f32 range, f32 accuracy), on the f32 workspaces
-    GN_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+    // right after the matcher anyway, pose_node.py:296-297) and, if an activation left the fp16 range, run the call again in f32x3
+    GN_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
     if (*ctx->ovf_host != 0u) {
       ++ctx->guard_trips;
-      const int pm = ctx->planes_mode, gv = ctx->gemm_variant, npl = ctx->no_planes, af = ctx->attn_f16;
-      ctx->planes_mode = 0; ctx->gemm_variant = 5; ctx->no_planes = 1;   // weights stay as hm16 planes: f32x3 splits the f32 weights on the fly
-      ctx->attn_f16 = 0;                                                   // and the attention operands go back to bf16 (f32's exponent range)
-      rc = run_matcher(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, idx, score, n_match,
-                       (hipStream_t)stream);
-      ctx->planes_mode = pm; ctx->gemm_variant = gv; ctx->no_planes = npl; ctx->attn_f16 = af;
+      const F32x3 f32x3(ctx);
+      rc = run_matcher(ctx, v, s);
       if (rc != GN_OK) return rc;
     }
   }
@@ -1531,74 +1517,34 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   if (!(safety >= 1.f) || !(floor_eps >= 0.f)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: safety must be >= 1, floor_eps >= 0");
   if (ctx->precision == GN_PREC_F32) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: this context already computes in exact f32");
   if (ctx->n_sub > 1 || ctx->overlap) { const int rcf = gn_flush(ctx, stream); if (rcf != GN_OK) return rcf; }
-  GN_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
-  const size_t np = (size_t)ctx->npad_run, n = (size_t)B * np;
+  const size_t np = (size_t)ctx->npad_run;
   int32_t* nm = nullptr;
   GN_HIP(hipMalloc((void**)&nm, (size_t)B * sizeof(int32_t)));
+  Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
+  v.idx = ctx->e_idx; v.score = ctx->e_score; v.n_match = nm;
   // passes: the context's arithmetic -- on BOTH block-tail levels under gn_set_ffn_products(0) -- then the exact-f32 kernels
   const int setting = ctx->ffn_products;
   const int n_lv = setting == 0 ? 2 : 1;
   const int lv[2] = {setting == 0 ? 2 : setting, 3};
-  std::vector<float> best[3], second[3];
+  const float L = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
+  CalPass whole[3];
   std::vector<int32_t> nv(2 * (size_t)B);
   unsigned int tripped = 0u;
   const bool lad = ctx->ladder && ctx->planes_mode && ctx->attn_f16 != 2;   // (gn_set_certify_ladder refuses every other context)
-  std::vector<float> cb_f32, c2_f32;                 // the exact pass's column best / runner-up (ladder only)
-  for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
-    std::unique_ptr<F32Scope> f32;
-    if (pass == n_lv) { f32.reset(new F32Scope(ctx)); ctx->cal_cols = lad; } else ctx->ffn_products = lv[pass];
-    const bool ig = ctx->in_group; ctx->in_group = true;       // (no nested certification, ovf_groups_last untouched)
-    rc = run_matcher(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, ctx->e_idx, ctx->e_score, nm, s);
-    ctx->in_group = ig; ctx->ffn_products = setting; ctx->cal_cols = false;
-    if (rc != GN_OK) break;
-    best[pass].resize(n); second[pass].resize(n);
-    unsigned int trip = 0u;
-    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(best[pass].data(), ctx->max0, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(second[pass].data(), ctx->max0b, n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(nv.data(), ctx->nvalid, nv.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (pass < n_lv && ctx->planes_mode && ctx->guard && hipMemcpy(&trip, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = GN_ERR_HIP;
-    if (rc == GN_OK && lad && pass == n_lv) {
-      cb_f32.resize(n); c2_f32.resize(n);
-      if (hipMemcpy(cb_f32.data(), ctx->colbest, n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c2_f32.data(), ctx->col2, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = GN_ERR_HIP;
-    }
-    tripped |= trip;
+  for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {      // (the exact pass keeps the column best / runner-up for the ladder)
+    rc = cal_pass(ctx, v, pass == n_lv ? kCalExactF32 : lv[pass], pass == n_lv && lad, &nv, whole[pass], s);
+    tripped |= whole[pass].trip;
   }
   // the ladder's middle level: mode-5 arithmetic on the whole sample and on its first pair alone (the ladder mostly runs small grids, whose kernels
   // differ), against the exact pass above, over every valid row's AND column's best score and runner-up
   double mid_mx = -1.0;
   for (int mp = 0; lad && mp < 2 && rc == GN_OK && !tripped; ++mp) {
-    const int Bm = mp == 0 ? B : 1;
-    std::vector<float> rb(n), r2(n), cb(n), c2(n);
-    unsigned int trip = 0u;
-    {
-      MidScope mid(ctx);
-      const bool ig = ctx->in_group; ctx->in_group = true; ctx->cal_cols = true;
-      rc = run_matcher(ctx, Bm, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, ctx->e_idx, ctx->e_score, nm, s);
-      ctx->in_group = ig; ctx->cal_cols = false;
-    }
+    CalPass mid;
+    rc = cal_pass(ctx, slice(v, 0, mp == 0 ? B : 1), kCalMid, true, nullptr, mid, s);
     if (rc != GN_OK) break;
-    const size_t nb = (size_t)Bm * np;
-    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(rb.data(), ctx->max0, nb * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(r2.data(), ctx->max0b, nb * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cb.data(), ctx->colbest, nb * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(c2.data(), ctx->col2, nb * 4, hipMemcpyDeviceToHost) != hipSuccess || (ctx->guard && hipMemcpy(&trip, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) { rc = GN_ERR_HIP; break; }
-    tripped |= trip;
-    const float Lm = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
-    double mx = 0.0, mx_all = 0.0; long long cnt = 0;
-    auto take = [&](float bm, float be, float sm, float se) {
-      const double d1 = std::fabs((double)bm - be), d2 = std::fabs((double)sm - se);
-      const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
-      mx_all = std::max(mx_all, d);
-      if (std::max(bm, be) >= Lm - 1.f) { ++cnt; mx = std::max(mx, d); }
-    };
-    for (int b = 0; b < Bm; ++b) {
-      const int n0 = nv[2 * b], n1 = nv[2 * b + 1];
-      if (n0 < 2 || n1 < 2) continue;
-      for (int i = 0; i < n0; ++i) { const size_t o = (size_t)b * np + i; take(rb[o], best[n_lv][o], r2[o], second[n_lv][o]); }
-      for (int j = 0; j < n1; ++j) { const size_t o = (size_t)b * np + j; take(cb[o], cb_f32[o], c2[o], c2_f32[o]); }
-    }
-    if (cnt == 0) mx = mx_all;
-    mid_mx = std::max(mid_mx, mx);
+    tripped |= mid.trip;
+    mid_mx = std::max(mid_mx, max_diff(mid, whole[n_lv], nv, mp == 0 ? B : 1, np, true, L));
   }
   // the sample's first pair alone, and with its reference side cut to 128 and to 2 keypoints: the one-pair grid of bucket remainders, and the
   // few-keypoint sides of a ragged stream, where the fp16 attention's rounding averages over few keys (measured against fp64 on a ragged bulk
@@ -1606,63 +1552,29 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   double var_mx[2] = {0.0, 0.0};
   int32_t* nr1 = nullptr;
   if (rc == GN_OK && !tripped && nv[0] >= 2 && nv[1] >= 2 && hipMalloc((void**)&nr1, sizeof(int32_t)) != hipSuccess) rc = GN_ERR_HIP;
+  Call v1 = slice(v, 0, 1);
+  v1.n_r = nr1;
   for (int var = 0; nr1 && rc == GN_OK && var < 3; ++var) {
     const int32_t nr_cut = var == 0 ? nv[1] : std::min(nv[1], var == 1 ? 128 : 2);
     if (hipMemcpy(nr1, &nr_cut, sizeof nr_cut, hipMemcpyHostToDevice) != hipSuccess) { rc = GN_ERR_HIP; break; }
-    std::vector<float> vb[3], vs[3];
+    CalPass p[3];
     unsigned int trip = 0u;
     for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
-      std::unique_ptr<F32Scope> f32;
-      if (pass == n_lv) f32.reset(new F32Scope(ctx)); else ctx->ffn_products = lv[pass];
-      const bool ig = ctx->in_group; ctx->in_group = true;
-      rc = run_matcher(ctx, 1, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, nr1, stride_r, ctx->e_idx, ctx->e_score, nm, s);
-      ctx->in_group = ig; ctx->ffn_products = setting;
-      if (rc != GN_OK) break;
-      vb[pass].resize(np); vs[pass].resize(np);
-      unsigned int t = 0u;
-      if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(vb[pass].data(), ctx->max0, np * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(vs[pass].data(), ctx->max0b, np * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-          (pass < n_lv && ctx->planes_mode && ctx->guard && hipMemcpy(&t, ctx->ovf, 4, hipMemcpyDeviceToHost) != hipSuccess)) rc = GN_ERR_HIP;
-      trip |= t;
+      rc = cal_pass(ctx, v1, pass == n_lv ? kCalExactF32 : lv[pass], false, nullptr, p[pass], s);
+      trip |= p[pass].trip;
     }
     if (rc != GN_OK || trip) continue;          // (a pass that left the fp16 range is re-run as a whole by the certificate: nothing to measure)
-    const float Lv = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
-    for (int k = 0; k < n_lv; ++k) {
-      double mx = 0.0, mx_all = 0.0; long long rows = 0;
-      for (int i = 0; i < nv[0]; ++i) {
-        const double d1 = std::fabs((double)vb[k][i] - vb[n_lv][i]), d2 = std::fabs((double)vs[k][i] - vs[n_lv][i]);
-        const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
-        mx_all = std::max(mx_all, d);
-        if (std::max(vb[k][i], vb[n_lv][i]) >= Lv - 1.f) { ++rows; mx = std::max(mx, d); }
-      }
-      var_mx[k] = std::max(var_mx[k], rows ? mx : mx_all);
-    }
+    for (int k = 0; k < n_lv; ++k) var_mx[k] = std::max(var_mx[k], max_diff(p[k], p[n_lv], nv, 1, np, false, L));
   }
   if (nr1) hipFree(nr1);
   hipFree(nm);
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
   if (tripped) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample left the fp16 range of this precision mode (nothing to calibrate: such calls are re-run as a whole)");
-  // largest difference between the two arithmetics over the entries a decision looks at: every valid row's best score and runner-up,
-  // restricted -- when there is a threshold -- to rows that come within 1 (in log units) of it in either arithmetic
-  const float L = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
+  // largest difference between the two arithmetics over every valid row's best score and runner-up (max_diff)
   float eps_of[2] = {0.f, 0.f}, mx_of[2] = {0.f, 0.f};
   for (int k = 0; k < n_lv; ++k) {
-    double mx = 0.0, mx_all = 0.0; long long rows = 0, rows_all = 0;
-    for (int b = 0; b < B; ++b) {
-      const int n0 = nv[2 * b], n1 = nv[2 * b + 1];
-      if (n0 < 2 || n1 < 2) continue;
-      for (int i = 0; i < n0; ++i) {
-        const size_t o = (size_t)b * np + i;
-        const float bf = best[k][o], be = best[n_lv][o], sf = second[k][o], se = second[n_lv][o];
-        const double d1 = std::fabs((double)bf - be), d2 = std::fabs((double)sf - se);
-        const double d = std::max(std::isfinite(d1) ? d1 : (double)INFINITY, std::isfinite(d2) ? d2 : 0.0);
-        ++rows_all; mx_all = std::max(mx_all, d);
-        if (!(std::max(bf, be) >= L - 1.f)) continue;
-        ++rows; mx = std::max(mx, d);
-      }
-    }
-    // (a sample without any row near the threshold -- every decision far away -- still calibrates: over all rows, which only makes eps larger)
-    if (rows == 0) { mx = mx_all; rows = rows_all; }
+    long long rows = 0;
+    double mx = max_diff(whole[k], whole[n_lv], nv, B, np, false, L, &rows);
     if (!std::isfinite(mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the sample");
     if (rows == 0) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample holds no pair with at least two keypoints per side (nothing to measure)");
     if (!std::isfinite(var_mx[k])) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the one-pair passes");
@@ -1787,31 +1699,51 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   mv(c->lists, c->lists_stride);
 }
 
-int estimate_impl(gn_ctx* ctx, int B, int kpt_format,
-                  const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-                  const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-                  const uint8_t* dem, int H, int W, const double* K9, int min_matches,
-                  double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream);
+int estimate_impl(gn_ctx* ctx, const Call& v, void* stream) {
+  if (!ctx->overlap) {
+    int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
+                      ctx->e_idx, ctx->e_score, v.n_match, stream);
+    if (rc != GN_OK) return rc;
+    rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
+                          ctx->e_mkp, ctx->e_obj, stream);
+    if (rc != GN_OK) return rc;
+    return gn_pnp_ransac(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+                         v.R, v.t, v.n_inliers, v.ok, stream);
+  }
+  // Overlapped pose stage: the latency-bound PnP kernels (a few hundred single-wave workgroups) of this call run on an
+  // internal stream while the caller's stream is free to start the next call's matcher.  The PnP inputs are
+  // double-buffered; R / t / n_inliers / ok of this call are complete once gn_flush() has been ordered behind it.
+  hipStream_t s = (hipStream_t)stream;
+  const int slot = (int)(ctx->calls++ & 1);
+  GN_HIP(hipSetDevice(ctx->device));
+  if (ctx->pnp_pending[slot]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot], 0));   // the PnP that last read this slot
+  int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
+                    ctx->e_idx, ctx->e_score, v.n_match, stream);
+  if (rc != GN_OK) return rc;
+  rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
+                        ctx->o_mkp[slot], ctx->o_obj[slot], stream);
+  if (rc != GN_OK) return rc;
+  GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  GN_HIP(hipEventRecord(ctx->ev_gather[slot], s));
+  GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot], 0));
+  rc = gn_pnp_ransac(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+                     v.R, v.t, v.n_inliers, v.ok, ctx->s_pnp);
+  if (rc != GN_OK) return rc;
+  GN_HIP(hipEventRecord(ctx->ev_pnp[slot], ctx->s_pnp));
+  ctx->pnp_pending[slot] = true;
+  return GN_OK;
+}
 
 // deferred certificate: wait for the flags of the pending call in `slot` (its kernels are behind at most one later call on the GPU), re-run
-// its flagged pairs from the saved arguments on `s`
+// its flagged pairs from the saved call on `s`
 int cert_resolve(gn_ctx* ctx, int slot, hipStream_t s) {
   gn_ctx::CertPending& p = ctx->cert_pend[slot];
   if (!p.active) return GN_OK;
   p.active = false;
   GN_HIP(hipEventSynchronize(p.ev));
-  const int kw = (p.kpt_format & 0xff) == GN_KPT_LAF ? 6 : (p.kpt_format & 0xff) == GN_KPT_RECORD ? kRecordFloats : 4;
-  const int in_dim = ctx->feature == GN_FEATURE_SIFT ? kInDim : kDim;
-  const int np_now = ctx->npad_run;
+  const Restore keep(ctx->npad_run);
   ctx->npad_run = p.npad_run;
-  const CertShape shp{p.stride_q, p.stride_r, p.H, p.W, kw, in_dim, (size_t)ctx->npad};
-  const CertView view{p.desc_q, p.kpt_q, p.desc_r, p.kpt_r, p.n_q, p.n_r, p.dem, p.R, p.t, p.n_match, p.n_inliers, p.ok, nullptr, nullptr};
-  const int rc = certify_rerun(ctx, p.B, s, shp, view, [&](const CertView& w, int n) {
-    return estimate_impl(ctx, n, p.kpt_format, w.desc_q, w.kpt_q, w.n_q, p.stride_q, w.desc_r, w.kpt_r, w.n_r, p.stride_r, w.dem, p.H, p.W, p.K9, p.min_matches,
-                         w.R, w.t, w.n_match, w.n_inliers, w.ok, s);
-  }, p.flags, p.level);
-  ctx->npad_run = np_now;
-  return rc;
+  return certify_rerun(ctx, s, p.call, [&](const Call& w) { return estimate_impl(ctx, w, s); }, p.flags, p.level);
 }
 }  // namespace
 
@@ -1827,10 +1759,11 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
     if (rcs == GN_OK) rcs = selfcheck_fused_projection(ctx);
     if (rcs != GN_OK) return rcs;
   }
+  Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
+  v.dem = dem; v.H = H; v.W = W; v.K9 = K9; v.min_matches = min_matches;
+  v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
   const int groups = std::min(ctx->n_sub, B);
-  if (groups <= 1 || ctx->overlap)
-    return estimate_impl(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, dem, H, W, K9, min_matches,
-                         R, t, n_match, n_inliers, ok, stream);
+  if (groups <= 1 || ctx->overlap) return estimate_impl(ctx, v, stream);
   if (ctx->npad <= 0) return fail(ctx, GN_ERR_ARG, "context has no workspaces (a gn_resize failed): call gn_resize again");
   if (B < 1 || B > ctx->max_batch) return fail(ctx, GN_ERR_ARG, "B out of range for this context");
   GN_HIP(hipSetDevice(ctx->device));
@@ -1844,8 +1777,6 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
   ctx->sub_last_B = B; ctx->sub_last_np = ctx->npad_run;
   ctx->ovf_groups_last = groups;
   GN_HIP(hipEventRecord(ctx->ev_fork, s));
-  const int kw = (kpt_format & 0xff) == GN_KPT_LAF ? 6 : (kpt_format & 0xff) == GN_KPT_RECORD ? kRecordFloats : 4;
-  const int in_dim = ctx->feature == GN_FEATURE_SIFT ? kInDim : kDim;
   int rc_all = GN_OK, b0 = 0;
   for (int g = 0; g < groups; ++g) {
     const int Bg = B / groups + (g < B % groups ? 1 : 0);
@@ -1853,11 +1784,7 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
     GN_HIP(hipStreamWaitEvent(sg, ctx->ev_fork, 0));
     shift_workspaces(ctx, b0, +1);
     ctx->in_group = true; ctx->ovf = ctx->ovf_base + g;            // this group's own guard word: cleared, raised and read on this group's stream only
-    const int rc = estimate_impl(ctx, Bg, kpt_format,
-                                 desc_q ? desc_q + (size_t)b0 * stride_q * in_dim : nullptr, kpt_q + (size_t)b0 * stride_q * kw, n_q + b0, stride_q,
-                                 desc_r ? desc_r + (size_t)b0 * stride_r * in_dim : nullptr, kpt_r + (size_t)b0 * stride_r * kw, n_r + b0, stride_r,
-                                 dem ? dem + (size_t)b0 * H * W : nullptr, H, W, K9, min_matches,
-                                 R + (size_t)b0 * 9, t + (size_t)b0 * 3, n_match + b0, n_inliers + b0, ok + b0, sg);
+    const int rc = estimate_impl(ctx, slice(v, b0, Bg), sg);
     shift_workspaces(ctx, b0, -1);
     ctx->ovf = ctx->ovf_base; ctx->in_group = false;
     if (rc != GN_OK && rc_all == GN_OK) rc_all = rc;
@@ -1880,21 +1807,15 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
     if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     else memset(p.flags + ctx->max_batch, 0, (size_t)B * sizeof(int32_t));
     GN_HIP(hipEventRecord(p.ev, s));
-    p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.B = B; p.kpt_format = kpt_format; p.stride_q = stride_q; p.stride_r = stride_r; p.H = H; p.W = W; p.min_matches = min_matches;
-    p.npad_run = ctx->npad_run; p.desc_q = desc_q; p.kpt_q = kpt_q; p.n_q = n_q; p.desc_r = desc_r; p.kpt_r = kpt_r; p.n_r = n_r; p.dem = dem;
-    memcpy(p.K9, K9, sizeof p.K9); p.R = R; p.t = t; p.n_match = n_match; p.n_inliers = n_inliers; p.ok = ok;
+    p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.npad_run = ctx->npad_run;
+    p.call = v; memcpy(p.K9, K9, sizeof p.K9); p.call.K9 = p.K9;
     ctx->cert_slot ^= 1;
     return cert_resolve(ctx, slot ^ 1, s);
   }
   if (!ctx->defer_join || ctx->certify == 2) { const int rcj = gn_flush(ctx, stream); if (rcj != GN_OK && rc_all == GN_OK) rc_all = rcj; }
   if (ctx->certify == 2 && rc_all == GN_OK) {
     // the groups are joined: one read-back of the call's per-pair flags, then matcher + gather + PnP of the flagged pairs again in exact f32
-    const CertShape shp{stride_q, stride_r, H, W, kw, in_dim, (size_t)ctx->npad};
-    const CertView view{desc_q, kpt_q, desc_r, kpt_r, n_q, n_r, dem, R, t, n_match, n_inliers, ok, nullptr, nullptr};
-    rc_all = certify_rerun(ctx, B, s, shp, view, [&](const CertView& w, int n) {
-      return estimate_impl(ctx, n, kpt_format, w.desc_q, w.kpt_q, w.n_q, stride_q, w.desc_r, w.kpt_r, w.n_r, stride_r, w.dem, H, W, K9, min_matches,
-                           w.R, w.t, w.n_match, w.n_inliers, w.ok, s);
-    });
+    rc_all = certify_rerun(ctx, s, v, [&](const Call& w) { return estimate_impl(ctx, w, s); });
   }
   return rc_all;
 }
@@ -1935,47 +1856,6 @@ int gn_set_substreams(gn_ctx* ctx, int n) {
   return GN_OK;
 }
 
-namespace {
-int estimate_impl(gn_ctx* ctx, int B, int kpt_format,
-                  const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-                  const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-                  const uint8_t* dem, int H, int W, const double* K9, int min_matches,
-                  double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream) {
-  if (!ctx->overlap) {
-    int rc = gn_match(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r,
-                      ctx->e_idx, ctx->e_score, n_match, stream);
-    if (rc != GN_OK) return rc;
-    rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, dem, H, W,
-                          ctx->e_mkp, ctx->e_obj, stream);
-    if (rc != GN_OK) return rc;
-    return gn_pnp_ransac(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, 10, 8.0f, 0.99, min_matches,
-                         R, t, n_inliers, ok, stream);
-  }
-  // Overlapped pose stage: the latency-bound PnP kernels (a few hundred single-wave workgroups) of this call run on an
-  // internal stream while the caller's stream is free to start the next call's matcher.  The PnP inputs are
-  // double-buffered; R / t / n_inliers / ok of this call are complete once gn_flush() has been ordered behind it.
-  hipStream_t s = (hipStream_t)stream;
-  const int slot = (int)(ctx->calls++ & 1);
-  GN_HIP(hipSetDevice(ctx->device));
-  if (ctx->pnp_pending[slot]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot], 0));   // the PnP that last read this slot
-  int rc = gn_match(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r,
-                    ctx->e_idx, ctx->e_score, n_match, stream);
-  if (rc != GN_OK) return rc;
-  rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, dem, H, W,
-                        ctx->o_mkp[slot], ctx->o_obj[slot], stream);
-  if (rc != GN_OK) return rc;
-  GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], n_match, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  GN_HIP(hipEventRecord(ctx->ev_gather[slot], s));
-  GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot], 0));
-  rc = gn_pnp_ransac(ctx, B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, K9, 10, 8.0f, 0.99, min_matches,
-                     R, t, n_inliers, ok, ctx->s_pnp);
-  if (rc != GN_OK) return rc;
-  GN_HIP(hipEventRecord(ctx->ev_pnp[slot], ctx->s_pnp));
-  ctx->pnp_pending[slot] = true;
-  return GN_OK;
-}
-
-}  // namespace
 
 int gn_set_overlap(gn_ctx* ctx, int enable) {
   if (!ctx) return GN_ERR_ARG;
