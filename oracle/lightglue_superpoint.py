@@ -45,14 +45,18 @@ def lightglue_forward(sd: Dict[str, Tensor], kpts0: Tensor, kpts1: Tensor, desc0
 
 
 def match(sd: Dict[str, Tensor], kpts0: Tensor, desc0: Tensor, kpts1: Tensor, desc1: Tensor, hw0=None, hw1=None,
-          filter_threshold: float = 0.1, taps: Optional[dict] = None):
+          filter_threshold: float = 0.1, taps: Optional[dict] = None, dtype: torch.dtype = torch.float32):
     """kornia ``LightGlueMatcher("superpoint").forward`` packing: (scores (K,1), idx (K,2) int64).  kpts (N,2), desc (N,256);
-    hw = (h, w) of the image or None -> keypoint extent (kornia's fallback)."""
+    hw = (h, w) of the image or None -> keypoint extent (kornia's fallback).  dtype=torch.float64 runs the same code on float64
+    weights and inputs (taps, log-assignment and scores then come out in float64)."""
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) for k, v in sd.items()}
+        kpts0, desc0, kpts1, desc1 = (t.to(dtype) for t in (kpts0, desc0, kpts1, desc1))
     if desc0.shape[0] < 2 or desc1.shape[0] < 2:
         return desc0.new_zeros((0, 1)), torch.zeros((0, 2), dtype=torch.int64)
     k0, k1 = kpts0[None], kpts1[None]
-    s0 = k0.max(dim=1)[0].reshape(-1, 2) if hw0 is None else torch.tensor([[hw0[1], hw0[0]]], dtype=torch.float32)
-    s1 = k1.max(dim=1)[0].reshape(-1, 2) if hw1 is None else torch.tensor([[hw1[1], hw1[0]]], dtype=torch.float32)
+    s0 = k0.max(dim=1)[0].reshape(-1, 2) if hw0 is None else torch.tensor([[hw0[1], hw0[0]]], dtype=dtype)
+    s1 = k1.max(dim=1)[0].reshape(-1, 2) if hw1 is None else torch.tensor([[hw1[1], hw1[0]]], dtype=dtype)
     with torch.inference_mode():
         pred = lightglue_forward(sd, k0, k1, desc0[None], desc1[None], s0, s1, filter_threshold=filter_threshold, taps=taps)
     m0, ms0 = pred["matches0"], pred["matching_scores0"]

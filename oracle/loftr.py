@@ -50,14 +50,29 @@ def _basic_block(sd: Dict[str, Tensor], p: str, x: Tensor, stride: int) -> Tenso
     return F.relu(x + y)
 
 
-def backbone(sd: Dict[str, Tensor], images: Tensor, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
-    """ResNetFPN_8_2.forward: images (N,1,H,W) -> (coarse (N,256,H/8,W/8), fine (N,128,H/2,W/2))."""
+def backbone_layer1(sd: Dict[str, Tensor], images: Tensor) -> Tuple[Tensor, Tensor]:
+    """Stem + layer1: images (N,1,H,W) -> (x0, x1), both (N,128,H/2,W/2)."""
     p = "backbone"
     x0 = F.relu(_bn(sd, p + ".bn1", F.conv2d(images, sd[p + ".conv1.weight"], None, stride=2, padding=3)))
     x1 = _basic_block(sd, p + ".layer1.1", _basic_block(sd, p + ".layer1.0", x0, 1), 1)        # 1/2
+    return x0, x1
+
+
+def backbone_layer23(sd: Dict[str, Tensor], x1: Tensor) -> Tuple[Tensor, Tensor]:
+    """layer2 + layer3 from a layer1 output: x1 (N,128,H/2,W/2) -> (x2 (N,196,H/4,W/4), x3 (N,256,H/8,W/8))."""
+    p = "backbone"
     x2 = _basic_block(sd, p + ".layer2.1", _basic_block(sd, p + ".layer2.0", x1, 2), 1)        # 1/4
     x3 = _basic_block(sd, p + ".layer3.1", _basic_block(sd, p + ".layer3.0", x2, 2), 1)        # 1/8
-    x3_out = F.conv2d(x3, sd[p + ".layer3_outconv.weight"])
+    return x2, x3
+
+
+def layer3_outconv(sd: Dict[str, Tensor], x3: Tensor) -> Tensor:
+    return F.conv2d(x3, sd["backbone.layer3_outconv.weight"])
+
+
+def fpn_head(sd: Dict[str, Tensor], x1: Tensor, x2: Tensor, x3_out: Tensor) -> Tuple[Tensor, Tensor]:
+    """The FPN head from layer1 / layer2 outputs and x3_out: -> (x2_out (N,196,H/4,W/4), x1_out (N,128,H/2,W/2))."""
+    p = "backbone"
     x3_out_2x = F.interpolate(x3_out, scale_factor=2.0, mode="bilinear", align_corners=True)
     x2_out = F.conv2d(x2, sd[p + ".layer2_outconv.weight"])
     q = p + ".layer2_outconv2"
@@ -68,24 +83,33 @@ def backbone(sd: Dict[str, Tensor], images: Tensor, taps: Optional[dict] = None)
     q = p + ".layer1_outconv2"
     t = F.leaky_relu(_bn(sd, q + ".1", F.conv2d(x1_out + x2_out_2x, sd[q + ".0.weight"], padding=1)))
     x1_out = F.conv2d(t, sd[q + ".3.weight"], padding=1)
+    return x2_out, x1_out
+
+
+def backbone(sd: Dict[str, Tensor], images: Tensor, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """ResNetFPN_8_2.forward: images (N,1,H,W) -> (coarse (N,256,H/8,W/8), fine (N,128,H/2,W/2))."""
+    x0, x1 = backbone_layer1(sd, images)
+    x2, x3 = backbone_layer23(sd, x1)
+    x3_out = layer3_outconv(sd, x3)
+    x2_out, x1_out = fpn_head(sd, x1, x2, x3_out)
     if taps is not None:
         taps.update(x0=x0, x1=x1, x2=x2, x3=x3, x3_out=x3_out, x2_out=x2_out, x1_out=x1_out)
     return x3_out, x1_out
 
 
 # ------------------------------------------------------------------------------------------------ position encoding
-def position_encoding_sine(d_model: int, h: int, w: int, temp_bug_fix: bool = False) -> Tensor:
+def position_encoding_sine(d_model: int, h: int, w: int, temp_bug_fix: bool = False, dtype: torch.dtype = torch.float32) -> Tensor:
     """PositionEncodingSine.pe[:, :, :h, :w] as (d_model, h, w).  The legacy (temp_bug_fix = False) divisor is restated literally:
     `-math.log(10000.0) / d_model // 2` parses as floor((-ln 1e4 / d_model) / 2) = -1.0, so div_term = exp(-k), k = 0, 2, 4, ..."""
-    y_position = torch.ones((h, w)).cumsum(0).float().unsqueeze(0)
-    x_position = torch.ones((h, w)).cumsum(1).float().unsqueeze(0)
-    k = torch.arange(0, d_model // 2, 2).float()
+    y_position = torch.ones((h, w)).cumsum(0).to(dtype).unsqueeze(0)
+    x_position = torch.ones((h, w)).cumsum(1).to(dtype).unsqueeze(0)
+    k = torch.arange(0, d_model // 2, 2).to(dtype)
     if temp_bug_fix:
         div_term = torch.exp(k * (-math.log(10000.0) / (d_model // 2)))
     else:
         div_term = torch.exp(k * (-math.log(10000.0) / d_model // 2))
     div_term = div_term[:, None, None]
-    pe = torch.zeros((d_model, h, w))
+    pe = torch.zeros((d_model, h, w), dtype=dtype)
     pe[0::4] = torch.sin(x_position * div_term)
     pe[1::4] = torch.cos(x_position * div_term)
     pe[2::4] = torch.sin(y_position * div_term)
@@ -158,7 +182,7 @@ def coarse_matching(feat_c0: Tensor, feat_c1: Tensor, hw0_c, hw1_c, scale: int =
     sim = torch.einsum("nlc,nsc->nls", f0, f1) / temperature
     conf = F.softmax(sim, 1) * F.softmax(sim, 2)
     if taps is not None:
-        taps["conf_matrix"] = conf
+        taps["sim_matrix"], taps["conf_matrix"] = sim, conf
     n = conf.shape[0]
     mask = (conf > thr).view(n, hw0_c[0], hw0_c[1], hw1_c[0], hw1_c[1]).clone()
     mask_border(mask, border_rm, False)
@@ -170,7 +194,7 @@ def coarse_matching(feat_c0: Tensor, feat_c1: Tensor, hw0_c, hw1_c, scale: int =
     mconf = conf[b_ids, i_ids, j_ids]
     mk0 = torch.stack([i_ids % hw0_c[1], i_ids // hw0_c[1]], dim=1) * scale
     mk1 = torch.stack([j_ids % hw1_c[1], j_ids // hw1_c[1]], dim=1) * scale
-    return b_ids, i_ids, j_ids, mconf, mk0.float(), mk1.float()
+    return b_ids, i_ids, j_ids, mconf, mk0.to(feat_c0.dtype), mk1.to(feat_c0.dtype)
 
 
 # ------------------------------------------------------------------------------------------------ fine level
@@ -181,7 +205,7 @@ def fine_preprocess(sd: Dict[str, Tensor], feat_f0: Tensor, feat_f1: Tensor, fea
     stride = 4   # hw0_f[0] // hw0_c[0]
     M = len(b_ids)
     if M == 0:
-        z = torch.empty(0, W * W, D_FINE)
+        z = torch.empty(0, W * W, D_FINE, dtype=feat_f0.dtype)
         return z, z
     c = feat_f0.shape[1]
     u0 = F.unfold(feat_f0, kernel_size=(W, W), stride=stride, padding=W // 2).view(feat_f0.shape[0], c, W * W, -1).permute(0, 3, 2, 1)
@@ -196,8 +220,8 @@ def fine_preprocess(sd: Dict[str, Tensor], feat_f0: Tensor, feat_f1: Tensor, fea
 def spatial_expectation2d_normalized(heat: Tensor) -> Tensor:
     """kornia.geometry.subpix.dsnt.spatial_expectation2d(heat[None], normalized_coordinates=True)[0]: (M, W, W) -> (M, 2) (x, y) in [-1, 1]."""
     m, h, w = heat.shape
-    xs = torch.linspace(-1, 1, w)
-    ys = torch.linspace(-1, 1, h)
+    xs = torch.linspace(-1, 1, w, dtype=heat.dtype)
+    ys = torch.linspace(-1, 1, h, dtype=heat.dtype)
     ex = (heat * xs[None, None, :]).sum((1, 2))
     ey = (heat * ys[None, :, None]).sum((1, 2))
     return torch.stack([ex, ey], -1)
@@ -218,27 +242,49 @@ def fine_matching(feat_f0: Tensor, feat_f1: Tensor, mkpts0_c: Tensor, mkpts1_c: 
 
 
 # ------------------------------------------------------------------------------------------------ whole model
-def loftr_forward(sd: Dict[str, Tensor], image0: Tensor, image1: Tensor, taps: Optional[dict] = None, fine: bool = True):
+def cast_state_dict(sd: Dict[str, Tensor], dtype: torch.dtype) -> Dict[str, Tensor]:
+    """The weights in `dtype` (the float32 dict itself when dtype is float32)."""
+    return sd if dtype == torch.float32 else {k: v.to(dtype) for k, v in sd.items()}
+
+
+def coarse_transformer(sd: Dict[str, Tensor], feats_c: Tensor, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """Position encoding + the coarse LocalFeatureTransformer from the backbone's coarse output feats_c (2,256,hc,wc) (x3_out):
+    -> (feat0, feat1), (1, hc*wc, 256) each."""
+    hc, wc = feats_c.shape[-2:]
+    pe = position_encoding_sine(D_COARSE, hc, wc, dtype=feats_c.dtype)
+    fc = (feats_c + pe[None]).flatten(2).transpose(1, 2)                               # (2, hc*wc, 256)
+    if taps is not None:
+        taps["coarse_in"] = fc
+    return local_feature_transformer(sd, "loftr_coarse", COARSE_LAYERS, fc[:1], fc[1:], taps)
+
+
+def fine_level(sd: Dict[str, Tensor], feats_f: Tensor, f0: Tensor, f1: Tensor, b_ids, i_ids, j_ids, mk0: Tensor, mk1: Tensor,
+               taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """FinePreprocess + the fine LocalFeatureTransformer + FineMatching from the 1/2-resolution map feats_f (2,128,H/2,W/2) (x1_out), the
+    coarse tokens f0 / f1 (1,L,256) and the coarse match list: -> (keypoints0, keypoints1)."""
+    ff0, ff1 = fine_preprocess(sd, feats_f[:1], feats_f[1:], f0, f1, b_ids, i_ids, j_ids)
+    if len(b_ids):
+        ff0, ff1 = local_feature_transformer(sd, "loftr_fine", FINE_LAYERS, ff0, ff1)
+    if taps is not None:
+        taps["fine_windows"] = (ff0, ff1)
+    return fine_matching(ff0, ff1, mk0, mk1)
+
+
+def loftr_forward(sd: Dict[str, Tensor], image0: Tensor, image1: Tensor, taps: Optional[dict] = None, fine: bool = True,
+                  dtype: torch.dtype = torch.float32):
     """LoFTR.forward on one pair of (H, W) float images in [0, 1] of EQUAL size, H and W multiples of 8.  Returns kornia's output dict:
-    keypoints0 / keypoints1 (M, 2) (x, y) pixels, confidence (M,), batch_indexes (M,) -- plus the coarse-level ids."""
+    keypoints0 / keypoints1 (M, 2) (x, y) pixels, confidence (M,), batch_indexes (M,) -- plus the coarse-level ids.
+    dtype=torch.float64 runs the same code on float64 weights and images (taps and outputs then come out in float64)."""
     with torch.inference_mode():
+        sd = cast_state_dict(sd, dtype)
         h, w = image0.shape
-        feats_c, feats_f = backbone(sd, torch.stack([image0, image1])[:, None], taps)
+        feats_c, feats_f = backbone(sd, torch.stack([image0, image1]).to(dtype)[:, None], taps)
         hc, wc = h // 8, w // 8
-        pe = position_encoding_sine(D_COARSE, hc, wc)
-        fc = (feats_c + pe[None]).flatten(2).transpose(1, 2)                           # (2, hc*wc, 256)
-        if taps is not None:
-            taps["coarse_in"] = fc
-        f0, f1 = local_feature_transformer(sd, "loftr_coarse", COARSE_LAYERS, fc[:1], fc[1:], taps)
+        f0, f1 = coarse_transformer(sd, feats_c, taps)
         b_ids, i_ids, j_ids, mconf, mk0, mk1 = coarse_matching(f0, f1, (hc, wc), (hc, wc), 8, taps=taps)
         out = dict(i_ids=i_ids, j_ids=j_ids, confidence=mconf, batch_indexes=b_ids, keypoints0_c=mk0, keypoints1_c=mk1)
         if fine:
-            ff0, ff1 = fine_preprocess(sd, feats_f[:1], feats_f[1:], f0, f1, b_ids, i_ids, j_ids)
-            if len(b_ids):
-                ff0, ff1 = local_feature_transformer(sd, "loftr_fine", FINE_LAYERS, ff0, ff1)
-            if taps is not None:
-                taps["fine_windows"] = (ff0, ff1)
-            mk0, mk1 = fine_matching(ff0, ff1, mk0, mk1)
+            mk0, mk1 = fine_level(sd, feats_f, f0, f1, b_ids, i_ids, j_ids, mk0, mk1, taps)
         out.update(keypoints0=mk0, keypoints1=mk1)
         return out
 

@@ -28,3 +28,78 @@ def test_fp64_reference_taps_are_float64_and_within_1e5_of_the_f32_oracle(state_
         assert t64["scores"].shape == (1, len(p.kp_q) + 1, len(p.kp_r) + 1)
         assert r64[2].dtype == torch.float64
         assert np.array_equal(r32[3].numpy(), r64[3].numpy()) and len(r64[3]) > 15
+
+
+def test_loftr_stage_entry_points_compose_to_the_whole_model_bitwise():
+    """tests/test_gpu_fp64_loftr.py feeds each stage of oracle/loftr.py its own input: chained on the oracle's own outputs, the entry points
+    are the whole model, bit for bit."""
+    from oracle import loftr as lf
+    sd = lf.synthetic_state_dict(0)
+    h, w = 96, 128
+    i0, i1 = lf.synthetic_pair(3, h, w)
+    taps = {}
+    ref = lf.loftr_forward(sd, i0, i1, taps=taps)
+    with torch.inference_mode():
+        _, x1 = lf.backbone_layer1(sd, torch.stack([i0, i1])[:, None])
+        x2, x3 = lf.backbone_layer23(sd, x1)
+        x3_out = lf.layer3_outconv(sd, x3)
+        x2_out, x1_out = lf.fpn_head(sd, x1, x2, x3_out)
+        f0, f1 = lf.coarse_transformer(sd, x3_out)
+        b, i, j, conf, k0, k1 = lf.coarse_matching(f0, f1, (h // 8, w // 8), (h // 8, w // 8), 8)
+        k0f, k1f = lf.fine_level(sd, x1_out, f0, f1, b, i, j, k0, k1)
+    for name, t in (("x1", x1), ("x3", x3), ("x3_out", x3_out), ("x2_out", x2_out), ("x1_out", x1_out)):
+        assert torch.equal(t, taps[name]), name
+    assert torch.equal(f0, taps["loftr_coarse.7"][0]) and torch.equal(f1, taps["loftr_coarse.7"][1])
+    assert torch.equal(i, ref["i_ids"]) and torch.equal(j, ref["j_ids"]) and torch.equal(conf, ref["confidence"]) and len(i) > 20
+    assert torch.equal(k0f, ref["keypoints0"]) and torch.equal(k1f, ref["keypoints1"])
+
+
+def test_loftr_fp64_reference_is_float64_and_within_f32_rounding_of_the_f32_oracle():
+    """oracle.loftr.loftr_forward(..., dtype=torch.float64): every tap float64, within f32 rounding of the f32 run (measured 3.5e-7 .. 1.7e-6 on
+    the features, 1.7e-5 on the dual-softmax matrix), the same coarse correspondences, fine keypoints within 1e-3 px.  The border-only 32 x 32
+    pair (no match) runs its fine level on empty windows in float64 too."""
+    from oracle import loftr as lf
+    torch.set_num_threads(max(1, min(len(os.sched_getaffinity(0)), 16)))
+    sd = lf.synthetic_state_dict(0)
+    for h, w, seed in ((96, 128, 3), (136, 200, 2), (32, 32, 1)):
+        i0, i1 = lf.synthetic_pair(seed, h, w)
+        t32, t64 = {}, {}
+        r32 = lf.loftr_forward(sd, i0, i1, taps=t32)
+        r64 = lf.loftr_forward(sd, i0, i1, taps=t64, dtype=torch.float64)
+        for k, bound in (("x1", 1e-5), ("x2", 1e-5), ("x3", 1e-5), ("x3_out", 1e-5), ("x2_out", 1e-5), ("x1_out", 1e-5), ("loftr_coarse.7", 1e-5),
+                         ("sim_matrix", 1e-5), ("conf_matrix", 1e-4), ("fine_windows", 1e-5)):
+            a, b = t32[k], t64[k]
+            if isinstance(a, tuple):
+                a, b = torch.cat(a), torch.cat(b)
+            assert b.dtype == torch.float64 and a.shape == b.shape, k
+            if b.numel():
+                assert float((a.double() - b).abs().max() / b.abs().max()) <= bound, k
+        for k in ("confidence", "keypoints0", "keypoints1", "keypoints1_c"):
+            assert r64[k].dtype == torch.float64, k
+        assert torch.equal(r32["i_ids"], r64["i_ids"]) and torch.equal(r32["j_ids"], r64["j_ids"])
+        assert len(r64["i_ids"]) > (20 if h > 32 else -1)
+        if len(r64["i_ids"]):
+            assert float((r32["confidence"].double() - r64["confidence"]).abs().max()) <= 1e-4
+            assert float((r32["keypoints1"].double() - r64["keypoints1"]).abs().max()) <= 1e-3
+        assert torch.equal(r32["keypoints0"].double(), r64["keypoints0"])
+
+
+def test_superpoint_lightglue_fp64_reference_is_float64_and_within_1e5_of_the_f32_oracle():
+    """oracle.lightglue_superpoint.match(..., dtype=torch.float64) -- the reference of the 256-d cases in tests/test_gpu_fp64_parity.py -- with the
+    keypoint extent and with a stated image size (the size tensors follow dtype)."""
+    from gisnav_amd.synthetic import make_pair_256
+    from gisnav_amd.weights import synthetic_state_dict
+    from oracle import lightglue_superpoint as lsp
+    torch.set_num_threads(max(1, min(len(os.sched_getaffinity(0)), 16)))
+    sd = {k: torch.from_numpy(v) for k, v in synthetic_state_dict(0, feature="superpoint").items()}
+    tq = torch.from_numpy
+    for p, hw in ((make_pair_256(40, n_q=300, n_r=280, h=480, w=640), None), (make_pair_256(41, n_q=257, n_r=129, h=480, w=640), (480, 640))):
+        t32, t64 = {}, {}
+        r32 = lsp.match(sd, tq(p.kp_q), tq(p.desc_q), tq(p.kp_r), tq(p.desc_r), hw0=hw, hw1=hw, taps=t32)
+        r64 = lsp.match(sd, tq(p.kp_q), tq(p.desc_q), tq(p.kp_r), tq(p.desc_r), hw0=hw, hw1=hw, taps=t64, dtype=torch.float64)
+        for k in [f"layer{i}_{s}" for i in range(9) for s in (0, 1)] + ["scores"]:
+            assert t64[k].dtype == torch.float64, k
+            a, b = t32[k].double().numpy(), t64[k].numpy()
+            assert a.shape == b.shape, k
+            assert np.abs(a - b).max() / np.abs(b).max() <= 1e-5, k
+        assert r64[0].dtype == torch.float64 and np.array_equal(r32[1].numpy(), r64[1].numpy()) and len(r64[1]) > 15
