@@ -217,9 +217,14 @@ struct gn_ctx {
   int* lists = nullptr; long long lists_stride = 0;   // work lists (launch_tile_lists), lists_stride ints per pair
   int n_sub = 1; hipStream_t sub_s[8] = {}; hipEvent_t ev_fork = nullptr; hipEvent_t ev_join[8] = {}; bool sub_pending[8] = {};
   // overlapped pose stage (gn_set_overlap): PnP of call n runs on an internal stream beside the matcher of call n+1
+  // and the pose stage of the sub-batch groups: every group of call n hands its PnP to the ONE PnP stream and its own stream goes on with call n + 1.
+  // The PnP inputs (o_*) are double-buffered by call parity; [slot][g] = group g's PnP of the call that used that slot (g = 0 without sub-batch groups)
   int overlap = 0; unsigned long long calls = 0;
-  hipStream_t s_pnp = nullptr; hipEvent_t ev_gather[2] = {nullptr, nullptr}, ev_pnp[2] = {nullptr, nullptr}; bool pnp_pending[2] = {false, false};
+  hipStream_t s_pnp = nullptr; hipEvent_t ev_gather[2][8] = {}, ev_pnp[2][8] = {}; bool pnp_pending[2][8] = {}, pnp_recorded[2][8] = {};
+  hipEvent_t ev_head[8] = {};      // group g's match head is done: the certificate's flags of the call exist (deferred certificate)
   float* o_mkp[2] = {nullptr, nullptr}; float* o_obj[2] = {nullptr, nullptr}; int32_t* o_nmatch[2] = {nullptr, nullptr};
+  int prep_fused = 1;      // knob 48.  1 (default): k_prep writes the hm16 descriptor rows and the rot4 table itself and k_extent clears the guard word;
+                           // 0: the separate k_split_hm16 / k_rot_table launches behind it (same bits; tests)
   // SIFT workspace (gn_sift_detect_and_compute), sized for the last image shape seen
   int sift_h = 0, sift_w = 0; std::vector<void*> sift_allocs; SiftPyramid sift_py; float* sift_tmp = nullptr;
   float* sift_dk = nullptr; std::vector<std::vector<float>> sift_kernels; std::vector<int> sift_koff;   // [0] = initial blur, [1..5] = layer blurs
@@ -653,7 +658,6 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
   const int vt_perm = (bf16v2 ? 1 : 0) | (c->dbg_vt_skip ? 2 : 0);   // k_attn_bf16_v5 reads V^T with keys permuted inside 16-groups   // k_attn_bf16_v4 reads permuted V^T
   const bool attn_planes = c->planes_mode && (bf16v2 || c->attn_f16 == 2);   // k_attn_bf16_v5 / k_attn_f16x2 write the hm16 rows themselves
   c->launch_count = 0;
-  if (c->planes_mode && c->guard) hipMemsetAsync(c->ovf, (c->dbg_trip_group && c->ovf == c->ovf_base + (c->dbg_trip_group - 1)) ? 1 : 0, sizeof(unsigned int), s);
   {
     StageTimer tm(c, s, ST_PREP);
     PrepArgs p;
@@ -663,15 +667,22 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     p.desc = c->desc; p.kxy = nullptr; p.cos_t = c->cos_t; p.sin_t = c->sin_t; p.nvalid = c->nvalid; p.extent = c->extent;
     p.size_q[0] = c->size_q[0]; p.size_q[1] = c->size_q[1]; p.size_r[0] = c->size_r[0]; p.size_r[1] = c->size_r[1];
     p.feature = c->feature; p.x = nullptr; p.xp = nullptr;
+    // the call's guard word starts clear -- or RAISED, developer knob 25 -- by k_extent, the call's first launch
+    p.ovf_clear = (c->planes_mode && c->guard) ? c->ovf : nullptr;
+    p.ovf_init = (c->dbg_trip_group && c->ovf == c->ovf_base + (c->dbg_trip_group - 1)) ? 1u : 0u;
+    p.desc_p = nullptr; p.rot4 = nullptr; p.rot_stride = (long long)c->Tmax;
     const bool planes_only = c->planes_mode && c->x_planes_only && c->n_layers > 0;
     if (c->feature == 1) {   // 256-d descriptors ARE the initial residual stream (no input_proj)
       p.x = planes_only ? nullptr : c->x; p.xp = c->planes_mode ? c->x_p : nullptr;
       launch_prep(p, s);
       if (c->rot4 && c->qkv_fused) launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, s);
     } else {
+      // k_prep also writes what k_rot_table and k_split_hm16 would make of its f32 outputs (which stay, for the modes that read them)
+      const bool rot = c->rot4 && c->qkv_fused, split = c->planes_mode != 0;
+      if (c->prep_fused) { p.rot4 = rot ? c->rot4 : nullptr; p.desc_p = split ? c->desc_p : nullptr; }
       launch_prep(p, s);
-      if (c->rot4 && c->qkv_fused) launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, s);
-      if (c->planes_mode) launch_split_hm16(c->desc, c->desc_p, T, kInDim, 1.0f, s);
+      if (rot && !p.rot4) launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, s);
+      if (split && !p.desc_p) launch_split_hm16(c->desc, c->desc_p, T, kInDim, 1.0f, s);
       GemmArgs g = gemm_args(c->desc, kInDim, c->input_proj, c->x, kDim, T);
       g.drop_f32 = planes_only ? 1 : 0;
       gemm(c, EPI_BIAS, g, s);
@@ -1220,7 +1231,7 @@ int gn_resize(gn_ctx* ctx, int max_kpts) {
   if (ctx->s_pnp) {                                    // the overlapped pose stage's double buffers follow the padded size too
     const size_t B = ctx->max_batch, np = ctx->npad;
     for (int i = 0; i < 2; ++i) {
-      ctx->pnp_pending[i] = false;
+      for (int g = 0; g < 8; ++g) ctx->pnp_pending[i][g] = false;
       int rc = ws_alloc(ctx, &ctx->o_mkp[i], B * np * 2); if (rc != GN_OK) return broken(rc);
       rc = ws_alloc(ctx, &ctx->o_obj[i], B * np * 3); if (rc != GN_OK) return broken(rc);
       rc = ws_alloc(ctx, &ctx->o_nmatch[i], B); if (rc != GN_OK) return broken(rc);
@@ -1247,11 +1258,9 @@ void gn_destroy(gn_ctx* ctx) {
     for (int i = 0; i < 8; ++i) if (ctx->sub_s[i]) { hipStreamSynchronize(ctx->sub_s[i]); hipEventDestroy(ctx->ev_join[i]); hipStreamDestroy(ctx->sub_s[i]); }
     hipEventDestroy(ctx->ev_fork);
   }
-  if (ctx->s_pnp) {
-    hipStreamSynchronize(ctx->s_pnp);
-    for (int i = 0; i < 2; ++i) { hipEventDestroy(ctx->ev_gather[i]); hipEventDestroy(ctx->ev_pnp[i]); }
-    hipStreamDestroy(ctx->s_pnp);
-  }
+  if (ctx->s_pnp) { hipStreamSynchronize(ctx->s_pnp); hipStreamDestroy(ctx->s_pnp); }
+  for (int g = 0; g < 8; ++g)
+    for (hipEvent_t e : {ctx->ev_gather[0][g], ctx->ev_gather[1][g], ctx->ev_pnp[0][g], ctx->ev_pnp[1][g], ctx->ev_head[g]}) if (e) hipEventDestroy(e);
   delete ctx;
 }
 
@@ -1696,41 +1705,80 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   const long long km = c->npad;
   mv(c->e_idx, km * 2); mv(c->e_score, km); mv(c->e_mkp, km * 2); mv(c->e_obj, km * 3);
   mv(c->mask_ws, km * 16); mv(c->hyp_ws, 16); mv(c->pts_ws, km * 5);
+  for (int i = 0; i < 2; ++i) { mv(c->o_mkp[i], km * 2); mv(c->o_obj[i], km * 3); mv(c->o_nmatch[i], 1); }
   mv(c->lists, c->lists_stride);
 }
 
-int estimate_impl(gn_ctx* ctx, const Call& v, void* stream) {
-  if (!ctx->overlap) {
-    int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
-                      ctx->e_idx, ctx->e_score, v.n_match, stream);
-    if (rc != GN_OK) return rc;
+// The PnP stream, its events and the double-buffered PnP inputs (gn_set_overlap, gn_set_substreams).
+int ensure_pnp_stage(gn_ctx* ctx) {
+  if (ctx->s_pnp) return GN_OK;
+  // s_pnp is what marks the stage as ready, so it is set last: a failure on the way leaves a context that tries again
+  const size_t B = ctx->max_batch, np = ctx->npad;
+  for (int i = 0; i < 2; ++i) {
+    int rc = ws_alloc(ctx, &ctx->o_mkp[i], B * np * 2); if (rc != GN_OK) return rc;
+    rc = ws_alloc(ctx, &ctx->o_obj[i], B * np * 3); if (rc != GN_OK) return rc;
+    rc = ws_alloc(ctx, &ctx->o_nmatch[i], B); if (rc != GN_OK) return rc;
+  }
+  auto event = [](hipEvent_t& e) { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); };
+  for (int g = 0; g < 8; ++g) {
+    for (int i = 0; i < 2; ++i) { GN_HIP(event(ctx->ev_gather[i][g])); GN_HIP(event(ctx->ev_pnp[i][g])); }
+    GN_HIP(event(ctx->ev_head[g]));
+  }
+  GN_HIP(hipStreamCreateWithFlags(&ctx->s_pnp, hipStreamNonBlocking));
+  return GN_OK;
+}
+
+// `s` behind every PnP that the PnP stream still holds
+int join_pnp(gn_ctx* ctx, hipStream_t s) {
+  for (int i = 0; i < 2; ++i)
+    for (int g = 0; g < 8; ++g)
+      if (ctx->pnp_pending[i][g]) { GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[i][g], 0)); ctx->pnp_pending[i][g] = false; }
+  return GN_OK;
+}
+
+// `s` behind every unjoined sub-batch group (its matcher and gather; its PnP is join_pnp's)
+int join_groups(gn_ctx* ctx, hipStream_t s) {
+  for (int g = 0; g < 8; ++g)
+    if (ctx->sub_pending[g]) { GN_HIP(hipStreamWaitEvent(s, ctx->ev_join[g], 0)); ctx->sub_pending[g] = false; }
+  return GN_OK;
+}
+
+// `s` behind everything the library's internal streams still hold
+int join_internal(gn_ctx* ctx, hipStream_t s) {
+  const int rc = join_pnp(ctx, s);
+  return rc != GN_OK ? rc : join_groups(ctx, s);
+}
+
+// Matcher, gather and PnP of call v -- or of sub-batch group g of a call, on the group's slice of the workspaces -- enqueued on `stream`.
+// slot < 0: all three on `stream`.  slot 0 / 1: the latency-bound PnP kernels (a few hundred single-wave workgroups) run on the PnP stream from
+// that slot of the double-buffered PnP inputs, and `stream` is free for the next call's matcher once the gather is enqueued; R / t / n_inliers / ok
+// are complete behind ev_pnp[slot][g] (gn_flush, or the waits gn_estimate enqueues one call later).
+int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g = 0) {
+  int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
+                    ctx->e_idx, ctx->e_score, v.n_match, stream);
+  if (rc != GN_OK) return rc;
+  if (slot < 0) {
     rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
                           ctx->e_mkp, ctx->e_obj, stream);
     if (rc != GN_OK) return rc;
     return gn_pnp_ransac(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
                          v.R, v.t, v.n_inliers, v.ok, stream);
   }
-  // Overlapped pose stage: the latency-bound PnP kernels (a few hundred single-wave workgroups) of this call run on an
-  // internal stream while the caller's stream is free to start the next call's matcher.  The PnP inputs are
-  // double-buffered; R / t / n_inliers / ok of this call are complete once gn_flush() has been ordered behind it.
   hipStream_t s = (hipStream_t)stream;
-  const int slot = (int)(ctx->calls++ & 1);
   GN_HIP(hipSetDevice(ctx->device));
-  if (ctx->pnp_pending[slot]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot], 0));   // the PnP that last read this slot
-  int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
-                    ctx->e_idx, ctx->e_score, v.n_match, stream);
-  if (rc != GN_OK) return rc;
+  GN_HIP(hipEventRecord(ctx->ev_head[g], s));
+  if (ctx->pnp_recorded[slot][g]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot][g], 0));   // the PnP that last read this slot (two calls ago)
   rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
                         ctx->o_mkp[slot], ctx->o_obj[slot], stream);
   if (rc != GN_OK) return rc;
   GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  GN_HIP(hipEventRecord(ctx->ev_gather[slot], s));
-  GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot], 0));
+  GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
+  GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
   rc = gn_pnp_ransac(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
                      v.R, v.t, v.n_inliers, v.ok, ctx->s_pnp);
   if (rc != GN_OK) return rc;
-  GN_HIP(hipEventRecord(ctx->ev_pnp[slot], ctx->s_pnp));
-  ctx->pnp_pending[slot] = true;
+  GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
+  ctx->pnp_pending[slot][g] = ctx->pnp_recorded[slot][g] = true;
   return GN_OK;
 }
 
@@ -1743,7 +1791,9 @@ int cert_resolve(gn_ctx* ctx, int slot, hipStream_t s) {
   GN_HIP(hipEventSynchronize(p.ev));
   const Restore keep(ctx->npad_run);
   ctx->npad_run = p.npad_run;
-  return certify_rerun(ctx, s, p.call, [&](const Call& w) { return estimate_impl(ctx, w, s); }, p.flags, p.level);
+  // a re-run writes outputs of this call and works in slices of the workspaces that the groups and the PnP stream may still be using: it
+  // goes behind every pending PnP (this call's above all) and every group first (calls without a flagged pair never get here)
+  return certify_rerun(ctx, s, p.call, [&](const Call& w) { const int rcj = join_internal(ctx, s); return rcj != GN_OK ? rcj : estimate_impl(ctx, w, s); }, p.flags, p.level);
 }
 }  // namespace
 
@@ -1763,20 +1813,32 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
   v.dem = dem; v.H = H; v.W = W; v.K9 = K9; v.min_matches = min_matches;
   v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
   const int groups = std::min(ctx->n_sub, B);
-  if (groups <= 1 || ctx->overlap) return estimate_impl(ctx, v, stream);
+  if (groups <= 1) {
+    // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the un-shifted workspaces, on the
+    // caller's stream: behind the groups first, and -- unless its own PnP goes to the PnP stream, which keeps the order -- behind their PnP.
+    GN_HIP(hipSetDevice(ctx->device));
+    const int rcj = ctx->overlap ? join_groups(ctx, (hipStream_t)stream) : join_internal(ctx, (hipStream_t)stream);
+    if (rcj != GN_OK) return rcj;
+    return ctx->overlap ? estimate_impl(ctx, v, stream, (int)(ctx->calls++ & 1), 0) : estimate_impl(ctx, v, stream);
+  }
   if (ctx->npad <= 0) return fail(ctx, GN_ERR_ARG, "context has no workspaces (a gn_resize failed): call gn_resize again");
   if (B < 1 || B > ctx->max_batch) return fail(ctx, GN_ERR_ARG, "B out of range for this context");
   GN_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   // deferred joins still pending from a call of another shape: group g of this call would overlap the workspace slice of a
   // different group of that call on another stream -> join them first (the fork event below is recorded behind the joins)
-  if (ctx->defer_join && (ctx->sub_last_B != B || ctx->sub_last_np != ctx->npad_run)) {
+  if ((ctx->defer_join || ctx->certify == 3) && (ctx->sub_last_B != B || ctx->sub_last_np != ctx->npad_run)) {      // (deferred certificate: the caller's stream joins the heads only)
     const int rcj = gn_flush(ctx, stream);
     if (rcj != GN_OK) return rcj;
   }
   ctx->sub_last_B = B; ctx->sub_last_np = ctx->npad_run;
   ctx->ovf_groups_last = groups;
   GN_HIP(hipEventRecord(ctx->ev_fork, s));
+  // Every group runs matcher and gather on its own stream and hands its PnP to the PnP stream (slot = parity of the call), so the group's stream is
+  // free for the next call while the PnP chains run.  Deferred certificate: the outputs of call n are final once call n + 1 has been enqueued --
+  // the caller's stream takes the earlier calls' PnP here, BEHIND the fork, so that no group of this call waits for them.
+  const int slot = (int)(ctx->calls++ & 1);
+  if (ctx->certify == 3) { const int rcj = join_pnp(ctx, s); if (rcj != GN_OK) return rcj; }
   int rc_all = GN_OK, b0 = 0;
   for (int g = 0; g < groups; ++g) {
     const int Bg = B / groups + (g < B % groups ? 1 : 0);
@@ -1784,7 +1846,7 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
     GN_HIP(hipStreamWaitEvent(sg, ctx->ev_fork, 0));
     shift_workspaces(ctx, b0, +1);
     ctx->in_group = true; ctx->ovf = ctx->ovf_base + g;            // this group's own guard word: cleared, raised and read on this group's stream only
-    const int rc = estimate_impl(ctx, slice(v, b0, Bg), sg);
+    const int rc = estimate_impl(ctx, slice(v, b0, Bg), sg, slot, g);
     shift_workspaces(ctx, b0, -1);
     ctx->ovf = ctx->ovf_base; ctx->in_group = false;
     if (rc != GN_OK && rc_all == GN_OK) rc_all = rc;
@@ -1796,10 +1858,10 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
   // stream order, like any other call.  gn_set_deferred_join(1) leaves the join to gn_flush (consecutive calls then pipeline
   // inside each group's stream; the caller keeps the INPUT buffers alive until it has flushed).
   if (ctx->certify == 3 && rc_all == GN_OK) {
-    // deferred certificate: join the groups (stream order only), leave this call's flags in a pinned slot behind an event, and resolve the
-    // PREVIOUS call now that this one is queued -- the host waits for call n while the GPU already works on call n + 1
-    for (int g = 0; g < 8; ++g)
-      if (ctx->sub_pending[g]) { GN_HIP(hipStreamWaitEvent(s, ctx->ev_join[g], 0)); ctx->sub_pending[g] = false; }
+    // deferred certificate: the caller's stream goes behind every group's match head (stream order only; gather and PnP of the call are still to
+    // come -- gn_flush, a re-run of this call and the next call's waits above take them), leaves this call's flags in a pinned slot behind an
+    // event, and resolves the PREVIOUS call now that this one is queued -- the host waits for call n while the GPU already works on call n + 1
+    for (int g = 0; g < groups; ++g) GN_HIP(hipStreamWaitEvent(s, ctx->ev_head[g], 0));
     const int slot = ctx->cert_slot;
     gn_ctx::CertPending& p = ctx->cert_pend[slot];
     if (p.active) { const int rcr = cert_resolve(ctx, slot, s); if (rcr != GN_OK) return rcr; }     // (cannot happen in the alternating order; kept for safety)
@@ -1836,6 +1898,7 @@ int gn_set_substreams(gn_ctx* ctx, int n) {
   if (!ctx || n < 1 || n > 8) return GN_ERR_ARG;
   GN_HIP(hipSetDevice(ctx->device));
   if (n > 1 && !ctx->ev_fork) GN_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+  if (n > 1) { const int rc = ensure_pnp_stage(ctx); if (rc != GN_OK) return rc; }      // the groups' pose stage runs on the PnP stream
   for (int i = 0; i < n && n > 1; ++i)
     if (!ctx->sub_s[i]) {
       if (ctx->cu_mask_mode != 0) {
@@ -1860,17 +1923,7 @@ int gn_set_substreams(gn_ctx* ctx, int n) {
 int gn_set_overlap(gn_ctx* ctx, int enable) {
   if (!ctx) return GN_ERR_ARG;
   GN_HIP(hipSetDevice(ctx->device));
-  if (enable && !ctx->s_pnp) {
-    GN_HIP(hipStreamCreateWithFlags(&ctx->s_pnp, hipStreamNonBlocking));
-    const size_t B = ctx->max_batch, np = ctx->npad;
-    for (int i = 0; i < 2; ++i) {
-      GN_HIP(hipEventCreateWithFlags(&ctx->ev_gather[i], hipEventDisableTiming));
-      GN_HIP(hipEventCreateWithFlags(&ctx->ev_pnp[i], hipEventDisableTiming));
-      int rc = ws_alloc(ctx, &ctx->o_mkp[i], B * np * 2); if (rc != GN_OK) return rc;
-      rc = ws_alloc(ctx, &ctx->o_obj[i], B * np * 3); if (rc != GN_OK) return rc;
-      rc = ws_alloc(ctx, &ctx->o_nmatch[i], B); if (rc != GN_OK) return rc;
-    }
-  }
+  if (enable) { const int rc = ensure_pnp_stage(ctx); if (rc != GN_OK) return rc; }
   if (!enable && ctx->s_pnp) GN_HIP(hipStreamSynchronize(ctx->s_pnp));
   ctx->overlap = enable ? 1 : 0;
   return GN_OK;
@@ -1879,10 +1932,7 @@ int gn_set_overlap(gn_ctx* ctx, int enable) {
 int gn_flush(gn_ctx* ctx, void* stream) {
   if (!ctx) return GN_ERR_ARG;
   GN_HIP(hipSetDevice(ctx->device));
-  for (int i = 0; i < 2; ++i)
-    if (ctx->pnp_pending[i]) { GN_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_pnp[i], 0)); ctx->pnp_pending[i] = false; }
-  for (int g = 0; g < 8; ++g)
-    if (ctx->sub_pending[g]) { GN_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->ev_join[g], 0)); ctx->sub_pending[g] = false; }
+  { const int rc = join_internal(ctx, (hipStream_t)stream); if (rc != GN_OK) return rc; }
   if (!ctx->cert_inner)
     for (int k = 0; k < 2; ++k) {       // deferred certificates still open: the older one first
       const int rc = cert_resolve(ctx, ctx->cert_slot ^ k, (hipStream_t)stream);
@@ -2301,7 +2351,7 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       {"sp_x", ctx->sp_x, ctx->sp_x ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},                         // raw words of the two activation buffers
       {"sp_y", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},
       {"sp_ts", ctx->sp_ts, ctx->sp_ts ? (size_t)8192 * 32 * 2 : 0},                                                     // phase stamps (knob 35), int64 pairs of 4-byte words
-      {"x_p", ctx->x_p, ctx->x_p ? T * kDim : 0}, {"msg_p", ctx->msg_p, ctx->msg_p ? T * kDim : 0},   // hm16 rows, raw (4 bytes per value)
+      {"desc_p", ctx->desc_p, ctx->desc_p ? T * kInDim : 0}, {"x_p", ctx->x_p, ctx->x_p ? T * kDim : 0}, {"msg_p", ctx->msg_p, ctx->msg_p ? T * kDim : 0},   // hm16 rows, raw (4 bytes per value)
       {"qkb", ctx->qkb, ctx->qkb ? T * kDim : 0}, {"rot4", ctx->rot4, ctx->rot4 ? T * 2 * kFreq : 0}, {"vtb", ctx->vtb, ctx->vtb ? T * kDim / 2 : 0}};
   for (const Ent& e : tab)
     if (strcmp(e.n, name) == 0) {
@@ -2478,6 +2528,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 31) ctx->use_lists = value;
   else if (which == 32) ctx->qkv_in_tail = value ? 1 : 0;
   else if (which == 33) ctx->skinny = value;
+  else if (which == 48) ctx->prep_fused = value ? 1 : 0;
   else if (which == 29) {   // CU shares for the sub-batch streams: takes effect for streams created afterwards
     GN_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 8; ++i) if (ctx->sub_s[i]) { hipStreamSynchronize(ctx->sub_s[i]); hipEventDestroy(ctx->ev_join[i]); hipStreamDestroy(ctx->sub_s[i]); ctx->sub_s[i] = nullptr; ctx->ev_join[i] = nullptr; }

@@ -251,6 +251,10 @@ struct PrepArgs {
   float size_q[2], size_r[2];   // image size (w, h) per side for normalize_keypoints; <= 0: the keypoint extent (hw = None in kornia's LightGlueMatcher)
   int feature;              // 0: SIFT (128-d descriptors, RootSIFT, Wr [32][4] on (x, y, scale, ori)); 1: SuperPoint-style (256-d descriptors used as they are, Wr [32][2] on (x, y))
   float* x; uint16_t* xp;   // feature 1: the descriptors go straight into the residual stream, f32 [T][256] and / or hm16 (either may be nullptr)
+  // optional second forms of k_prep's outputs, so that the default path needs no launch_split_hm16 / launch_rot_table behind it (same bits as theirs):
+  uint16_t* desc_p;         // feature 0: hm16 rows of desc, or nullptr
+  float* rot4; long long rot_stride;   // [16][rot_stride] float4 (cos, cos, sin, sin) rotary table for k_qkv, or nullptr
+  unsigned int* ovf_clear; unsigned int ovf_init;   // f16x2 domain guard word of the call: k_extent stores ovf_init into it (nullptr: left alone)
 };
 void launch_prep(const PrepArgs& a, hipStream_t s);
 void launch_ln_gelu(float* h, const float* gamma, const float* beta, int rows, hipStream_t s,

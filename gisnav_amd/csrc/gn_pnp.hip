@@ -1,5 +1,6 @@
-// Batched PnP + RANSAC + Rodrigues on gfx950: k_pnp_hyp = one single-wave workgroup per (pair, RANSAC hypothesis) -- the cv::RNG stream does not depend on
-// the models, so the <= 10 hypotheses of a pair run concurrently --, k_pnp_refine = one wave per pair (best-model replay, initial guess, LM, Rodrigues).
+// Batched PnP + RANSAC + Rodrigues on gfx950: k_pnp_hyp = one wave per (pair, RANSAC hypothesis), eight independent waves to a workgroup, each on its
+// own slice of LDS and with no workgroup barrier -- the cv::RNG stream does not depend on the models, so the <= 10 hypotheses of a pair run
+// concurrently --, k_pnp_refine = one wave per pair (best-model replay, initial guess, LM, Rodrigues).
 //
 // Stands in for `cv2.solvePnPRansac(obj, img, K, zeros(4,1), useExtrinsicGuess=False,
 // iterationsCount=10)` + `cv2.Rodrigues` as called by `compute_pose`
@@ -66,9 +67,15 @@ __device__ __forceinline__ double fast_rcp(double x) {
   e = __builtin_fma(-x, y, 1.0);
   return __builtin_fma(y, e, y);
 }
-// Every PnP kernel runs single-wave workgroups, so a workgroup barrier is a wave barrier: it orders the
-// LDS traffic exchanged between lanes and costs next to nothing.
-__device__ inline void wave_sync() { __syncthreads(); }
+// Every PnP wave works alone on its own `Shared` (k_pnp_hyp packs several such waves into one workgroup, and they take different trip
+// counts: a workgroup barrier would not be safe there).  The lanes of one wave exchange data through LDS (k_pnp_refine with more than kLdsPts
+// inliers: through its global workspace): a release / acquire fence pair -- the waits of __syncthreads() for the wave's outstanding memory
+// operations, no reordering by the compiler across it, and no s_barrier -- is all the exchange needs.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 struct Shared {
   double A[144];
@@ -1355,15 +1362,23 @@ __device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const fl
   return true;
 }
 
-// Two launches per batch.  k_pnp_hyp: one single-wave workgroup per (pair, RANSAC hypothesis) -- the
-// RNG stream and therefore the subsets do not depend on the models, so workgroup h replays cv::RNG to its
-// own subset, runs EPnP and scores it with the full 512-register budget of a lone wave.  k_pnp_refine:
+// Two launches per batch.  k_pnp_hyp: one wave per (pair, RANSAC hypothesis) -- the RNG stream and therefore
+// the subsets do not depend on the models, so wave h replays cv::RNG to its own subset, runs EPnP and scores
+// it.  The waves are independent (own slice of LDS, no workgroup barrier) and are launched kHypPack to a
+// workgroup, two per SIMD with their 255 registers: the 160 waves of a 16-pair group then sit on 20 compute
+// units instead of being dealt out one to a unit over 160 of them, where each of these ~100 us serial f64
+// chains keeps a matcher workgroup of a concurrent stream (one per unit, all its registers) from starting.  k_pnp_refine:
 // one wave per pair replays the sequential `good > max(maxGood, 4)` / RANSACUpdateNumIters logic over
 // the results in hypothesis order (hypotheses past the adapted iteration count are ignored, exactly as
 // the sequential loop would never have computed them) and refines the winner.
-__global__ __launch_bounds__(64) void k_pnp_hyp(PnpArgs a) {
-  __shared__ Shared sh;
-  const int b = blockIdx.y, wave = blockIdx.x, lane = threadIdx.x;
+constexpr int kHypPack = 8;
+__global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
+  __shared__ Shared shs[kHypPack];
+  const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int id = blockIdx.x * kHypPack + slot;      // hypothesis `wave` of pair b
+  if (id >= nh * a.B) return;
+  const int b = id / nh, wave = id - b * nh;
+  Shared& sh = shs[slot];
   const int n = a.n_pts[b];
   const float* obj = a.obj + (size_t)b * a.kstride * 3;
   const float* img = a.img + (size_t)b * a.kstride * 2;
@@ -1777,7 +1792,7 @@ void launch_epnp_debug(const double* pws, const double* us, double* out, int n, 
 
 void launch_pnp(const PnpArgs& a, hipStream_t s) {
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
-  hipLaunchKernelGGL(k_pnp_hyp, dim3(nh, a.B), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_pnp_hyp, dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, nh);
   hipLaunchKernelGGL(k_pnp_refine, dim3(a.B), dim3(64), 0, s, a);
 }
 

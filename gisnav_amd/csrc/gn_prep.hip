@@ -65,6 +65,26 @@ __global__ __launch_bounds__(256) void k_extent(PrepArgs a) {
     a.extent[bs * 2 + 0] = given[0] > 0.f ? given[0] : fmaxf(fmaxf(sx[0], sx[1]), fmaxf(sx[2], sx[3]));
     a.extent[bs * 2 + 1] = given[1] > 0.f ? given[1] : fmaxf(fmaxf(sy[0], sy[1]), fmaxf(sy[2], sy[3]));
     a.nvalid[bs] = n;
+    if (bs == 0 && a.ovf_clear != nullptr) *a.ovf_clear = a.ovf_init;   // the call's f16x2 guard word starts clear (every later launch of the call may raise it)
+  }
+}
+
+// one token's share of the hm16 descriptor rows and of the rot4 table, written by the wave that has just produced the f32 values: the same bits
+// k_split_hm16 (scale 1) and k_rot_table make of them.  d0 / d1: descriptor columns lane / lane + 64; c / sn: cos / sin of frequency `lane` (< kFreq)
+__device__ __forceinline__ void prep_second_forms(const PrepArgs& a, size_t tok, int lane, float d0, float d1, float c, float sn) {
+  if (a.desc_p != nullptr) {
+    const _Float16 h0 = (_Float16)d0, h1 = (_Float16)d1;
+    const _Float16 m0 = (_Float16)(d0 - (float)h0), m1 = (_Float16)(d1 - (float)h1);
+    uint16_t* q0 = a.desc_p + hm16_off(tok, kInDim, lane), *q1 = a.desc_p + hm16_off(tok, kInDim, lane + 64);
+    q0[0] = __builtin_bit_cast(uint16_t, h0); q0[16] = __builtin_bit_cast(uint16_t, m0);
+    q1[0] = __builtin_bit_cast(uint16_t, h1); q1[16] = __builtin_bit_cast(uint16_t, m1);
+  }
+  if (a.rot4 != nullptr) {      // (wave-uniform: every lane takes part in the exchange, the even lanes below kFreq store)
+    const float c1 = __shfl_down(c, 1), s1 = __shfl_down(sn, 1);
+    if (lane < kFreq && (lane & 1) == 0) {
+      const f32x4 v = {c, c1, sn, s1};
+      reinterpret_cast<f32x4*>(a.rot4)[(size_t)(lane >> 1) * a.rot_stride + tok] = v;
+    }
   }
 }
 
@@ -80,22 +100,23 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs a) {
   if (i >= n) {  // padding slot: finite, inert values
     dout[lane] = 0.f; dout[lane + 64] = 0.f;
     if (lane < kFreq) { a.cos_t[tok * kFreq + lane] = 1.f; a.sin_t[tok * kFreq + lane] = 0.f; }
+    prep_second_forms(a, tok, lane, 0.f, 0.f, 1.f, 0.f);
     return;
   }
   const int fmt_ = a.kpt_format & 0xff;
   // GN_KPT_RECORD: the descriptor is the tail of the keypoint's own 532-byte wire record (4-byte aligned only: scalar loads)
   const float* din = fmt_ == GN_KPT_RECORD ? (side ? a.kpt_r : a.kpt_q) + ((size_t)b * stride + i) * kRecordFloats + 5
                                            : (side ? a.desc_r : a.desc_q) + ((size_t)b * stride + i) * kInDim;
-  const float d0 = din[lane], d1 = din[lane + 64];
-  if (a.kpt_format & GN_DESC_ROOTSIFT) {
-    dout[lane] = d0; dout[lane + 64] = d1;
-  } else {
+  float d0 = din[lane], d1 = din[lane + 64];
+  if (!(a.kpt_format & GN_DESC_ROOTSIFT)) {
     const float l1 = wave_sum(fabsf(d0) + fabsf(d1));
     const float den = fmaxf(l1, 1e-12f);  // F.normalize(p=1, eps=1e-12)
-    dout[lane] = sqrtf(d0 / den);
-    dout[lane + 64] = sqrtf(d1 / den);
+    d0 = sqrtf(d0 / den);
+    d1 = sqrtf(d1 / den);
   }
+  dout[lane] = d0; dout[lane + 64] = d1;
 
+  float ce = 1.f, se = 0.f;
   if (lane < kFreq) {
     const int fmt = a.kpt_format & 0xff;
     const int w = fmt == GN_KPT_LAF ? 6 : fmt == GN_KPT_RECORD ? kRecordFloats : 4;
@@ -107,9 +128,11 @@ __global__ __launch_bounds__(256) void k_prep(PrepArgs a) {
     const float xn = (x - sx / 2.0f) / sc, yn = (y - sy / 2.0f) / sc;  // normalize_keypoints
     const float* wr = a.wr + lane * 4;
     const float e = wr[0] * xn + wr[1] * yn + wr[2] * scale + wr[3] * ori;
-    a.cos_t[tok * kFreq + lane] = cosf(e);
-    a.sin_t[tok * kFreq + lane] = sinf(e);
+    ce = cosf(e); se = sinf(e);
+    a.cos_t[tok * kFreq + lane] = ce;
+    a.sin_t[tok * kFreq + lane] = se;
   }
+  prep_second_forms(a, tok, lane, d0, d1, ce, se);
 }
 
 // LightGlue(features = "superpoint" / any 256-d extractor): descriptors are used as they are (input_proj is the identity when

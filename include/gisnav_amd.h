@@ -138,7 +138,10 @@ int gn_get_guard_status(gn_ctx* ctx, void* stream, int32_t* last_call_tripped, i
  *   mode 0  off (default): no flags are written;
  *   mode 1  flags only, stream-ordered, no host synchronisation: gn_get_uncertain reads them;
  *   mode 3  as mode 2, but gn_estimate with sub-batch streams resolves call n's flags after call n + 1 has been enqueued (or in gn_flush): the caller keeps
- *           the inputs AND outputs of call n untouched until then (two alternating output sets); no host wait on an idle GPU;
+ *           the inputs AND outputs of call n untouched until then (two alternating output sets); no host wait on an idle GPU.
+ *           When such a gn_estimate returns, `stream` is behind the call's match heads only: its gather and PnP are still in flight on the
+ *           library's own streams.  A later gn_estimate orders itself behind them; every OTHER entry point that uses the context's match or
+ *           PnP workspaces (gn_match, gn_gather_points, gn_pnp_ransac, ...) needs a gn_flush first;
  *   mode 2  certified results: gn_match / gn_estimate synchronise the stream once per call, read the flags and run every flagged pair
  *           again -- matcher, and for gn_estimate also gather + PnP -- on GN_PREC_F32's kernels (the context keeps f32 weights and f32
  *           workspaces in every mode).  A call whose activations left the fp16 range is flagged as a whole (flag value 2), so this mode
