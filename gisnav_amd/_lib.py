@@ -38,6 +38,11 @@ SIGNATURES = {
                                 VP, VP, VP, VP, VP]),
     "gn_estimate": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int,
                               c_f64p, C.c_int, VP, VP, VP, VP, VP, VP]),
+    # the *_cov entry points: the same lists + sigma_px, cov_rt [B][36] f64, sigma_hat [B] f64, cov_ok [B] u8 in front of the stream
+    "gn_pnp_ransac_cov": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_int, C.c_float, C.c_double, C.c_int,
+                                    VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
+    "gn_estimate_cov": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int,
+                                  c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
     "gn_set_overlap": (C.c_int, [VP, C.c_int]),
     "gn_flush": (C.c_int, [VP, VP]),
     "gn_set_substreams": (C.c_int, [VP, C.c_int]),
@@ -61,11 +66,15 @@ SIGNATURES = {
     "gn_vo_match": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, VP, VP, C.c_int, C.c_double, VP, VP, VP, VP, VP, VP]),
     "gn_vo_estimate": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_double, C.c_int,
                                  VP, VP, VP, VP, VP, VP]),
+    "gn_vo_estimate_cov": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_double, C.c_int,
+                                     VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
     "gn_rotate_crop_center": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, c_f64p, VP]),
     "gn_stereo_reference": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, VP, c_f64p, VP]),
     "gn_proj_to_affine": (C.c_int, [C.c_char_p, c_f64p]),
     "gn_wgs84_to_ecef": (C.c_int, [C.c_double, C.c_double, C.c_double, c_f64p]),
     "gn_pose_to_earth": (C.c_int, [c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p]),
+    "gn_pose_cov_to_camera": (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p]),
+    "gn_pose_cov_to_earth": (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, c_f64p]),
     "gn_sift_detect_and_compute": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_sift_detect_and_compute_batch": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_sift_last_totals": (C.c_int, [VP, C.c_int, C.POINTER(C.c_int32)]),

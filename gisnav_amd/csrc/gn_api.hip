@@ -42,6 +42,7 @@ struct Call {
   const float *desc_q = nullptr, *kpt_q = nullptr, *desc_r = nullptr, *kpt_r = nullptr; const int32_t *n_q = nullptr, *n_r = nullptr;
   const uint8_t* dem = nullptr; int H = 0, W = 0;
   double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr; int64_t* idx = nullptr; float* score = nullptr;
+  double *cov = nullptr, *sigma_hat = nullptr; uint8_t* cov_ok = nullptr; double sigma_px = 0.0;   // pose covariance (gn_estimate_cov): null = not asked for
   const double* K9 = nullptr; int min_matches = 0;
   int kw = 0, in_dim = 0; size_t km = 0;   // floats per keypoint, per descriptor; match-list stride (gn_kmax)
   Call() = default;
@@ -60,6 +61,7 @@ template <typename F, typename... C> void pair_arrays(const Call& h, F&& f, C&..
   f((size_t)4, false, c.n_q...); f((size_t)4, false, c.n_r...); f((size_t)h.H * h.W, false, c.dem...);
   f((size_t)72, true, c.R...); f((size_t)24, true, c.t...); f((size_t)4, true, c.n_match...); f((size_t)4, true, c.n_inliers...); f((size_t)1, true, c.ok...);
   f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...);
+  f((size_t)288, true, c.cov...); f((size_t)8, true, c.sigma_hat...); f((size_t)1, true, c.cov_ok...);
 }
 template <typename T> T* byte_offset(T* p, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes); }
 
@@ -1666,11 +1668,14 @@ int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int
   return GN_OK;
 }
 
-int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
-                  const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
-                  double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream) {
+namespace {
+// gn_pnp_ransac (cov, sigma_hat, cov_ok all null) and gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine)
+int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+             const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
+             double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!ctx || !obj || !img || !n_pts || !K9 || !R || !t || !n_inliers || !ok || B < 1 || B > ctx->max_batch)
     return fail(ctx, GN_ERR_ARG, "bad gn_pnp_ransac argument");
+  if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
   if (kstride < 1 || kstride > ctx->npad) return fail(ctx, GN_ERR_ARG, "kstride exceeds max_kpts of this context");
   if (iterations_count < 1 || iterations_count > 16) return fail(ctx, GN_ERR_ARG, "iterations_count must be in 1..16 (PoseNode uses 10)");
   GN_HIP(hipSetDevice(ctx->device));
@@ -1680,10 +1685,28 @@ int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const 
   a.iterations = iterations_count; a.reproj = reproj_error_px; a.confidence = confidence; a.min_pts = min_pts;
   a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = ctx->mask_ws; a.hyp = ctx->hyp_ws; a.pts_ws = ctx->pts_ws;
   a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(ctx->sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
+  a.sigma_px = sigma_px; a.cov = cov; a.sigma_hat = sigma_hat; a.cov_ok = cov_ok;
   StageTimer tm(ctx, (hipStream_t)stream, ST_PNP);
   launch_pnp(a, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
   return GN_OK;
+}
+}  // namespace
+
+int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+                  const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
+                  double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream) {
+  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+                  0.0, nullptr, nullptr, nullptr, stream);
+}
+
+int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+                      const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
+                      double* R, double* t, int32_t* n_inliers, uint8_t* ok,
+                      double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+  if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_pnp_ransac_cov: null covariance output");
+  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+                  sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
 namespace {
@@ -1761,8 +1784,8 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
     rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
                           ctx->e_mkp, ctx->e_obj, stream);
     if (rc != GN_OK) return rc;
-    return gn_pnp_ransac(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
-                         v.R, v.t, v.n_inliers, v.ok, stream);
+    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+                    v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream);
   }
   hipStream_t s = (hipStream_t)stream;
   GN_HIP(hipSetDevice(ctx->device));
@@ -1774,8 +1797,8 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
   GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
-  rc = gn_pnp_ransac(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
-                     v.R, v.t, v.n_inliers, v.ok, ctx->s_pnp);
+  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+                v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp);
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
   ctx->pnp_pending[slot][g] = ctx->pnp_recorded[slot][g] = true;
@@ -1797,11 +1820,14 @@ int cert_resolve(gn_ctx* ctx, int slot, hipStream_t s) {
 }
 }  // namespace
 
-int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
-                const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-                const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-                const uint8_t* dem, int H, int W, const double* K9, int min_matches,
-                double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream) {
+namespace {
+// gn_estimate (covariance pointers null) and gn_estimate_cov
+int estimate_call(gn_ctx* ctx, int B, int kpt_format,
+                  const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                  const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                  const uint8_t* dem, int H, int W, const double* K9, int min_matches,
+                  double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                  double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
   if (ctx->fused_proj_pending && ctx->npad > 0 && gn_missing_tensors(ctx) == 0) {      // (the sub-batch groups below skip it: their workspace pointers are shifted)
     GN_HIP(hipSetDevice(ctx->device));
@@ -1812,6 +1838,7 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
   Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
   v.dem = dem; v.H = H; v.W = W; v.K9 = K9; v.min_matches = min_matches;
   v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
+  v.sigma_px = sigma_px; v.cov = cov; v.sigma_hat = sigma_hat; v.cov_ok = cov_ok;
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
     // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the un-shifted workspaces, on the
@@ -1880,6 +1907,27 @@ int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
     rc_all = certify_rerun(ctx, s, v, [&](const Call& w) { return estimate_impl(ctx, w, s); });
   }
   return rc_all;
+}
+}  // namespace
+
+int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
+                const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                const uint8_t* dem, int H, int W, const double* K9, int min_matches,
+                double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream) {
+  return estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, dem, H, W, K9, min_matches,
+                       R, t, n_match, n_inliers, ok, 0.0, nullptr, nullptr, nullptr, stream);
+}
+
+int gn_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
+                    const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                    const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                    const uint8_t* dem, int H, int W, const double* K9, int min_matches,
+                    double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                    double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+  if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_estimate_cov: null covariance output");
+  return estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, dem, H, W, K9, min_matches,
+                       R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
 int gn_set_deferred_join(gn_ctx* ctx, int enable) {
@@ -1981,11 +2029,13 @@ int gn_vo_match(gn_ctx* ctx, int B, const float* desc_q, const int32_t* n_q, int
 
 // TwistNode._pose lines 227-289 for B frame pairs: 2-NN match -> ratio test -> MIN_MATCHES gate -> compute_pose with
 // a zero elevation raster (planar PnP)
-int gn_vo_estimate(gn_ctx* ctx, int B, int kpt_format,
-                   const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-                   const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-                   const double* K9, double ratio, int min_matches,
-                   double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream) {
+namespace {
+int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
+                     const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                     const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                     const double* K9, double ratio, int min_matches,
+                     double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                     double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
   int rc = gn_vo_match(ctx, B, desc_q, n_q, stride_q, desc_r, n_r, stride_r, ratio, ctx->e_idx, ctx->e_score, n_match,
                        nullptr, nullptr, stream);
@@ -1993,8 +2043,29 @@ int gn_vo_estimate(gn_ctx* ctx, int B, int kpt_format,
   rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, nullptr, 0, 0,
                         ctx->e_mkp, ctx->e_obj, stream);
   if (rc != GN_OK) return rc;
-  return gn_pnp_ransac(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, 10, 8.0f, 0.99, min_matches,
-                       R, t, n_inliers, ok, stream);
+  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, 10, 8.0f, 0.99, min_matches,
+                  R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream);
+}
+}  // namespace
+
+int gn_vo_estimate(gn_ctx* ctx, int B, int kpt_format,
+                   const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                   const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                   const double* K9, double ratio, int min_matches,
+                   double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream) {
+  return vo_estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, K9, ratio, min_matches,
+                          R, t, n_match, n_inliers, ok, 0.0, nullptr, nullptr, nullptr, stream);
+}
+
+int gn_vo_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
+                       const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                       const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                       const double* K9, double ratio, int min_matches,
+                       double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+  if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_vo_estimate_cov: null covariance output");
+  return vo_estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, K9, ratio, min_matches,
+                          R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
 namespace {

@@ -310,6 +310,11 @@ struct PnpArgs {
   HypResult* hyp;            // [B][16]
   float* pts_ws;             // [B][kstride][5] scratch: a pair's compacted inliers when they exceed k_pnp_refine's LDS capacity (2048)
   long long* dbg_ts;         // developer: nullptr, or [B][16 + 1][16] s_memtime phase stamps (k_pnp_hyp waves, then k_pnp_refine)
+  // pose covariance (gn_pnp_ransac_cov): all three null = not asked for, k_pnp_cov is not launched
+  double sigma_px = 0.0;     // > 0: the stated pixel sigma; else the residuals' own
+  double* cov = nullptr;     // [B][36]
+  double* sigma_hat = nullptr;   // [B]
+  uint8_t* cov_ok = nullptr;     // [B]
 };
 void launch_pnp(const PnpArgs& a, hipStream_t s);
 void launch_epnp_debug(const double* pws, const double* us, double* out, int n, hipStream_t s);

@@ -1,6 +1,7 @@
 // Batched PnP + RANSAC + Rodrigues on gfx950: k_pnp_hyp = one wave per (pair, RANSAC hypothesis), eight independent waves to a workgroup, each on its
 // own slice of LDS and with no workgroup barrier -- the cv::RNG stream does not depend on the models, so the <= 10 hypotheses of a pair run
-// concurrently --, k_pnp_refine = one wave per pair (best-model replay, initial guess, LM, Rodrigues).
+// concurrently --, k_pnp_refine = one wave per pair (best-model replay, initial guess, LM, Rodrigues); on request k_pnp_cov = one wave per pair
+// (covariance of the returned pose from the winner's inliers).
 //
 // Stands in for `cv2.solvePnPRansac(obj, img, K, zeros(4,1), useExtrinsicGuess=False,
 // iterationsCount=10)` + `cv2.Rodrigues` as called by `compute_pose`
@@ -918,15 +919,10 @@ __device__ bool epnp5(Shared& sh, int lane, double Rb[3][3], double tb[3], doubl
 // ------------------------------------------------------------------------------------------------
 struct Cam { double fx, fy, cx, cy; };
 
-// |e|^2, and optionally J^T J (upper, 21) and J^T e (6), over the n (compacted inlier) points
-__device__ inline double lm_accumulate(const float* obj, const float* img, int n, int lane,
-                                       const Cam& cam, const double p[6], bool want_j, double JtJ[21], double Jte[6]) {
-  double R[3][3], dR[3][9];
-  rodrigues_v2m(p, R, dR, want_j);
-  double acc[28];
-#pragma unroll
-  for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-  for (int i = lane; i < n; i += 64) {
+// point i's share of |e|^2 (acc[27]) and optionally of J^T J (upper, acc[0..20]) and J^T e (acc[21..26]) at the pose p = (rvec, tvec), R = R(rvec),
+// dR = dR / drvec: f32 inputs widened, everything else f64
+__device__ __forceinline__ void lm_point(const float* obj, const float* img, int i, const Cam& cam, const double p[6], const double R[3][3],
+                                         const double dR[3][9], bool want_j, double acc[28]) {
     const double M0 = obj[3 * i], M1 = obj[3 * i + 1], M2 = obj[3 * i + 2];
     const double X = R[0][0] * M0 + R[0][1] * M1 + R[0][2] * M2 + p[3];
     const double Y = R[1][0] * M0 + R[1][1] * M1 + R[1][2] * M2 + p[4];
@@ -958,7 +954,17 @@ __device__ inline double lm_accumulate(const float* obj, const float* img, int n
         acc[21 + r] += jx[r] * ex + jy[r] * ey;
       }
     }
-  }
+}
+
+// |e|^2, and optionally J^T J (upper, 21) and J^T e (6), over the n (compacted inlier) points
+__device__ inline double lm_accumulate(const float* obj, const float* img, int n, int lane,
+                                       const Cam& cam, const double p[6], bool want_j, double JtJ[21], double Jte[6]) {
+  double R[3][3], dR[3][9];
+  rodrigues_v2m(p, R, dR, want_j);
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+  for (int i = lane; i < n; i += 64) lm_point(obj, img, i, cam, p, R, dR, want_j, acc);
   const int lo = want_j ? 0 : 27;
 #pragma unroll
   for (int k = 0; k < 28; ++k)
@@ -1035,6 +1041,22 @@ __device__ inline unsigned rng_next(unsigned long long& st) {
 
 constexpr int kMaxHyp = 16;   // RANSAC hypotheses evaluated concurrently, one wavefront each
 
+// The sequential `good > max(maxGood, 4)` / RANSACUpdateNumIters loop replayed over the hypotheses k_pnp_hyp left, in hypothesis order (those past
+// the adapted iteration count are ignored, as the sequential loop would never have computed them): the winner's index (-1: none) and inlier count.
+__device__ __forceinline__ int select_hypothesis(const HypResult* hyp, int nhyp, int n, double confidence, int& max_good) {
+  int niters = nhyp, best = -1;
+  max_good = 0;
+  for (int it = 0; it < nhyp; ++it) {
+    if (it >= niters) break;
+    if (!hyp[it].valid) continue;
+    const int good = hyp[it].good;
+    if (good > (max_good > 4 ? max_good : 4)) {
+      best = it; max_good = good;
+      niters = ransac_update_iters(confidence, (double)(n - good) / n, 5, niters);
+    }
+  }
+  return best;
+}
 
 // planar-structure initial guess of cvFindExtrinsicCameraParams2 (homography from the model plane)
 __device__ __noinline__ bool pnp_init_planar(Shared& sh, const float* obj, const float* img, int ninl, int lane, const Cam& cam, const double mc[3], const double Vc[3][3], double p[6]) {
@@ -1642,16 +1664,8 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   }
 
   // ---- sequential selection over the hypotheses ----------------------------------------------------
-  int niters = nhyp, max_good = 0, best = -1;
-  for (int it = 0; it < nhyp; ++it) {
-    if (it >= niters) break;
-    if (!hyp[it].valid) continue;
-    const int good = hyp[it].good;
-    if (good > (max_good > 4 ? max_good : 4)) {
-      best = it; max_good = good;
-      niters = ransac_update_iters(a.confidence, (double)(n - good) / n, 5, niters);
-    }
-  }
+  int max_good;
+  const int best = select_hypothesis(hyp, nhyp, n, a.confidence, max_good);
   if (best < 0) {
     if (lane < 9) Rout[lane] = (lane % 4 == 0) ? 1.0 : 0.0;
     if (lane < 3) tout[lane] = 0.0;
@@ -1759,6 +1773,116 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
     a.n_inliers[b] = ninl;
   }
 }
+
+// ---- pose covariance (gn_pnp_ransac_cov; DESIGN.md "Pose covariance") --------------------------------------------------------------------
+// cov = s^2 (J^T J)^-1 at the pose k_pnp_refine returned, over the inliers of the winning hypothesis: one wave per pair, launched behind
+// k_pnp_refine on the same stream and only when asked for.  The wave finds the winner by the replay k_pnp_refine uses, strides the pair's points
+// over its lanes with the mask test (no compaction: one pass), accumulates the 21 upper entries of N = J^T J and |e|^2 in f64 per lane exactly as
+// lm_accumulate forms them, reduces with wsum and inverts N wave-uniformly: N = L D L^T without pivoting, every pivot required to exceed 1e-12 of
+// its diagonal entry, N^-1 = M^T D^-1 M with M = L^-1 (upper triangle computed, mirrored: symmetric by construction); lane 0 writes the results.  rvec comes from the
+// returned R by rodrigues_m2v.  No LDS, no barrier; kCovPack waves to a workgroup for the reason given at k_pnp_hyp: these are serial f64 chains
+// (22 DPP reductions and a few hundred dependent f64 operations behind one pass over the points), and dealt out one wave to a workgroup they
+// would each hold a compute unit against a matcher workgroup of a concurrent stream.
+constexpr int kCovPack = 8;
+__global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
+  const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int b = blockIdx.x * kCovPack + slot;
+  if (b >= a.B) return;
+  double* const cov = a.cov + (size_t)b * 36;
+  const int n = a.n_pts[b], ninl = a.n_inliers[b];
+  const int dof = 2 * ninl - 6;
+  bool good = a.ok[b] != 0 && dof > 0;
+  // the inlier set: every point in solvePnPRansac's `npoints == 4` / `model_points == npoints` branches (k_pnp_refine), else the winner's mask
+  const uint8_t* mask = nullptr;
+  if (good && !((n == 4 && a.min_pts <= 4) || (n == 5 && a.min_pts <= 5))) {
+    int max_good;
+    const int best = select_hypothesis(a.hyp + (size_t)b * kMaxHyp, a.iterations, n, a.confidence, max_good);
+    good = best >= 0;
+    mask = a.mask_ws + ((size_t)b * kMaxHyp + (best < 0 ? 0 : best)) * a.kstride;
+  }
+  double c36[36], sig = 0.0;
+#pragma unroll
+  for (int k = 0; k < 36; ++k) c36[k] = 0.0;
+  if (good) {
+    const float* obj = a.obj + (size_t)b * a.kstride * 3;
+    const float* img = a.img + (size_t)b * a.kstride * 2;
+    const Cam cam = {a.fx, a.fy, a.cx, a.cy};
+    double Rm[3][3], p[6], R[3][3], dR[3][9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { p[3 + i] = a.t[(size_t)b * 3 + i];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Rm[i][j] = a.R[(size_t)b * 9 + 3 * i + j]; }
+    rodrigues_m2v(Rm, p);
+    rodrigues_v2m(p, R, dR, true);
+    double acc[28];
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+    for (int i = lane; i < n; i += 64)
+      if (!mask || mask[i]) lm_point(obj, img, i, cam, p, R, dR, true, acc);
+    double N[6][6];
+    int q = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) { N[r][c] = wsum(acc[q]); ++q; }
+    const double e2 = wsum(acc[27]);
+    // N = L D L^T; M = L^-1 (unit lower triangular) by forward substitution on the identity
+    double L[6][6], d[6], M[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double dj = N[j][j];
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+        if (k < j) dj -= L[j][k] * L[j][k] * d[k];
+      good = good && dj > 1e-12 * N[j][j];
+      d[j] = dj;
+      const double inv = 1.0 / dj;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+        if (i > j) {
+          double v = N[j][i];
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            if (k < j) v -= L[i][k] * L[j][k] * d[k];
+          L[i][j] = v * inv;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j)
+        if (j <= i) {
+          double v = i == j ? 1.0 : 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            if (k >= j && k < i) v -= L[i][k] * M[k][j];
+          M[i][j] = v;
+        }
+    const double s2hat = e2 / dof;
+    const double s2 = a.sigma_px > 0.0 ? a.sigma_px * a.sigma_px : s2hat;
+    sig = sqrt(s2hat);
+    good = good && isfinite(sig);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j)
+        if (j >= i) {
+          double v = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            if (k >= j) v += M[k][i] * M[k][j] / d[k];
+          v *= s2;
+          good = good && isfinite(v);
+          c36[6 * i + j] = v; c36[6 * j + i] = v;
+        }
+  }
+  // everything is wave-uniform: lane 0 writes; a pair without a covariance gets zeros
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) cov[k] = good ? c36[k] : 0.0;
+    a.sigma_hat[b] = good ? sig : 0.0; a.cov_ok[b] = good ? 1 : 0;
+  }
+}
 }  // namespace
 
 // test hook: EPnP on n independent 5-point sets (world points f64 [n][5][3], normalised image points
@@ -1794,6 +1918,7 @@ void launch_pnp(const PnpArgs& a, hipStream_t s) {
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
   hipLaunchKernelGGL(k_pnp_hyp, dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, nh);
   hipLaunchKernelGGL(k_pnp_refine, dim3(a.B), dim3(64), 0, s, a);
+  if (a.cov) hipLaunchKernelGGL(k_pnp_cov, dim3((a.B + kCovPack - 1) / kCovPack), dim3(64 * kCovPack), 0, s, a);
 }
 
 }  // namespace gn

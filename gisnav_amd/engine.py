@@ -411,15 +411,31 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_gather_points")
         return mkp_q, obj
 
+    def _alloc_cov(self, B: int) -> dict:
+        d = self.device
+        return dict(cov=torch.empty((B, 6, 6), dtype=torch.float64, device=d), sigma=torch.empty((B,), dtype=torch.float64, device=d),
+                    cov_ok=torch.empty((B,), dtype=torch.uint8, device=d))
+
     def pnp_ransac(self, obj, img, n_pts, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
-                   reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5):
-        """gn_pnp_ransac.  obj [B,S,3] f32, img [B,S,2] f32, n_pts [B] i32 (device)."""
+                   reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
+                   covariance: bool = False, sigma_px: float = 0.0):
+        """gn_pnp_ransac.  obj [B,S,3] f32, img [B,S,2] f32, n_pts [B] i32 (device).  Returns (R, t, n_inliers, ok); with covariance=True
+        (gn_pnp_ransac_cov) also cov [B,6,6] f64 of (rvec, tvec), sigma [B] f64 (a-posteriori pixel sigma) and cov_ok [B] u8.  sigma_px > 0
+        states the pixel noise; 0 scales the covariance with the residuals' own sigma."""
         B = obj.shape[0]
         R = torch.empty((B, 3, 3), dtype=torch.float64, device=self.device)
         t = torch.empty((B, 3, 1), dtype=torch.float64, device=self.device)
         n_inl = torch.empty((B,), dtype=torch.int32, device=self.device)
         ok = torch.empty((B,), dtype=torch.uint8, device=self.device)
         K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        if covariance:
+            c = self._alloc_cov(B)
+            rc = self.lib.gn_pnp_ransac_cov(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
+                                            K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                                            _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), float(sigma_px), _ptr(c["cov"]), _ptr(c["sigma"]), _ptr(c["cov_ok"]),
+                                            self._stream())
+            _lib.check(self.ctx, rc, "gn_pnp_ransac_cov")
+            return R, t, n_inl, ok, c["cov"], c["sigma"], c["cov_ok"]
         rc = self.lib.gn_pnp_ransac(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
                                     K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
                                     _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), self._stream())
@@ -443,10 +459,12 @@ class PoseEngine:
         return self._downloader(*tensors)
 
     def pnp_ransac_host(self, obj: np.ndarray, img: np.ndarray, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
-                        reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5):
+                        reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
+                        covariance: bool = False, sigma_px: float = 0.0):
         """gn_pnp_ransac for ONE correspondence list given as host arrays (seam B2): obj (n, 3), img (n, 2) -> (R (3,3) f64, t (3,1) f64, n_inliers, ok)
-        as host values.  One pinned staging block in ([n | pad | obj | img], one asynchronous copy), one 112-byte block out: pageable transfers of
-        this size were measured to stall for ~90 ms every few dozen calls on the MI355X boxes (tools/bench_seams.py), pinned ones never."""
+        as host values.  One pinned staging block in ([n | pad | obj | img], one asynchronous copy), one 416-byte block out: pageable transfers of
+        this size were measured to stall for ~90 ms every few dozen calls on the MI355X boxes (tools/bench_seams.py), pinned ones never.
+        covariance=True (gn_pnp_ransac_cov) appends (cov (6,6) f64, sigma, cov_ok) to the result."""
         n = int(len(obj))
         if n > self.kmax:
             raise _lib.GnError(f"{n} correspondences exceed this context's max_kpts {self.kmax}")
@@ -454,9 +472,9 @@ class PoseEngine:
         if io is None or io["cap"] != self.kmax:
             cap = self.kmax
             pin = torch.empty(8 + 5 * cap, dtype=torch.float32, pin_memory=True)
-            out = torch.zeros(112, dtype=torch.uint8, device=self.device)
+            out = torch.zeros(416, dtype=torch.uint8, device=self.device)      # R 72 | t 24 | pad 4 | n_inliers 4 | ok 1 | pad 7 | cov 288 | sigma 8 | cov_ok 1 (+ pad)
             io = self._pnp_io = dict(cap=cap, pin=pin, pin_np=pin.numpy(), dev=torch.empty(8 + 5 * cap, dtype=torch.float32, device=self.device), out=out,
-                                     host=torch.empty(112, dtype=torch.uint8, pin_memory=True))
+                                     host=torch.empty(416, dtype=torch.uint8, pin_memory=True))
             io["host_np"] = io["host"].numpy()
         h = io["pin_np"]
         h[:1].view(np.int32)[0] = n
@@ -466,14 +484,22 @@ class PoseEngine:
         d, o = io["dev"], io["out"]
         d[:i0 + 2 * n].copy_(io["pin"][:i0 + 2 * n], non_blocking=True)
         K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
-        rc = self.lib.gn_pnp_ransac(self.ctx, 1, _ptr(d[4:4 + 3 * n]), _ptr(d[i0:i0 + 2 * n]), _ptr(d[:1].view(torch.int32)), n,
-                                    K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
-                                    _ptr(o[0:72]), _ptr(o[72:96]), _ptr(o[100:104]), _ptr(o[104:105]), self._stream())
-        _lib.check(self.ctx, rc, "gn_pnp_ransac")
-        io["host"].copy_(o, non_blocking=True)
+        args = (self.ctx, 1, _ptr(d[4:4 + 3 * n]), _ptr(d[i0:i0 + 2 * n]), _ptr(d[:1].view(torch.int32)), n,
+                K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                _ptr(o[0:72]), _ptr(o[72:96]), _ptr(o[100:104]), _ptr(o[104:105]))
+        if covariance:
+            rc = self.lib.gn_pnp_ransac_cov(*args, float(sigma_px), _ptr(o[112:400]), _ptr(o[400:408]), _ptr(o[408:409]), self._stream())
+        else:
+            rc = self.lib.gn_pnp_ransac(*args, self._stream())
+        _lib.check(self.ctx, rc, "gn_pnp_ransac_cov" if covariance else "gn_pnp_ransac")
+        nb = 416 if covariance else 112
+        io["host"][:nb].copy_(o[:nb], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         r = io["host_np"]
-        return (r[0:72].view(np.float64).reshape(3, 3).copy(), r[72:96].view(np.float64).reshape(3, 1).copy(), int(r[100:104].view(np.int32)[0]), bool(r[104]))
+        res = (r[0:72].view(np.float64).reshape(3, 3).copy(), r[72:96].view(np.float64).reshape(3, 1).copy(), int(r[100:104].view(np.int32)[0]), bool(r[104]))
+        if covariance:
+            res += (r[112:400].view(np.float64).reshape(6, 6).copy(), float(r[400:408].view(np.float64)[0]), bool(r[408]))
+        return res
 
     def set_ragged(self, ragged: Optional[bool]) -> None:
         """Override of a choice the library makes by itself.  The big kernels skip tiles that hold only padding either way; the block tail has two
@@ -505,11 +531,13 @@ class PoseEngine:
         _lib.check(self.ctx, self.lib.gn_flush(self.ctx, self._stream()), "gn_flush")
         self._last_out_ptr = None
 
-    def estimate(self, inputs: dict, K: np.ndarray, min_matches: int = MIN_MATCHES, out: Optional[dict] = None):
-        """gn_estimate on staged inputs: PoseNode._pose lines 246-308 for the whole batch."""
+    def estimate(self, inputs: dict, K: np.ndarray, min_matches: int = MIN_MATCHES, out: Optional[dict] = None,
+                 covariance: bool = False, sigma_px: float = 0.0):
+        """gn_estimate on staged inputs: PoseNode._pose lines 246-308 for the whole batch.  covariance=True (gn_estimate_cov): `out` also
+        carries cov [B,6,6], sigma [B], cov_ok [B] (alloc_outputs(B, covariance=True)), complete when R / t / ok are."""
         B = inputs["kpt_q"].shape[0]
         if out is None:
-            out = self.alloc_outputs(B)
+            out = self.alloc_outputs(B, covariance)
         if getattr(self, "_certify_mode", 0) == 3:
             if self._last_out_ptr == out["R"].data_ptr():
                 raise _lib.GnError("deferred certificate: this call would write the outputs of the previous call, whose flagged pairs may still be re-run -- "
@@ -519,13 +547,16 @@ class PoseEngine:
         H, W = (dem.shape[1], dem.shape[2]) if dem is not None else (0, 0)
         K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
         # (GN_KPT_RECORD inputs carry the descriptors inside the keypoint records: desc_q / desc_r are None)
-        rc = self.lib.gn_estimate(self.ctx, B, inputs["kpt_format"],
-                                  _ptr(inputs.get("desc_q")), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["kpt_q"].shape[1],
-                                  _ptr(inputs.get("desc_r")), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["kpt_r"].shape[1],
-                                  _ptr(dem), H, W, K9.ctypes.data_as(_lib.c_f64p), min_matches,
-                                  _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]),
-                                  self._stream())
-        _lib.check(self.ctx, rc, "gn_estimate")
+        args = (self.ctx, B, inputs["kpt_format"],
+                _ptr(inputs.get("desc_q")), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["kpt_q"].shape[1],
+                _ptr(inputs.get("desc_r")), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["kpt_r"].shape[1],
+                _ptr(dem), H, W, K9.ctypes.data_as(_lib.c_f64p), min_matches,
+                _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
+        if covariance:
+            rc = self.lib.gn_estimate_cov(*args, float(sigma_px), _ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"]), self._stream())
+        else:
+            rc = self.lib.gn_estimate(*args, self._stream())
+        _lib.check(self.ctx, rc, "gn_estimate_cov" if covariance else "gn_estimate")
         return out
 
     def estimate_bucketed(self, inputs: dict, K: np.ndarray, n_q_host, n_r_host, bucket_pairs: int = 8, min_matches: int = MIN_MATCHES,
@@ -618,19 +649,23 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_vo_match")
         return (idx, dist, n_good, nn_idx, nn_dist) if want_knn else (idx, dist, n_good)
 
-    def vo_estimate(self, inputs: dict, K: np.ndarray, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None):
-        """gn_vo_estimate on staged inputs: TwistNode._pose lines 227-289 for the whole batch."""
+    def vo_estimate(self, inputs: dict, K: np.ndarray, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None,
+                    covariance: bool = False, sigma_px: float = 0.0):
+        """gn_vo_estimate on staged inputs: TwistNode._pose lines 227-289 for the whole batch (covariance=True: gn_vo_estimate_cov, as estimate)."""
         B = inputs["desc_q"].shape[0]
         if out is None:
-            out = self.alloc_outputs(B)
+            out = self.alloc_outputs(B, covariance)
         K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
-        rc = self.lib.gn_vo_estimate(self.ctx, B, inputs["kpt_format"],
-                                     _ptr(inputs["desc_q"]), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["desc_q"].shape[1],
-                                     _ptr(inputs["desc_r"]), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["desc_r"].shape[1],
-                                     K9.ctypes.data_as(_lib.c_f64p), float(ratio), min_matches,
-                                     _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]),
-                                     self._stream())
-        _lib.check(self.ctx, rc, "gn_vo_estimate")
+        args = (self.ctx, B, inputs["kpt_format"],
+                _ptr(inputs["desc_q"]), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["desc_q"].shape[1],
+                _ptr(inputs["desc_r"]), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["desc_r"].shape[1],
+                K9.ctypes.data_as(_lib.c_f64p), float(ratio), min_matches,
+                _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
+        if covariance:
+            rc = self.lib.gn_vo_estimate_cov(*args, float(sigma_px), _ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"]), self._stream())
+        else:
+            rc = self.lib.gn_vo_estimate(*args, self._stream())
+        _lib.check(self.ctx, rc, "gn_vo_estimate_cov" if covariance else "gn_vo_estimate")
         return out
 
     def vo_estimate_images(self, frames_q, frames_r, K: np.ndarray, sift=None, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None):
@@ -651,11 +686,14 @@ class PoseEngine:
         inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], kpt_format=_lib.GN_KPT_XYSA)
         return self.vo_estimate(inputs, K, ratio, min_matches, out=out), n
 
-    def alloc_outputs(self, B: int) -> dict:
+    def alloc_outputs(self, B: int, covariance: bool = False) -> dict:
         d = self.device
-        return dict(R=torch.empty((B, 3, 3), dtype=torch.float64, device=d), t=torch.empty((B, 3, 1), dtype=torch.float64, device=d),
-                    n_match=torch.empty((B,), dtype=torch.int32, device=d), n_inliers=torch.empty((B,), dtype=torch.int32, device=d),
-                    ok=torch.empty((B,), dtype=torch.uint8, device=d))
+        out = dict(R=torch.empty((B, 3, 3), dtype=torch.float64, device=d), t=torch.empty((B, 3, 1), dtype=torch.float64, device=d),
+                   n_match=torch.empty((B,), dtype=torch.int32, device=d), n_inliers=torch.empty((B,), dtype=torch.int32, device=d),
+                   ok=torch.empty((B,), dtype=torch.uint8, device=d))
+        if covariance:
+            out.update(self._alloc_cov(B))
+        return out
 
     # ------------------------------------------------------------------ test hooks
     def debug_read(self, name: str, count: int, dtype=np.float32) -> np.ndarray:

@@ -137,11 +137,13 @@ class LoFTR:
         return buf[: int(n)]
 
 
-def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Tensor, dem, K, min_matches: int = 15, conf_threshold: float = 0.0):
+def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Tensor, dem, K, min_matches: int = 15, conf_threshold: float = 0.0,
+               return_covariance: bool = False):
     """Camera frame <-> map tile pose with the detector-free matcher in front of the SAME solver as the SIFT / LightGlue path: LoFTR matches
     (`keypoints0` in the frame, `keypoints1` in the tile) -> DEM lift of the tile points (`_shared.py:95-102`) -> solvePnPRansac + Rodrigues
     (`gn_gather_points`, `gn_pnp_ransac`; seam B2).  Everything stays on the device.  frame01 / tile01: (H, W) float in [0, 1];
-    dem: (H, W) uint8 or None.  Returns (R (3,3), t (3,1), n_matches) or None below `min_matches` / when RANSAC finds no model."""
+    dem: (H, W) uint8 or None.  Returns (R (3,3), t (3,1), n_matches) or None below `min_matches` / when RANSAC finds no model;
+    with return_covariance also the 6x6 covariance of (rvec, tvec) from the inliers (None when it is not defined) as a fourth entry."""
     out = matcher({"image0": frame01, "image1": tile01})
     keep = out["confidence"] > conf_threshold
     k0, k1 = out["keypoints0"][keep], out["keypoints1"][keep]
@@ -159,7 +161,10 @@ def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Te
     nm = torch.tensor([n], dtype=torch.int32, device=dev)
     d = None if dem is None else torch.as_tensor(np.ascontiguousarray(dem, np.uint8), device=dev)[None]
     mkp, obj = engine.gather_points(pad(k0), pad(k1), idx_full, nm, d, _lib.GN_KPT_XYSA)
-    R, t, n_inl, ok = engine.pnp_ransac(obj, mkp, nm, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches)
+    res = engine.pnp_ransac(obj, mkp, nm, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance)
+    R, t, ok = res[0], res[1], res[3]
     if not bool(ok.cpu()[0]):
         return None
+    if return_covariance:
+        return R[0].cpu().numpy(), t[0].cpu().numpy(), n, (res[4][0].cpu().numpy() if bool(res[6].cpu()[0]) else None)
     return R[0].cpu().numpy(), t[0].cpu().numpy(), n

@@ -4,7 +4,8 @@ Mirror of ros/gisnav/gisnav/core/_shared.py:89-125 (also used by TwistNode with 
 core/twist_node.py:289): numpy in, `(R (3,3) f64, t (3,1) f64)` out.  The DEM lookup is the
 host-side marshalling of the reference's `_compute_3d_points`; RANSAC, EPnP, the iterative refinement
 and Rodrigues run in `gn_pnp_ransac` on the GPU.  Returns None where the reference would fail
-(cv2 returning no model).
+(cv2 returning no model).  `return_covariance=True` adds the 6x6 covariance of (rvec, tvec) from the
+inliers (`gn_pnp_ransac_cov`, DESIGN.md "Pose covariance"), or None in its place when it is not defined.
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ def init(device: int = 0, max_points: int = 4096) -> PoseEngine:
 
 
 def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevation: Optional[np.ndarray],
-                 engine: Optional[PoseEngine] = None) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+                 engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0) -> Optional[Tuple[np.ndarray, ...]]:
     n = len(mkp_qry)
     if n < 4:                     # cv2.solvePnPRansac asserts npoints >= 4 (the reference would raise); the shim reports "no pose"
         return None
@@ -49,7 +50,10 @@ def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevatio
         obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
     img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
     k_matrix = np.asarray(camera_info.k, dtype=np.float64).reshape((3, 3))
-    R, t, _, ok = eng.pnp_ransac_host(obj, img, k_matrix, RANSAC_ITERATIONS, min_pts=4)   # n == 4: OpenCV's P3P branch
-    if not ok:
+    res = eng.pnp_ransac_host(obj, img, k_matrix, RANSAC_ITERATIONS, min_pts=4,   # n == 4: OpenCV's P3P branch
+                              covariance=return_covariance, sigma_px=sigma_px)
+    if not res[3]:
         return None
-    return R, t
+    if return_covariance:
+        return res[0], res[1], (res[4] if res[6] else None)
+    return res[0], res[1]

@@ -28,7 +28,8 @@ class PoseNode:
     MIN_MATCHES = MIN_MATCHES    # pose_node.py:63
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
-                 certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False):
+                 certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
+                 sigma_px: float = 0.0):
         from .matcher import _check_ladder
         ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
         self._engine = PoseEngine(device, max_batch=1, max_kpts=max_kpts, precision=precision, state_dict=state_dict,
@@ -50,6 +51,11 @@ class PoseNode:
         self.camera_info: Optional[CameraInfo] = None
         self.pose_image: Optional[OrthoStereoImage] = None
         self.last_num_matches = 0
+        # covariance=True: every estimate() also asks for the 6x6 covariance of (rvec, tvec) from the PnP inliers (gn_estimate_cov) and leaves
+        # it in last_covariance (None when no pose was returned or the covariance is not defined); the return value stays (r, t)
+        self._covariance, self._sigma_px = bool(covariance), float(sigma_px)
+        self.last_covariance: Optional[np.ndarray] = None
+        self.last_sigma_px = 0.0
         # The DEM raster goes to the device with EVERY message, like in the reference (which never caches it): upstream re-stamps dem_msg with
         # the keypoint cloud's stamp on each message (stereo_node.py:272), so a cache keyed on the DEM's own stamp never hits on real traffic and
         # serves a stale raster to a caller that reuses a stamp.  cache_dem = True keys the device copy on the REFERENCE image's stamp instead --
@@ -67,6 +73,7 @@ class PoseNode:
 
     def estimate(self, camera_info: CameraInfo, msg: OrthoStereoImage) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         eng, dev = self._engine, self._engine.device
+        self.last_covariance, self.last_sigma_px = None, 0.0
         # pose_node.py:207-213 parses the 532-byte records with np.frombuffer and re-assembles keypoint / descriptor arrays on the host;
         # here the message bytes go to the device AS THEY ARE (GN_KPT_RECORD): k_prep reads x, y, size, angle and the descriptor
         # straight from the records
@@ -91,7 +98,7 @@ class PoseNode:
         # transfers and four blocking reads, as a literal transcription of pose_node.py:254-265 would issue, were a sixth of the message latency):
         #   in : a pinned staging block [n as int32 | 3 pad | n records of 133 floats], copied with one asynchronous transfer;
         #        the DEM raster is uploaded when its stamp (or shape) changes, like the tile's features;
-        #   out: R | t | n_match | n_inliers | ok are views of one device block, read back with one transfer.
+        #   out: R | t | n_match | n_inliers | ok (| cov | sigma | cov_ok) are views of one device block, read back with one transfer.
         self._ensure_io(eng.kmax)
         self._pin_np[4:4 + n * 133] = np.frombuffer(msg.query_sift, dtype=np.float32, count=n * 133)
         self._pin_np[:1].view(np.int32)[0] = n
@@ -120,10 +127,12 @@ class PoseNode:
                         eng.set_certify_ladder(True, eps_mid=self._cal_eps_mid)
                 except _lib.GnError:      # (a sample that cannot calibrate -- it left the fp16 range -- : the next message tries again)
                     pass
-            eng.estimate(inputs, np.asarray(camera_info.k, np.float64).reshape(3, 3), self.MIN_MATCHES, out=self._out)
+            eng.estimate(inputs, np.asarray(camera_info.k, np.float64).reshape(3, 3), self.MIN_MATCHES, out=self._out,
+                         covariance=self._covariance, sigma_px=self._sigma_px)
         finally:
             eng.set_active_kpts(eng.kmax)                   # sticky context state: restore
-        self._out_host.copy_(self._out_flat, non_blocking=True)
+        nb = 416 if self._covariance else 112
+        self._out_host[:nb].copy_(self._out_flat[:nb], non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
         h = self._out_host_np
         self.last_num_matches = int(h[96:100].view(np.int32)[0])
@@ -131,6 +140,9 @@ class PoseNode:
             return None
         if not h[104]:                                      # pose_node.py:305-307
             return None
+        if self._covariance and h[408]:
+            self.last_covariance = h[112:400].view(np.float64).reshape(6, 6).copy()
+            self.last_sigma_px = float(h[400:408].view(np.float64)[0])
         return h[0:72].view(np.float64).reshape(3, 3).copy(), h[72:96].view(np.float64).reshape(3, 1).copy()
 
     def _ensure_io(self, kmax: int) -> None:
@@ -141,10 +153,12 @@ class PoseNode:
         self._pin = torch.empty(4 + kmax * 133, dtype=torch.float32, pin_memory=True)
         self._pin_np = self._pin.numpy()
         self._dev_in = torch.empty(4 + kmax * 133, dtype=torch.float32, device=dev)
-        self._out_flat = torch.zeros(112, dtype=torch.uint8, device=dev)      # R 72 B | t 24 B | n_match 4 | n_inliers 4 | ok 1 (+ pad)
+        # R 72 B | t 24 B | n_match 4 | n_inliers 4 | ok 1 (+ pad to 112) | cov 288 B | sigma 8 B | cov_ok 1 (+ pad)
+        self._out_flat = torch.zeros(416, dtype=torch.uint8, device=dev)
         f = self._out_flat
         self._out = dict(R=f[0:72].view(torch.float64).view(1, 3, 3), t=f[72:96].view(torch.float64).view(1, 3, 1), n_match=f[96:100].view(torch.int32),
-                         n_inliers=f[100:104].view(torch.int32), ok=f[104:105])
-        self._out_host = torch.empty(112, dtype=torch.uint8, pin_memory=True)
+                         n_inliers=f[100:104].view(torch.int32), ok=f[104:105], cov=f[112:400].view(torch.float64).view(1, 6, 6),
+                         sigma=f[400:408].view(torch.float64), cov_ok=f[408:409])
+        self._out_host = torch.empty(416, dtype=torch.uint8, pin_memory=True)
         self._out_host_np = self._out_host.numpy()
         self._io_kmax = kmax

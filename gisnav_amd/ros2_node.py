@@ -11,7 +11,7 @@ that wants the complete node applies INTEGRATION.md 2's two-line edit to the ref
     ROS messages -> `gisnav_amd.wire` dataclasses (the bytes of `query_sift.data` untouched, the mono8 rasters as numpy views)
                  -> `PoseNode.estimate` (matcher + DEM lift + PnP on the GPU: pose_node.py:207-308)
                  -> `georef.pose_to_earth` (pose_node.py:333-381: camera position through the CRS affine to WGS 84 to ECEF, orientation ENU -> ECEF)
-                 -> PoseWithCovarianceStamped, stamped like pose_node.py:489-495
+                 -> PoseWithCovarianceStamped, stamped like pose_node.py:489-495, `pose.covariance` from the PnP inliers (`fill_pose_message`)
 
 rclpy, sensor_msgs, geometry_msgs and gisnav_msgs are NOT part of this repository's image: importing this module always works, building the node
 class needs them (`make_node_class()` raises ImportError naming what is missing).  The message conversion is plain Python on duck-typed
@@ -65,11 +65,28 @@ def camera_info_from_ros(msg: Any) -> CameraInfo:
     return CameraInfo(k=np.asarray(msg.k, np.float64).reshape(9), height=int(msg.height), width=int(msg.width))
 
 
-def pose_fields(r: np.ndarray, t: np.ndarray, crs: str, ref_shape) -> Optional[dict]:
+def pose_fields(r: np.ndarray, t: np.ndarray, crs: str, ref_shape, cov_rt: Optional[np.ndarray] = None) -> Optional[dict]:
     """(r, t) of the solver -> the fields of the published pose: ECEF position, (x, y, z, w) orientation (pose_node.py:333-381); None when the
-    camera centre falls outside the reference raster (pose_node.py:341-343)."""
+    camera centre falls outside the reference raster (pose_node.py:341-343).  cov_rt (PoseNode.last_covariance) adds "covariance": the 6x6
+    earth-frame covariance in the order of geometry_msgs/PoseWithCovariance."""
     from .georef import pose_to_earth
-    return pose_to_earth(r, t, crs, ref_shape)
+    return pose_to_earth(r, t, crs, ref_shape, cov_rt=cov_rt)
+
+
+def fill_pose_message(out: Any, fields: dict, stamp: Stamp, frame_id: str = "earth") -> Any:
+    """Fill a (duck-typed) geometry_msgs/PoseWithCovarianceStamped from `pose_fields`' result: header, position, orientation, and
+    `pose.covariance` as 36 row-major floats (x, y, z, rotation about the fixed X, Y, Z axes) when the fields carry a covariance.  Without
+    one -- the solver's cov_ok was 0, or the node does not ask for it -- the message's covariance is left as it was constructed: all zeros."""
+    out.header.frame_id = frame_id
+    out.header.stamp.sec, out.header.stamp.nanosec = stamp.sec, stamp.nanosec
+    p, q = fields["position"], fields["orientation"]
+    out.pose.pose.position.x, out.pose.pose.position.y, out.pose.pose.position.z = float(p[0]), float(p[1]), float(p[2])
+    o = out.pose.pose.orientation
+    o.x, o.y, o.z, o.w = float(q[0]), float(q[1]), float(q[2]), float(q[3])
+    cov = fields.get("covariance")
+    if cov is not None:
+        out.pose.covariance = [float(v) for v in np.asarray(cov, np.float64).reshape(36)]
+    return out
 
 
 def make_node_class():
@@ -91,7 +108,7 @@ def make_node_class():
 
         def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", **kwargs):
             super().__init__(*args, **kwargs)
-            self._impl = PoseNode(state_dict, device=device, precision=precision)
+            self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True)
             self._camera_info: Optional[CameraInfo] = None
             qos = QoSPresetProfiles.SENSOR_DATA.value
             self._pub = self.create_publisher(PoseWithCovarianceStamped, ROS_TOPIC_POSE_EARTH, qos)
@@ -115,17 +132,12 @@ def make_node_class():
             if pose is None:
                 self.get_logger().warning(f"no pose ({self._impl.last_num_matches} matches)")
                 return
-            fields = pose_fields(pose[0], pose[1], wire.crs, wire.reference.data.shape)
+            fields = pose_fields(pose[0], pose[1], wire.crs, wire.reference.data.shape, cov_rt=self._impl.last_covariance)
             if fields is None:
                 self.get_logger().warning("camera centre outside the reference raster - no pose")
                 return
-            out = PoseWithCovarianceStamped()      # covariance stays all-zero, as in the reference (pose_node.py:478-495 fills pose and header only)
-            out.header.frame_id = "earth"
-            out.header.stamp.sec, out.header.stamp.nanosec = wire.query_stamp.sec, wire.query_stamp.nanosec
-            p, q = fields["position"], fields["orientation"]
-            out.pose.pose.position.x, out.pose.pose.position.y, out.pose.pose.position.z = float(p[0]), float(p[1]), float(p[2])
-            o = out.pose.pose.orientation
-            o.x, o.y, o.z, o.w = float(q[0]), float(q[1]), float(q[2]), float(q[3])
-            self._pub.publish(out)
+            # pose.covariance: the first-order covariance of the PnP estimate pushed to the earth frame (the reference leaves it all-zero:
+            # pose_node.py:477 "TODO: re-enable covariance/implement error model"); zeros remain only when the solver reports cov_ok = 0
+            self._pub.publish(fill_pose_message(PoseWithCovarianceStamped(), fields, wire.query_stamp))
 
     return GisnavAmdPoseNode

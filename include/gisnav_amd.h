@@ -18,6 +18,7 @@
  *                                (gn_set_active_kpts: padded size per call, for batches well below max_kpts)
  *   gn_pose_to_earth (+ gn_proj_to_affine, gn_wgs84_to_ecef)   the georeferencing after the pose
  *                                                 pose_node.py:333-381, _transformations.py:298-393
+ *   gn_*_cov, gn_pose_cov_to_camera / _to_earth  the covariance the reference leaves at zero (pose_node.py:477)
  * and, widening to the feeders of that path:
  *   gn_sift_detect_and_compute(_batch)   cv2.SIFT_create().detectAndCompute(img, None)
  *                                                 pose_node.py:122,230-232; twist_node.py:93,227-245
@@ -280,12 +281,36 @@ int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const 
                   const double* K9_host, int iterations_count, float reproj_error_px, double confidence,
                   int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream);
 
+/* gn_pnp_ransac + the first-order covariance of the returned pose (DESIGN.md "Pose covariance"; the reference publishes all zeros:
+ * pose_node.py:477 "TODO: re-enable covariance/implement error model").  R / t / n_inliers / ok are bit for bit gn_pnp_ransac's.  Per pair
+ * with ok = 1: I = the inliers of the winning RANSAC hypothesis (all points when n_pts is 4 or 5), e_i = project(rvec, tvec; X_i) - u_i in
+ * f64 on the widened f32 inputs, J = de / d(rvec, tvec), N = J^T J, dof = 2 |I| - 6,
+ *   sigma_hat [B] f64 = sqrt(sum |e_i|^2 / dof)             the a-posteriori pixel sigma
+ *   cov_rt [B][36] f64 = s^2 N^-1, row-major, symmetric, order (r0, r1, r2, t0, t1, t2); s = sigma_px when sigma_px > 0 (the caller states
+ *                        the pixel noise), else sigma_hat
+ *   cov_ok [B] u8      = 1 iff ok, dof > 0, every LDL^T pivot of N exceeds 1e-12 of its diagonal entry, and every output is finite;
+ *                        otherwise 0, with cov_rt all zeros and sigma_hat 0.
+ * Not modelled: DEM height error, match-score weighting, the discreteness of the inlier selection. */
+int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+                      const double* K9_host, int iterations_count, float reproj_error_px, double confidence,
+                      int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok,
+                      double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
+
 /* PoseNode._pose lines 246-308 for B pairs: match -> gather -> MIN_MATCHES gate -> PnP. */
 int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
                 const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
                 const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
                 const uint8_t* dem, int H, int W, const double* K9_host, int min_matches,
                 double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream);
+
+/* gn_estimate with gn_pnp_ransac_cov as its last stage.  cov_rt / sigma_hat / cov_ok are per-pair outputs like R / t / ok: complete when those are, in
+ * every mode (gn_set_overlap, gn_set_substreams, gn_set_deferred_join, gn_set_certify 2 and 3 -- a re-run pair gets the re-run's covariance). */
+int gn_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
+                    const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                    const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                    const uint8_t* dem, int H, int W, const double* K9_host, int min_matches,
+                    double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                    double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
 
 /* Throughput option for back-to-back gn_estimate calls (batch serving): with overlap enabled the PnP stage of a call
  * runs on an internal stream beside the matcher of the NEXT call (its inputs are double-buffered).  R / t /
@@ -336,6 +361,14 @@ int gn_vo_estimate(gn_ctx* ctx, int B, int kpt_format,
                    const double* K9_host, double ratio, int min_matches,
                    double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok, void* stream);
 
+/* gn_vo_estimate with gn_pnp_ransac_cov as its last stage. */
+int gn_vo_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
+                       const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                       const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                       const double* K9_host, double ratio, int min_matches,
+                       double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
+
 /* ---- StereoNode reference-raster preparation ----------------------- */
 /* StereoNode._rotate_and_crop_center(image, angle_degrees, shape) -- ros/gisnav/gisnav/core/stereo_node.py:292-335:
  * cv2.getRotationMatrix2D((W//2, H//2), angle, 1.0) + cv2.warpAffine(image, M, (W, H)) [INTER_LINEAR, constant 0
@@ -359,6 +392,16 @@ int gn_wgs84_to_ecef(double lon_deg, double lat_deg, double alt_m, double* xyz3)
  * raster (the node returns None, pose_node.py:339-341). */
 int gn_pose_to_earth(const double* R9, const double* t3, const double* affine12, int ref_h, int ref_w,
                      double* position_ecef3, double* quat_xyzw4, double* lonlatalt3);
+
+/* cov_rt of gn_pnp_ransac_cov (HOST, 6x6 row-major) -> covariance of the camera in the raster frame, order (cx, cy, cz, phi_x, phi_y, phi_z):
+ * c = -R^T t [raster px], phi [rad] the increment of R_wc = R^T with R_wc,true = Exp(phi) R_wc.  Closed form: phi = -J_r(rvec) d rvec (J_r the
+ * right Jacobian of SO(3)), dc = -R^T dt - [c]x phi. */
+int gn_pose_cov_to_camera(const double* R9, const double* t3, const double* cov_rt36, double* cov_cam36);
+/* ... and pushed through gn_pose_to_earth's map: order (ECEF x, y, z [m], psi_x, psi_y, psi_z [rad]) with q_true = dq(psi) (x) q_est for the
+ * quaternion gn_pose_to_earth returns (rotation about the fixed axes: the layout of geometry_msgs/PoseWithCovariance.covariance).  Returns
+ * GN_OK, or 1 exactly where gn_pose_to_earth returns 1 (cov_earth36 is then not written). */
+int gn_pose_cov_to_earth(const double* R9, const double* t3, const double* cov_rt36, const double* affine12, int ref_h, int ref_w,
+                         double* cov_earth36);
 
 /* ---- SIFT feature extraction ------------------------------------------ */
 /* cv2.SIFT_create().detectAndCompute(gray, None) with OpenCV's defaults -- the tile extractor of PoseNode
