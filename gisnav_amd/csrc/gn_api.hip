@@ -2380,13 +2380,19 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     conv(4, Y, X, n, H / 4, W / 4, 1);     conv(5, X, Y, n, H / 4, W / 4, 1, 1);                    // block 2 -> Y [H/8][W/8][128]
     conv(6, Y, X, n, h, w, 1);             conv(7, X, Y, n, h, w, 1);                               // block 3 -> Y = encoder output
     conv(8, Y, X, n, h, w, 1);             conv(9, X, Z, n, h, w, 0);                               // detector head: Z = logits [h][w][128 (65 used)]
+    // developer knob 39 stopped the pass in front of the logits / the raw descriptor map: the stages that read them are skipped as well (they would
+    // run on another pass's buffers), the keypoint count is 0 / the descriptor rows stay the caller's
+    const bool tail_det = ctx->sp_stop <= 0 || ctx->sp_stop >= 9, tail_desc = ctx->sp_stop <= 0 || ctx->sp_stop >= 11;
+    if (tail_det) {
     sp_scores(Z, ctx->sp[9].cout_pad, ctx->sp_maps[0], n, h, w, s);
     sp_nms(ctx->sp_maps[0], n, H, W, 4, ctx->sp_maps[1], ctx->sp_maps[2], ctx->sp_maps[3], ctx->sp_maps[4], ctx->sp_maps[5], s);
     sp_select(ctx->sp_maps[5], n, H, W, 0.005f, 4, ctx->sp_cand, ctx->sp_counts, ctx->sp_cap, max_kpts,
               kpt_xysa + (size_t)b0 * max_kpts * 4, score ? score + (size_t)b0 * max_kpts : ctx->sp_maps[1], ctx->sp_index, max_kpts, s);
+    }
     conv(10, Y, X, n, h, w, 1);            conv(11, X, Z, n, h, w, 0);                          // descriptor head: Z = raw descriptor map [h][w][256]
-    sp_describe(Z, n, h, w, kpt_xysa + (size_t)b0 * max_kpts * 4, ctx->sp_counts, max_kpts, max_kpts, desc + (size_t)b0 * max_kpts * 256, s);
-    GN_HIP(hipMemcpyAsync(counts.data(), ctx->sp_counts, (size_t)n * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (tail_desc) sp_describe(Z, n, h, w, kpt_xysa + (size_t)b0 * max_kpts * 4, ctx->sp_counts, max_kpts, max_kpts, desc + (size_t)b0 * max_kpts * 256, s);
+    std::fill(counts.begin(), counts.end(), 0);
+    if (tail_det) GN_HIP(hipMemcpyAsync(counts.data(), ctx->sp_counts, (size_t)n * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     unsigned int tripped = 0;
     if (split) GN_HIP(hipMemcpyAsync(&tripped, ctx->ovf_base + 8, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
@@ -2421,6 +2427,7 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       {"sp_cand", ctx->sp_cand, ctx->sp_cand ? (size_t)ctx->sp_chunk * ctx->sp_cap * 2 : 0},                            // (raster index, score bits) pairs, [image][cap]
       {"sp_x", ctx->sp_x, ctx->sp_x ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},                         // raw words of the two activation buffers
       {"sp_y", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},
+      {"sp_z", ctx->sp_z, ctx->sp_z ? (size_t)ctx->sp_chunk * (ctx->sp_h / 8) * (ctx->sp_w / 8) * 256 : 0},          // f32: the raw descriptor map [h][w][256] after a full pass, the logits [h][w][128] after a pass stopped at layer 9 (knob 39)
       {"sp_ts", ctx->sp_ts, ctx->sp_ts ? (size_t)8192 * 32 * 2 : 0},                                                     // phase stamps (knob 35), int64 pairs of 4-byte words
       {"desc_p", ctx->desc_p, ctx->desc_p ? T * kInDim : 0}, {"x_p", ctx->x_p, ctx->x_p ? T * kDim : 0}, {"msg_p", ctx->msg_p, ctx->msg_p ? T * kDim : 0},   // hm16 rows, raw (4 bytes per value)
       {"qkb", ctx->qkb, ctx->qkb ? T * kDim : 0}, {"rot4", ctx->rot4, ctx->rot4 ? T * 2 * kFreq : 0}, {"vtb", ctx->vtb, ctx->vtb ? T * kDim / 2 : 0}};
@@ -2447,6 +2454,12 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       }
       return (int64_t)count;
     }
+  if (strcmp(name, "sp_split_trips") == 0) {      // one int64: passes of this context that the split-fp16 guard repeated on the exact f32 convolutions
+    if (max_bytes < 8) return GN_ERR_ARG;
+    const long long trips = ctx->sp_split_trips;
+    memcpy(host_out, &trips, 8);
+    return 1;
+  }
   if (strcmp(name, "e_idx") == 0) {
     size_t count = B * np * 2;
     if ((int64_t)(count * 8) > max_bytes) count = (size_t)max_bytes / 8;

@@ -326,6 +326,11 @@ class PoseEngine:
     def sp_set_arithmetic(self, mode: int) -> None:
         _lib.check(self.ctx, self.lib.gn_sp_set_arithmetic(self.ctx, int(mode)), "gn_sp_set_arithmetic")
 
+    def sp_split_trips(self) -> int:
+        """Passes of this context's SuperPoint extractor that the split-fp16 guard repeated on the exact f32 convolutions (an activation left fp16's
+        range); read-only (gn_debug_read("sp_split_trips"))."""
+        return int(self.debug_read("sp_split_trips", 1, dtype=np.int64)[0])
+
     def sp_load_state_dict(self, sd) -> None:
         for name, arr in sd.items():
             if hasattr(arr, "detach"):

@@ -491,7 +491,10 @@ int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int
  * Names: "desc" "cos" "sin" "x" "qkv" "ctx" "msg" "h" "md" "ls" "sim" "rowmax" "rowlog"
  * "colmax" "collog" "m0" "m1" (ints are returned bit-cast in float slots). Returns the element
  * count copied, or a negative status.  "sim" exists only after the unfused match head (developer knob 16 = 0), gn_vo_match or a
- * phase-stamp knob allocated it: the matcher itself never materialises the similarity matrix (it returns 0 elements before that). */
+ * phase-stamp knob allocated it: the matcher itself never materialises the similarity matrix (it returns 0 elements before that).
+ * SuperPoint extractor (last pass): "sp_enc" "sp_scores" "sp_nms" "sp_counts" "sp_cand" "sp_x" "sp_y" (raw words of the two activation
+ * buffers), "sp_z" (f32: the raw descriptor map [h][w][256]; the logits [h][w][128] when developer knob 39 stopped the pass at layer 9), and
+ * "sp_split_trips" (ONE int64, 8 bytes: how many passes of this context the split-fp16 guard repeated on the exact f32 convolutions). */
 int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream);
 /* Stand-alone kernels for unit tests: Y[M,N] = A[M,K] W[N,K]^T + bias (f32 MFMA path). */
 int gn_debug_gemm(gn_ctx* ctx, int M, int N, int K, const float* A, const float* W, const float* bias,

@@ -25,19 +25,39 @@ Tensor = torch.Tensor
 KEYPOINT_THRESHOLD = 0.005
 NMS_RADIUS = 4
 BORDER = 4
+# the 12 convolutions in the extractor's order (kSpNames in csrc/gn_api.hip): encoder 0..7, detector head 8, 9, descriptor head 10, 11 (both heads
+# read layer 7's output).  ReLU behind every layer but the two head outputs; the extractor fuses the 2x2 max-pool into layers 1, 3 and 5
+LAYER_NAMES = [f"encoder.conv_blocks.{b}.conv_{a}" for b in range(4) for a in "ab"] + [
+    "keypoint_decoder.conv_score_a", "keypoint_decoder.conv_score_b", "descriptor_decoder.conv_descriptor_a", "descriptor_decoder.conv_descriptor_b"]
+
+
+def cast_state_dict(sd: Dict[str, Tensor], dtype: torch.dtype) -> Dict[str, Tensor]:
+    """The weights in `dtype` (the float32 dict itself when dtype is float32)."""
+    return sd if dtype == torch.float32 else {k: v.to(dtype) for k, v in sd.items()}
+
+
+def conv_layer(sd: Dict[str, Tensor], i: int, x: Tensor) -> Tensor:
+    """Layer i (0..11, LAYER_NAMES order) on its own input (1,Cin,H,W), in x's dtype: convolution, ReLU (not on layers 9 and 11), and the 2x2 max-pool
+    where the extractor fuses it (behind layers 1, 3 and 5)."""
+    name = LAYER_NAMES[i]
+    w = sd[name + ".weight"]
+    x = F.conv2d(x, w, sd[name + ".bias"], padding=w.shape[-1] // 2)
+    if i not in (9, 11):
+        x = F.relu(x)
+    if i in (1, 3, 5):
+        x = F.max_pool2d(x, 2, 2)
+    return x
 
 
 def encoder(sd: Dict[str, Tensor], image: Tensor, taps: Optional[dict] = None) -> Tensor:
     """image (1,1,H,W) f32 in [0,1] -> (1,128,H/8,W/8)."""
     x = image
-    for b in range(4):
-        p = f"encoder.conv_blocks.{b}"
-        x = F.relu(F.conv2d(x, sd[p + ".conv_a.weight"], sd[p + ".conv_a.bias"], padding=1))
-        x = F.relu(F.conv2d(x, sd[p + ".conv_b.weight"], sd[p + ".conv_b.bias"], padding=1))
-        if b < 3:
-            x = F.max_pool2d(x, 2, 2)
+    for i in range(8):
+        x = conv_layer(sd, i, x)
         if taps is not None:
-            taps[f"block{b}"] = x
+            taps[f"layer{i}"] = x
+            if i % 2:
+                taps[f"block{i // 2}"] = x
     return x
 
 
@@ -55,14 +75,21 @@ def simple_nms(scores: Tensor, radius: int) -> Tensor:
     return torch.where(max_mask, scores, zeros)
 
 
-def pixel_scores(sd: Dict[str, Tensor], enc: Tensor) -> Tensor:
-    """(1,128,h,w) -> NMS'ed score map (1, 8h, 8w)."""
-    s = F.relu(F.conv2d(enc, sd["keypoint_decoder.conv_score_a.weight"], sd["keypoint_decoder.conv_score_a.bias"], padding=1))
-    s = F.conv2d(s, sd["keypoint_decoder.conv_score_b.weight"], sd["keypoint_decoder.conv_score_b.bias"])
-    s = F.softmax(s, 1)[:, :-1]
+def cell_scores(logits: Tensor) -> Tensor:
+    """(1,65,h,w) logits -> score map (1, 8h, 8w) before NMS: softmax over the 65 bins, dustbin dropped, 8x8 depth-to-space."""
+    s = F.softmax(logits, 1)[:, :-1]
     b, _, h, w = s.shape
     s = s.permute(0, 2, 3, 1).reshape(b, h, w, 8, 8)
-    s = s.permute(0, 1, 3, 2, 4).reshape(b, h * 8, w * 8)
+    return s.permute(0, 1, 3, 2, 4).reshape(b, h * 8, w * 8)
+
+
+def pixel_scores(sd: Dict[str, Tensor], enc: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """(1,128,h,w) -> NMS'ed score map (1, 8h, 8w)."""
+    s8 = conv_layer(sd, 8, enc)
+    logits = conv_layer(sd, 9, s8)
+    s = cell_scores(logits)
+    if taps is not None:
+        taps["layer8"], taps["logits"], taps["cell_scores"] = s8, logits, s
     return simple_nms(s, NMS_RADIUS)
 
 
@@ -79,14 +106,39 @@ def extract_keypoints(scores: Tensor, max_keypoints: int):
     return torch.flip(kp, [1]).to(sc.dtype), sc                         # (x, y)
 
 
-def descriptor_map(sd: Dict[str, Tensor], enc: Tensor) -> Tensor:
-    d = F.conv2d(F.relu(F.conv2d(enc, sd["descriptor_decoder.conv_descriptor_a.weight"], sd["descriptor_decoder.conv_descriptor_a.bias"], padding=1)),
-                 sd["descriptor_decoder.conv_descriptor_b.weight"], sd["descriptor_decoder.conv_descriptor_b.bias"])
-    return F.normalize(d, p=2, dim=1)
+def select(nms: Tensor, max_keypoints: int):
+    """The keypoint list of an NMS'ed map (1,H,W), deterministic on ties -- the order k_sp_select documents: candidates are the pixels above the
+    threshold with y, x >= BORDER (the far borders are never tested: the transformers quirk of extract_keypoints), ordered by score descending, then
+    raster index ascending; the first max_keypoints of them.  -> (keypoints (K,2) (x, y) in nms's dtype, scores (K,), raster indices (K,) int64).
+    Equals extract_keypoints as a set whenever the candidate scores are distinct (torch.topk leaves the order of ties unspecified)."""
+    _, height, width = nms.shape
+    flat = nms[0].reshape(-1)
+    idx = torch.arange(height * width)
+    ok = (flat > KEYPOINT_THRESHOLD) & (idx // width >= BORDER) & (idx % width >= BORDER)
+    idx, sc = idx[ok], flat[ok]
+    order = torch.argsort(sc, descending=True, stable=True)          # stable: equal scores keep their raster order
+    if max_keypoints >= 0:
+        order = order[:max_keypoints]
+    idx, sc = idx[order], sc[order]
+    return torch.stack([idx % width, idx // width], 1).to(sc.dtype), sc, idx
 
 
-def sample_descriptors(keypoints: Tensor, dmap: Tensor, scale: int = 8) -> Tensor:
-    """keypoints (K,2) (x, y) pixels, dmap (1,256,h,w) -> (K,256)."""
+def raw_descriptor_map(sd: Dict[str, Tensor], enc: Tensor, taps: Optional[dict] = None) -> Tensor:
+    """(1,128,h,w) -> conv_descriptor_b's output (1,256,h,w), not yet normalised (what the extractor keeps)."""
+    d10 = conv_layer(sd, 10, enc)
+    if taps is not None:
+        taps["layer10"] = d10
+    return conv_layer(sd, 11, d10)
+
+
+def descriptor_map(sd: Dict[str, Tensor], enc: Tensor, taps: Optional[dict] = None) -> Tensor:
+    return F.normalize(raw_descriptor_map(sd, enc, taps), p=2, dim=1)
+
+
+def sample_descriptors(keypoints: Tensor, raw_dmap: Tensor, scale: int = 8) -> Tensor:
+    """keypoints (K,2) (x, y) pixels, raw_dmap (1,256,h,w) as conv_descriptor_b leaves it (L2-normalised over the channels here, as the first step)
+    -> (K,256) unit vectors."""
+    dmap = F.normalize(raw_dmap, p=2, dim=1)
     b, c, h, w = dmap.shape
     kp = keypoints[None] - scale / 2 + 0.5
     kp = kp / torch.tensor([[(w * scale - scale / 2 - 0.5), (h * scale - scale / 2 - 0.5)]]).to(kp)
@@ -95,18 +147,22 @@ def sample_descriptors(keypoints: Tensor, dmap: Tensor, scale: int = 8) -> Tenso
     return F.normalize(d, p=2, dim=1)[0].t()
 
 
-def detect_and_describe(sd: Dict[str, Tensor], gray01: Tensor, max_keypoints: int = 1024, taps: Optional[dict] = None):
-    """gray01 (H,W) f32 in [0,1], H and W multiples of 8 -> (keypoints (K,2) f32 (x, y), scores (K,), descriptors (K,256))."""
+def detect_and_describe(sd: Dict[str, Tensor], gray01: Tensor, max_keypoints: int = 1024, taps: Optional[dict] = None, dtype: torch.dtype = torch.float32):
+    """gray01 (H,W) f32 in [0,1], H and W multiples of 8 -> (keypoints (K,2) (x, y), scores (K,), descriptors (K,256)), all in `dtype`: float64 runs
+    the same code on float64 weights and pixels (the reference of tests/test_gpu_fp64_superpoint.py).  taps: layer0 .. layer8, layer10, logits,
+    cell_scores, scores (after NMS), raw_dmap, dmap (normalised)."""
+    sd = cast_state_dict(sd, dtype)
     with torch.inference_mode():
-        enc = encoder(sd, gray01[None, None], taps)
-        scores = pixel_scores(sd, enc)
+        enc = encoder(sd, gray01.to(dtype)[None, None], taps)
+        scores = pixel_scores(sd, enc, taps)
         if taps is not None:
             taps["scores"] = scores
         kp, sc = extract_keypoints(scores, max_keypoints)
-        dmap = descriptor_map(sd, enc)
+        raw = raw_descriptor_map(sd, enc, taps)
         if taps is not None:
-            taps["dmap"] = dmap
-        return kp, sc, sample_descriptors(kp, dmap)
+            taps["raw_dmap"] = raw
+            taps["dmap"] = F.normalize(raw, p=2, dim=1)
+        return kp, sc, sample_descriptors(kp, raw)
 
 
 def synthetic_state_dict(seed: int = 0) -> Dict[str, Tensor]:

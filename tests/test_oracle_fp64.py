@@ -103,3 +103,108 @@ def test_superpoint_lightglue_fp64_reference_is_float64_and_within_1e5_of_the_f3
             assert a.shape == b.shape, k
             assert np.abs(a - b).max() / np.abs(b).max() <= 1e-5, k
         assert r64[0].dtype == torch.float64 and np.array_equal(r32[1].numpy(), r64[1].numpy()) and len(r64[1]) > 15
+
+
+def _superpoint_chain(sd, img, k, dtype):
+    """oracle/superpoint.py's stage entry points chained on their own outputs, in `dtype`"""
+    from oracle import superpoint as osp
+    sd = osp.cast_state_dict(sd, dtype)
+    t = {}
+    with torch.inference_mode():
+        x = img.to(dtype)[None, None]
+        for i in range(8):
+            x = t[f"layer{i}"] = osp.conv_layer(sd, i, x)
+        t["layer8"] = osp.conv_layer(sd, 8, x)
+        t["logits"] = osp.conv_layer(sd, 9, t["layer8"])
+        t["cell_scores"] = osp.cell_scores(t["logits"])
+        t["scores"] = osp.simple_nms(t["cell_scores"], osp.NMS_RADIUS)
+        kp, sc, idx = osp.select(t["scores"], k)
+        t["layer10"] = osp.conv_layer(sd, 10, x)
+        t["raw_dmap"] = osp.conv_layer(sd, 11, t["layer10"])
+        d = osp.sample_descriptors(kp, t["raw_dmap"])
+    return kp, sc, d, idx, t
+
+
+def _in_select_order(kp, sc, d, w):
+    """extract_keypoints leaves the list in raster order when it holds no more than k candidates (torch.topk only runs beyond k): the same rows, score
+    descending then raster index ascending"""
+    idx = (kp[:, 1] * w + kp[:, 0]).long()
+    order = sorted(range(len(kp)), key=lambda i: (-float(sc[i]), int(idx[i])))
+    return kp[order], sc[order], d[order]
+
+
+SP_TAPS = [f"layer{i}" for i in range(9)] + ["layer10", "logits", "raw_dmap", "cell_scores", "scores"]
+
+
+def test_superpoint_stage_entry_points_compose_to_the_whole_model_bitwise():
+    """tests/test_gpu_fp64_superpoint.py feeds each stage of oracle/superpoint.py its own input: chained on the oracle's own f32 outputs, the entry
+    points are detect_and_describe, bit for bit -- every tap, and (the test image's candidate scores are distinct, asserted) keypoints, scores and
+    descriptors in order, with fewer candidates than k and with more."""
+    from oracle import superpoint as osp
+    from test_superpoint import _test_image
+    sd = osp.synthetic_state_dict(0)
+    for seed, (h, w), k in ((4, (136, 200), 2048), (4, (136, 200), 300), (2, (64, 40), 300)):
+        img = torch.from_numpy(_test_image(seed, h, w))
+        taps = {}
+        kp, sc, d = _in_select_order(*osp.detect_and_describe(sd, img, k, taps=taps), w)
+        ckp, csc, cd, cidx, ct = _superpoint_chain(sd, img, k, torch.float32)
+        for name in SP_TAPS:
+            assert torch.equal(taps[name], ct[name]), name
+        allsc = osp.select(ct["scores"], -1)[1]
+        assert len(torch.unique(allsc)) == len(allsc) > 0, "the test image has tied candidate scores"
+        assert (len(allsc) > k) == (k == 300 and h == 136)
+        assert len(kp) == min(k, len(allsc))
+        assert torch.equal(kp, ckp) and torch.equal(sc, csc) and torch.equal(d, cd)
+        assert torch.equal(cidx, (ckp[:, 1] * w + ckp[:, 0]).long())
+
+
+def test_superpoint_fp64_reference_is_float64_and_within_1e5_of_the_f32_oracle():
+    """detect_and_describe(..., dtype=torch.float64): every tap float64 and within 1e-5 of the f32 run (convolutions relative to max |fp64|, the
+    softmax scores absolute), the same keypoints in the same order on the tie-free test image; the chained fp64 entry points give the same."""
+    from oracle import superpoint as osp
+    from test_superpoint import _test_image
+    torch.set_num_threads(max(1, min(len(os.sched_getaffinity(0)), 16)))
+    sd = osp.synthetic_state_dict(0)
+    for seed, (h, w), k in ((4, (136, 200), 300), (2, (64, 40), 300), (3, (16, 520), 300)):
+        img = torch.from_numpy(_test_image(seed, h, w))
+        t32, t64 = {}, {}
+        kp32, sc32, d32 = osp.detect_and_describe(sd, img, k, taps=t32)
+        kp64, sc64, d64 = osp.detect_and_describe(sd, img, k, taps=t64, dtype=torch.float64)
+        (kp32, sc32, d32), (kp64, sc64, d64) = _in_select_order(kp32, sc32, d32, w), _in_select_order(kp64, sc64, d64, w)
+        for name in SP_TAPS + ["dmap"]:
+            a, b = t32[name], t64[name]
+            assert b.dtype == torch.float64 and a.dtype == torch.float32 and a.shape == b.shape, name
+            err = float((a.double() - b).abs().max())
+            if name not in ("cell_scores", "scores"):
+                err /= float(b.abs().max())
+            assert err <= 1e-5, (name, err)
+        assert kp64.dtype == sc64.dtype == d64.dtype == torch.float64
+        assert len(kp64) > 0 and torch.equal(kp32.double(), kp64)
+        assert float((sc32.double() - sc64).abs().max()) <= 1e-5 and float((d32.double() - d64).abs().max()) <= 1e-5
+        ckp, csc, cd, _, ct = _superpoint_chain(sd, img, k, torch.float64)
+        assert all(ct[name].dtype == torch.float64 for name in SP_TAPS)
+        assert torch.equal(ckp, kp64) and torch.equal(csc, sc64) and torch.equal(cd, d64)
+
+
+def test_superpoint_select_is_the_transformers_set_on_distinct_scores_and_ordered_on_ties():
+    """select(nms, k): the set extract_keypoints (the transformers pin) returns whenever the scores are distinct; on tied scores -- where torch.topk's
+    order is unspecified -- score descending, then raster index ascending, the order k_sp_select documents."""
+    from oracle import superpoint as osp
+    g = torch.Generator().manual_seed(5)
+    for h, w, k in ((24, 40, 10), (24, 40, 200), (24, 40, 5000), (16, 16, 7)):
+        m = torch.rand(1, h, w, generator=g) * 0.02                   # about 3 / 4 of the pixels above the 0.005 threshold
+        assert len(torch.unique(m)) == m.numel()
+        kp, sc, idx = osp.select(m, k)
+        ekp, esc = osp.extract_keypoints(m, k)
+        n_cand = int(((m[0] > osp.KEYPOINT_THRESHOLD)[osp.BORDER:, osp.BORDER:]).sum())
+        assert len(kp) == min(k, n_cand) == len(ekp)
+        assert {(float(x), float(y), float(s)) for (x, y), s in zip(kp, sc)} == {(float(x), float(y), float(s)) for (x, y), s in zip(ekp, esc)}
+        assert bool((sc[:-1] > sc[1:]).all()) and bool((kp >= osp.BORDER).all())
+    # ties: three score levels over a 16 x 24 map, far border pixels included (never tested against the far border), near borders excluded
+    m = torch.zeros(1, 16, 24)
+    m[0, 2:, 2:] = torch.tensor([0.25, 0.5, 0.004])[torch.randint(0, 3, (14, 22), generator=g)]
+    want = sorted(((-float(m[0, y, x]), y * 24 + x) for y in range(4, 16) for x in range(4, 24) if m[0, y, x] > 0.005))
+    for k in (1, 17, len(want) - 1, len(want), len(want) + 5):
+        kp, sc, idx = osp.select(m, k)
+        assert [(-float(s), int(i)) for s, i in zip(sc, idx)] == want[:k]
+        assert torch.equal(kp, torch.stack([idx % 24, idx // 24], 1).float())

@@ -260,9 +260,16 @@ def test_superpoint_split_convolutions_fall_back_when_activations_leave_fp16_ran
     for prec in ("f32", "f16x2_bf16_attn"):
         eng = PoseEngine(0, max_batch=1, max_kpts=128, precision=prec, feature="superpoint")
         sp = SuperPoint(engine=eng, max_keypoints=256, state_dict=sd)
+        assert eng.sp_split_trips() == 0
         kpt, score, desc, n = sp.detect_and_describe_device(img[None])
         torch.cuda.synchronize()
         res[prec] = (kpt[0, :int(n[0])].cpu().numpy(), score[0, :int(n[0])].cpu().numpy(), desc[0, :int(n[0])].cpu().numpy(), int(n[0]))
+        # the guard's counter (gn_debug_read("sp_split_trips")): exactly one trip per pass that tripped, none in an f32 context
+        assert eng.sp_split_trips() == (0 if prec == "f32" else 1)
+        again = sp.detect_and_describe_device(img[None])
+        torch.cuda.synchronize()
+        assert eng.sp_split_trips() == (0 if prec == "f32" else 2)
+        assert torch.equal(again[0], kpt) and torch.equal(again[1], score) and torch.equal(again[2], desc) and int(again[3][0]) == int(n[0])
     a, b = res["f32"], res["f16x2_bf16_attn"]
     assert a[3] == b[3] > 0 and np.isfinite(b[2]).all()
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])               # the SAME exact-f32 kernels ran

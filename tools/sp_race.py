@@ -1,6 +1,6 @@
 """Developer tool: run-to-run differences of the SuperPoint layer outputs, layer by layer (knob 39 stops the extractor behind a layer)."""
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gisnav_amd.engine import PoseEngine
 from gisnav_amd.superpoint import SuperPoint
 from oracle import superpoint as osp
@@ -17,10 +17,7 @@ for stop, (name, div, C, (th, tw)) in layers.items():
     eng.lib.gn_debug_set_variant(eng.ctx, 39, stop)
     outs = []
     for rep in range(reps):
-        try:
-            sp.detect_and_describe_device(img)
-        except Exception:
-            pass      # (the skipped layers leave garbage for the detector: candidate overflow)
+        sp.detect_and_describe_device(img)      # (the stages behind a skipped layer are skipped too: n = 0)
         torch.cuda.synchronize()
         outs.append(eng.debug_read(name, oh * ow * C).view(np.uint32).reshape(oh, ow, C).copy())
     bad = [r for r in range(1, reps) if not np.array_equal(outs[0], outs[r])]
