@@ -107,7 +107,7 @@ struct GemmArgs {
   // a row tile whose first row r has (mlim_seg ? r % mlim_seg : r) >= mlim[0] * mlim_mul is skipped (its rows of Y keep what they held)
   const int* mlim; int mlim_mul; int mlim_seg;
 };
-void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s);
+void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int sel_m = 0);
 void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s);   // fp16-plane operands (Ap, Wp)
 void launch_mfma_probe(float* out, int blocks, int iters, hipStream_t s);
 void launch_lds_dma_probe(const float* pattern, unsigned int* out, int blocks, int spin, hipStream_t s);

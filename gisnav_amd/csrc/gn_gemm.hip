@@ -1310,7 +1310,9 @@ void launch_mfma_probe(float* out, int blocks, int iters, hipStream_t s) {
   hipLaunchKernelGGL(k_mfma_probe, dim3(blocks), dim3(256), 0, s, out, iters);
 }
 
-void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s) {
+// sel_m > 0: the rows that CHOOSE the tile form below (the grids always cover a.M): a caller whose M stacks several independent problems passes
+// the rows of one, so that each of them runs on the form it would run on alone (batched LoFTR)
+void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int sel_m) {
   g_last_kernel = g_gemm_variant == 5 || (g_gemm_variant >= 50 && g_gemm_variant < 60) ? "k_gemm_f32x3<" : g_gemm_variant >= 6 ? "k_gemm_f16x2<" : "k_gemm_f32_v3<";
   dim3 grid(a.N / BN, a.M / BM, batch), block(256);
   if (g_gemm_variant == 4 && epi == EPI_BIAS) {
@@ -1357,12 +1359,13 @@ void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s) {
   }
   // small grids: 64-row tiles when 128 x 128 tiles would leave more than a third of the CUs without a workgroup (same bits: k_gemm_f32_m64)
   if (g_gemm_m64 && (epi == EPI_BIAS || epi == EPI_PLAIN || epi == EPI_RELU || epi == EPI_SCALE_COLS || epi == EPI_ROTARY || epi == EPI_RESIDUAL) &&
-      (long long)grid.x * grid.y * grid.z <= g_gemm_m64) {
+      (long long)grid.x * ((sel_m > 0 ? sel_m : a.M) / BM) * grid.z <= g_gemm_m64) {
     const dim3 g64(a.N / BN, a.M / 64, batch);
+    const long long sel64 = (long long)g64.x * ((sel_m > 0 ? sel_m : a.M) / 64) * g64.z;
     // developer knob 44: 0 = k_gemm_f32_m64 always; 1 (default) = k_gemm_f32_r64 on 64 x 64 tiles when 64 x 128 tiles leave half of the CUs idle (at most
     // 128 workgroups: 19.9 -> 14.5 us per GEMM of a one-pair call), k_gemm_f32_m64 otherwise; 2 = the ring kernel on 64 x 128 tiles everywhere (measured:
     // 19.4 against 19.9 us -- it is the tile count, not the ring, that pays; its 96 KB of LDS leave one workgroup per CU)
-    const bool n64 = g_gemm_r64 == 1 && (long long)g64.x * g64.y * g64.z <= 128 && a.N % 64 == 0;
+    const bool n64 = g_gemm_r64 == 1 && sel64 <= 128 && a.N % 64 == 0;
     if (n64 || g_gemm_r64 == 2) {
       const dim3 gr(n64 ? a.N / 64 : a.N / BN, a.M / 64, batch);
       g_last_kernel = "k_gemm_f32_r64<";

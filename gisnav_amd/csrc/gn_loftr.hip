@@ -14,6 +14,10 @@
 //   matching     0.2, border 2, mutual maxima, matches in ascending query cell -- row / column statistics in three passes over S.
 //   fine level   5x5 windows of the 1/2-resolution FPN map around every coarse match, merged with the coarse features, one (self, cross)
 //                encoder pass per window pair, softmax correlation heat map -> expectation -> sub-pixel offset on the reference side.
+//   batches      B pairs per call (gn_loftr_match_batch): every buffer side-major over the pairs ([2][B]...; the cross partner of sequence s is
+//                s +- B), coarse matching with the pair in the grid, per-pair result segments and counts, the fine level ONCE over the matches
+//                of all pairs (k_lf_concat's list).  Kernel forms are chosen from the shape of one pair, so a pair's bits do not depend on the
+//                batch; the fp16-range guard is one word per pair and only flagged pairs are repeated on the exact kernels.  DESIGN.md 9a.
 #include "gn_common.h"
 
 #include <cmath>
@@ -106,6 +110,7 @@ struct LfConvArgs {
   // split-fp16 arithmetic (k_lf_conv_h): weights as fp16 pairs in fragment order (sp_weight_fragments_hm16), the affine scale with the
   // inverse of the weights' power-of-two scale folded in, the fp16-range guard word
   const uint16_t* wfh; const float* scale_h; unsigned int* ovf;
+  int pairs;                                // images are [2][pairs]: image n belongs to pair n % pairs, whose guard word is ovf[n % pairs]
   int cin_real;                             // input channels that exist (196 of Cin = 224 in LoFTR's middle layers): 8- (k_lf_conv) / 16-channel (k_lf_conv_h) steps behind them multiply zeros and are skipped
 };
 
@@ -441,7 +446,7 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
       par ^= 1;
     }
   }
-  ovf_commit(a.ovf, amax);
+  ovf_commit(a.ovf + img % a.pairs, amax);
   const int gx = x0 + ql;
   float* out = a.out + (long long)img * a.Hout * a.Wout * a.Cout;
   const float* res = a.resid ? a.resid + (long long)img * a.Hout * a.Wout * a.Cout : nullptr;
@@ -492,9 +497,9 @@ __global__ __launch_bounds__(256) void k_lf_up2_add(const float* a, const float*
 
 // ------------------------------------------------------------------------------------------------ token-side kernels
 // x[img][l][256] = feat[img][l][256] + pe[l][256] for l < L, 0 for L <= l < Lp
-__global__ __launch_bounds__(256) void k_lf_posenc(const float* feat, const float* pe, float* x, int L, int Lp) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // float4 index over [2][Lp][64]
-  if (idx >= 2LL * Lp * 64) return;
+__global__ __launch_bounds__(256) void k_lf_posenc(const float* feat, const float* pe, float* x, int L, int Lp, int nimg) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;      // float4 index over [nimg][Lp][64]
+  if (idx >= (long long)nimg * Lp * 64) return;
   const int c4 = (int)(idx & 63);
   const long long t = idx >> 6;
   const int img = (int)(t / Lp), l = (int)(t - (long long)img * Lp);
@@ -676,11 +681,17 @@ __global__ __launch_bounds__(256) void k_lf_scale(const float* x, float* y, floa
 }
 
 // split-fp16 mode: any value that left fp16's range inside a GEMM shows up as inf / NaN downstream -- raise the guard word
-__global__ __launch_bounds__(256) void k_lf_check_finite(const float* x, long long n4, unsigned int* flag) {
+// clears the guard words at the head of a forward.  A kernel, not hipMemsetAsync: replayed from a captured graph, the memset node of more than one
+// word was seen to fill the words with a stray byte pattern on every second replay, which sent every pair of the batch to the exact kernels
+__global__ void k_lf_clear_words(unsigned int* w, int n) {
+  if ((int)threadIdx.x < n) w[threadIdx.x] = 0u;
+}
+// x is [2][pairs] sequences of seq4 float4 each: the word raised is the one of the sequence's pair
+__global__ __launch_bounds__(256) void k_lf_check_finite(const float* x, long long n4, unsigned int* flag, long long seq4, int pairs) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
   const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-  if (!(fabsf(v.x) < 3.0e38f && fabsf(v.y) < 3.0e38f && fabsf(v.z) < 3.0e38f && fabsf(v.w) < 3.0e38f)) atomicOr(flag, 1u);
+  if (!(fabsf(v.x) < 3.0e38f && fabsf(v.y) < 3.0e38f && fabsf(v.z) < 3.0e38f && fabsf(v.w) < 3.0e38f)) atomicOr(flag + (int)((i / seq4) % pairs), 1u);
 }
 
 // ------------------------------------------------------------------------------------------------ coarse matching
@@ -690,11 +701,14 @@ __device__ __forceinline__ float lf_conf(float s, float rmax, float rsum, float 
   return (expf(s - cmax) / csum) * (expf(s - rmax) / rsum);
 }
 constexpr int kLfU = 5;       // loads in flight per thread in the passes over the similarity matrix
+// Every kernel of this stage takes the pair from its grid (blockIdx.y of the row kernels, blockIdx.z of the column kernels): sim is
+// [pairs][ld][ld], the statistics vectors [pairs][ld], the column partials [pairs][nsplit][ld]
 // one block per row i: max and sum of exponentials over j < L
 __global__ __launch_bounds__(256) void k_lf_row_stats(const float* sim, int ld, int L, float temp, float* rmax, float* rsum) {
   __shared__ float red[8];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const float* row = sim + (long long)i * ld;
+  const float* row = sim + ((long long)blockIdx.y * ld + i) * ld;
+  rmax += (long long)blockIdx.y * ld; rsum += (long long)blockIdx.y * ld;
   // (late round 5, here and in the four kernels below: a thread's loads are requested kLfU at a time before the first is used -- same elements in the
   // same order per thread, so the same bits; with one load in flight per loop iteration these passes over the 92 MB matrix ran at 1.3-2.5 TB/s: k_lf_conf_colmax 74 -> 59 us, k_lf_col_stats 63 -> below 50,
   // the row passes -3 us each; the same treatment of k_lf_fine_attn's staging loop bought nothing -- that kernel is bound by its LDS reads)
@@ -728,6 +742,7 @@ __global__ __launch_bounds__(256) void k_lf_row_stats(const float* sim, int ld, 
 __global__ __launch_bounds__(256) void k_lf_col_stats(const float* sim, int ld, int L, float temp, float* pmax, float* psum, int rows_per) {
   const int j = blockIdx.x * 256 + threadIdx.x, sp = blockIdx.y;
   if (j >= L) return;
+  sim += (long long)blockIdx.z * ld * ld; pmax += (long long)blockIdx.z * gridDim.y * ld; psum += (long long)blockIdx.z * gridDim.y * ld;
   const int i0 = sp * rows_per, i1 = min(L, i0 + rows_per);
   float m = -INFINITY, s = 0.f;
   for (int ib = i0; ib < i1; ib += 2 * kLfU) {
@@ -743,9 +758,10 @@ __global__ __launch_bounds__(256) void k_lf_col_stats(const float* sim, int ld, 
   }
   pmax[(long long)sp * L + j] = m; psum[(long long)sp * L + j] = s;
 }
-__global__ __launch_bounds__(256) void k_lf_col_merge(const float* pmax, const float* psum, int nsplit, int L, float* cmax, float* csum) {
+__global__ __launch_bounds__(256) void k_lf_col_merge(const float* pmax, const float* psum, int nsplit, int L, int ld, float* cmax, float* csum) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= L) return;
+  pmax += (long long)blockIdx.z * nsplit * ld; psum += (long long)blockIdx.z * nsplit * ld; cmax += (long long)blockIdx.z * ld; csum += (long long)blockIdx.z * ld;
   float m = -INFINITY;
   for (int sp = 0; sp < nsplit; ++sp) m = fmaxf(m, pmax[(long long)sp * L + j]);
   float s = 0.f;
@@ -756,7 +772,9 @@ __global__ __launch_bounds__(256) void k_lf_col_merge(const float* pmax, const f
 __global__ __launch_bounds__(256) void k_lf_conf_rowmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* crow) {
   __shared__ float red[4];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const float* row = sim + (long long)i * ld;
+  const long long po = (long long)blockIdx.y * ld;
+  const float* row = sim + (po + i) * ld;
+  rmax += po; rsum += po; cmax += po; csum += po; crow += po;
   const float rm = rmax[i], rs = rsum[i];
   float m = 0.f;
   for (int j0 = tid; j0 < L; j0 += 256 * kLfU) {
@@ -775,6 +793,8 @@ __global__ __launch_bounds__(256) void k_lf_conf_rowmax(const float* sim, int ld
 __global__ __launch_bounds__(256) void k_lf_conf_colmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* part, int rows_per) {
   const int j = blockIdx.x * 256 + threadIdx.x, sp = blockIdx.y;
   if (j >= L) return;
+  const long long po = (long long)blockIdx.z * ld;
+  sim += po * ld; rmax += po; rsum += po; cmax += po; csum += po; part += po * gridDim.y;
   const int i0 = sp * rows_per, i1 = min(L, i0 + rows_per);
   const float cm = cmax[j], cs = csum[j];
   float m = 0.f;
@@ -787,9 +807,10 @@ __global__ __launch_bounds__(256) void k_lf_conf_colmax(const float* sim, int ld
   }
   part[(long long)sp * L + j] = m;
 }
-__global__ __launch_bounds__(256) void k_lf_max_merge(const float* part, int nsplit, int L, float* out) {
+__global__ __launch_bounds__(256) void k_lf_max_merge(const float* part, int nsplit, int L, int ld, float* out) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= L) return;
+  part += (long long)blockIdx.z * nsplit * ld; out += (long long)blockIdx.z * ld;
   float m = 0.f;
   for (int sp = 0; sp < nsplit; ++sp) m = fmaxf(m, part[(long long)sp * L + j]);
   out[j] = m;
@@ -803,7 +824,9 @@ __global__ __launch_bounds__(256) void k_lf_mutual(const float* sim, int ld, int
   __syncthreads();
   const int yi = i / wc, xi = i - yi * wc;
   const bool in_i = yi >= border && yi < hc - border && xi >= border && xi < wc - border;
-  const float* row = sim + (long long)i * ld;
+  const long long po = (long long)blockIdx.y * ld;
+  const float* row = sim + (po + i) * ld;
+  rmax += po; rsum += po; cmax += po; csum += po; crow += po; ccol += po; jsel += po; csel += po;
   const float rm = rmax[i], rs = rsum[i], cr = crow[i];
   if (in_i)
     for (int j0 = tid; j0 < L; j0 += 256 * kLfU) {
@@ -829,10 +852,15 @@ __global__ __launch_bounds__(256) void k_lf_mutual(const float* sim, int ld, int
     csel[i] = j == 0x7fffffff ? 0.f : lf_conf(row[j] / temp, rm, rs, cmax[j], csum[j]);
   }
 }
-// ordered compaction (ascending i, like torch.where): one block
-__global__ __launch_bounds__(1024) void k_lf_compact(const int* jsel, const float* csel, int L, int wc, int scale, int max_out, int* i_ids, int* j_ids, float* conf, float* k0, float* k1, int* n_out) {
+// ordered compaction (ascending i, like torch.where): one block per pair; jsel / csel [pairs][ld], the outputs in segments of max_out matches
+__global__ __launch_bounds__(1024) void k_lf_compact(const int* jsel, const float* csel, int L, int ld, int wc, int scale, int max_out, int* i_ids, int* j_ids, float* conf, float* k0, float* k1, int* n_out) {
   __shared__ int wcount[16], base;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    const long long so = (long long)blockIdx.x * max_out;
+    jsel += (long long)blockIdx.x * ld; csel += (long long)blockIdx.x * ld;
+    i_ids += so; j_ids += so; conf += so; k0 += 2 * so; k1 += 2 * so; n_out += blockIdx.x;
+  }
   if (tid == 0) base = 0;
   __syncthreads();
   for (int i0 = 0; i0 < L; i0 += 1024) {
@@ -856,12 +884,23 @@ __global__ __launch_bounds__(1024) void k_lf_compact(const int* jsel, const floa
   }
   if (tid == 0) *n_out = min(base, max_out);
 }
+// the matches of all pairs as ONE list for the fine level (kornia's b_ids / i_ids / j_ids): cat[off_p + l] = p * seg + l, the match's place in the
+// segmented result buffers (its pair is cat / seg), off_p = n[0] + .. + n[p - 1]; *n_tot = the length of the list.  One block per pair.
+__global__ __launch_bounds__(256) void k_lf_concat(const int* n, int seg, int* cat, int* n_tot) {
+  const int p = blockIdx.x;
+  int off = 0;
+  for (int q = 0; q < p; ++q) off += n[q];
+  const int np = n[p];
+  for (int l = threadIdx.x; l < np; l += 256) cat[off + l] = p * seg + l;
+  if (p == (int)gridDim.x - 1 && threadIdx.x == 0) *n_tot = off + np;
+}
 
 // ------------------------------------------------------------------------------------------------ fine level
 // FinePreprocess: rows [m][ww][256] = [ unfold_5x5(feat_f, stride 4, pad 2)[cell(m)][ww][0..127] | down_proj(coarse feature of the match)[0..127] ]
 // for side 0 (cells i_ids) in rows [0, M) and side 1 (cells j_ids) in rows [M, 2 M); merge_feat is then one GEMM over K = 256.
-__global__ __launch_bounds__(256) void k_lf_fine_gather(const float* ff /*[2][Hf][Wf][128]*/, int Hf, int Wf, int wc, const int* i_ids, const int* j_ids, const int* n_match, int Mp,
-                                                       const float* cwin /*[2 Mp][128]*/, float* rows /*[2 Mp * 25][256]*/) {
+// (Mp: the windows a side has room for, all pairs together; a window's cell and pair come through cat, see k_lf_concat)
+__global__ __launch_bounds__(256) void k_lf_fine_gather(const float* ff /*[2][pairs][Hf][Wf][128]*/, int Hf, int Wf, int wc, const int* i_ids, const int* j_ids, const int* cat, int seg, int pairs,
+                                                       const int* n_match, int Mp, const float* cwin /*[2 Mp][128]*/, float* rows /*[2 Mp * 25][256]*/) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;          // float4 index over [2 Mp][25][64]
   if (idx >= 2LL * Mp * kLfWW * 64) return;
   const int c4 = (int)(idx & 63);
@@ -873,28 +912,33 @@ __global__ __launch_bounds__(256) void k_lf_fine_gather(const float* ff /*[2][Hf
   if (m * kLfWW + ww >= (M * kLfWW + 127) / 128 * 128) return;         // behind the last 128-row tile a GEMM of the fine level touches (GemmArgs::mlim)
   if (m < M) {
     if (c4 < 32) {
-      const int cell = side ? j_ids[m] : i_ids[m];
+      const int src = cat[m], pair = src / seg;
+      const int cell = side ? j_ids[src] : i_ids[src];
       const int cy = cell / wc, cx = cell - cy * wc;
       const int y = cy * 4 - 2 + ww / 5, x = cx * 4 - 2 + ww % 5;          // F.unfold(kernel 5, stride 4, padding 2): zero outside
-      if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = *reinterpret_cast<const f32x4*>(ff + (((long long)side * Hf + y) * Wf + x) * 128 + c4 * 4);
+      if (y >= 0 && y < Hf && x >= 0 && x < Wf) v = *reinterpret_cast<const f32x4*>(ff + ((((long long)side * pairs + pair) * Hf + y) * Wf + x) * 128 + c4 * 4);
     } else {
       v = *reinterpret_cast<const f32x4*>(cwin + (long long)m2 * 128 + (c4 - 32) * 4);
     }
   }
   *reinterpret_cast<f32x4*>(rows + ((long long)m2 * kLfWW + ww) * 256 + c4 * 4) = v;
 }
-// rows [2 Mp][256] = [coarse feature of cell i (side 0) / j (side 1)] for down_proj
-__global__ __launch_bounds__(256) void k_lf_coarse_gather(const float* f0, const float* f1, const int* i_ids, const int* j_ids, const int* n_match, int Mp, float* rows) {
+// rows [2 Mp][256] = [coarse feature of cell i (side 0) / j (side 1)] for down_proj; tok [2][pairs][Lp][256]
+__global__ __launch_bounds__(256) void k_lf_coarse_gather(const float* tok, int Lp, int pairs, const int* i_ids, const int* j_ids, const int* cat, int seg, const int* n_match, int Mp, float* rows) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= 2LL * Mp * 64) return;
   const int c4 = (int)(idx & 63), m2 = (int)(idx >> 6), side = m2 >= Mp ? 1 : 0, m = m2 - side * Mp;
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (m < *n_match) v = *reinterpret_cast<const f32x4*>((side ? f1 + (long long)j_ids[m] * 256 : f0 + (long long)i_ids[m] * 256) + c4 * 4);
+  if (m < *n_match) {
+    const int src = cat[m], pair = src / seg;
+    v = *reinterpret_cast<const f32x4*>(tok + (((long long)side * pairs + pair) * Lp + (side ? j_ids[src] : i_ids[src])) * 256 + c4 * 4);
+  }
   *reinterpret_cast<f32x4*>(rows + (long long)m2 * 256 + c4 * 4) = v;
 }
 // FineMatching: one wave per match: sim_r = <f0[centre], f1[r]>, softmax(sim / sqrt(128)), expectation over the normalised 5x5 grid,
 // k1_f = k1_c + expectation * 2 * 2
-__global__ __launch_bounds__(256) void k_lf_fine_match(const float* f0 /*[Mp*25][128]*/, const float* f1, const int* n_match, const float* k1c, float* k1f) {
+// (match m of the list is match cat[m] of the segmented k1c / k1f; ovf, when given, is the fp16-range guard: a result that is not finite raises its pair's word)
+__global__ __launch_bounds__(256) void k_lf_fine_match(const float* f0 /*[Mp*25][128]*/, const float* f1, const int* n_match, const int* cat, int seg, const float* k1c, float* k1f, unsigned int* ovf) {
   const int lane = threadIdx.x & 63, m = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= *n_match) return;
   const float* c = f0 + ((long long)m * kLfWW + 12) * 128;
@@ -911,7 +955,12 @@ __global__ __launch_bounds__(256) void k_lf_fine_match(const float* f0 /*[Mp*25]
     const float e = expf(sim[r] - mx);
     den += e; ex += e * (-1.f + 0.5f * (float)(r % 5)); ey += e * (-1.f + 0.5f * (float)(r / 5));
   }
-  if (lane == 0) { k1f[2 * m] = k1c[2 * m] + (ex / den) * 2.f * 2.f; k1f[2 * m + 1] = k1c[2 * m + 1] + (ey / den) * 2.f * 2.f; }
+  if (lane == 0) {
+    const int src = cat[m];
+    const float x = k1c[2 * src] + (ex / den) * 2.f * 2.f, y = k1c[2 * src + 1] + (ey / den) * 2.f * 2.f;
+    k1f[2 * src] = x; k1f[2 * src + 1] = y;
+    if (ovf != nullptr && !(fabsf(x) < 3.0e38f && fabsf(y) < 3.0e38f)) atomicOr(ovf + src / seg, 1u);
+  }
 }
 
 }  // namespace
@@ -934,6 +983,7 @@ int pad32(int c) { return (c + 31) / 32 * 32; }
 
 struct gn_loftr {
   int device = 0, H = 0, W = 0, hc = 0, wc = 0, L = 0, Lp = 0, fine = 1, max_matches = 0, Mp = 0;
+  int max_pairs = 1, B = 1;             // pairs the buffers have room for; pairs of the forward in flight (every buffer is laid out densely for B: [2][B]... side-major)
   std::string err;
   std::map<std::string, LfConv> conv;          // by module name, e.g. "backbone.layer1.0.conv1"
   LfLayer coarse[8], finel[2];
@@ -946,13 +996,14 @@ struct gn_loftr {
   float *x3_out = nullptr, *x2_out = nullptr, *x1_out = nullptr, *fpn_a = nullptr, *fpn_b = nullptr;
   float *pe = nullptr, *tok = nullptr, *qkv = nullptr, *att = nullptr, *msg = nullptr, *hid = nullptr, *kvpart = nullptr, *kv = nullptr, *fs = nullptr, *sim = nullptr;
   float *rmax = nullptr, *rsum = nullptr, *cmax = nullptr, *csum = nullptr, *crow = nullptr, *ccol = nullptr, *cpart_a = nullptr, *cpart_b = nullptr, *csel = nullptr;
-  int *jsel = nullptr, *i_ids = nullptr, *j_ids = nullptr, *n_dev = nullptr;
+  int *jsel = nullptr, *i_ids = nullptr, *j_ids = nullptr, *n_dev = nullptr;      // n_dev [max_pairs] per-pair counts
+  int *cat = nullptr, *n_tot = nullptr;                                          // the fine level's list over all pairs (k_lf_concat) and its length
   float *k0c = nullptr, *k1c = nullptr, *mconf = nullptr;
   float *frows = nullptr, *fc = nullptr, *fwin = nullptr, *ftok = nullptr, *fqkv = nullptr, *fatt = nullptr, *fmsg = nullptr, *fhid = nullptr, *fkvpart = nullptr, *fkv = nullptr;
   int* n_host = nullptr;
-  int use_graph = 1; bool graph_failed[2] = {false, false}; hipGraphExec_t graph_exec[2] = {nullptr, nullptr}; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per arithmetic
+  int use_graph = 1; std::map<int, hipGraphExec_t> graph_exec; std::map<int, bool> graph_failed; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per (arithmetic, B): key 2 B + arithmetic
   int arith = 0;                        // gn_loftr_set_arithmetic: 0 exact f32, 1 split fp16 (f32-accurate)
-  unsigned int* ovf = nullptr; long long ovf_trips = 0;   // split mode: fp16-range guard word (device), calls that fell back to the exact kernels
+  unsigned int* ovf = nullptr; long long ovf_trips = 0;   // split mode: fp16-range guard words (device, one per pair), pairs that fell back to the exact kernels
 };
 
 namespace {
@@ -1053,7 +1104,7 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
   LfConvArgs a;
   a.in = in; a.Hin = Hin; a.Win = Win; a.Cin = c.cin_p; a.wf = c.wf; a.scale = c.scale; a.shift = c.shift; a.resid = resid;
   a.out = out; a.Hout = Hin / stride; a.Wout = Win / stride; a.Cout = c.cout_p; a.act = act;
-  a.wfh = c.wfh; a.scale_h = c.scale_h; a.ovf = ctx->ovf;
+  a.wfh = c.wfh; a.scale_h = c.scale_h; a.ovf = ctx->ovf; a.pairs = N / 2;
   a.cin_real = (gn::g_lf_conv_knob & 8) ? c.cin_p : c.cin;        // developer knob 42, bit 3: multiply the zero padding like rounds 3-4 did
   const bool hm = ctx->arith == 1 && c.wfh != nullptr;
   const int og = (c.cout_p + 63) / 64;
@@ -1064,7 +1115,8 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
   const bool fast = !(gn::g_lf_conv_knob & 16) && c.cout_p % 64 == 0 && a.cin_real % 32 == 0 && a.cin_real == c.cin_p;     // k_lf_conv<.., FAST> (knob 42 bit 4: off)
   const bool pf = !(gn::g_lf_conv_knob & 1);                                   // developer knob 42, bit 0: the staging form of rounds 3-4
   const double ovh = (gn::g_lf_conv_knob >> 8) ? (gn::g_lf_conv_knob >> 8) * 0.01 : (pf ? 0.25 : 0.75);    // bits 8..: the per-workgroup overhead of the cost model, in 1/100 units
-  auto units = [&](int rpw) { const long long wg = (long long)((a.Wout + 31) / 32) * ((a.Hout + 4 * rpw - 1) / (4 * rpw)) * N * og; return (double)((wg + 255) / 256) * (rpw + ovh); };
+  // (the model counts the workgroups of ONE pair, N = 2, whatever the batch: the kernel form a pair runs on, and with it its bits, must not depend on its neighbours)
+  auto units = [&](int rpw) { const long long wg = (long long)((a.Wout + 31) / 32) * ((a.Hout + 4 * rpw - 1) / (4 * rpw)) * 2 * og; return (double)((wg + 255) / 256) * (rpw + ovh); };
   const dim3 blk(256);
   auto grid = [&](int rpw) { return dim3((a.Wout + 31) / 32, (a.Hout + 4 * rpw - 1) / (4 * rpw), N * og); };
   if (stride == 1) {
@@ -1090,16 +1142,17 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
 }
 
 thread_local int g_lf_gemm_variant = 3;   // set by lf_forward from the context it runs (per host thread)
+thread_local int g_lf_pairs = 1;          // pairs of the forward being launched: a GEMM over the rows of all pairs picks its tile form from the rows of ONE (launch_gemm_f32's sel_m)
 struct LfLimit { const int* n = nullptr; int mul = 0, seg = 0; };     // GemmArgs::mlim
 void lf_gemm(const float* A, int lda, const float* A2, int lda2, int K1, const float* Wt, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K, hipStream_t s, bool relu = false,
-             LfLimit lim = LfLimit()) {
+             LfLimit lim = LfLimit(), int pairs = 0 /* pairs whose rows M holds; 0 = all of the forward's */) {
   GemmArgs g;
   memset(&g, 0, sizeof g);
   g.mlim = lim.n; g.mlim_mul = lim.mul; g.mlim_seg = lim.seg;
   g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = A2 ? K1 : K; g.W = Wt; g.ldw = ldw; g.bias = bias; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.acc_scale = 1.f;
   const int saved = gn::g_gemm_variant;
   gn::g_gemm_variant = g_lf_gemm_variant;                   // 3 = the exact-f32 MFMA GEMM, whatever other contexts selected; 6 = every f32 operand split into two fp16 terms on the fly (gn_loftr_set_arithmetic)
-  launch_gemm_f32(relu ? EPI_RELU : bias ? EPI_BIAS : EPI_PLAIN, g, 1, s);      // (relu: the MLP's first layer, max(x, 0) applied to the value the plain epilogue would store)
+  launch_gemm_f32(relu ? EPI_RELU : bias ? EPI_BIAS : EPI_PLAIN, g, 1, s, M / (pairs > 0 ? pairs : g_lf_pairs));      // (relu: the MLP's first layer, max(x, 0) applied to the value the plain epilogue would store)
   gn::g_gemm_variant = saved;
 }
 
@@ -1131,26 +1184,27 @@ void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pa
     hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)half, d, seq_rows, 0, hl.n, hl.mul, hl.seg);
     return;
   }
-  if (cross && nall == 2 && hd == 32 && seq_rows % 128 == 0) {
-    // the coarse level's cross halves: only sequence a = mode - 1 is updated, only sequence b = 1 - a is attended to -- project q for a's rows,
-    // k | v for b's rows, and run merge / MLP / norms over a's rows alone (half the work of the general path below)
-    const int a = mode - 1, b = 1 - a;
-    float* xa = x + (size_t)a * seq_rows * d; const float* xb = x + (size_t)b * seq_rows * d;
-    float* qa = qkv + (size_t)a * seq_rows * 3 * d; float* kvb = qkv + (size_t)b * seq_rows * 3 * d + d;
-    float* atta = att + (size_t)a * seq_rows * d; float* msga = msg + (size_t)a * seq_rows * d; float* hida = hid + (size_t)a * seq_rows * 2 * d;
-    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, seq_rows, d, d, s);
-    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, seq_rows, 2 * d, d, s);
+  if (cross && nall % 2 == 0 && hd == 32 && seq_rows % 128 == 0) {
+    // the coarse level's cross halves on the side-major token buffer [2][pairs] sequences: only side a = mode - 1 is updated, only side b = 1 - a is
+    // attended to (the partner of sequence s is s +- pairs) -- project q for a's rows, k | v for b's rows, and run merge / MLP / norms over a's rows
+    // alone (half the work of the general path below).  K^T V stays per sequence, its chunk and split chosen from Lseq alone
+    const int a = mode - 1, b = 1 - a, np = nall / 2, half = np * seq_rows;
+    float* xa = x + (size_t)a * half * d; const float* xb = x + (size_t)b * half * d;
+    float* qa = qkv + (size_t)a * half * 3 * d; float* kvb = qkv + (size_t)b * half * 3 * d + d;
+    float* atta = att + (size_t)a * half * d; float* msga = msg + (size_t)a * half * d; float* hida = hid + (size_t)a * half * 2 * d;
+    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, half, d, d, s);
+    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, half, 2 * d, d, s);
     const int chunk = 192, nsplit = (Lseq + chunk - 1) / chunk;
     const long long per = (long long)heads * 33 * 32;
-    hipLaunchKernelGGL(k_lf_kv_partial<32>, dim3(heads, nsplit, 1), dim3(256), 0, s, kvb, kvb + d, 3 * d, 0LL, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
-    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, 1);
+    hipLaunchKernelGGL(k_lf_kv_partial<32>, dim3(heads, nsplit, np), dim3(256), 0, s, kvb, kvb + d, 3 * d, (long long)seq_rows * 3 * d, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
+    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per * np + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, np);
     const size_t smem = (size_t)(per + 8 * d) * sizeof(float);
-    hipLaunchKernelGGL(k_lf_attn_apply<32>, dim3((Lseq + 7) / 8, 1), dim3(256), smem, s, qa, 3 * d, 0LL, kv, 0, atta, d, 0LL, Lseq, (float)Lseq, heads);
-    lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, seq_rows, d, d, s);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((seq_rows + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)seq_rows, d, seq_rows, 0);
-    lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, seq_rows, 2 * d, 2 * d, s, true);
-    lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, seq_rows, d, 2 * d, s);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((seq_rows + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)seq_rows, d, seq_rows, 0);
+    hipLaunchKernelGGL(k_lf_attn_apply<32>, dim3((Lseq + 7) / 8, np), dim3(256), smem, s, qa, 3 * d, (long long)seq_rows * 3 * d, kv, 0, atta, d, (long long)seq_rows * d, Lseq, (float)Lseq, heads);
+    lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, half, d, d, s);
+    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)half, d, seq_rows, 0);
+    lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, half, 2 * d, 2 * d, s, true);
+    lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, half, d, 2 * d, s);
+    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)half, d, seq_rows, 0);
     return;
   }
   lf_gemm(x, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qkv, 3 * d, rows_pad, 3 * d, d, s, false, lim);
@@ -1180,9 +1234,12 @@ extern "C" {
 
 const char* gn_loftr_last_error(const gn_loftr* ctx) { return ctx ? ctx->err.c_str() : g_lf_err.c_str(); }
 
-int gn_loftr_create(int device, int H, int W, int max_matches, int fine, gn_loftr** out) {
+int gn_loftr_create(int device, int H, int W, int max_matches, int fine, gn_loftr** out) { return gn_loftr_create_batch(device, 1, H, W, max_matches, fine, out); }
+
+int gn_loftr_create_batch(int device, int max_pairs, int H, int W, int max_matches, int fine, gn_loftr** out) {
   gn_loftr* ctx = nullptr;
   if (!out || H < 32 || W < 32 || (H % 8) || (W % 8) || max_matches < 1) return lf_fail(nullptr, GN_ERR_ARG, "gn_loftr_create: H, W multiples of 8 (>= 32), max_matches >= 1");
+  if (max_pairs < 1) return lf_fail(nullptr, GN_ERR_ARG, "gn_loftr_create_batch: max_pairs >= 1");
   LF_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   LF_HIP(hipGetDeviceProperties(&prop, device));
@@ -1194,23 +1251,29 @@ int gn_loftr_create(int device, int H, int W, int max_matches, int fine, gn_loft
   // y dimension of its GEMM grids in units of 128: Mp <= 131072 keeps that below 65536 (a 4096 x 4096 image has 262144 cells: capped there)
   ctx->max_matches = std::min(std::min(max_matches, ctx->L), 131072);
   ctx->Mp = (ctx->max_matches + 127) / 128 * 128;
+  ctx->max_pairs = max_pairs;
+  // (the same bound for the fine level's one list over all pairs)
+  if ((long long)max_pairs * ctx->Mp > 131072) { const int mp = ctx->Mp; delete ctx; return lf_fail(nullptr, GN_ERR_ARG, "gn_loftr_create_batch: max_pairs x " + std::to_string(mp) + " match slots exceed 131072"); }
+  const size_t P = (size_t)max_pairs;
   const size_t h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, hc = ctx->hc, wc = ctx->wc, Lp = ctx->Lp, L = ctx->L;
 #define LF_A(field, n) do { int rc_ = lf_alloc(ctx, &ctx->field, (n)); if (rc_ != GN_OK) { gn_loftr_destroy(ctx); return rc_; } } while (0)
-  LF_A(img, 2 * (size_t)H * W);
-  LF_A(x0, 2 * h2 * w2 * 128); LF_A(x1, 2 * h2 * w2 * 128); LF_A(t1, 2 * h2 * w2 * 224);
-  LF_A(x2, 2 * h4 * w4 * 224); LF_A(t2, 2 * h4 * w4 * 256); LF_A(x3, 2 * hc * wc * 256); LF_A(t3, 2 * hc * wc * 256);
-  LF_A(x3_out, 2 * hc * wc * 256); LF_A(x2_out, 2 * h4 * w4 * 256); LF_A(fpn_a, 2 * h2 * w2 * 224); LF_A(fpn_b, 2 * h2 * w2 * 224); LF_A(x1_out, 2 * h2 * w2 * 128);
-  LF_A(pe, L * 256); LF_A(tok, 2 * Lp * 256); LF_A(qkv, 2 * Lp * 768); LF_A(att, 2 * Lp * 256); LF_A(msg, 2 * Lp * 256); LF_A(hid, 2 * Lp * 512);
-  LF_A(kvpart, 2 * ((L + 191) / 192) * 8 * 33 * 32); LF_A(kv, 2 * 8 * 33 * 32); LF_A(fs, 2 * Lp * 256); LF_A(sim, Lp * Lp);
-  LF_A(rmax, Lp); LF_A(rsum, Lp); LF_A(cmax, Lp); LF_A(csum, Lp); LF_A(crow, Lp); LF_A(ccol, Lp); LF_A(cpart_a, 32 * Lp); LF_A(cpart_b, 32 * Lp); LF_A(csel, Lp);
-  LF_A(ovf, 4); LF_A(jsel, Lp); LF_A(i_ids, ctx->Mp); LF_A(j_ids, ctx->Mp); LF_A(n_dev, 4); LF_A(k0c, 2 * (size_t)ctx->Mp); LF_A(k1c, 2 * (size_t)ctx->Mp); LF_A(mconf, ctx->Mp);
+  // every buffer has room for max_pairs pairs (P); a call with B of them uses the front of each, laid out for B
+  LF_A(img, P * 2 * (size_t)H * W);
+  LF_A(x0, P * 2 * h2 * w2 * 128); LF_A(x1, P * 2 * h2 * w2 * 128); LF_A(t1, P * 2 * h2 * w2 * 224);
+  LF_A(x2, P * 2 * h4 * w4 * 224); LF_A(t2, P * 2 * h4 * w4 * 256); LF_A(x3, P * 2 * hc * wc * 256); LF_A(t3, P * 2 * hc * wc * 256);
+  LF_A(x3_out, P * 2 * hc * wc * 256); LF_A(x2_out, P * 2 * h4 * w4 * 256); LF_A(fpn_a, P * 2 * h2 * w2 * 224); LF_A(fpn_b, P * 2 * h2 * w2 * 224); LF_A(x1_out, P * 2 * h2 * w2 * 128);
+  LF_A(pe, L * 256); LF_A(tok, P * 2 * Lp * 256); LF_A(qkv, P * 2 * Lp * 768); LF_A(att, P * 2 * Lp * 256); LF_A(msg, P * 2 * Lp * 256); LF_A(hid, P * 2 * Lp * 512);
+  LF_A(kvpart, P * 2 * ((L + 191) / 192) * 8 * 33 * 32); LF_A(kv, P * 2 * 8 * 33 * 32); LF_A(fs, P * 2 * Lp * 256); LF_A(sim, P * Lp * Lp);
+  LF_A(rmax, P * Lp); LF_A(rsum, P * Lp); LF_A(cmax, P * Lp); LF_A(csum, P * Lp); LF_A(crow, P * Lp); LF_A(ccol, P * Lp); LF_A(cpart_a, P * 32 * Lp); LF_A(cpart_b, P * 32 * Lp); LF_A(csel, P * Lp);
+  LF_A(ovf, P + 4); LF_A(jsel, P * Lp); LF_A(i_ids, P * ctx->Mp); LF_A(j_ids, P * ctx->Mp); LF_A(n_dev, P + 4); LF_A(k0c, P * 2 * (size_t)ctx->Mp); LF_A(k1c, P * 2 * (size_t)ctx->Mp); LF_A(mconf, P * ctx->Mp);
+  LF_A(cat, P * ctx->Mp); LF_A(n_tot, 4);
   if (ctx->fine) {
-    const size_t R = 2 * (size_t)ctx->Mp * kLfWW;      // window tokens of both sides
-    LF_A(fc, 2 * (size_t)ctx->Mp * 256); LF_A(fwin, 2 * (size_t)ctx->Mp * 128); LF_A(frows, R * 256); LF_A(ftok, R * 128); LF_A(fqkv, R * 384); LF_A(fatt, R * 128);
-    LF_A(fmsg, R * 128); LF_A(fhid, R * 256); LF_A(fkvpart, 2 * (size_t)ctx->Mp * 8 * 17 * 16); LF_A(fkv, 2 * (size_t)ctx->Mp * 8 * 17 * 16);
+    const size_t R = P * 2 * (size_t)ctx->Mp * kLfWW;      // window tokens of both sides
+    LF_A(fc, P * 2 * (size_t)ctx->Mp * 256); LF_A(fwin, P * 2 * (size_t)ctx->Mp * 128); LF_A(frows, R * 256); LF_A(ftok, R * 128); LF_A(fqkv, R * 384); LF_A(fatt, R * 128);
+    LF_A(fmsg, R * 128); LF_A(fhid, R * 256); LF_A(fkvpart, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16); LF_A(fkv, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16);
   }
 #undef LF_A
-  if (hipHostMalloc((void**)&ctx->n_host, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) { gn_loftr_destroy(ctx); return lf_fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
+  if (hipHostMalloc((void**)&ctx->n_host, (2 * P + 4) * sizeof(int), hipHostMallocDefault) != hipSuccess) { gn_loftr_destroy(ctx); return lf_fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
   {   // PositionEncodingSine, legacy divisor (temp_bug_fix = False): div_term_i = exp(-2 i); token l = y * wc + x, positions 1-based
     std::vector<float> pe((size_t)L * 256);
     for (int y = 0; y < (int)hc; ++y)
@@ -1230,7 +1293,7 @@ int gn_loftr_create(int device, int H, int W, int max_matches, int fine, gn_loft
 void gn_loftr_destroy(gn_loftr* ctx) {
   if (!ctx) return;
   hipSetDevice(ctx->device);
-  for (int i = 0; i < 2; ++i) if (ctx->graph_exec[i]) hipGraphExecDestroy(ctx->graph_exec[i]);
+  for (auto& g : ctx->graph_exec) if (g.second) hipGraphExecDestroy(g.second);
   if (ctx->cap_stream) hipStreamDestroy(ctx->cap_stream);
   for (void* p : ctx->allocs) hipFree(p);
   if (ctx->n_host) hipHostFree(ctx->n_host);
@@ -1321,88 +1384,94 @@ int gn_loftr_missing_tensors(const gn_loftr* ctx) {
   return missing;
 }
 
-// LoFTR.forward on one pair of equally sized images.  image0 / image1: DEVICE f32 [H][W] in [0, 1].  Outputs (device): kpts0 / kpts1
-// [max_matches][2] (x, y) pixels -- kpts0 on the 1/8 grid, kpts1 refined by the fine level when the context has one --, conf [max_matches],
-// optional ij [max_matches][2] int32 coarse cell ids; *n_host (HOST) = number of matches (the call synchronises `stream` once to return it).
-// the whole forward from ctx->img to the context's result buffers (k0c, k1c / fc, mconf, i_ids, j_ids, n_dev) on stream s: ~190 dependent
-// launches with no host decision in between (the match count stays on the device), so it can be captured into one hipGraph
+// LoFTR.forward on ctx->B pairs of equally sized images: the whole forward from ctx->img ([2][B][H][W]: the B image0 then the B image1) to the
+// context's result buffers (k0c, k1c / fc, mconf, i_ids, j_ids in per-pair segments of max_matches; n_dev[B]) on stream s: ~190 dependent launches
+// with no host decision in between (the match counts stay on the device), so it can be captured into one hipGraph, a single linear chain.
+// Every buffer is side-major over the pairs -- images, backbone maps and tokens [2][B]..., the cross partner of sequence q is q +- B -- and every
+// choice of a kernel form is made from the shape of ONE pair (lf_conv's cost model, launch_gemm_f32's sel_m, the K^T V chunks): a pair's result
+// does not depend on B, on its place in the batch or on its neighbours, bit for bit, and B = 1 is the layout of the one-pair call
 static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   const int H = ctx->H, W = ctx->W, h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, hc = ctx->hc, wc = ctx->wc, L = ctx->L, Lp = ctx->Lp;
+  const int B = ctx->B, N = 2 * B;
   g_lf_gemm_variant = ctx->arith == 1 ? 6 : 3;
-  LF_HIP(hipMemsetAsync(ctx->ovf, 0, sizeof(unsigned int), s));
-  // ---- backbone (both images as a batch of 2)
+  g_lf_pairs = B;
+  for (int b0 = 0; b0 < B; b0 += 256) hipLaunchKernelGGL(k_lf_clear_words, dim3(1), dim3(256), 0, s, ctx->ovf + b0, std::min(256, B - b0));
+  // ---- backbone (the images of both sides as a batch of 2 B)
   {
     const LfConv& c = ctx->conv["backbone.conv1"];
     const long long n = (long long)h2 * w2 * 8;
-    if (gn::g_lf_conv_knob & 4) hipLaunchKernelGGL(k_lf_conv1<true>, dim3((unsigned)((n + 255) / 256), 1, 2), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
-    else hipLaunchKernelGGL(k_lf_conv1<false>, dim3((unsigned)((n + 255) / 256), 1, 2), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
+    if (gn::g_lf_conv_knob & 4) hipLaunchKernelGGL(k_lf_conv1<true>, dim3((unsigned)((n + 255) / 256), 1, N), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
+    else hipLaunchKernelGGL(k_lf_conv1<false>, dim3((unsigned)((n + 255) / 256), 1, N), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
   }
   auto block = [&](const std::string& p, const float* x, int Hin, int Win, int stride, float* tmp, float* ds, float* out) {
     // y = relu(bn1(conv1(x))); y = bn2(conv2(y)); x' = stride != 1 ? bn(conv1x1(x)) : x; out = relu(x' + y)
-    lf_conv(ctx, (p + ".conv1").c_str(), x, 2, Hin, Win, tmp, stride, nullptr, 1, s);
+    lf_conv(ctx, (p + ".conv1").c_str(), x, N, Hin, Win, tmp, stride, nullptr, 1, s);
     const float* skip = x;
-    if (stride != 1) { lf_conv(ctx, (p + ".downsample.0").c_str(), x, 2, Hin, Win, ds, stride, nullptr, 0, s); skip = ds; }
-    lf_conv(ctx, (p + ".conv2").c_str(), tmp, 2, Hin / stride, Win / stride, out, 1, skip, 1, s);
+    if (stride != 1) { lf_conv(ctx, (p + ".downsample.0").c_str(), x, N, Hin, Win, ds, stride, nullptr, 0, s); skip = ds; }
+    lf_conv(ctx, (p + ".conv2").c_str(), tmp, N, Hin / stride, Win / stride, out, 1, skip, 1, s);
   };
   block("backbone.layer1.0", ctx->x0, h2, w2, 1, ctx->t1, nullptr, ctx->x1);        // x0 -> x1
   block("backbone.layer1.1", ctx->x1, h2, w2, 1, ctx->t1, nullptr, ctx->x0);        // x1 -> x0 (= layer1 output, "x1" of the paper)
   float* const X1 = ctx->x0;
   block("backbone.layer2.0", X1, h2, w2, 2, ctx->t2, ctx->x2_out, ctx->x2);         // (x2_out is free until the FPN head)
   block("backbone.layer2.1", ctx->x2, h4, w4, 1, ctx->t2, nullptr, ctx->x2_out);
-  LF_HIP(hipMemcpyAsync(ctx->x2, ctx->x2_out, (size_t)2 * h4 * w4 * 224 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  LF_HIP(hipMemcpyAsync(ctx->x2, ctx->x2_out, (size_t)N * h4 * w4 * 224 * sizeof(float), hipMemcpyDeviceToDevice, s));
   block("backbone.layer3.0", ctx->x2, h4, w4, 2, ctx->t3, ctx->x3_out, ctx->x3);
   block("backbone.layer3.1", ctx->x3, hc, wc, 1, ctx->t3, nullptr, ctx->x3_out);
-  LF_HIP(hipMemcpyAsync(ctx->x3, ctx->x3_out, (size_t)2 * hc * wc * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  lf_conv(ctx, "backbone.layer3_outconv", ctx->x3, 2, hc, wc, ctx->x3_out, 1, nullptr, 0, s);
+  LF_HIP(hipMemcpyAsync(ctx->x3, ctx->x3_out, (size_t)N * hc * wc * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  lf_conv(ctx, "backbone.layer3_outconv", ctx->x3, N, hc, wc, ctx->x3_out, 1, nullptr, 0, s);
   if (ctx->fine) {
     // x2_out = layer2_outconv2(layer2_outconv(x2) + up2(x3_out)); x1_out = layer1_outconv2(layer1_outconv(x1) + up2(x2_out))
-    lf_conv(ctx, "backbone.layer2_outconv", ctx->x2, 2, h4, w4, ctx->t2, 1, nullptr, 0, s);
-    { const long long n4 = 2LL * h4 * w4 * 64; hipLaunchKernelGGL(k_lf_up2_add, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->t2, ctx->x3_out, ctx->t2, h4, w4, 256, n4); }
-    lf_conv(ctx, "backbone.layer2_outconv2.0", ctx->t2, 2, h4, w4, ctx->x2_out, 1, nullptr, 2, s);
-    lf_conv(ctx, "backbone.layer2_outconv2.3", ctx->x2_out, 2, h4, w4, ctx->x2, 1, nullptr, 0, s);       // [.][224]: x2 is dead, reuse
-    lf_conv(ctx, "backbone.layer1_outconv", X1, 2, h2, w2, ctx->fpn_a, 1, nullptr, 0, s);
-    { const long long n4 = 2LL * h2 * w2 * 56; hipLaunchKernelGGL(k_lf_up2_add, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->fpn_a, ctx->x2, ctx->fpn_a, h2, w2, 224, n4); }
-    lf_conv(ctx, "backbone.layer1_outconv2.0", ctx->fpn_a, 2, h2, w2, ctx->fpn_b, 1, nullptr, 2, s);
-    lf_conv(ctx, "backbone.layer1_outconv2.3", ctx->fpn_b, 2, h2, w2, ctx->x1_out, 1, nullptr, 0, s);
+    lf_conv(ctx, "backbone.layer2_outconv", ctx->x2, N, h4, w4, ctx->t2, 1, nullptr, 0, s);
+    { const long long n4 = (long long)N * h4 * w4 * 64; hipLaunchKernelGGL(k_lf_up2_add, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->t2, ctx->x3_out, ctx->t2, h4, w4, 256, n4); }
+    lf_conv(ctx, "backbone.layer2_outconv2.0", ctx->t2, N, h4, w4, ctx->x2_out, 1, nullptr, 2, s);
+    lf_conv(ctx, "backbone.layer2_outconv2.3", ctx->x2_out, N, h4, w4, ctx->x2, 1, nullptr, 0, s);       // [.][224]: x2 is dead, reuse
+    lf_conv(ctx, "backbone.layer1_outconv", X1, N, h2, w2, ctx->fpn_a, 1, nullptr, 0, s);
+    { const long long n4 = (long long)N * h2 * w2 * 56; hipLaunchKernelGGL(k_lf_up2_add, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->fpn_a, ctx->x2, ctx->fpn_a, h2, w2, 224, n4); }
+    lf_conv(ctx, "backbone.layer1_outconv2.0", ctx->fpn_a, N, h2, w2, ctx->fpn_b, 1, nullptr, 2, s);
+    lf_conv(ctx, "backbone.layer1_outconv2.3", ctx->fpn_b, N, h2, w2, ctx->x1_out, 1, nullptr, 0, s);
   }
-  // ---- coarse transformer
-  hipLaunchKernelGGL(k_lf_posenc, dim3((unsigned)((2LL * Lp * 64 + 255) / 256)), dim3(256), 0, s, ctx->x3_out, ctx->pe, ctx->tok, L, Lp);
+  // ---- coarse transformer: tok [2][B][Lp][256]; self layers over the 2 B sequences, cross layers as two halves (side 0 from side 1, then side 1 from the UPDATED side 0)
+  const long long tok4 = (long long)N * Lp * 64;
+  hipLaunchKernelGGL(k_lf_posenc, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->x3_out, ctx->pe, ctx->tok, L, Lp, N);
   for (int i = 0; i < 8; ++i) {
     const LfLayer& ly = ctx->coarse[i];
     if ((i & 1) == 0) {
-      lf_encoder(ly, ctx->tok, Lp, L, 2 * Lp, kLfDim, 0, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
-    } else {   // feat0 <- layer(feat0, feat1); then feat1 <- layer(feat1, feat0 UPDATED): two passes, each updating one sequence
-      lf_encoder(ly, ctx->tok, Lp, L, 2 * Lp, kLfDim, 1, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
-      lf_encoder(ly, ctx->tok, Lp, L, 2 * Lp, kLfDim, 1, 2, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 0, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+    } else {   // feat0 <- layer(feat0, feat1); then feat1 <- layer(feat1, feat0 UPDATED): two passes, each updating one side
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, 2, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
     }
   }
-  if (ctx->arith == 1) { const long long n4 = 2LL * Lp * 64; hipLaunchKernelGGL(k_lf_check_finite, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->tok, n4, ctx->ovf); }
-  // ---- coarse matching
+  if (ctx->arith == 1) hipLaunchKernelGGL(k_lf_check_finite, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->tok, tok4, ctx->ovf, (long long)Lp * 64, B);
+  // ---- coarse matching, every kernel over the B pairs at once: sim [B][Lp][Lp]
   const float temp = 0.1f;
-  { const long long n4 = 2LL * Lp * 64; hipLaunchKernelGGL(k_lf_scale, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->tok, ctx->fs, 16.0f, n4); }
-  lf_gemm(ctx->fs, 256, nullptr, 0, 0, ctx->fs + (size_t)Lp * 256, 256, nullptr, ctx->sim, Lp, Lp, Lp, 256, s);
+  hipLaunchKernelGGL(k_lf_scale, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->tok, ctx->fs, 16.0f, tok4);
+  for (int b = 0; b < B; ++b)
+    lf_gemm(ctx->fs + (size_t)b * Lp * 256, 256, nullptr, 0, 0, ctx->fs + (size_t)(B + b) * Lp * 256, 256, nullptr, ctx->sim + (size_t)b * Lp * Lp, Lp, Lp, Lp, 256, s, false, LfLimit(), 1);
   const int nsplit = 32, rows_per = (L + nsplit - 1) / nsplit;
-  hipLaunchKernelGGL(k_lf_row_stats, dim3(L), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum);
-  hipLaunchKernelGGL(k_lf_col_stats, dim3((L + 255) / 256, nsplit), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->cpart_a, ctx->cpart_b, rows_per);
-  hipLaunchKernelGGL(k_lf_col_merge, dim3((L + 255) / 256), dim3(256), 0, s, ctx->cpart_a, ctx->cpart_b, nsplit, L, ctx->cmax, ctx->csum);
-  hipLaunchKernelGGL(k_lf_conf_rowmax, dim3(L), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow);
-  hipLaunchKernelGGL(k_lf_conf_colmax, dim3((L + 255) / 256, nsplit), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->cpart_a, rows_per);
-  hipLaunchKernelGGL(k_lf_max_merge, dim3((L + 255) / 256), dim3(256), 0, s, ctx->cpart_a, nsplit, L, ctx->ccol);
-  hipLaunchKernelGGL(k_lf_mutual, dim3(L), dim3(256), 0, s, ctx->sim, Lp, L, hc, wc, temp, 0.2f, 2, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, ctx->ccol, ctx->jsel, ctx->csel);
-  hipLaunchKernelGGL(k_lf_compact, dim3(1), dim3(1024), 0, s, ctx->jsel, ctx->csel, L, wc, 8, ctx->max_matches, ctx->i_ids, ctx->j_ids, ctx->mconf, ctx->k0c, ctx->k1c, ctx->n_dev);
-  const int M = ctx->max_matches, Mp = ctx->Mp;
+  hipLaunchKernelGGL(k_lf_row_stats, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum);
+  hipLaunchKernelGGL(k_lf_col_stats, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->cpart_a, ctx->cpart_b, rows_per);
+  hipLaunchKernelGGL(k_lf_col_merge, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, ctx->cpart_b, nsplit, L, Lp, ctx->cmax, ctx->csum);
+  hipLaunchKernelGGL(k_lf_conf_rowmax, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow);
+  hipLaunchKernelGGL(k_lf_conf_colmax, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->cpart_a, rows_per);
+  hipLaunchKernelGGL(k_lf_max_merge, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, nsplit, L, Lp, ctx->ccol);
+  hipLaunchKernelGGL(k_lf_mutual, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, hc, wc, temp, 0.2f, 2, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, ctx->ccol, ctx->jsel, ctx->csel);
+  const int M = ctx->max_matches, Mp = B * ctx->Mp;      // M: a pair's segment; Mp: the windows a side of the fine level has room for, all pairs together
+  hipLaunchKernelGGL(k_lf_compact, dim3(B), dim3(1024), 0, s, ctx->jsel, ctx->csel, L, Lp, wc, 8, M, ctx->i_ids, ctx->j_ids, ctx->mconf, ctx->k0c, ctx->k1c, ctx->n_dev);
   if (ctx->fine) {
-    // ---- fine level: windows of both sides as 2 Mp sequences of 25 tokens (side 0 first); cross pairs are (m, Mp + m)
+    // ---- fine level, once over the matches of all pairs (k_lf_concat's list): windows of both sides as 2 Mp sequences of 25 tokens (side 0 first); cross pairs are (m, Mp + m)
     const int R = 2 * Mp * kLfWW;                       // token rows; 2 * Mp * 25 is a multiple of 128 (Mp is)
-    hipLaunchKernelGGL(k_lf_coarse_gather, dim3((unsigned)((2LL * Mp * 64 + 255) / 256)), dim3(256), 0, s, ctx->tok, ctx->tok + (size_t)Lp * 256, ctx->i_ids, ctx->j_ids, ctx->n_dev, Mp, ctx->fc);
+    hipLaunchKernelGGL(k_lf_concat, dim3(B), dim3(256), 0, s, ctx->n_dev, M, ctx->cat, ctx->n_tot);
+    hipLaunchKernelGGL(k_lf_coarse_gather, dim3((unsigned)((2LL * Mp * 64 + 255) / 256)), dim3(256), 0, s, ctx->tok, Lp, B, ctx->i_ids, ctx->j_ids, ctx->cat, M, ctx->n_tot, Mp, ctx->fc);
     // round 5 (developer knob 42, bit 1 = the form of rounds 3-4): the fine level works on the windows of the matches there ARE (the count stays on
     // the device: row tiles, rows and sequences behind it leave at once -- kornia's fine level runs on exactly the M matched windows) and keeps
     // the two sides one behind the other, so that a cross half projects, merges and normalises only the side it updates
     const bool lean = !(gn::g_lf_conv_knob & 2);
     LfLimit lim1, lim25;
-    if (lean) { lim1.n = ctx->n_dev; lim1.mul = 1; lim1.seg = Mp; lim25.n = ctx->n_dev; lim25.mul = kLfWW; lim25.seg = Mp * kLfWW; }
+    if (lean) { lim1.n = ctx->n_tot; lim1.mul = 1; lim1.seg = Mp; lim25.n = ctx->n_tot; lim25.mul = kLfWW; lim25.seg = Mp * kLfWW; }
     lf_gemm(ctx->fc, 256, nullptr, 0, 0, ctx->down_proj.w, 256, ctx->down_proj.b, ctx->fwin, 128, 2 * Mp, 128, 256, s, false, lim1);
-    hipLaunchKernelGGL(k_lf_fine_gather, dim3((unsigned)((2LL * Mp * kLfWW * 64 + 255) / 256)), dim3(256), 0, s, ctx->x1_out, h2, w2, wc, ctx->i_ids, ctx->j_ids, ctx->n_dev, Mp, ctx->fwin, ctx->frows);
+    hipLaunchKernelGGL(k_lf_fine_gather, dim3((unsigned)((2LL * Mp * kLfWW * 64 + 255) / 256)), dim3(256), 0, s, ctx->x1_out, h2, w2, wc, ctx->i_ids, ctx->j_ids, ctx->cat, M, B, ctx->n_tot, Mp, ctx->fwin, ctx->frows);
     lf_gemm(ctx->frows, 256, nullptr, 0, 0, ctx->merge_feat.w, 256, ctx->merge_feat.b, ctx->ftok, 128, R, 128, 256, s, false, lim25);
     if (lean) {
       // ftok [2][Mp][25][128] as it is: sequence q of side 0 pairs with q + Mp
@@ -1433,8 +1502,9 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
       LF_HIP(hipMemcpy2DAsync(ctx->ftok + (size_t)side * Mp * kLfWW * 128, (size_t)kLfWW * 128 * sizeof(float), ft + (size_t)side * kLfWW * 128, 2 * (size_t)kLfWW * 128 * sizeof(float),
                               (size_t)kLfWW * 128 * sizeof(float), Mp, hipMemcpyDeviceToDevice, s));
     }
-    hipLaunchKernelGGL(k_lf_fine_match, dim3((M + 3) / 4), dim3(256), 0, s, ctx->ftok, ctx->ftok + (size_t)Mp * kLfWW * 128, ctx->n_dev, ctx->k1c, ctx->fc);
-    if (ctx->arith == 1) { const long long n4 = (long long)M * 2 / 4; if (n4 > 0) hipLaunchKernelGGL(k_lf_check_finite, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ctx->fc, n4, ctx->ovf); }
+    // (the refined points go into fc, dead since down_proj read it: [B][M][2]; in split arithmetic a result that is not finite raises its pair's guard word)
+    hipLaunchKernelGGL(k_lf_fine_match, dim3((unsigned)(((long long)B * M + 3) / 4)), dim3(256), 0, s, ctx->ftok, ctx->ftok + (size_t)Mp * kLfWW * 128, ctx->n_tot, ctx->cat, M, ctx->k1c, ctx->fc,
+                       ctx->arith == 1 ? ctx->ovf : (unsigned int*)nullptr);
   }
   return GN_OK;
 }
@@ -1451,21 +1521,14 @@ int gn_loftr_set_graph(gn_loftr* ctx, int enable) {
   return GN_OK;
 }
 
-int gn_loftr_match(gn_loftr* ctx, const float* image0, const float* image1, float* kpts0, float* kpts1, float* conf, int32_t* ij, int32_t* n_host, void* stream) {
-  if (!ctx || !image0 || !image1 || !kpts0 || !kpts1 || !conf || !n_host) return lf_fail(ctx, GN_ERR_ARG, "null pointer passed to gn_loftr_match");
-  LF_HIP(hipSetDevice(ctx->device));
-  if (gn_loftr_missing_tensors(ctx) != 0) return lf_fail(ctx, GN_ERR_WEIGHTS, "LoFTR weights not fully loaded");
-  if (!ctx->finalised) { const int rc = lf_finalise(ctx); if (rc != GN_OK) return rc; }
-  hipStream_t s = (hipStream_t)stream;
-  const int H = ctx->H, W = ctx->W, M = ctx->max_matches;
-  LF_HIP(hipMemcpyAsync(ctx->img, image0, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, s));
-  LF_HIP(hipMemcpyAsync(ctx->img + (size_t)H * W, image1, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, s));
-  bool ran = false;
-  if (ctx->use_graph) {
-    // every pointer inside the forward belongs to the context and the shapes are fixed at creation: capture the ~190 launches ONCE on an
+// the forward for ctx->B pairs already in ctx->img, as a replay of the (arithmetic, B) graph or as plain launches
+static int lf_run(gn_loftr* ctx, hipStream_t s, bool allow_graph) {
+  if (ctx->use_graph && allow_graph) {
+    // every pointer inside the forward belongs to the context and the shapes are fixed by (H, W, B): capture the ~190 launches ONCE per (arithmetic, B) on an
     // internal stream and replay them as one graph launch (the host was the slower side between the small kernels of the fine level)
-    hipGraphExec_t& gexec = ctx->graph_exec[ctx->arith];
-    if (!gexec && !ctx->graph_failed[ctx->arith]) {
+    const int key = 2 * ctx->B + ctx->arith;
+    hipGraphExec_t& gexec = ctx->graph_exec[key];
+    if (!gexec && !ctx->graph_failed[key]) {
       hipGraph_t graph = nullptr;
       bool ok = true;
       if (!ctx->cap_stream) ok = hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) == hipSuccess;
@@ -1476,54 +1539,112 @@ int gn_loftr_match(gn_loftr* ctx, const float* image0, const float* image1, floa
       }
       ok = ok && hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0) == hipSuccess;
       if (graph) hipGraphDestroy(graph);
-      if (!ok) { ctx->graph_failed[ctx->arith] = true; gexec = nullptr; (void)hipGetLastError(); }
+      if (!ok) { ctx->graph_failed[key] = true; gexec = nullptr; (void)hipGetLastError(); }
     }
-    if (gexec) { LF_HIP(hipGraphLaunch(gexec, s)); ran = true; }
+    if (gexec) { LF_HIP(hipGraphLaunch(gexec, s)); return GN_OK; }
   }
-  if (!ran) { const int rc = lf_forward(ctx, s); if (rc != GN_OK) return rc; }
-  if (ctx->arith == 1) {   // split-fp16 arithmetic: a value outside fp16's range anywhere in the forward -> repeat it on the exact-f32 kernels
-    LF_HIP(hipMemcpyAsync(ctx->n_host + 1, ctx->ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    LF_HIP(hipStreamSynchronize(s));
-    if (ctx->n_host[1] != 0) {
-      ++ctx->ovf_trips;
-      ctx->arith = 0;
-      const int rc = lf_forward(ctx, s);
-      ctx->arith = 1;
-      if (rc != GN_OK) return rc;
-    }
-  }
-  LF_HIP(hipMemcpyAsync(kpts0, ctx->k0c, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  LF_HIP(hipMemcpyAsync(conf, ctx->mconf, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, s));
-  LF_HIP(hipMemcpyAsync(kpts1, ctx->fine ? ctx->fc : ctx->k1c, (size_t)M * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return lf_forward(ctx, s);
+}
+
+// the result segments [r0, r0 + n) of the context -> the caller's segments [u0, u0 + n)
+static int lf_copy_out(gn_loftr* ctx, int r0, int u0, int n, float* kpts0, float* kpts1, float* conf, int32_t* ij, int32_t* n_match_dev, hipStream_t s) {
+  const size_t M = (size_t)ctx->max_matches, ro = r0 * M, uo = u0 * M, cnt = n * M;
+  LF_HIP(hipMemcpyAsync(kpts0 + 2 * uo, ctx->k0c + 2 * ro, cnt * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  LF_HIP(hipMemcpyAsync(conf + uo, ctx->mconf + ro, cnt * sizeof(float), hipMemcpyDeviceToDevice, s));
+  LF_HIP(hipMemcpyAsync(kpts1 + 2 * uo, (ctx->fine ? ctx->fc : ctx->k1c) + 2 * ro, cnt * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (ij) {
-    LF_HIP(hipMemcpy2DAsync(ij, 2 * sizeof(int), ctx->i_ids, sizeof(int), sizeof(int), M, hipMemcpyDeviceToDevice, s));
-    LF_HIP(hipMemcpy2DAsync(ij + 1, 2 * sizeof(int), ctx->j_ids, sizeof(int), sizeof(int), M, hipMemcpyDeviceToDevice, s));
+    LF_HIP(hipMemcpy2DAsync(ij + 2 * uo, 2 * sizeof(int), ctx->i_ids + ro, sizeof(int), sizeof(int), cnt, hipMemcpyDeviceToDevice, s));
+    LF_HIP(hipMemcpy2DAsync(ij + 2 * uo + 1, 2 * sizeof(int), ctx->j_ids + ro, sizeof(int), sizeof(int), cnt, hipMemcpyDeviceToDevice, s));
   }
-  LF_HIP(hipMemcpyAsync(ctx->n_host, ctx->n_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-  LF_HIP(hipStreamSynchronize(s));
-  *n_host = ctx->n_host[0];
+  if (n_match_dev) LF_HIP(hipMemcpyAsync(n_match_dev + u0, ctx->n_dev + r0, n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  return GN_OK;
+}
+
+int gn_loftr_cap(const gn_loftr* ctx) { return ctx ? ctx->max_matches : GN_ERR_ARG; }
+
+int gn_loftr_match(gn_loftr* ctx, const float* image0, const float* image1, float* kpts0, float* kpts1, float* conf, int32_t* ij, int32_t* n_host, void* stream) {
+  if (!n_host) return lf_fail(ctx, GN_ERR_ARG, "null pointer passed to gn_loftr_match");
+  return gn_loftr_match_batch(ctx, 1, image0, image1, kpts0, kpts1, conf, ij, nullptr, n_host, stream);
+}
+
+int gn_loftr_match_batch(gn_loftr* ctx, int B, const float* image0, const float* image1, float* kpts0, float* kpts1, float* conf, int32_t* ij, int32_t* n_match_dev, int32_t* n_host,
+                         void* stream) {
+  if (!ctx || !image0 || !image1 || !kpts0 || !kpts1 || !conf) return lf_fail(ctx, GN_ERR_ARG, "null pointer passed to gn_loftr_match");
+  if (B < 1 || B > ctx->max_pairs) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_match_batch: B = " + std::to_string(B) + " outside 1 .. max_pairs = " + std::to_string(ctx->max_pairs));
+  LF_HIP(hipSetDevice(ctx->device));
+  if (gn_loftr_missing_tensors(ctx) != 0) return lf_fail(ctx, GN_ERR_WEIGHTS, "LoFTR weights not fully loaded");
+  if (!ctx->finalised) { const int rc = lf_finalise(ctx); if (rc != GN_OK) return rc; }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t HW = (size_t)ctx->H * ctx->W;
+  ctx->B = B;
+  LF_HIP(hipMemcpyAsync(ctx->img, image0, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+  LF_HIP(hipMemcpyAsync(ctx->img + B * HW, image1, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+  int rc = lf_run(ctx, s, true);
+  if (rc != GN_OK) return rc;
+  int* const cnt_host = ctx->n_host;                 // pinned: [max_pairs] counts, then [max_pairs] guard words
+  unsigned int* const ovf_host = reinterpret_cast<unsigned int*>(ctx->n_host + ctx->max_pairs);
+  std::vector<int> redo;
+  if (ctx->arith == 1) {   // split-fp16 arithmetic: a value outside fp16's range anywhere in a pair's forward -> that pair again on the exact-f32 kernels
+    // (the counts come along: with every pair in range this is the call's one synchronisation)
+    LF_HIP(hipMemcpyAsync(ovf_host, ctx->ovf, B * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    LF_HIP(hipMemcpyAsync(cnt_host, ctx->n_dev, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    LF_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) if (ovf_host[b] != 0) redo.push_back(b);
+  }
+  const bool counts_read = ctx->arith == 1 && redo.empty();
+  if ((int)redo.size() < B) {
+    rc = lf_copy_out(ctx, 0, 0, B, kpts0, kpts1, conf, ij, n_match_dev, s);
+    if (rc != GN_OK) return rc;
+    if (n_host && ctx->arith == 0) LF_HIP(hipMemcpyAsync(cnt_host, ctx->n_dev, B * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  if (!redo.empty()) {
+    // the flagged pairs as a smaller batch of their own (a pair's exact result does not depend on the batch it runs in); their segments and
+    // counts replace the split ones, every other pair keeps its split-arithmetic bits
+    const int Br = (int)redo.size();
+    ctx->ovf_trips += Br;
+    for (int r = 0; r < Br; ++r) {
+      LF_HIP(hipMemcpyAsync(ctx->img + r * HW, image0 + redo[r] * HW, HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+      LF_HIP(hipMemcpyAsync(ctx->img + (Br + r) * HW, image1 + redo[r] * HW, HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    ctx->B = Br; ctx->arith = 0;
+    rc = lf_run(ctx, s, false);
+    ctx->arith = 1;
+    if (rc != GN_OK) return rc;
+    for (int r = 0; r < Br; ++r) {
+      rc = lf_copy_out(ctx, r, redo[r], 1, kpts0, kpts1, conf, ij, n_match_dev, s);
+      if (rc != GN_OK) return rc;
+      if (n_host) LF_HIP(hipMemcpyAsync(cnt_host + redo[r], ctx->n_dev + r, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (n_host) {
+    if (!counts_read) LF_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < B; ++b) n_host[b] = cnt_host[b];
+  }
   LF_HIP(hipGetLastError());
   return GN_OK;
 }
 
 // test hook: copy an internal tensor to HOST memory after synchronising.  Names: "x0" (stem, [2][H/2][W/2][128]), "x1" (layer1 output),
 // "x2" (224-channel rows), "x3", "x3_out", "x1_out", "tok" ([2][Lp][256] coarse tokens after the transformer), "sim", "conf_row" / "conf_col" maxima.
+// After a call with B pairs every one of them is the batched buffer: [2][B]... for the maps and tokens, [B]... for the matching stage, [2][B Mp]... for "ftok".
 int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream) {
   if (!ctx || !name || !host_out) return GN_ERR_ARG;
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GN_ERR_HIP;
-  const size_t h2 = ctx->H / 2, w2 = ctx->W / 2, h4 = ctx->H / 4, w4 = ctx->W / 4, hc = ctx->hc, wc = ctx->wc, Lp = ctx->Lp;
+  const size_t h2 = ctx->H / 2, w2 = ctx->W / 2, h4 = ctx->H / 4, w4 = ctx->W / 4, hc = ctx->hc, wc = ctx->wc, Lp = ctx->Lp, B = (size_t)ctx->B;   // (B: pairs of the last forward)
   const std::string n = name;
   const float* p = nullptr; size_t count = 0;
-  if (n == "x1") { p = ctx->x0; count = 2 * h2 * w2 * 128; }
-  else if (n == "x2") { p = ctx->x2; count = 2 * h4 * w4 * 224; }
-  else if (n == "x3") { p = ctx->x3; count = 2 * hc * wc * 256; }
-  else if (n == "x3_out") { p = ctx->x3_out; count = 2 * hc * wc * 256; }
-  else if (n == "x1_out") { p = ctx->x1_out; count = 2 * h2 * w2 * 128; }
-  else if (n == "tok") { p = ctx->tok; count = 2 * Lp * 256; }
-  else if (n == "sim") { p = ctx->sim; count = Lp * Lp; }
-  else if (n == "crow") { p = ctx->crow; count = Lp; }
-  else if (n == "ccol") { p = ctx->ccol; count = Lp; }
-  else if (n == "ftok") { p = ctx->ftok; count = ctx->fine ? 2 * (size_t)ctx->Mp * kLfWW * 128 : 0; }
+  if (n == "x1") { p = ctx->x0; count = B * 2 * h2 * w2 * 128; }
+  else if (n == "x2") { p = ctx->x2; count = B * 2 * h4 * w4 * 224; }
+  else if (n == "x3") { p = ctx->x3; count = B * 2 * hc * wc * 256; }
+  else if (n == "x3_out") { p = ctx->x3_out; count = B * 2 * hc * wc * 256; }
+  else if (n == "x1_out") { p = ctx->x1_out; count = B * 2 * h2 * w2 * 128; }
+  else if (n == "tok") { p = ctx->tok; count = B * 2 * Lp * 256; }
+  else if (n == "sim") { p = ctx->sim; count = B * Lp * Lp; }
+  else if (n == "crow") { p = ctx->crow; count = B * Lp; }
+  else if (n == "ccol") { p = ctx->ccol; count = B * Lp; }
+  else if (n == "ovf") { p = reinterpret_cast<const float*>(ctx->ovf); count = B; }              // the guard words of the last forward, as raw 32-bit words
+  else if (n == "ovf_trips") { if (max_bytes < (int64_t)sizeof(float)) return GN_ERR_ARG; *reinterpret_cast<float*>(host_out) = (float)ctx->ovf_trips; return 1; }   // pairs repeated on the exact kernels so far
+  else if (n == "ftok") { p = ctx->ftok; count = ctx->fine ? B * 2 * (size_t)ctx->Mp * kLfWW * 128 : 0; }
   else return GN_ERR_NAME;
   count = std::min<size_t>(count, (size_t)max_bytes / sizeof(float));
   if (hipMemcpy(host_out, p, count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return GN_ERR_HIP;

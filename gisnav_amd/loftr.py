@@ -15,9 +15,11 @@ from . import _lib
 
 
 class LoFTR:
-    """`LoFTR(state_dict=...).to("cuda:0").eval()`; `out = m({"image0": img0, "image1": img1})` with (1, 1, H, W) or (H, W) float images in
-    [0, 1] of equal size (H, W multiples of 8) -> {"keypoints0" (M, 2), "keypoints1" (M, 2), "confidence" (M,), "batch_indexes" (M,)} on the
-    input device, matches in ascending coarse cell of image0.  `fine=False` stops after the coarse level (keypoints on the 1/8 grid)."""
+    """`LoFTR(state_dict=...).to("cuda:0").eval()`; `out = m({"image0": img0, "image1": img1})` with (B, 1, H, W), (B, H, W) or (H, W) float
+    images in [0, 1] of equal size (H, W multiples of 8) -> {"keypoints0" (M, 2), "keypoints1" (M, 2), "confidence" (M,), "batch_indexes" (M,)}
+    on the input device: the matches of all B pairs in ascending (pair, coarse cell of image0) order, `batch_indexes` the pair of each (kornia's
+    layout).  The B pairs go through ONE call of the library (gn_loftr_match_batch); a pair's rows do not depend on the batch it is in, bit for
+    bit.  `fine=False` stops after the coarse level (keypoints on the 1/8 grid)."""
 
     def __init__(self, pretrained: Optional[str] = None, *, state_dict: Optional[Dict] = None, max_matches: Optional[int] = None, fine: bool = True, graph: bool = True,
                  arithmetic: str = "exact_f32"):
@@ -26,7 +28,7 @@ class LoFTR:
         # max_matches None = every mutual match (at most one per coarse cell of image0), as kornia returns them; a number caps the list (first in raster order)
         self._sd, self._max, self._fine, self._graph = state_dict, (None if max_matches is None else int(max_matches)), bool(fine), bool(graph)
         self._arith = {"exact_f32": 0, "split_fp16": 1}[arithmetic]   # split_fp16: f32-accurate 2-term fp16 operands (gn_loftr_set_arithmetic)
-        self._ctx, self._shape, self._device = None, None, None
+        self._ctx, self._shape, self._device, self._pairs = None, None, None, 0
         self.lib = None
 
     @staticmethod
@@ -73,17 +75,19 @@ class LoFTR:
         L = (H // 8) * (W // 8)
         return min(L if self._max is None else min(self._max, L), 131072)     # (gn_loftr_create's own bound)
 
-    def _ensure(self, H: int, W: int) -> None:
-        if self._ctx is not None and self._shape == (H, W):
+    def _ensure(self, H: int, W: int, B: int = 1) -> None:
+        """One context per image shape, sized for the largest batch seen: re-created only when the shape changes or B exceeds its max_pairs."""
+        if self._ctx is not None and self._shape == (H, W) and B <= self._pairs:
             return
         if self._ctx is not None:
             self.lib.gn_loftr_destroy(self._ctx)
             self._ctx = None
         ctx = C.c_void_p()
-        rc = self.lib.gn_loftr_create(self._device.index or 0, H, W, self._cap(H, W), int(self._fine), C.byref(ctx))
+        pairs = max(B, self._pairs if self._shape == (H, W) else 1)
+        rc = self.lib.gn_loftr_create_batch(self._device.index or 0, pairs, H, W, self._cap(H, W), int(self._fine), C.byref(ctx))
         if rc < 0:
-            raise _lib.GnError(f"gn_loftr_create failed ({rc}): {self.lib.gn_loftr_last_error(None).decode()}")
-        self._ctx, self._shape = ctx, (H, W)
+            raise _lib.GnError(f"gn_loftr_create_batch failed ({rc}): {self.lib.gn_loftr_last_error(None).decode()}")
+        self._ctx, self._shape, self._pairs = ctx, (H, W), pairs
         self.lib.gn_loftr_set_graph(ctx, int(self._graph))
         self.lib.gn_loftr_set_arithmetic(ctx, self._arith)
         for name, arr in self._sd.items():
@@ -100,31 +104,64 @@ class LoFTR:
         if missing:
             raise _lib.GnError(f"{missing} required LoFTR tensors missing from the state dict")
 
+    @staticmethod
+    def _batch_shape(i0, i1):
+        """(B, H, W) of the two inputs, which must agree in all three -- checked on the shapes alone, before anything touches the device."""
+        def one(t, name):
+            sh = tuple(int(v) for v in t.shape)
+            if len(sh) == 2:
+                return (1,) + sh
+            if len(sh) == 3:
+                return sh
+            if len(sh) == 4 and sh[1] == 1:
+                return (sh[0], sh[2], sh[3])
+            raise _lib.GnError(f"{name}: expected (B, 1, H, W), (B, H, W) or (H, W), got {sh}")
+        s0, s1 = one(i0, "image0"), one(i1, "image1")
+        if s0 != s1:
+            raise _lib.GnError(f"image0 {s0} and image1 {s1} must have one batch size and one image size (the published model pads / masks otherwise; not built)")
+        if s0[0] < 1:
+            raise _lib.GnError("empty batch")
+        return s0
+
     @torch.inference_mode()
-    def __call__(self, data: Dict[str, torch.Tensor], with_ids: bool = False) -> Dict[str, torch.Tensor]:
+    def match_segments(self, image0, image1, host_counts: bool = True):
+        """The library's own output layout for B pairs (one gn_loftr_match_batch): {"keypoints0" / "keypoints1" (B, cap, 2), "confidence" (B, cap),
+        "ij" (B, cap, 2) int32, "n" (B,) int32} on the matcher's device -- pair b's matches are the first n[b] rows of its segment, which is what
+        gn_gather_points / gn_pnp_ransac take -- and "n_host" (list of B ints, or None with host_counts=False: in exact-f32 arithmetic the call
+        then does not synchronise the stream)."""
+        B, H, W = self._batch_shape(image0, image1)
         if self._device is None:
             raise _lib.GnError("call .to(device) first")
-        i0, i1 = data["image0"], data["image1"]
-        if i0.shape != i1.shape:
-            raise _lib.GnError("image0 and image1 must have one size (the published model pads / masks otherwise; not built)")
-        in_dev = i0.device
-        f = lambda t: t.to(device=self._device, dtype=torch.float32).reshape(t.shape[-2], t.shape[-1]).contiguous()  # noqa: E731
-        a, b = f(i0), f(i1)
-        H, W = int(a.shape[0]), int(a.shape[1])
-        self._ensure(H, W)
+        f = lambda t: t.to(device=self._device, dtype=torch.float32).reshape(B, H, W).contiguous()  # noqa: E731
+        a, b = f(image0), f(image1)
+        self._ensure(H, W, B)
         M = self._cap(H, W)
-        k0 = torch.empty((M, 2), dtype=torch.float32, device=self._device); k1 = torch.empty_like(k0)
-        conf = torch.empty((M,), dtype=torch.float32, device=self._device)
-        ij = torch.empty((M, 2), dtype=torch.int32, device=self._device)
-        n = C.c_int32(0)
+        k0 = torch.empty((B, M, 2), dtype=torch.float32, device=self._device); k1 = torch.empty_like(k0)
+        conf = torch.empty((B, M), dtype=torch.float32, device=self._device)
+        ij = torch.empty((B, M, 2), dtype=torch.int32, device=self._device)
+        n_dev = torch.empty((B,), dtype=torch.int32, device=self._device)
+        n = (C.c_int32 * B)() if host_counts else None
         stream = C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        self._check(self.lib.gn_loftr_match(self._ctx, p(a), p(b), p(k0), p(k1), p(conf), p(ij), C.byref(n), stream), "gn_loftr_match")
-        m = int(n.value)
-        out = {"keypoints0": k0[:m].to(in_dev), "keypoints1": k1[:m].to(in_dev), "confidence": conf[:m].to(in_dev),
-               "batch_indexes": torch.zeros(m, dtype=torch.int64, device=in_dev)}
+        self._check(self.lib.gn_loftr_match_batch(self._ctx, B, p(a), p(b), p(k0), p(k1), p(conf), p(ij), p(n_dev), n, stream), "gn_loftr_match_batch")
+        return {"keypoints0": k0, "keypoints1": k1, "confidence": conf, "ij": ij, "n": n_dev, "n_host": [int(v) for v in n] if host_counts else None}
+
+    @torch.inference_mode()
+    def __call__(self, data: Dict[str, torch.Tensor], with_ids: bool = False) -> Dict[str, torch.Tensor]:
+        i0, i1 = data["image0"], data["image1"]
+        self._batch_shape(i0, i1)                      # (refused on the shapes alone, before any device call)
+        if self._device is None:
+            raise _lib.GnError("call .to(device) first")
+        in_dev = i0.device
+        seg = self.match_segments(i0, i1)
+        ns = seg["n_host"]
+        cat = lambda t: (t[0, :ns[0]] if len(ns) == 1 else torch.cat([t[b, :m] for b, m in enumerate(ns)], 0)).to(in_dev)  # noqa: E731
+        out = {"keypoints0": cat(seg["keypoints0"]), "keypoints1": cat(seg["keypoints1"]), "confidence": cat(seg["confidence"]),
+               "batch_indexes": torch.zeros(ns[0], dtype=torch.int64, device=in_dev) if len(ns) == 1 else
+               torch.repeat_interleave(torch.arange(len(ns), dtype=torch.int64, device=self._device), seg["n"].long(), output_size=sum(ns)).to(in_dev)}
         if with_ids:
-            out["i_ids"], out["j_ids"] = ij[:m, 0].to(in_dev).long(), ij[:m, 1].to(in_dev).long()
+            ij = cat(seg["ij"])
+            out["i_ids"], out["j_ids"] = ij[:, 0].long(), ij[:, 1].long()
         return out
 
     forward = __call__
@@ -168,3 +205,48 @@ def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Te
     if return_covariance:
         return R[0].cpu().numpy(), t[0].cpu().numpy(), n, (res[4][0].cpu().numpy() if bool(res[6].cpu()[0]) else None)
     return R[0].cpu().numpy(), t[0].cpu().numpy(), n
+
+
+def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_matches: int = 15, conf_threshold: float = 0.0, return_covariance: bool = False):
+    """`loftr_pose` for B pairs at once: frames01 / tiles01 (B, H, W) (or sequences of B (H, W) images), dems (B, H, W) uint8 (or a sequence of
+    B) or None.  ONE batched match (the counts stay on the device), the confidence filter as a stable per-pair compaction on the device, ONE
+    gn_gather_points, ONE gn_pnp_ransac over the B pairs and ONE read-back.  Returns a list of B entries, each what `loftr_pose` returns for that
+    pair (None below `min_matches` / without a model).  The engine must have been created with max_batch >= B; it is grown to the matcher's
+    per-pair cap when that exceeds its keypoint capacity."""
+    stack = lambda x: x if isinstance(x, torch.Tensor) else torch.stack([torch.as_tensor(v) for v in x])  # noqa: E731
+    frames01, tiles01 = stack(frames01), stack(tiles01)
+    B, H, W = matcher._batch_shape(frames01, tiles01)
+    if B > engine.max_batch:
+        raise _lib.GnError(f"{B} pairs exceed the engine's max_batch {engine.max_batch}")
+    seg = matcher.match_segments(frames01, tiles01, host_counts=False)
+    dev = engine.device
+    k0, k1, conf, n = (seg[k].to(dev) for k in ("keypoints0", "keypoints1", "confidence", "n"))
+    cap = int(k0.shape[1])
+    # stable per-pair compaction of the rows that pass the confidence filter (plumbing): kept rows first, in their order
+    keep = (torch.arange(cap, device=dev)[None, :] < n[:, None]) & (conf > conf_threshold)
+    order = torch.argsort((~keep).to(torch.uint8), dim=1, stable=True)
+    cnt = keep.sum(1).to(torch.int32)
+    g = lambda k: torch.cat([torch.gather(k, 1, order[:, :, None].expand(B, cap, 2)), torch.zeros((B, cap, 2), dtype=torch.float32, device=dev)], 2).contiguous()  # noqa: E731  GN_KPT_XYSA rows
+    if cap > engine.kmax:
+        engine.grow(((cap + 1023) // 1024) * 1024)
+    idx = torch.arange(engine.kmax, dtype=torch.int64, device=dev).repeat_interleave(2).reshape(1, engine.kmax, 2).repeat(B, 1, 1)
+    idx = torch.where(torch.arange(engine.kmax, device=dev)[None, :, None] < cnt[:, None, None], idx, torch.zeros_like(idx)).contiguous()
+    d = None
+    if dems is not None:
+        d = dems.to(dev) if isinstance(dems, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.stack([np.asarray(v) for v in dems]), np.uint8), device=dev)
+        d = d.to(torch.uint8).contiguous()
+    mkp, obj = engine.gather_points(g(k0), g(k1), idx, cnt, d, _lib.GN_KPT_XYSA)
+    res = engine.pnp_ransac(obj, mkp, cnt, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance)
+    back = [res[0], res[1], res[3], cnt] + ([res[4], res[6]] if return_covariance else [])
+    host = engine.to_host(*back)
+    R, t, ok, cn = host[:4]
+    out = []
+    for b in range(B):
+        nb = int(cn[b])
+        if nb < min_matches or not bool(ok[b]):
+            out.append(None)
+        elif return_covariance:
+            out.append((np.array(R[b]), np.array(t[b]), nb, np.array(host[4][b]) if bool(host[5][b]) else None))
+        else:
+            out.append((np.array(R[b]), np.array(t[b]), nb))
+    return out

@@ -475,15 +475,32 @@ int gn_loftr_missing_tensors(const gn_loftr* ctx);
  * the call synchronises `stream` once to return it. */
 int gn_loftr_match(gn_loftr* ctx, const float* image0, const float* image1, float* kpts0, float* kpts1, float* conf, int32_t* ij,
                    int32_t* n_host, void* stream);
+/* The same matcher on B pairs per call.  gn_loftr_create_batch sizes the context for up to max_pairs pairs of one image shape (device memory
+ * grows with max_pairs: one similarity matrix and one set of activations per pair; creation fails with GN_ERR_HIP when it does not fit, and
+ * with GN_ERR_ARG when max_pairs x the padded per-pair match slots exceed 131072); gn_loftr_create is the max_pairs = 1 case and
+ * gn_loftr_match the B = 1 call of the same code.  gn_loftr_cap: the per-pair segment length cap = min(max_matches, H/8 * W/8, 131072).
+ * image0 / image1: DEVICE f32 [B][H][W], 1 <= B <= max_pairs (GN_ERR_ARG otherwise).  Outputs (device) in per-pair segments of cap rows: kpts0 /
+ * kpts1 [B][cap][2], conf [B][cap], ij [B][cap][2] (may be NULL); pair b's matches are the first n[b] rows of its segment, in ascending cell of
+ * image0 -- the layout gn_gather_points / gn_pnp_ransac take with kstride = cap and n_pts = n_match_dev.  n_match_dev (DEVICE [B], may be NULL)
+ * and n_host (HOST [B], may be NULL) receive the counts.  A pair's outputs do not depend on B, on its place in the batch or on the other pairs,
+ * bit for bit.  Synchronisation: in exact-f32 arithmetic without n_host the call does not synchronise `stream` (the counts stay on the device
+ * for the solver); with n_host it synchronises once for the whole batch; split-fp16 arithmetic always synchronises once to read the per-pair
+ * range guards (and once more only when a pair had to be repeated).  One hipGraph is captured lazily per (arithmetic, B). */
+int gn_loftr_create_batch(int device, int max_pairs, int H, int W, int max_matches, int fine, gn_loftr** out);
+int gn_loftr_match_batch(gn_loftr* ctx, int B, const float* image0, const float* image1, float* kpts0, float* kpts1, float* conf, int32_t* ij,
+                         int32_t* n_match_dev, int32_t* n_host, void* stream);
+int gn_loftr_cap(const gn_loftr* ctx);
 /* 1 (default): the forward's ~190 dependent launches are captured once into a hipGraph (all buffers belong to the context, the match count
  * stays on the device) and replayed with one graph launch per call; 0: plain stream launches (same kernels, same results). */
 int gn_loftr_set_graph(gn_loftr* ctx, int enable);
 /* Arithmetic of the convolutions and linear layers: 0 (default) exact f32 (v_mfma_f32_32x32x2_f32) -- what configs[1] names; 1 split fp16: every
  * f32 operand as two fp16 terms, three fp16 MFMA products, f32 accumulation (the matcher's f16x2 scheme: f32-accurate, 5 x the matrix-pipe
- * rate).  Mode 1 guards fp16's range: a forward in which any activation left it is repeated on the exact kernels before the call returns. */
+ * rate).  Mode 1 guards fp16's range PER PAIR: the pairs of a call in whose forward any activation left it are repeated on the exact kernels, as a
+ * smaller batch, before the call returns; the other pairs keep their split-arithmetic results. */
 int gn_loftr_set_arithmetic(gn_loftr* ctx, int mode);
 /* test hook: internal tensor -> HOST after synchronising.  Names: "x1" "x2" "x3" "x3_out" "x1_out" (NHWC, 196 channels padded to 224),
- * "tok" ([2][Lp][256] coarse features after the transformer), "sim", "crow", "ccol", "ftok".  Returns the element count or a negative status. */
+ * "tok" ([2][Lp][256] coarse features after the transformer), "sim", "crow", "ccol", "ftok".  Returns the element count or a negative status.
+ * After a call with B pairs the buffers are side-major over the pairs: [2][B]... maps and tokens, [B]... "sim" / "crow" / "ccol". */
 int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream);
 
 /* ---- test / profiling hooks (not part of the drop-in surface) --------------------------- */
