@@ -768,52 +768,135 @@ __global__ __launch_bounds__(256) void k_lf_col_merge(const float* pmax, const f
   for (int sp = 0; sp < nsplit; ++sp) { const float pm = pmax[(long long)sp * L + j]; if (pm > -INFINITY) s += psum[(long long)sp * L + j] * expf(pm - m); }
   cmax[j] = m; csum[j] = s;
 }
-// max of conf over j per row (block per row) and over i per column (thread per column, split + merge)
-__global__ __launch_bounds__(256) void k_lf_conf_rowmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* crow) {
-  __shared__ float red[4];
+// max of conf over j per row (block per row) and over i per column (thread per column, split + merge).
+// CERT (gn_loftr_set_certify): every maximum also keeps its RUNNER-UP, multiplicity counted -- second = max(second, min(best, c)), partials merged as
+// max(second_a, second_b, min(best_a, best_b)), the match head's idiom (gn_match_head.hip) -- into crow2 / ccol2.  Confidences are >= 0, so an empty
+// partial is (0, 0).  The maxima themselves are the same bits with and without CERT (a maximum does not depend on what else is tracked).
+template <bool CERT>
+__global__ __launch_bounds__(256) void k_lf_conf_rowmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* crow, float* crow2) {
+  __shared__ float red[CERT ? 8 : 4];
   const int i = blockIdx.x, tid = threadIdx.x;
   const long long po = (long long)blockIdx.y * ld;
   const float* row = sim + (po + i) * ld;
   rmax += po; rsum += po; cmax += po; csum += po; crow += po;
   const float rm = rmax[i], rs = rsum[i];
-  float m = 0.f;
+  float m = 0.f, m2 = 0.f;
   for (int j0 = tid; j0 < L; j0 += 256 * kLfU) {
     float x[kLfU], cm[kLfU], cs[kLfU];
 #pragma unroll
     for (int u = 0; u < kLfU; ++u) { const int j = j0 + 256 * u; const bool in = j < L; x[u] = in ? row[j] : 0.f; cm[u] = in ? cmax[j] : 0.f; cs[u] = in ? csum[j] : 1.f; }
 #pragma unroll
-    for (int u = 0; u < kLfU; ++u) if (j0 + 256 * u < L) m = fmaxf(m, lf_conf(x[u] / temp, rm, rs, cm[u], cs[u]));
+    for (int u = 0; u < kLfU; ++u) if (j0 + 256 * u < L) {
+      const float c = lf_conf(x[u] / temp, rm, rs, cm[u], cs[u]);
+      if (CERT) m2 = fmaxf(m2, fminf(m, c));
+      m = fmaxf(m, c);
+    }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((tid & 63) == 0) red[tid >> 6] = m;
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o);
+    if (CERT) { const float o2 = __shfl_xor(m2, o); m2 = fmaxf(fmaxf(m2, o2), fminf(m, om)); }
+    m = fmaxf(m, om);
+  }
+  if ((tid & 63) == 0) { red[tid >> 6] = m; if (CERT) red[4 + (tid >> 6)] = m2; }
   __syncthreads();
-  if (tid == 0) crow[i] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  if (tid == 0) {
+    crow[i] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (CERT) {
+      float b = red[0], s2 = red[4];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) { s2 = fmaxf(fmaxf(s2, red[4 + w]), fminf(b, red[w])); b = fmaxf(b, red[w]); }
+      crow2[po + i] = s2;
+    }
+  }
 }
-__global__ __launch_bounds__(256) void k_lf_conf_colmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* part, int rows_per) {
+template <bool CERT>
+__global__ __launch_bounds__(256) void k_lf_conf_colmax(const float* sim, int ld, int L, float temp, const float* rmax, const float* rsum, const float* cmax, const float* csum, float* part, float* part2, int rows_per) {
   const int j = blockIdx.x * 256 + threadIdx.x, sp = blockIdx.y;
   if (j >= L) return;
   const long long po = (long long)blockIdx.z * ld;
   sim += po * ld; rmax += po; rsum += po; cmax += po; csum += po; part += po * gridDim.y;
   const int i0 = sp * rows_per, i1 = min(L, i0 + rows_per);
   const float cm = cmax[j], cs = csum[j];
-  float m = 0.f;
+  float m = 0.f, m2 = 0.f;
   for (int ib = i0; ib < i1; ib += 2 * kLfU) {
     float xv[2 * kLfU];
 #pragma unroll
     for (int u = 0; u < 2 * kLfU; ++u) xv[u] = ib + u < i1 ? sim[(long long)(ib + u) * ld + j] : 0.f;
 #pragma unroll
-    for (int u = 0; u < 2 * kLfU; ++u) if (ib + u < i1) m = fmaxf(m, lf_conf(xv[u] / temp, rmax[ib + u], rsum[ib + u], cm, cs));
+    for (int u = 0; u < 2 * kLfU; ++u) if (ib + u < i1) {
+      const float c = lf_conf(xv[u] / temp, rmax[ib + u], rsum[ib + u], cm, cs);
+      if (CERT) m2 = fmaxf(m2, fminf(m, c));
+      m = fmaxf(m, c);
+    }
   }
   part[(long long)sp * L + j] = m;
+  if (CERT) part2[po * gridDim.y + (long long)sp * L + j] = m2;
 }
-__global__ __launch_bounds__(256) void k_lf_max_merge(const float* part, int nsplit, int L, int ld, float* out) {
+template <bool CERT>
+__global__ __launch_bounds__(256) void k_lf_max_merge(const float* part, const float* part2, int nsplit, int L, int ld, float* out, float* out2) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= L) return;
   part += (long long)blockIdx.z * nsplit * ld; out += (long long)blockIdx.z * ld;
-  float m = 0.f;
-  for (int sp = 0; sp < nsplit; ++sp) m = fmaxf(m, part[(long long)sp * L + j]);
+  float m = 0.f, m2 = 0.f;
+  for (int sp = 0; sp < nsplit; ++sp) {
+    const float pm = part[(long long)sp * L + j];
+    if (CERT) m2 = fmaxf(fmaxf(m2, part2[(long long)blockIdx.z * nsplit * ld + (long long)sp * L + j]), fminf(m, pm));
+    m = fmaxf(m, pm);
+  }
   out[j] = m;
+  if (CERT) out2[(long long)blockIdx.z * ld + j] = m2;
+}
+// The certificate of a pair's coarse match list, one workgroup per pair, after k_lf_mutual.  eps bounds |conf - conf_f32| entry-wise;
+// a cell is interior when it lies at least `border` cells from every edge (k_lf_mutual's predicate; a border cell is in no match in either
+// arithmetic).  unc[pair] = 1 when (a) an interior row has best >= thr - eps and leads its runner-up by <= 2 eps, (b) the same for an interior
+// column, or (c) an interior row's best lies within eps of thr; else 0 (always written: the word needs no clearing).  eps comes from a device
+// word, so a captured graph follows a change of it.
+__global__ __launch_bounds__(256) void k_lf_certify(const float* crow, const float* crow2, const float* ccol, const float* ccol2, int L, int ld, int hc, int wc, float thr, int border,
+                                                   const float* eps_word, unsigned int* unc) {
+  const long long po = (long long)blockIdx.x * ld;
+  const float eps = *eps_word;
+  int bad = 0;
+  for (int l = threadIdx.x; l < L; l += 256) {
+    const int y = l / wc, x = l - y * wc;
+    if (!(y >= border && y < hc - border && x >= border && x < wc - border)) continue;
+    const float rb = crow[po + l], r2 = crow2[po + l], cb = ccol[po + l], c2 = ccol2[po + l];
+    bad |= (rb >= thr - eps && rb - r2 <= 2.f * eps) || (cb >= thr - eps && cb - c2 <= 2.f * eps) || fabsf(rb - thr) <= eps;
+  }
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) unc[blockIdx.x] = bad ? 1u : 0u;
+}
+// Calibration only (gn_loftr_calibrate_certify): max over j < L of |conf_a[i][j] - conf_b[i][j]| for row i of a pair (block per row, as k_lf_conf_rowmax),
+// each matrix with its own row and column statistics; k_lf_absdiff_merge then takes the maximum over the rows of a pair (one block per pair).
+struct LfConfSrc { const float *sim, *rmax, *rsum, *cmax, *csum; };
+__global__ __launch_bounds__(256) void k_lf_conf_absdiff(LfConfSrc a, LfConfSrc b, int ld, int L, float temp, float* part) {
+  __shared__ float red[4];
+  const int i = blockIdx.x, tid = threadIdx.x;
+  const long long po = (long long)blockIdx.y * ld;
+  const float* ra = a.sim + (po + i) * ld; const float* rb = b.sim + (po + i) * ld;
+  const float rma = a.rmax[po + i], rsa = a.rsum[po + i], rmb = b.rmax[po + i], rsb = b.rsum[po + i];
+  float m = 0.f;
+  for (int j = tid; j < L; j += 256) {
+    const float ca = lf_conf(ra[j] / temp, rma, rsa, a.cmax[po + j], a.csum[po + j]);
+    const float cb = lf_conf(rb[j] / temp, rmb, rsb, b.cmax[po + j], b.csum[po + j]);
+    m = fmaxf(m, fabsf(ca - cb));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) part[po + i] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__global__ __launch_bounds__(256) void k_lf_absdiff_merge(const float* part, int L, int ld, float* out) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  float m = 0.f;
+  for (int i = tid; i < L; i += 256) m = fmaxf(m, part[(long long)blockIdx.x * ld + i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) out[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 // get_coarse_match for row i: the first j with conf > thr, both cells inside the border, conf == row max and conf == column max
 __global__ __launch_bounds__(256) void k_lf_mutual(const float* sim, int ld, int L, int hc, int wc, float temp, float thr, int border, const float* rmax, const float* rsum,
@@ -1001,9 +1084,16 @@ struct gn_loftr {
   float *k0c = nullptr, *k1c = nullptr, *mconf = nullptr;
   float *frows = nullptr, *fc = nullptr, *fwin = nullptr, *ftok = nullptr, *fqkv = nullptr, *fatt = nullptr, *fmsg = nullptr, *fhid = nullptr, *fkvpart = nullptr, *fkv = nullptr;
   int* n_host = nullptr;
-  int use_graph = 1; std::map<int, hipGraphExec_t> graph_exec; std::map<int, bool> graph_failed; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per (arithmetic, B): key 2 B + arithmetic
+  int use_graph = 1; std::map<int, hipGraphExec_t> graph_exec; std::map<int, bool> graph_failed; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per (arithmetic, certificate, B): key 4 B + 2 certified + arithmetic
   int arith = 0;                        // gn_loftr_set_arithmetic: 0 exact f32, 1 split fp16 (f32-accurate)
   unsigned int* ovf = nullptr; long long ovf_trips = 0;   // split mode: fp16-range guard words (device, one per pair), pairs that fell back to the exact kernels
+  // gn_loftr_set_certify: certify 0 off / 1 flags / 2 flags + exact-f32 re-run; cert_fwd: the forward being enqueued evaluates the
+  // certificate (off in the re-run); eps_set < 0 = "the calibrated one" (eps_cal, < 0 while there is none: gn_loftr_load_tensor discards it);
+  // eps_dev the device word k_lf_certify reads, eps_dev_val what it holds (refreshed on the call's stream from the pinned eps_host when it differs)
+  int certify = 0; bool cert_fwd = false; float eps_set = -1.f, eps_cal = -1.f, eps_dev_val = -1.f;
+  float *crow2 = nullptr, *ccol2 = nullptr, *eps_dev = nullptr, *eps_host = nullptr; unsigned int* unc = nullptr;
+  std::vector<int32_t> unc_last;                 // the flags of the last certified call (gn_loftr_get_uncertain)
+  long long cert_stats[4] = {0, 0, 0, 0};         // pairs seen, pairs flagged, pairs re-run for the certificate, pairs re-run for the guard
 };
 
 namespace {
@@ -1265,6 +1355,7 @@ int gn_loftr_create_batch(int device, int max_pairs, int H, int W, int max_match
   LF_A(pe, L * 256); LF_A(tok, P * 2 * Lp * 256); LF_A(qkv, P * 2 * Lp * 768); LF_A(att, P * 2 * Lp * 256); LF_A(msg, P * 2 * Lp * 256); LF_A(hid, P * 2 * Lp * 512);
   LF_A(kvpart, P * 2 * ((L + 191) / 192) * 8 * 33 * 32); LF_A(kv, P * 2 * 8 * 33 * 32); LF_A(fs, P * 2 * Lp * 256); LF_A(sim, P * Lp * Lp);
   LF_A(rmax, P * Lp); LF_A(rsum, P * Lp); LF_A(cmax, P * Lp); LF_A(csum, P * Lp); LF_A(crow, P * Lp); LF_A(ccol, P * Lp); LF_A(cpart_a, P * 32 * Lp); LF_A(cpart_b, P * 32 * Lp); LF_A(csel, P * Lp);
+  LF_A(crow2, P * Lp); LF_A(ccol2, P * Lp); LF_A(unc, P + 4); LF_A(eps_dev, 4);
   LF_A(ovf, P + 4); LF_A(jsel, P * Lp); LF_A(i_ids, P * ctx->Mp); LF_A(j_ids, P * ctx->Mp); LF_A(n_dev, P + 4); LF_A(k0c, P * 2 * (size_t)ctx->Mp); LF_A(k1c, P * 2 * (size_t)ctx->Mp); LF_A(mconf, P * ctx->Mp);
   LF_A(cat, P * ctx->Mp); LF_A(n_tot, 4);
   if (ctx->fine) {
@@ -1273,7 +1364,8 @@ int gn_loftr_create_batch(int device, int max_pairs, int H, int W, int max_match
     LF_A(fmsg, R * 128); LF_A(fhid, R * 256); LF_A(fkvpart, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16); LF_A(fkv, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16);
   }
 #undef LF_A
-  if (hipHostMalloc((void**)&ctx->n_host, (2 * P + 4) * sizeof(int), hipHostMallocDefault) != hipSuccess) { gn_loftr_destroy(ctx); return lf_fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
+  if (hipHostMalloc((void**)&ctx->n_host, (3 * P + 8) * sizeof(int), hipHostMallocDefault) != hipSuccess) { gn_loftr_destroy(ctx); return lf_fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
+  ctx->eps_host = reinterpret_cast<float*>(ctx->n_host + 3 * P + 4);       // pinned: [P] counts, [P] guard words, [P] certificate flags, then the eps word
   {   // PositionEncodingSine, legacy divisor (temp_bug_fix = False): div_term_i = exp(-2 i); token l = y * wc + x, positions 1-based
     std::vector<float> pe((size_t)L * 256);
     for (int y = 0; y < (int)hc; ++y)
@@ -1304,6 +1396,7 @@ int gn_loftr_load_tensor(gn_loftr* ctx, const char* name_c, const float* host, c
   if (!ctx || !name_c || !host || !shape || ndim < 1 || ndim > 4) return lf_fail(ctx, GN_ERR_ARG, "bad gn_loftr_load_tensor argument");
   LF_HIP(hipSetDevice(ctx->device));
   const std::string name = name_c;
+  ctx->eps_cal = -1.f;                           // a calibrated certificate eps belongs to the weights it was measured on
   if (name == "pos_encoding.pe" || name.find("num_batches_tracked") != std::string::npos) return GN_OK;
   const size_t dot = name.rfind('.');
   if (dot == std::string::npos) return lf_fail(ctx, GN_ERR_NAME, "unknown tensor " + name);
@@ -1453,10 +1546,18 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   hipLaunchKernelGGL(k_lf_row_stats, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum);
   hipLaunchKernelGGL(k_lf_col_stats, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->cpart_a, ctx->cpart_b, rows_per);
   hipLaunchKernelGGL(k_lf_col_merge, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, ctx->cpart_b, nsplit, L, Lp, ctx->cmax, ctx->csum);
-  hipLaunchKernelGGL(k_lf_conf_rowmax, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow);
-  hipLaunchKernelGGL(k_lf_conf_colmax, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->cpart_a, rows_per);
-  hipLaunchKernelGGL(k_lf_max_merge, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, nsplit, L, Lp, ctx->ccol);
-  hipLaunchKernelGGL(k_lf_mutual, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, hc, wc, temp, 0.2f, 2, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, ctx->ccol, ctx->jsel, ctx->csel);
+  const float thr = 0.2f; const int border = 2;
+  if (ctx->cert_fwd) {   // the same maxima, plus every row's and column's runner-up (cpart_b is idle since k_lf_col_merge: the columns' runner-up partials)
+    hipLaunchKernelGGL(k_lf_conf_rowmax<true>, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, ctx->crow2);
+    hipLaunchKernelGGL(k_lf_conf_colmax<true>, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->cpart_a, ctx->cpart_b, rows_per);
+    hipLaunchKernelGGL(k_lf_max_merge<true>, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, ctx->cpart_b, nsplit, L, Lp, ctx->ccol, ctx->ccol2);
+  } else {
+    hipLaunchKernelGGL(k_lf_conf_rowmax<false>, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, (float*)nullptr);
+    hipLaunchKernelGGL(k_lf_conf_colmax<false>, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->cpart_a, (float*)nullptr, rows_per);
+    hipLaunchKernelGGL(k_lf_max_merge<false>, dim3((L + 255) / 256, 1, B), dim3(256), 0, s, ctx->cpart_a, (const float*)nullptr, nsplit, L, Lp, ctx->ccol, (float*)nullptr);
+  }
+  hipLaunchKernelGGL(k_lf_mutual, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, hc, wc, temp, thr, border, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum, ctx->crow, ctx->ccol, ctx->jsel, ctx->csel);
+  if (ctx->cert_fwd) hipLaunchKernelGGL(k_lf_certify, dim3(B), dim3(256), 0, s, ctx->crow, ctx->crow2, ctx->ccol, ctx->ccol2, L, Lp, hc, wc, thr, border, ctx->eps_dev, ctx->unc);
   const int M = ctx->max_matches, Mp = B * ctx->Mp;      // M: a pair's segment; Mp: the windows a side of the fine level has room for, all pairs together
   hipLaunchKernelGGL(k_lf_compact, dim3(B), dim3(1024), 0, s, ctx->jsel, ctx->csel, L, Lp, wc, 8, M, ctx->i_ids, ctx->j_ids, ctx->mconf, ctx->k0c, ctx->k1c, ctx->n_dev);
   if (ctx->fine) {
@@ -1511,7 +1612,34 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
 
 int gn_loftr_set_arithmetic(gn_loftr* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 1) return GN_ERR_ARG;
+  if (mode == 0 && ctx->certify == 2) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_arithmetic: certify mode 2 re-runs flagged pairs in exact f32 and needs arithmetic 1");
   ctx->arith = mode;
+  return GN_OK;
+}
+
+int gn_loftr_set_certify(gn_loftr* ctx, int mode, float eps) {
+  if (!ctx) return GN_ERR_ARG;
+  if (mode < 0 || mode > 2) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_certify: mode 0 (off), 1 (flags) or 2 (flags + exact-f32 re-run)");
+  if (mode == 2 && ctx->arith != 1) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_certify: mode 2 re-runs flagged pairs in exact f32 and needs arithmetic 1 (split fp16)");
+  if (mode >= 1) {
+    if (!(eps < 1.f)) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_certify: eps must be < 1 (or < 0 for the calibrated one)");
+    if (eps < 0.f && ctx->eps_cal < 0.f) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_certify: no eps given and none calibrated (gn_loftr_calibrate_certify)");
+    ctx->eps_set = eps;
+  }
+  ctx->certify = mode;
+  return GN_OK;
+}
+
+int gn_loftr_get_uncertain(gn_loftr* ctx, int B, int32_t* flags_host) {
+  if (!ctx || !flags_host || B < 1) return lf_fail(ctx, GN_ERR_ARG, "bad gn_loftr_get_uncertain argument");
+  if ((int)ctx->unc_last.size() != B) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_get_uncertain: the last certified call had " + std::to_string(ctx->unc_last.size()) + " pairs");
+  for (int b = 0; b < B; ++b) flags_host[b] = ctx->unc_last[b];
+  return GN_OK;
+}
+
+int gn_loftr_get_certify_stats(gn_loftr* ctx, int64_t* out4) {
+  if (!ctx || !out4) return lf_fail(ctx, GN_ERR_ARG, "bad gn_loftr_get_certify_stats argument");
+  for (int k = 0; k < 4; ++k) out4[k] = ctx->cert_stats[k];
   return GN_OK;
 }
 
@@ -1524,9 +1652,9 @@ int gn_loftr_set_graph(gn_loftr* ctx, int enable) {
 // the forward for ctx->B pairs already in ctx->img, as a replay of the (arithmetic, B) graph or as plain launches
 static int lf_run(gn_loftr* ctx, hipStream_t s, bool allow_graph) {
   if (ctx->use_graph && allow_graph) {
-    // every pointer inside the forward belongs to the context and the shapes are fixed by (H, W, B): capture the ~190 launches ONCE per (arithmetic, B) on an
+    // every pointer inside the forward belongs to the context and the shapes are fixed by (H, W, B): capture the ~190 launches ONCE per (arithmetic, certificate, B) on an
     // internal stream and replay them as one graph launch (the host was the slower side between the small kernels of the fine level)
-    const int key = 2 * ctx->B + ctx->arith;
+    const int key = 4 * ctx->B + 2 * (ctx->cert_fwd ? 1 : 0) + ctx->arith;
     hipGraphExec_t& gexec = ctx->graph_exec[key];
     if (!gexec && !ctx->graph_failed[key]) {
       hipGraph_t graph = nullptr;
@@ -1576,32 +1704,52 @@ int gn_loftr_match_batch(gn_loftr* ctx, int B, const float* image0, const float*
   if (!ctx->finalised) { const int rc = lf_finalise(ctx); if (rc != GN_OK) return rc; }
   hipStream_t s = (hipStream_t)stream;
   const size_t HW = (size_t)ctx->H * ctx->W;
-  ctx->B = B;
+  const bool cert = ctx->certify >= 1;
+  if (cert) {
+    const float eps = ctx->eps_set < 0.f ? ctx->eps_cal : ctx->eps_set;
+    if (eps < 0.f) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_match_batch: the certificate is on but has no eps (the calibrated one was discarded by gn_loftr_load_tensor: calibrate again)");
+    if (eps != ctx->eps_dev_val) {   // (every certified call synchronises before it returns, so the pinned word is not in flight here)
+      *ctx->eps_host = eps;
+      LF_HIP(hipMemcpyAsync(ctx->eps_dev, ctx->eps_host, sizeof(float), hipMemcpyHostToDevice, s));
+      ctx->eps_dev_val = eps;
+    }
+  }
+  ctx->B = B; ctx->cert_fwd = cert;
   LF_HIP(hipMemcpyAsync(ctx->img, image0, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
   LF_HIP(hipMemcpyAsync(ctx->img + B * HW, image1, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
   int rc = lf_run(ctx, s, true);
+  ctx->cert_fwd = false;
   if (rc != GN_OK) return rc;
-  int* const cnt_host = ctx->n_host;                 // pinned: [max_pairs] counts, then [max_pairs] guard words
+  int* const cnt_host = ctx->n_host;                 // pinned: [max_pairs] counts, then [max_pairs] guard words, then [max_pairs] certificate flags
   unsigned int* const ovf_host = reinterpret_cast<unsigned int*>(ctx->n_host + ctx->max_pairs);
+  unsigned int* const unc_host = reinterpret_cast<unsigned int*>(ctx->n_host + 2 * ctx->max_pairs);
   std::vector<int> redo;
-  if (ctx->arith == 1) {   // split-fp16 arithmetic: a value outside fp16's range anywhere in a pair's forward -> that pair again on the exact-f32 kernels
-    // (the counts come along: with every pair in range this is the call's one synchronisation)
-    LF_HIP(hipMemcpyAsync(ovf_host, ctx->ovf, B * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  if (ctx->arith == 1 || cert) {   // split-fp16 arithmetic: a value outside fp16's range anywhere in a pair's forward -> that pair again on the exact-f32 kernels
+    // (the counts and the certificate's flags come along: with every pair in range and vouched for this is the call's one synchronisation)
+    if (ctx->arith == 1) LF_HIP(hipMemcpyAsync(ovf_host, ctx->ovf, B * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    if (cert) LF_HIP(hipMemcpyAsync(unc_host, ctx->unc, B * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     LF_HIP(hipMemcpyAsync(cnt_host, ctx->n_dev, B * sizeof(int), hipMemcpyDeviceToHost, s));
     LF_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < B; ++b) if (ovf_host[b] != 0) redo.push_back(b);
+    if (cert) ctx->unc_last.assign(B, 0);
+    for (int b = 0; b < B; ++b) {
+      const bool guard = ctx->arith == 1 && ovf_host[b] != 0;
+      // a pair whose guard tripped comes back exact whatever the certificate says of its out-of-range numbers: it is not counted as flagged
+      const bool flag = cert && !guard && unc_host[b] != 0;
+      if (cert) { ctx->unc_last[b] = flag ? 1 : 0; ctx->cert_stats[0] += 1; ctx->cert_stats[1] += flag; ctx->cert_stats[2] += flag && ctx->certify == 2; ctx->cert_stats[3] += guard; }
+      if (guard || (flag && ctx->certify == 2)) redo.push_back(b);
+    }
   }
-  const bool counts_read = ctx->arith == 1 && redo.empty();
+  const bool counts_read = (ctx->arith == 1 || cert) && redo.empty();
   if ((int)redo.size() < B) {
     rc = lf_copy_out(ctx, 0, 0, B, kpts0, kpts1, conf, ij, n_match_dev, s);
     if (rc != GN_OK) return rc;
-    if (n_host && ctx->arith == 0) LF_HIP(hipMemcpyAsync(cnt_host, ctx->n_dev, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (n_host && ctx->arith == 0 && !cert) LF_HIP(hipMemcpyAsync(cnt_host, ctx->n_dev, B * sizeof(int), hipMemcpyDeviceToHost, s));
   }
   if (!redo.empty()) {
     // the flagged pairs as a smaller batch of their own (a pair's exact result does not depend on the batch it runs in); their segments and
-    // counts replace the split ones, every other pair keeps its split-arithmetic bits
+    // counts replace the split ones, every other pair keeps its split-arithmetic bits.  The re-run evaluates no certificate.
     const int Br = (int)redo.size();
-    ctx->ovf_trips += Br;
+    for (int r = 0; r < Br; ++r) ctx->ovf_trips += ovf_host[redo[r]] != 0;
     for (int r = 0; r < Br; ++r) {
       LF_HIP(hipMemcpyAsync(ctx->img + r * HW, image0 + redo[r] * HW, HW * sizeof(float), hipMemcpyDeviceToDevice, s));
       LF_HIP(hipMemcpyAsync(ctx->img + (Br + r) * HW, image1 + redo[r] * HW, HW * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1624,6 +1772,63 @@ int gn_loftr_match_batch(gn_loftr* ctx, int B, const float* image0, const float*
   return GN_OK;
 }
 
+// The certificate's eps, measured: the sample's B pairs run in split-fp16 arithmetic, their similarity matrices and row / column
+// statistics are kept in a buffer that lives for this call only (Lp x Lp floats per pair: 92 MB at 640 x 480), then again in exact f32;
+// d_max = max over pairs and over i, j < L of |conf_split - conf_f32|, eps = max(floor_eps, safety x d_max), stored as the calibrated eps.
+// out (HOST): d_max, eps.  Fails when the fp16-range guard tripped on the sample (such a pair has no split-arithmetic result to bound).
+int gn_loftr_calibrate_certify(gn_loftr* ctx, int B, const float* image0, const float* image1, float safety, float floor_eps, float* out, void* stream) {
+  if (!ctx || !image0 || !image1 || !out) return lf_fail(ctx, GN_ERR_ARG, "null pointer passed to gn_loftr_calibrate_certify");
+  if (B < 1 || B > ctx->max_pairs) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_calibrate_certify: B = " + std::to_string(B) + " outside 1 .. max_pairs = " + std::to_string(ctx->max_pairs));
+  if (!(safety >= 1.f) || !(floor_eps >= 0.f && floor_eps < 1.f)) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_calibrate_certify: safety >= 1 and 0 <= floor_eps < 1");
+  LF_HIP(hipSetDevice(ctx->device));
+  if (gn_loftr_missing_tensors(ctx) != 0) return lf_fail(ctx, GN_ERR_WEIGHTS, "LoFTR weights not fully loaded");
+  if (!ctx->finalised) { const int rc = lf_finalise(ctx); if (rc != GN_OK) return rc; }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t HW = (size_t)ctx->H * ctx->W, Lp = (size_t)ctx->Lp, nsim = (size_t)B * Lp * Lp, nvec = (size_t)B * Lp;
+  const int arith0 = ctx->arith;
+  auto forward = [&](int arith) -> int {
+    ctx->B = B; ctx->cert_fwd = false;
+    LF_HIP(hipMemcpyAsync(ctx->img, image0, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+    LF_HIP(hipMemcpyAsync(ctx->img + B * HW, image1, B * HW * sizeof(float), hipMemcpyDeviceToDevice, s));
+    ctx->arith = arith;
+    const int rc = lf_run(ctx, s, false);
+    ctx->arith = arith0;
+    return rc;
+  };
+  int rc = forward(1);
+  if (rc != GN_OK) return rc;
+  unsigned int* const ovf_host = reinterpret_cast<unsigned int*>(ctx->n_host + ctx->max_pairs);
+  LF_HIP(hipMemcpyAsync(ovf_host, ctx->ovf, B * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  LF_HIP(hipStreamSynchronize(s));
+  for (int b = 0; b < B; ++b)
+    if (ovf_host[b] != 0) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_calibrate_certify: pair " + std::to_string(b) + " of the sample left fp16's range (the guard tripped): calibrate on in-range images");
+  struct Keep { float* p = nullptr; ~Keep() { if (p) hipFree(p); } } keep;      // freed on every way out
+  LF_HIP(hipMalloc((void**)&keep.p, (nsim + 5 * nvec + B + 4) * sizeof(float)));
+  float* const k_sim = keep.p; float* const k_vec = k_sim + nsim; float* const k_part = k_vec + 4 * nvec; float* const k_out = k_part + nvec;
+  LF_HIP(hipMemcpyAsync(k_sim, ctx->sim, nsim * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const float* stats[4] = {ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum};
+  for (int k = 0; k < 4; ++k) LF_HIP(hipMemcpyAsync(k_vec + k * nvec, stats[k], nvec * sizeof(float), hipMemcpyDeviceToDevice, s));
+  rc = forward(0);
+  if (rc != GN_OK) return rc;
+  const LfConfSrc a{k_sim, k_vec, k_vec + nvec, k_vec + 2 * nvec, k_vec + 3 * nvec}, b{ctx->sim, ctx->rmax, ctx->rsum, ctx->cmax, ctx->csum};
+  hipLaunchKernelGGL(k_lf_conf_absdiff, dim3(ctx->L, B), dim3(256), 0, s, a, b, ctx->Lp, ctx->L, 0.1f, k_part);
+  hipLaunchKernelGGL(k_lf_absdiff_merge, dim3(B), dim3(256), 0, s, k_part, ctx->L, ctx->Lp, k_out);
+  std::vector<float> d(B);
+  LF_HIP(hipMemcpyAsync(d.data(), k_out, B * sizeof(float), hipMemcpyDeviceToHost, s));
+  LF_HIP(hipStreamSynchronize(s));
+  LF_HIP(hipGetLastError());
+  float d_max = 0.f;
+  for (int p = 0; p < B; ++p) {
+    if (!(d[p] >= 0.f && d[p] < 1.f)) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_calibrate_certify: the confidence difference of pair " + std::to_string(p) + " is not a number in [0, 1)");
+    d_max = std::max(d_max, d[p]);
+  }
+  const float eps = std::max(floor_eps, safety * d_max);
+  if (!(eps < 1.f)) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_calibrate_certify: safety x d_max reaches 1: the two arithmetics do not agree on this sample");
+  ctx->eps_cal = eps;
+  out[0] = d_max; out[1] = eps;
+  return GN_OK;
+}
+
 // test hook: copy an internal tensor to HOST memory after synchronising.  Names: "x0" (stem, [2][H/2][W/2][128]), "x1" (layer1 output),
 // "x2" (224-channel rows), "x3", "x3_out", "x1_out", "tok" ([2][Lp][256] coarse tokens after the transformer), "sim", "conf_row" / "conf_col" maxima.
 // After a call with B pairs every one of them is the batched buffer: [2][B]... for the maps and tokens, [B]... for the matching stage, [2][B Mp]... for "ftok".
@@ -1642,6 +1847,9 @@ int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int
   else if (n == "sim") { p = ctx->sim; count = B * Lp * Lp; }
   else if (n == "crow") { p = ctx->crow; count = B * Lp; }
   else if (n == "ccol") { p = ctx->ccol; count = B * Lp; }
+  else if (n == "crow2") { p = ctx->crow2; count = B * Lp; }                                    // the runner-ups of the last CERTIFIED forward
+  else if (n == "ccol2") { p = ctx->ccol2; count = B * Lp; }
+  else if (n == "unc") { p = reinterpret_cast<const float*>(ctx->unc); count = B; }              // the certificate's words of the last certified forward, as raw 32-bit words
   else if (n == "ovf") { p = reinterpret_cast<const float*>(ctx->ovf); count = B; }              // the guard words of the last forward, as raw 32-bit words
   else if (n == "ovf_trips") { if (max_bytes < (int64_t)sizeof(float)) return GN_ERR_ARG; *reinterpret_cast<float*>(host_out) = (float)ctx->ovf_trips; return 1; }   // pairs repeated on the exact kernels so far
   else if (n == "ftok") { p = ctx->ftok; count = ctx->fine ? B * 2 * (size_t)ctx->Mp * kLfWW * 128 : 0; }

@@ -19,15 +19,28 @@ class LoFTR:
     images in [0, 1] of equal size (H, W multiples of 8) -> {"keypoints0" (M, 2), "keypoints1" (M, 2), "confidence" (M,), "batch_indexes" (M,)}
     on the input device: the matches of all B pairs in ascending (pair, coarse cell of image0) order, `batch_indexes` the pair of each (kornia's
     layout).  The B pairs go through ONE call of the library (gn_loftr_match_batch); a pair's rows do not depend on the batch it is in, bit for
-    bit.  `fine=False` stops after the coarse level (keypoints on the 1/8 grid)."""
+    bit.  `fine=False` stops after the coarse level (keypoints on the 1/8 grid).  `certify="flags" | "rerun"` (off by default)
+    certifies each pair's coarse (i, j) list against exact f32: flagged pairs are reported (`match_segments(...)["uncertain"]`) or, with
+    "rerun" on `arithmetic="split_fp16"`, repeated on the exact-f32 kernels inside the call; eps from `certify_eps=` or `calibrate_certify`."""
 
     def __init__(self, pretrained: Optional[str] = None, *, state_dict: Optional[Dict] = None, max_matches: Optional[int] = None, fine: bool = True, graph: bool = True,
-                 arithmetic: str = "exact_f32"):
+                 arithmetic: str = "exact_f32", certify=False, certify_eps: Optional[float] = None):
         if state_dict is None:
             state_dict = self._find_pretrained(pretrained or "outdoor")
         # max_matches None = every mutual match (at most one per coarse cell of image0), as kornia returns them; a number caps the list (first in raster order)
         self._sd, self._max, self._fine, self._graph = state_dict, (None if max_matches is None else int(max_matches)), bool(fine), bool(graph)
         self._arith = {"exact_f32": 0, "split_fp16": 1}[arithmetic]   # split_fp16: f32-accurate 2-term fp16 operands (gn_loftr_set_arithmetic)
+        # certify (gn_loftr_set_certify): False off; "flags" marks the pairs whose coarse (i, j) list the arithmetic's error could change;
+        # "rerun" (split_fp16 only) also repeats them on the exact-f32 kernels inside the call.  eps: `certify_eps` for every image shape, or
+        # the one `calibrate_certify` measured, kept per (H, W) and re-applied when the context is re-created
+        if certify not in (False, None, "flags", "rerun"):
+            raise _lib.GnError(f"certify must be False, 'flags' or 'rerun', got {certify!r}")
+        self._certify = {"flags": 1, "rerun": 2}.get(certify, 0)
+        if self._certify == 2 and self._arith != 1:
+            raise _lib.GnError("certify='rerun' repeats flagged pairs in exact f32: it needs arithmetic='split_fp16'")
+        if certify_eps is not None and not 0.0 <= float(certify_eps) < 1.0:
+            raise _lib.GnError(f"certify_eps must lie in [0, 1), got {certify_eps!r}")
+        self._eps_all, self._eps = (None if certify_eps is None else float(certify_eps)), {}
         self._ctx, self._shape, self._device, self._pairs = None, None, None, 0
         self.lib = None
 
@@ -103,6 +116,46 @@ class LoFTR:
         missing = self.lib.gn_loftr_missing_tensors(ctx)
         if missing:
             raise _lib.GnError(f"{missing} required LoFTR tensors missing from the state dict")
+        eps = self._eps.get((H, W), self._eps_all)
+        if self._certify and eps is not None:          # (a shape without an eps is refused by match_segments)
+            self._check(self.lib.gn_loftr_set_certify(ctx, self._certify, eps), "gn_loftr_set_certify")
+
+    def calibrate_certify(self, image0, image1, safety: float = 4.0, floor_eps: float = 1e-5) -> Dict[str, float]:
+        """Measure the certificate's eps for this image shape on a sample of pairs (gn_loftr_calibrate_certify): the sample runs in split-fp16
+        and in exact-f32 arithmetic, d_max = the largest entry-wise difference of the two dual-softmax confidence matrices over the sample,
+        eps = max(floor_eps, safety x d_max).  The eps is kept for (H, W) and used by every later call on that shape.  Returns {"d_max", "eps"}."""
+        B, H, W = self._batch_shape(image0, image1)
+        if self._device is None:
+            raise _lib.GnError("call .to(device) first")
+        f = lambda t: t.to(device=self._device, dtype=torch.float32).reshape(B, H, W).contiguous()  # noqa: E731
+        a, b = f(image0), f(image1)
+        self._ensure(H, W, B)
+        out = (C.c_float * 2)()
+        stream = C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        self._check(self.lib.gn_loftr_calibrate_certify(self._ctx, B, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), float(safety), float(floor_eps), out, stream),
+                    "gn_loftr_calibrate_certify")
+        self._eps[(H, W)] = float(out[1])
+        if self._certify:
+            self._check(self.lib.gn_loftr_set_certify(self._ctx, self._certify, -1.0), "gn_loftr_set_certify")     # eps < 0: the calibrated one
+        return {"d_max": float(out[0]), "eps": float(out[1])}
+
+    def set_certify_eps(self, eps: float) -> None:
+        """State the certificate's eps for every image shape from now on (replaces `certify_eps` and any calibrated value)."""
+        if not 0.0 <= float(eps) < 1.0:
+            raise _lib.GnError(f"certify_eps must lie in [0, 1), got {eps!r}")
+        self._eps_all, self._eps = float(eps), {}
+        if self._ctx is not None and self._certify:
+            self._check(self.lib.gn_loftr_set_certify(self._ctx, self._certify, self._eps_all), "gn_loftr_set_certify")
+
+    def certify_stats(self) -> Dict[str, int]:
+        """Counters of the current context since it was created: pairs seen by certified calls, pairs the certificate flagged, pairs repeated
+        in exact f32 because of a flag, pairs repeated because the fp16-range guard tripped."""
+        keys = ("pairs", "flagged", "rerun_certificate", "rerun_guard")
+        if self._ctx is None:
+            return dict.fromkeys(keys, 0)
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.gn_loftr_get_certify_stats(self._ctx, out), "gn_loftr_get_certify_stats")
+        return {k: int(v) for k, v in zip(keys, out)}
 
     @staticmethod
     def _batch_shape(i0, i1):
@@ -135,6 +188,8 @@ class LoFTR:
         f = lambda t: t.to(device=self._device, dtype=torch.float32).reshape(B, H, W).contiguous()  # noqa: E731
         a, b = f(image0), f(image1)
         self._ensure(H, W, B)
+        if self._certify and self._eps.get((H, W), self._eps_all) is None:
+            raise _lib.GnError(f"certify is on but no eps is known for {H}x{W} images: pass certify_eps= or call calibrate_certify on a sample of that shape")
         M = self._cap(H, W)
         k0 = torch.empty((B, M, 2), dtype=torch.float32, device=self._device); k1 = torch.empty_like(k0)
         conf = torch.empty((B, M), dtype=torch.float32, device=self._device)
@@ -144,7 +199,12 @@ class LoFTR:
         stream = C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         self._check(self.lib.gn_loftr_match_batch(self._ctx, B, p(a), p(b), p(k0), p(k1), p(conf), p(ij), p(n_dev), n, stream), "gn_loftr_match_batch")
-        return {"keypoints0": k0, "keypoints1": k1, "confidence": conf, "ij": ij, "n": n_dev, "n_host": [int(v) for v in n] if host_counts else None}
+        out = {"keypoints0": k0, "keypoints1": k1, "confidence": conf, "ij": ij, "n": n_dev, "n_host": [int(v) for v in n] if host_counts else None}
+        if self._certify:
+            flags = (C.c_int32 * B)()
+            self._check(self.lib.gn_loftr_get_uncertain(self._ctx, B, flags), "gn_loftr_get_uncertain")
+            out["uncertain"] = torch.tensor([bool(v) for v in flags], dtype=torch.bool)
+        return out
 
     @torch.inference_mode()
     def __call__(self, data: Dict[str, torch.Tensor], with_ids: bool = False) -> Dict[str, torch.Tensor]:

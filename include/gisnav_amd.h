@@ -498,8 +498,32 @@ int gn_loftr_set_graph(gn_loftr* ctx, int enable);
  * rate).  Mode 1 guards fp16's range PER PAIR: the pairs of a call in whose forward any activation left it are repeated on the exact kernels, as a
  * smaller batch, before the call returns; the other pairs keep their split-arithmetic results. */
 int gn_loftr_set_arithmetic(gn_loftr* ctx, int mode);
+/* Certified coarse matches: a per-pair certificate that the coarse (i, j) list of this arithmetic is the one exact f32 computes.
+ * With eps a bound on |conf - conf_f32| entry-wise, thr = 0.2, border = 2 and a coarse cell INTERIOR when it lies at least `border` cells from every
+ * edge, a pair is flagged when (a) an interior row's best confidence is >= thr - eps and leads its runner-up (multiplicity counted: a tie has gap
+ * 0) by <= 2 eps, (b) the same for an interior column, or (c) an interior row's best lies within eps of thr.  An unflagged pair's list is f32's.
+ * mode 0 (default): off -- outputs, launches and time are those of a library without the certificate.  mode 1: flags only, the results stay the
+ * context's arithmetic (on an exact-f32 context: the pairs f32's own rounding decides).  mode 2: flagged pairs are repeated on the exact-f32
+ * kernels inside the call, together with the pairs of the fp16-range guard, and overwrite their segments; needs arithmetic 1 (GN_ERR_ARG
+ * otherwise, and gn_loftr_set_arithmetic(0) is refused while it is on).  eps: 0 <= eps < 1 states it; eps < 0 means the one
+ * gn_loftr_calibrate_certify measured (GN_ERR_ARG when there is none).  A certified call synchronises once (flags, guard words and counts in one
+ * read), also in exact-f32 arithmetic; eps may change between calls (the captured graph reads it from device memory). */
+int gn_loftr_set_certify(gn_loftr* ctx, int mode, float eps);
+/* Measure eps on a sample of B pairs (DEVICE f32 [B][H][W], B <= max_pairs): the sample runs in split-fp16 and in exact-f32 arithmetic,
+ * d_max = max over the pairs and all i, j of |conf_split - conf_f32|, eps = max(floor_eps, safety x d_max) becomes the context's calibrated eps.
+ * out (HOST): {d_max, eps}.  safety >= 1, 0 <= floor_eps < 1.  Fails (GN_ERR_ARG) when the fp16-range guard trips on the sample.  Holds one more
+ * similarity matrix per pair for the duration of the call.  gn_loftr_load_tensor afterwards discards the calibrated eps: it belongs to its weights. */
+int gn_loftr_calibrate_certify(gn_loftr* ctx, int B, const float* image0, const float* image1, float safety, float floor_eps, float* out,
+                               void* stream);
+/* flags_host (HOST int32 [B]): 1 for the pairs of the last certified call (B = its batch size) that the certificate flagged -- in mode 2 the
+ * pairs that were repeated for it.  A pair repeated for the fp16-range guard is exact already and not flagged. */
+int gn_loftr_get_uncertain(gn_loftr* ctx, int B, int32_t* flags_host);
+/* out4 (HOST int64 [4]) since the context was created: pairs seen by certified calls, pairs flagged, pairs repeated for the certificate, pairs
+ * repeated for the fp16-range guard. */
+int gn_loftr_get_certify_stats(gn_loftr* ctx, int64_t* out4);
 /* test hook: internal tensor -> HOST after synchronising.  Names: "x1" "x2" "x3" "x3_out" "x1_out" (NHWC, 196 channels padded to 224),
- * "tok" ([2][Lp][256] coarse features after the transformer), "sim", "crow", "ccol", "ftok".  Returns the element count or a negative status.
+ * "tok" ([2][Lp][256] coarse features after the transformer), "sim", "crow", "ccol", "ftok"; of the last certified forward "crow2", "ccol2" (the
+ * runner-ups) and "unc" (the certificate's words, raw).  Returns the element count or a negative status.
  * After a call with B pairs the buffers are side-major over the pairs: [2][B]... maps and tokens, [B]... "sim" / "crow" / "ccol". */
 int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream);
 
