@@ -2557,6 +2557,7 @@ static bool retired_variant(int which, int value) {
                    value == 71 || value == 72 || value >= 1000;
     case 8: return value != 0 && value != 1;
     case 12: return value != 0 && value != 8 && value != 136;
+    case 42: return (value & 0xff) != 0;      // LoFTR's forms of rounds 3-4; bits 8.. (lf_conv's cost model) live on
     default: return false;
   }
 }

@@ -30,16 +30,14 @@ thread_local std::string g_lf_err;
 constexpr int kLfDim = 256, kLfHeads = 8, kLfFine = 128, kLfWW = 25;
 
 // ------------------------------------------------------------------------------------------------ stem: 7x7 stride 2, 1 -> 128
-// thread -> (output pixel, 16-channel group); weights + affine in LDS.  Round 5: the weights sit TRANSPOSED there ([tap][channel]) and a thread reads
-// its 16 channels of a tap as four 16-byte pieces (the [channel][tap] form read one float per multiply-add through 4-way bank conflicts: the
-// kernel was LDS-bound at 181 us for 79 MB of output); every channel still accumulates its taps in the order 0 .. 48: the same bits.  OLD = the
-// form of rounds 3-4 (developer knob 42, bit 2)
-template <bool OLD>
+// thread -> (output pixel, one of eight channel groups); weights + affine in LDS, the weights TRANSPOSED ([tap][channel], as lf_finalise uploads them): a thread
+// reads its 16 channels of a tap as four 16-byte pieces (a [channel][tap] layout read one float per multiply-add through 4-way bank conflicts: the
+// kernel was LDS-bound at 181 us for 79 MB of output); every channel accumulates its taps in the order 0 .. 48
 __global__ __launch_bounds__(256) void k_lf_conv1(const float* in, const float* w, const float* scale, const float* shift, float* out, int H, int W) {
   __shared__ __attribute__((aligned(16))) float ws[128 * 49 + 256];
   for (int q = threadIdx.x; q < 128 * 49 + 256; q += 256) {
     float x;
-    if (q < 128 * 49) x = OLD ? w[q] : w[128 * 49 + q];       // (the [tap][channel] copy lf_finalise put behind the [channel][tap] one)
+    if (q < 128 * 49) x = w[q];
     else x = q < 128 * 49 + 128 ? scale[q - 128 * 49] : shift[q - 128 * 49 - 128];
     ws[q] = x;
   }
@@ -57,45 +55,28 @@ __global__ __launch_bounds__(256) void k_lf_conv1(const float* in, const float* 
     const int yy = 2 * y + t / 7 - 3, xx = 2 * x + t % 7 - 3;
     v[t] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? img[(long long)yy * W + xx] : 0.f;
   }
-  float* o = out + ((long long)blockIdx.z * Ho * Wo + pix) * 128 + grp * 16;
-  if (OLD) {
+  // lane (pixel, grp) owns the channels 32 c4 + 4 grp .. + 3, c4 = 0 .. 3: the eight lanes of a pixel read 128 contiguous bytes of a tap's weights
+  // and store 128 contiguous bytes of the pixel's row per instruction (with 16 channels in a row per lane every store instruction wrote 16 bytes
+  // out of every 64)
+  f32x4 acc[4];
+#pragma unroll
+  for (int c4 = 0; c4 < 4; ++c4) acc[c4] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 49; ++t)
 #pragma unroll
     for (int c4 = 0; c4 < 4; ++c4) {
-      f32x4 r;
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(ws + t * 128 + c4 * 32 + grp * 4);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = grp * 16 + c4 * 4 + e;
-        float acc = 0.f;
-#pragma unroll
-        for (int t = 0; t < 49; ++t) acc = fmaf(ws[c * 49 + t], v[t], acc);
-        r[e] = fmaxf(acc * ws[128 * 49 + c] + ws[128 * 49 + 128 + c], 0.f);
-      }
-      *reinterpret_cast<f32x4*>(o + c4 * 4) = r;
+      for (int e = 0; e < 4; ++e) acc[c4][e] = fmaf(w4[e], v[t], acc[c4][e]);
     }
-  } else {
-    // lane (pixel, grp) owns the channels 32 c4 + 4 grp .. + 3, c4 = 0 .. 3: the eight lanes of a pixel read 128 contiguous bytes of a tap's weights
-    // and store 128 contiguous bytes of the pixel's row per instruction (with 16 channels in a row per lane every store instruction wrote 16 bytes
-    // out of every 64)
-    f32x4 acc[4];
+  float* const op = out + ((long long)blockIdx.z * Ho * Wo + pix) * 128 + grp * 4;
 #pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) acc[c4] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int c4 = 0; c4 < 4; ++c4) {
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(ws + 128 * 49 + c4 * 32 + grp * 4), sh = *reinterpret_cast<const f32x4*>(ws + 128 * 49 + 128 + c4 * 32 + grp * 4);
+    f32x4 r;
 #pragma unroll
-    for (int t = 0; t < 49; ++t)
-#pragma unroll
-      for (int c4 = 0; c4 < 4; ++c4) {
-        const f32x4 w4 = *reinterpret_cast<const f32x4*>(ws + t * 128 + c4 * 32 + grp * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[c4][e] = fmaf(w4[e], v[t], acc[c4][e]);
-      }
-    float* const op = out + ((long long)blockIdx.z * Ho * Wo + pix) * 128 + grp * 4;
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      const f32x4 sc = *reinterpret_cast<const f32x4*>(ws + 128 * 49 + c4 * 32 + grp * 4), sh = *reinterpret_cast<const f32x4*>(ws + 128 * 49 + 128 + c4 * 32 + grp * 4);
-      f32x4 r;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = fmaxf(acc[c4][e] * sc[e] + sh[e], 0.f);
-      *reinterpret_cast<f32x4*>(op + c4 * 32) = r;
-    }
+    for (int e = 0; e < 4; ++e) r[e] = fmaxf(acc[c4][e] * sc[e] + sh[e], 0.f);
+    *reinterpret_cast<f32x4*>(op + c4 * 32) = r;
   }
 }
 
@@ -117,16 +98,16 @@ struct LfConvArgs {
 // grid (ceil(Wout / 32), ceil(Hout / (4 RPW)), N * ceil(Cout / 64)); 4 waves, wave w = output rows [RPW w, RPW w + RPW) of the tile,
 // 32 output columns, two 32-channel tiles.  Halo tile: ((4 RPW - 1) S + KS) x (31 S + KS) input pixels x CH channels, 16-byte chunk
 // c of pixel column lx at position c ^ sw(lx).
-// PF (round 5): the halo tile of the NEXT channel slice is requested into registers behind the first tap of the current one and written to
-// LDS at the slice boundary -- with one or two workgroups per CU nothing else hid the global latency of the staging pass (~7 us per slice
-// beside ~17 us of MFMAs at RPW = 2; profiles/r05e_loftr_layers_exact_f32.txt); same values in the same LDS places: bitwise the same output
-// FAST (late round 5): every output-channel group has both 32-channel tiles and every 32-channel slice is whole (Cout % 64 == 0, real Cin % 32 == 0:
+// The halo tile of the NEXT channel slice is requested into registers behind the first tap of the current one (fetch) and written to LDS at
+// the slice boundary (commit) -- with one or two workgroups per CU nothing else hides the global latency of the staging pass (~7 us per slice
+// beside ~17 us of MFMAs at RPW = 2; profiles/r05e_loftr_layers_exact_f32.txt)
+// FAST: every output-channel group has both 32-channel tiles and every 32-channel slice is whole (Cout % 64 == 0, real Cin % 32 == 0:
 // LoFTR's 128- and 256-channel layers) -- the MFMA stream of a tap is then ONE basic block: counters showed the matrix pipe busy 0.60-0.71 at 2.3 GHz, and
 // the disassembly why: the run-time tests of `two` and of the channel-step limit sat between the MFMAs, so every 32-channel step began with its two
 // ds_read_b128 and waited for them (the scheduler does not move loads across branches).  FAST requests the next step's fragments before the current
 // step's MFMAs.  Same MFMAs in the same order: same bits.
-template <int KS, int S, int RPW, int CH, bool PF, bool FAST = false>
-__global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_conv(LfConvArgs a) {
+template <int KS, int S, int RPW, int CH, bool FAST>
+__global__ __launch_bounds__(256, (RPW <= 2 && S == 1) ? 2 : 1) void k_lf_conv(LfConvArgs a) {
   constexpr int TAPS = KS * KS, PAD = KS / 2;
   constexpr int TH = 4 * RPW, LH = (TH - 1) * S + KS, LW = 31 * S + KS, NCH = CH / 4;
   __shared__ __attribute__((aligned(16))) float tile[LH * LW * CH];
@@ -164,8 +145,8 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
     }
   };
   load_w(wcur, 0, 0);
-  constexpr int NP = LH * LW * NCH, NQ = (NP + 255) / 256, SB = 8;
-  f32x4 pre[PF ? NQ : 1];
+  constexpr int NP = LH * LW * NCH, NQ = (NP + 255) / 256;
+  f32x4 pre[NQ];
   auto fetch = [&](int c0_) __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < NQ; ++e) {
@@ -189,33 +170,10 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
       *reinterpret_cast<f32x4*>(tile + pix * CH + ((chunk ^ sw(lx)) * 4)) = pre[e];
     }
   };
-  if (PF) fetch(0);
+  fetch(0);
   for (int c0 = 0; c0 < a.Cin; c0 += CH) {
     __syncthreads();
-    if (PF) commit();
-#pragma unroll 1
-    for (int q0 = 0; !PF && q0 < NQ; q0 += SB) {
-      f32x4 v[SB];
-#pragma unroll
-      for (int e = 0; e < SB; ++e) {
-        const int q = (q0 + e) * 256 + tid;
-        const int pix = q / NCH, chunk = q - pix * NCH;
-        const int ly = pix / LW, lx = pix - ly * LW;
-        const int gy = gy0 + ly, gx = gx0 + lx;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        v[e] = z;
-        if (q < NP && gy >= 0 && gy < a.Hin && gx >= 0 && gx < a.Win)
-          v[e] = *reinterpret_cast<const f32x4*>(in + ((long long)gy * a.Win + gx) * a.Cin + c0 + chunk * 4);
-      }
-#pragma unroll
-      for (int e = 0; e < SB; ++e) {
-        const int q = (q0 + e) * 256 + tid;
-        if (q >= NP) continue;
-        const int pix = q / NCH, chunk = q - pix * NCH;
-        const int lx = pix % LW;
-        *reinterpret_cast<f32x4*>(tile + pix * CH + ((chunk ^ sw(lx)) * 4)) = v[e];
-      }
-    }
+    commit();
     __syncthreads();
 #pragma unroll 1
     for (int tap = 0; tap < TAPS; ++tap) {
@@ -223,7 +181,7 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
       // next tap of this slice, or the first tap of the next slice (its request then also overlaps the staging of that slice)
       const bool last_tap = tap + 1 == TAPS;
       if (!last_tap || c0 + CH < a.Cin) load_w(wnxt, last_tap ? c0 + CH : c0, last_tap ? 0 : tap + 1);
-      if (PF && tap == 0 && c0 + CH < a.Cin) fetch(c0 + CH);     // behind the next tap's weights: it has two taps of MFMAs to land in
+      if (tap == 0 && c0 + CH < a.Cin) fetch(c0 + CH);     // behind the next tap's weights: it has two taps of MFMAs to land in
       if (FAST) {
         f32x4 fb2[2][RPW];
         auto read_fb = [&](int buf, int s) __attribute__((always_inline)) {
@@ -302,8 +260,8 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
 // high terms then 16 residual terms); weights are pre-split at load time with a power-of-two scale (folded into the epilogue's affine map)
 // and, per tap, fetched ONCE per workgroup into a double-buffered LDS block (per-wave fetches would make the L2 -> CU ingest the bottleneck at
 // this MFMA rate).  An activation that does not fit fp16 raises a.ovf: the caller repeats the forward on the exact kernels.
-template <int KS, int S, int RPW, int CH, bool PF>      // PF: as in k_lf_conv
-__global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_conv_h(LfConvArgs a) {
+template <int KS, int S, int RPW, int CH>
+__global__ __launch_bounds__(256, (RPW <= 2 && S == 1) ? 2 : 1) void k_lf_conv_h(LfConvArgs a) {
   typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
   typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
   constexpr int TAPS = KS * KS, PAD = KS / 2;
@@ -344,8 +302,8 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
 #pragma unroll
   for (int e = 0; e < WPT; ++e) wnext[e] = wsrc(0, 0, e);
   int par = 0;
-  constexpr int NQF = LH * LW * (CH / 4), NQ = (NQF + 255) / 256, SB = 8;
-  f32x4 pre[PF ? NQ : 1];
+  constexpr int NQF = LH * LW * (CH / 4), NQ = (NQF + 255) / 256;
+  f32x4 pre[NQ];      // the next slice's halo tile on its way to LDS, as in k_lf_conv
   auto fetch = [&](int c0_) __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < NQ; ++e) {
@@ -366,6 +324,7 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
       if (q >= NQF) continue;
       const int pix = q / (CH / 4), chunk = q - pix * (CH / 4);
       const int lx = pix % LW;
+      // channels 4 chunk .. + 3 of the slice: k-step chunk >> 2, piece 4 (chunk >> 2) + 2 term + ((chunk & 3) >> 1), 8-byte half (chunk & 1)
       const h16x4 h4 = __builtin_convertvector(pre[e], h16x4);
       const h16x4 m4 = __builtin_convertvector(pre[e] - __builtin_convertvector(h4, f32x4), h16x4);
       ovf_track(amax, pre[e].x, pre[e].y); ovf_track(amax, pre[e].z, pre[e].w);
@@ -374,39 +333,10 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
       *reinterpret_cast<h16x4*>(tb + pix * (CH * 4) + (((piece + 2) ^ sw(lx)) * 16) + sub) = m4;
     }
   };
-  if (PF) fetch(0);
+  fetch(0);
   for (int c0 = 0; c0 < a.Cin; c0 += CH) {
     __syncthreads();
-    if (PF) commit();
-#pragma unroll 1
-    for (int q0 = 0; !PF && q0 < NQ; q0 += SB) {
-      f32x4 v[SB];
-#pragma unroll
-      for (int e = 0; e < SB; ++e) {
-        const int q = (q0 + e) * 256 + tid;
-        const int pix = q / (CH / 4), chunk = q - pix * (CH / 4);
-        const int ly = pix / LW, lx = pix - ly * LW;
-        const int gy = gy0 + ly, gx = gx0 + lx;
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        v[e] = z;
-        if (q < NQF && gy >= 0 && gy < a.Hin && gx >= 0 && gx < a.Win)
-          v[e] = *reinterpret_cast<const f32x4*>(in + ((long long)gy * a.Win + gx) * a.Cin + c0 + chunk * 4);
-      }
-#pragma unroll
-      for (int e = 0; e < SB; ++e) {
-        const int q = (q0 + e) * 256 + tid;
-        if (q >= NQF) continue;
-        const int pix = q / (CH / 4), chunk = q - pix * (CH / 4);
-        const int lx = pix % LW;
-        // channels 4 chunk .. + 3 of the slice: k-step chunk >> 2, piece 4 (chunk >> 2) + 2 term + ((chunk & 3) >> 1), 8-byte half (chunk & 1)
-        const h16x4 h4 = __builtin_convertvector(v[e], h16x4);
-        const h16x4 m4 = __builtin_convertvector(v[e] - __builtin_convertvector(h4, f32x4), h16x4);
-        ovf_track(amax, v[e].x, v[e].y); ovf_track(amax, v[e].z, v[e].w);
-        const int piece = 4 * (chunk >> 2) + ((chunk & 3) >> 1), sub = (chunk & 1) * 8;
-        *reinterpret_cast<h16x4*>(tb + pix * (CH * 4) + ((piece ^ sw(lx)) * 16) + sub) = h4;
-        *reinterpret_cast<h16x4*>(tb + pix * (CH * 4) + (((piece + 2) ^ sw(lx)) * 16) + sub) = m4;
-      }
-    }
+    commit();
 #pragma unroll 1
     for (int tap = 0; tap < TAPS; ++tap) {
       const int ty = tap / KS, tx = tap - ty * KS;
@@ -418,7 +348,7 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
 #pragma unroll
         for (int e = 0; e < WPT; ++e) wnext[e] = wsrc(last_tap ? c0 + CH : c0, last_tap ? 0 : tap + 1, e);
       }
-      if (PF && tap == 0 && c0 + CH < a.Cin) fetch(c0 + CH);
+      if (tap == 0 && c0 + CH < a.Cin) fetch(c0 + CH);
       __syncthreads();     // this tap's weights (and, at tap 0, the halo tile) are in LDS; the block written two taps ago is no longer read
 #pragma unroll
       for (int s = 0; s < NKS; ++s) {
@@ -447,6 +377,8 @@ __global__ __launch_bounds__(256, (PF && RPW <= 2 && S == 1) ? 2 : 1) void k_lf_
     }
   }
   ovf_commit(a.ovf + img % a.pairs, amax);
+  // epilogue: k_lf_conv's, with the scale that carries the inverse of the weights' power-of-two scale (a copy on purpose, like `fetch`: one shared
+  // always-inline helper for the two kernels changed the instruction schedule of both -- profiles/loftr_retire_isa.json)
   const int gx = x0 + ql;
   float* out = a.out + (long long)img * a.Hout * a.Wout * a.Cout;
   const float* res = a.resid ? a.resid + (long long)img * a.Hout * a.Wout * a.Cout : nullptr;
@@ -512,7 +444,7 @@ __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x + 1.f : (exp
 
 // K^T V and sum K of one (sequence, head) over a chunk of tokens.  k / v rows with row pitch ld, head h at column h * HD; grid
 // (heads, nsplit, nseq); thread t -> (d = t / (HD / 4), v4 = (t % (HD / 4)) * 4), t < HD * HD / 4.  Partial results:
-// part[seq][split][head][HD + 1][HD] (row HD = sum K).  HD = 32 (coarse: 256 / 8) or 16 (fine: 128 / 8).
+// part[seq][split][head][HD + 1][HD] (row HD = sum K).  HD = 32 (coarse: 256 / 8); the fine level (HD = 16) has k_lf_fine_attn.
 template <int HD>
 __global__ __launch_bounds__(256) void k_lf_kv_partial(const float* k, const float* v, int ld, long long seq_stride, int S, int chunk, float vdiv, float* part, int nsplit, int heads) {
   __shared__ float ks[64][HD + 1], vs[64][HD];
@@ -564,15 +496,15 @@ __global__ __launch_bounds__(256) void k_lf_kv_reduce(const float* part, float* 
   kv[idx] = s;
 }
 // out[seq][l][h][v] = (sum_d Q[d] KV[d][v]) * Z * S, Z = 1 / (sum_d Q[d] Ksum[d] + eps), Q = elu(q) + 1.  One block = 8 tokens of one
-// sequence; thread t < heads * HD -> (head = t / HD, v = t % HD); the KV of sequence seq ^ 1 when `cross`.
+// sequence; thread t < heads * HD -> (head = t / HD, v = t % HD).  For a cross half the caller passes the KV of the OTHER side's sequences.
 template <int HD>
-__global__ __launch_bounds__(256) void k_lf_attn_apply(const float* q, int ldq, long long q_seq_stride, const float* kv, int cross, float* out, int ldo, long long o_seq_stride,
+__global__ __launch_bounds__(256) void k_lf_attn_apply(const float* q, int ldq, long long q_seq_stride, const float* kv, float* out, int ldo, long long o_seq_stride,
                                                       int L, float slen, int heads) {
   extern __shared__ float sm[];                // KV [heads][HD + 1][HD] then Q tile [8][D]
   const int D = heads * HD, KVN = heads * (HD + 1) * HD;
   const int seq = blockIdx.y, tid = threadIdx.x;
   float* kvs = sm; float* qs = sm + KVN;
-  const float* kvg = kv + (long long)(cross ? (seq ^ 1) : seq) * KVN;
+  const float* kvg = kv + (long long)seq * KVN;
   for (int i = tid; i < KVN; i += 256) kvs[i] = kvg[i];
   const int l0 = blockIdx.x * 8;
   for (int i = tid; i < 8 * D; i += 256) {
@@ -593,14 +525,13 @@ __global__ __launch_bounds__(256) void k_lf_attn_apply(const float* q, int ldq, 
 }
 
 // The fine level's linear attention in ONE launch: sequences of <= 32 tokens, 8 heads x 16 (d = 128).  One block per sequence; thread t -> (head
-// t >> 4, v = t & 15).  K^T V (values / S), sum K and the application to the block's own queries, all from LDS; the source is the sequence
-// itself or its partner seq ^ 1 (cross).  Same summation orders as k_lf_kv_partial<16> (one chunk) + k_lf_attn_apply<16>.
-// partner: the sequence attended to is seq ^ 1 (cross = 1, partner = 0: interleaved pairs), seq + partner (partner != 0: side-major buffers, the
-// other side's window of the same match) or seq itself; seq0: first sequence of the launch; nlim / per_side: sequences whose window index
-// (seq % per_side) is at or behind nlim[0] (the match count, on the device) are skipped
-__global__ __launch_bounds__(128) void k_lf_fine_attn(const float* qkv /*[nseq][S][384]*/, int S, int cross, float* out /*[nseq][S][128]*/, int seq0, int partner, const int* nlim, int per_side) {
+// t >> 4, v = t & 15).  K^T V (values / S), sum K and the application to the block's own queries, all from LDS, in the summation orders of
+// k_lf_kv_partial (one chunk) + k_lf_attn_apply.  The sequence attended to is seq + partner: 0 = itself, +- the windows of a side = the other
+// side's window of the same match (the buffers are side-major); seq0: first sequence of the launch; nlim / per_side: sequences whose window
+// index (seq % per_side) is at or behind nlim[0] (the match count, on the device) are skipped
+__global__ __launch_bounds__(128) void k_lf_fine_attn(const float* qkv /*[nseq][S][384]*/, int S, float* out /*[nseq][S][128]*/, int seq0, int partner, const int* nlim, int per_side) {
   __shared__ float qs[32][128], ks[32][129], vs[32][128];
-  const int seq = seq0 + blockIdx.x, src = partner != 0 ? seq + partner : cross ? (seq ^ 1) : seq, tid = threadIdx.x;
+  const int seq = seq0 + blockIdx.x, src = seq + partner, tid = threadIdx.x;
   if (nlim != nullptr && seq % per_side >= nlim[0]) return;
   const float vdiv = (float)S;
   for (int i = tid; i < S * 32; i += 128) {
@@ -636,15 +567,13 @@ __device__ inline float wsum(float v) {
   return v;
 }
 // LayerNorm over rows of C (128 or 256; eps 1e-5, affine), optional residual: out = (resid ? resid : 0) + LN(in).  One wave per row.
-// mode 0: every row; 1 / 2: only rows of even / odd sequences (sequence = row / seq_rows) -- the two halves of a 'cross' layer.
 // mlim / mlim_mul / mlim_seg: GemmArgs' row limit (rows r with (seg ? r % seg : r) >= mlim[0] * mul are skipped)
-__global__ __launch_bounds__(256) void k_lf_layernorm(const float* in, const float* g, const float* b, const float* resid, float* out, long long rows, int C, int seq_rows, int mode,
+__global__ __launch_bounds__(256) void k_lf_layernorm(const float* in, const float* g, const float* b, const float* resid, float* out, long long rows, int C,
                                                      const int* mlim = nullptr, int mlim_mul = 0, int mlim_seg = 0) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   if (mlim != nullptr && (mlim_seg > 0 ? row % mlim_seg : row) >= (long long)mlim[0] * mlim_mul) return;
-  if (mode != 0 && (int)((row / seq_rows) & 1) != mode - 1) return;
   // a lane owns C / 64 = 2 or 4 CONSECUTIVE values: one 8- or 16-byte access each for the row, the affine pair and the residual
   float v[4], gg[4], bb[4], rr[4] = {0.f, 0.f, 0.f, 0.f};
   const long long base = row * C;
@@ -1082,7 +1011,7 @@ struct gn_loftr {
   int *jsel = nullptr, *i_ids = nullptr, *j_ids = nullptr, *n_dev = nullptr;      // n_dev [max_pairs] per-pair counts
   int *cat = nullptr, *n_tot = nullptr;                                          // the fine level's list over all pairs (k_lf_concat) and its length
   float *k0c = nullptr, *k1c = nullptr, *mconf = nullptr;
-  float *frows = nullptr, *fc = nullptr, *fwin = nullptr, *ftok = nullptr, *fqkv = nullptr, *fatt = nullptr, *fmsg = nullptr, *fhid = nullptr, *fkvpart = nullptr, *fkv = nullptr;
+  float *frows = nullptr, *fc = nullptr, *fwin = nullptr, *ftok = nullptr, *fqkv = nullptr, *fatt = nullptr, *fmsg = nullptr, *fhid = nullptr;
   int* n_host = nullptr;
   int use_graph = 1; std::map<int, hipGraphExec_t> graph_exec; std::map<int, bool> graph_failed; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per (arithmetic, certificate, B): key 4 B + 2 certified + arithmetic
   int arith = 0;                        // gn_loftr_set_arithmetic: 0 exact f32, 1 split fp16 (f32-accurate)
@@ -1153,13 +1082,12 @@ int lf_finalise(gn_loftr* ctx) {
     }
     int rc = lf_upload(ctx, &c.scale, scale.data(), scale.size()); if (rc != GN_OK) return rc;
     rc = lf_upload(ctx, &c.shift, shift.data(), shift.size()); if (rc != GN_OK) return rc;
-    if (ci == 0) {   // stem: [128][49] as it is, and behind it the same weights as [49][128] (what k_lf_conv1<false> keeps in LDS: a coalesced copy instead of a strided gather per workgroup)
+    if (ci == 0) {   // stem: [128][49] transposed to [49][128], the order k_lf_conv1 keeps in LDS (a coalesced copy instead of a strided gather per workgroup)
       if (c.hw.size() != (size_t)128 * 49) return lf_fail(ctx, GN_ERR_SHAPE, "backbone.conv1.weight: expected [128][1][7][7]");
-      std::vector<float> both(c.hw);
-      both.resize(2 * c.hw.size());
+      std::vector<float> wt(c.hw.size());
       for (int o = 0; o < 128; ++o)
-        for (int t = 0; t < 49; ++t) both[128 * 49 + t * 128 + o] = c.hw[(size_t)o * 49 + t];
-      rc = lf_upload(ctx, &c.wf, both.data(), both.size()); if (rc != GN_OK) return rc;
+        for (int t = 0; t < 49; ++t) wt[(size_t)t * 128 + o] = c.hw[(size_t)o * 49 + t];
+      rc = lf_upload(ctx, &c.wf, wt.data(), wt.size()); if (rc != GN_OK) return rc;
       continue;
     }
     std::vector<float> wp((size_t)c.cout * c.cin_p * taps, 0.f);     // input channels padded with zeros
@@ -1195,16 +1123,16 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
   a.in = in; a.Hin = Hin; a.Win = Win; a.Cin = c.cin_p; a.wf = c.wf; a.scale = c.scale; a.shift = c.shift; a.resid = resid;
   a.out = out; a.Hout = Hin / stride; a.Wout = Win / stride; a.Cout = c.cout_p; a.act = act;
   a.wfh = c.wfh; a.scale_h = c.scale_h; a.ovf = ctx->ovf; a.pairs = N / 2;
-  a.cin_real = (gn::g_lf_conv_knob & 8) ? c.cin_p : c.cin;        // developer knob 42, bit 3: multiply the zero padding like rounds 3-4 did
+  a.cin_real = c.cin;
   const bool hm = ctx->arith == 1 && c.wfh != nullptr;
   const int og = (c.cout_p + 63) / 64;
   // rows per wave (RPW): the workgroup covers 4 RPW output rows x 32 columns x 64 channels and one workgroup fits a CU, so a launch takes
   // ceil(workgroups / 256) rounds of RPW units each -- pick the RPW with the fewest units (layer1 at 240x320: 600 workgroups = 3 rounds of 4
   // against 1200 = 5 rounds of 2; the 1/8-resolution layers fill 96 CUs with RPW = 4 and 192 with 2)
-  // (+ 0.75: the halo rows, the weight stream and the prologue a workgroup pays whatever its height -- without it RPW = 1 wins ties it loses on the GPU)
-  const bool fast = !(gn::g_lf_conv_knob & 16) && c.cout_p % 64 == 0 && a.cin_real % 32 == 0 && a.cin_real == c.cin_p;     // k_lf_conv<.., FAST> (knob 42 bit 4: off)
-  const bool pf = !(gn::g_lf_conv_knob & 1);                                   // developer knob 42, bit 0: the staging form of rounds 3-4
-  const double ovh = (gn::g_lf_conv_knob >> 8) ? (gn::g_lf_conv_knob >> 8) * 0.01 : (pf ? 0.25 : 0.75);    // bits 8..: the per-workgroup overhead of the cost model, in 1/100 units
+  // (+ 0.25: the halo rows, the weight stream and the prologue a workgroup pays whatever its height -- without it RPW = 1 wins ties it loses on the GPU;
+  // developer knob 42, bits 8..: another overhead, in 1/100 units -- the tile height must not change a bit, tests/test_gpu_fp64_loftr.py)
+  const bool fast = c.cout_p % 64 == 0 && c.cin == c.cin_p;      // k_lf_conv<.., FAST>: both 32-channel tiles in every group, every 32-channel slice whole
+  const double ovh = (gn::g_lf_conv_knob >> 8) ? (gn::g_lf_conv_knob >> 8) * 0.01 : 0.25;
   // (the model counts the workgroups of ONE pair, N = 2, whatever the batch: the kernel form a pair runs on, and with it its bits, must not depend on its neighbours)
   auto units = [&](int rpw) { const long long wg = (long long)((a.Wout + 31) / 32) * ((a.Hout + 4 * rpw - 1) / (4 * rpw)) * 2 * og; return (double)((wg + 255) / 256) * (rpw + ovh); };
   const dim3 blk(256);
@@ -1213,10 +1141,8 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
     int rpw = 4;
     if (units(2) < units(rpw)) rpw = 2;
     if (units(1) < units(rpw)) rpw = 1;
-#define LF_LAUNCH(KS_, S_, R_, C_) do { if (hm && pf) hipLaunchKernelGGL((k_lf_conv_h<KS_, S_, R_, C_, true>), grid(R_), blk, 0, s, a); \
-                                        else if (hm) hipLaunchKernelGGL((k_lf_conv_h<KS_, S_, R_, C_, false>), grid(R_), blk, 0, s, a); \
-                                        else if (pf && fast) hipLaunchKernelGGL((k_lf_conv<KS_, S_, R_, C_, true, true>), grid(R_), blk, 0, s, a); \
-                                        else if (pf) hipLaunchKernelGGL((k_lf_conv<KS_, S_, R_, C_, true>), grid(R_), blk, 0, s, a); \
+#define LF_LAUNCH(KS_, S_, R_, C_) do { if (hm) hipLaunchKernelGGL((k_lf_conv_h<KS_, S_, R_, C_>), grid(R_), blk, 0, s, a); \
+                                        else if (fast) hipLaunchKernelGGL((k_lf_conv<KS_, S_, R_, C_, true>), grid(R_), blk, 0, s, a); \
                                         else hipLaunchKernelGGL((k_lf_conv<KS_, S_, R_, C_, false>), grid(R_), blk, 0, s, a); } while (0)
     if (c.ks == 3) {
       if (rpw == 4) LF_LAUNCH(3, 1, 4, 32); else if (rpw == 2) LF_LAUNCH(3, 1, 2, 32); else LF_LAUNCH(3, 1, 1, 32);
@@ -1248,75 +1174,45 @@ void lf_gemm(const float* A, int lda, const float* A2, int lda2, int K1, const f
 
 // One LoFTREncoderLayer over the sequences of buffer x ([rows_pad][d], sequences `seq_rows` rows apart, Lseq valid tokens each):
 //   x <- x + norm2(mlp([x, norm1(merge(attn(q(x), k(src), v(src))))])).
-// cross = 0: every sequence attends to itself (mode 0 updates all).  cross = 1: sequence s attends to sequence s ^ 1; a 'cross' LAYER is
-// two calls, mode 1 (even sequences = side 0 updated from side 1) then mode 2 (odd sequences from the UPDATED even ones) -- the
-// sequential order of LocalFeatureTransformer.forward.  Projections run over the whole buffer (keeps M a multiple of 128).
-// lim (fine level only): the windows behind the match count are skipped (LfLimit; the buffers then hold the sides one behind the other:
-// side_seqs windows each, the cross partner of sequence q is q +- side_seqs)
-void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pad, int d, int cross, int mode,
-                float* qkv, float* att, float* msg, float* hid, float* kvpart, float* kv, hipStream_t s, LfLimit lim = LfLimit(), int side_seqs = 0) {
-  const int heads = kLfHeads, hd = d / heads, nall = rows_pad / seq_rows;
-  if (side_seqs > 0 && cross) {
-    // the fine level's cross halves on side-major buffers (round 5; the same split as the coarse level's below): only side a = mode - 1 is updated,
-    // only side b is attended to -- q for a's rows, k | v for b's, merge / MLP / norms over a's rows: half of what the general path computes
-    const int a = mode - 1, b = 1 - a, half = side_seqs * seq_rows;
-    LfLimit hl = lim; hl.seg = 0;                                   // one side: rows [0, n * 25) are the valid ones
-    float* xa = x + (size_t)a * half * d; const float* xb = x + (size_t)b * half * d;
-    float* qa = qkv + (size_t)a * half * 3 * d; float* kvb = qkv + (size_t)b * half * 3 * d + d;
-    float* atta = att + (size_t)a * half * d; float* msga = msg + (size_t)a * half * d; float* hida = hid + (size_t)a * half * 2 * d;
-    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, half, d, d, s, false, hl);
-    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, half, 2 * d, d, s, false, hl);
-    hipLaunchKernelGGL(k_lf_fine_attn, dim3(side_seqs), dim3(128), 0, s, qkv, Lseq, 1, att, a * side_seqs, (b - a) * side_seqs, lim.n, side_seqs);
-    lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, half, d, d, s, false, hl);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)half, d, seq_rows, 0, hl.n, hl.mul, hl.seg);
-    lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, half, 2 * d, 2 * d, s, true, hl);
-    lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, half, d, 2 * d, s, false, hl);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)half, d, seq_rows, 0, hl.n, hl.mul, hl.seg);
-    return;
+// The buffers are side-major: the sequences of side 0, then as many of side 1; the cross partner of a sequence is the one half the buffer away.
+// side < 0: a 'self' layer, every sequence attends to itself and all are updated.  side = 0 / 1: one half of a 'cross' layer -- only side a = side
+// is updated, only side b = 1 - a is attended to: q is projected for a's rows, k | v for b's, merge / MLP / norms run over a's rows alone.  A cross
+// LAYER is two calls, side 0 (from side 1) then side 1 (from the UPDATED side 0): the sequential order of LocalFeatureTransformer.forward.
+// d = 256: the coarse level (K^T V per sequence as a two-stage token reduction, its chunk and split chosen from Lseq alone); d = 128: the fine
+// level (windows of Lseq = seq_rows = 25 tokens, k_lf_fine_attn; kvpart / kv unused).  lim (fine level only): the windows behind the match count
+// are skipped (LfLimit with seg = the rows of one side)
+void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pad, int d, int side,
+                float* qkv, float* att, float* msg, float* hid, float* kvpart, float* kv, hipStream_t s, LfLimit lim = LfLimit()) {
+  const int heads = kLfHeads, per_side = rows_pad / seq_rows / 2;
+  const bool cross = side >= 0;
+  const int a = cross ? side : 0, b = cross ? 1 - side : 0;          // (self: "side a" is the whole buffer, attended to by itself)
+  const int nseq = cross ? per_side : 2 * per_side, rows = nseq * seq_rows, half = per_side * seq_rows;
+  LfLimit hl = lim;
+  if (cross) hl.seg = 0;                                            // one side: rows [0, n * 25) are the valid ones
+  float* xa = x + (size_t)a * half * d; const float* xb = x + (size_t)b * half * d;
+  float* qa = qkv + (size_t)a * half * 3 * d; float* kvb = qkv + (size_t)b * half * 3 * d + d;
+  float* atta = att + (size_t)a * half * d; float* msga = msg + (size_t)a * half * d; float* hida = hid + (size_t)a * half * 2 * d;
+  if (cross) {
+    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, rows, d, d, s, false, hl);
+    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, rows, 2 * d, d, s, false, hl);
+  } else {
+    lf_gemm(x, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qkv, 3 * d, rows, 3 * d, d, s, false, hl);
   }
-  if (cross && nall % 2 == 0 && hd == 32 && seq_rows % 128 == 0) {
-    // the coarse level's cross halves on the side-major token buffer [2][pairs] sequences: only side a = mode - 1 is updated, only side b = 1 - a is
-    // attended to (the partner of sequence s is s +- pairs) -- project q for a's rows, k | v for b's rows, and run merge / MLP / norms over a's rows
-    // alone (half the work of the general path below).  K^T V stays per sequence, its chunk and split chosen from Lseq alone
-    const int a = mode - 1, b = 1 - a, np = nall / 2, half = np * seq_rows;
-    float* xa = x + (size_t)a * half * d; const float* xb = x + (size_t)b * half * d;
-    float* qa = qkv + (size_t)a * half * 3 * d; float* kvb = qkv + (size_t)b * half * 3 * d + d;
-    float* atta = att + (size_t)a * half * d; float* msga = msg + (size_t)a * half * d; float* hida = hid + (size_t)a * half * 2 * d;
-    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, half, d, d, s);
-    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, half, 2 * d, d, s);
+  if (d == kLfDim) {
     const int chunk = 192, nsplit = (Lseq + chunk - 1) / chunk;
     const long long per = (long long)heads * 33 * 32;
-    hipLaunchKernelGGL(k_lf_kv_partial<32>, dim3(heads, nsplit, np), dim3(256), 0, s, kvb, kvb + d, 3 * d, (long long)seq_rows * 3 * d, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
-    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per * np + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, np);
     const size_t smem = (size_t)(per + 8 * d) * sizeof(float);
-    hipLaunchKernelGGL(k_lf_attn_apply<32>, dim3((Lseq + 7) / 8, np), dim3(256), smem, s, qa, 3 * d, (long long)seq_rows * 3 * d, kv, 0, atta, d, (long long)seq_rows * d, Lseq, (float)Lseq, heads);
-    lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, half, d, d, s);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)half, d, seq_rows, 0);
-    lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, half, 2 * d, 2 * d, s, true);
-    lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, half, d, 2 * d, s);
-    hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((half + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)half, d, seq_rows, 0);
-    return;
-  }
-  lf_gemm(x, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qkv, 3 * d, rows_pad, 3 * d, d, s, false, lim);
-  const int chunk = Lseq <= 64 ? 64 : 192, nsplit = (Lseq + chunk - 1) / chunk;
-  const long long per = (long long)heads * (hd + 1) * hd;
-  const size_t smem = (size_t)(per + 8 * d) * sizeof(float);
-  if (hd == 32) {
-    hipLaunchKernelGGL(k_lf_kv_partial<32>, dim3(heads, nsplit, nall), dim3(256), 0, s, qkv + d, qkv + 2 * d, 3 * d, (long long)seq_rows * 3 * d, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
-    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per * nall + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, nall);
-    hipLaunchKernelGGL(k_lf_attn_apply<32>, dim3((Lseq + 7) / 8, nall), dim3(256), smem, s, qkv, 3 * d, (long long)seq_rows * 3 * d, kv, cross, att, d, (long long)seq_rows * d, Lseq, (float)Lseq, heads);
-  } else if (Lseq <= 32 && seq_rows == Lseq && d == 128) {
-    hipLaunchKernelGGL(k_lf_fine_attn, dim3(nall), dim3(128), 0, s, qkv, Lseq, cross, att, 0, 0, lim.n, side_seqs > 0 ? side_seqs : nall);
+    hipLaunchKernelGGL(k_lf_kv_partial<32>, dim3(heads, nsplit, nseq), dim3(256), 0, s, kvb, kvb + d, 3 * d, (long long)seq_rows * 3 * d, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
+    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per * nseq + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, nseq);
+    hipLaunchKernelGGL(k_lf_attn_apply<32>, dim3((Lseq + 7) / 8, nseq), dim3(256), smem, s, qa, 3 * d, (long long)seq_rows * 3 * d, kv, atta, d, (long long)seq_rows * d, Lseq, (float)Lseq, heads);
   } else {
-    hipLaunchKernelGGL(k_lf_kv_partial<16>, dim3(heads, nsplit, nall), dim3(256), 0, s, qkv + d, qkv + 2 * d, 3 * d, (long long)seq_rows * 3 * d, Lseq, chunk, (float)Lseq, kvpart, nsplit, heads);
-    hipLaunchKernelGGL(k_lf_kv_reduce, dim3((unsigned)((per * nall + 255) / 256)), dim3(256), 0, s, kvpart, kv, nsplit, per, nall);
-    hipLaunchKernelGGL(k_lf_attn_apply<16>, dim3((Lseq + 7) / 8, nall), dim3(256), smem, s, qkv, 3 * d, (long long)seq_rows * 3 * d, kv, cross, att, d, (long long)seq_rows * d, Lseq, (float)Lseq, heads);
+    hipLaunchKernelGGL(k_lf_fine_attn, dim3(nseq), dim3(128), 0, s, qkv, Lseq, att, a * per_side, (b - a) * per_side, lim.n, per_side);
   }
-  lf_gemm(att, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msg, d, rows_pad, d, d, s, false, lim);
-  hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, s, msg, ly.n1g, ly.n1b, (const float*)nullptr, msg, (long long)rows_pad, d, seq_rows, 0, lim.n, lim.mul, lim.seg);
-  lf_gemm(x, d, msg, d, d, ly.mlp0.w, 2 * d, nullptr, hid, 2 * d, rows_pad, 2 * d, 2 * d, s, true, lim);
-  lf_gemm(hid, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, att, d, rows_pad, d, 2 * d, s, false, lim);
-  hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, s, att, ly.n2g, ly.n2b, x, x, (long long)rows_pad, d, seq_rows, mode, lim.n, lim.mul, lim.seg);
+  lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, rows, d, d, s, false, hl);
+  hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)rows, d, hl.n, hl.mul, hl.seg);
+  lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, rows, 2 * d, 2 * d, s, true, hl);
+  lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, rows, d, 2 * d, s, false, hl);
+  hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)rows, d, hl.n, hl.mul, hl.seg);
 }
 }  // namespace
 
@@ -1361,7 +1257,7 @@ int gn_loftr_create_batch(int device, int max_pairs, int H, int W, int max_match
   if (ctx->fine) {
     const size_t R = P * 2 * (size_t)ctx->Mp * kLfWW;      // window tokens of both sides
     LF_A(fc, P * 2 * (size_t)ctx->Mp * 256); LF_A(fwin, P * 2 * (size_t)ctx->Mp * 128); LF_A(frows, R * 256); LF_A(ftok, R * 128); LF_A(fqkv, R * 384); LF_A(fatt, R * 128);
-    LF_A(fmsg, R * 128); LF_A(fhid, R * 256); LF_A(fkvpart, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16); LF_A(fkv, P * 2 * (size_t)ctx->Mp * 8 * 17 * 16);
+    LF_A(fmsg, R * 128); LF_A(fhid, R * 256);
   }
 #undef LF_A
   if (hipHostMalloc((void**)&ctx->n_host, (3 * P + 8) * sizeof(int), hipHostMallocDefault) != hipSuccess) { gn_loftr_destroy(ctx); return lf_fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
@@ -1493,8 +1389,7 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   {
     const LfConv& c = ctx->conv["backbone.conv1"];
     const long long n = (long long)h2 * w2 * 8;
-    if (gn::g_lf_conv_knob & 4) hipLaunchKernelGGL(k_lf_conv1<true>, dim3((unsigned)((n + 255) / 256), 1, N), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
-    else hipLaunchKernelGGL(k_lf_conv1<false>, dim3((unsigned)((n + 255) / 256), 1, N), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
+    hipLaunchKernelGGL(k_lf_conv1, dim3((unsigned)((n + 255) / 256), 1, N), dim3(256), 0, s, ctx->img, c.wf, c.scale, c.shift, ctx->x0, H, W);
   }
   auto block = [&](const std::string& p, const float* x, int Hin, int Win, int stride, float* tmp, float* ds, float* out) {
     // y = relu(bn1(conv1(x))); y = bn2(conv2(y)); x' = stride != 1 ? bn(conv1x1(x)) : x; out = relu(x' + y)
@@ -1530,10 +1425,10 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   for (int i = 0; i < 8; ++i) {
     const LfLayer& ly = ctx->coarse[i];
     if ((i & 1) == 0) {
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 0, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, -1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
     } else {   // feat0 <- layer(feat0, feat1); then feat1 <- layer(feat1, feat0 UPDATED): two passes, each updating one side
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, 2, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
     }
   }
   if (ctx->arith == 1) hipLaunchKernelGGL(k_lf_check_finite, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->tok, tok4, ctx->ovf, (long long)Lp * 64, B);
@@ -1565,44 +1460,17 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
     const int R = 2 * Mp * kLfWW;                       // token rows; 2 * Mp * 25 is a multiple of 128 (Mp is)
     hipLaunchKernelGGL(k_lf_concat, dim3(B), dim3(256), 0, s, ctx->n_dev, M, ctx->cat, ctx->n_tot);
     hipLaunchKernelGGL(k_lf_coarse_gather, dim3((unsigned)((2LL * Mp * 64 + 255) / 256)), dim3(256), 0, s, ctx->tok, Lp, B, ctx->i_ids, ctx->j_ids, ctx->cat, M, ctx->n_tot, Mp, ctx->fc);
-    // round 5 (developer knob 42, bit 1 = the form of rounds 3-4): the fine level works on the windows of the matches there ARE (the count stays on
-    // the device: row tiles, rows and sequences behind it leave at once -- kornia's fine level runs on exactly the M matched windows) and keeps
-    // the two sides one behind the other, so that a cross half projects, merges and normalises only the side it updates
-    const bool lean = !(gn::g_lf_conv_knob & 2);
+    // the fine level works on the windows of the matches there ARE (the count stays on the device: row tiles, rows and sequences behind it leave at
+    // once -- kornia's fine level runs on exactly the M matched windows) and keeps the two sides one behind the other, ftok [2][Mp][25][128]: window q
+    // of side 0 pairs with window q + Mp, and a cross half projects, merges and normalises only the side it updates
     LfLimit lim1, lim25;
-    if (lean) { lim1.n = ctx->n_tot; lim1.mul = 1; lim1.seg = Mp; lim25.n = ctx->n_tot; lim25.mul = kLfWW; lim25.seg = Mp * kLfWW; }
+    lim1.n = ctx->n_tot; lim1.mul = 1; lim1.seg = Mp; lim25.n = ctx->n_tot; lim25.mul = kLfWW; lim25.seg = Mp * kLfWW;
     lf_gemm(ctx->fc, 256, nullptr, 0, 0, ctx->down_proj.w, 256, ctx->down_proj.b, ctx->fwin, 128, 2 * Mp, 128, 256, s, false, lim1);
     hipLaunchKernelGGL(k_lf_fine_gather, dim3((unsigned)((2LL * Mp * kLfWW * 64 + 255) / 256)), dim3(256), 0, s, ctx->x1_out, h2, w2, wc, ctx->i_ids, ctx->j_ids, ctx->cat, M, B, ctx->n_tot, Mp, ctx->fwin, ctx->frows);
     lf_gemm(ctx->frows, 256, nullptr, 0, 0, ctx->merge_feat.w, 256, ctx->merge_feat.b, ctx->ftok, 128, R, 128, 256, s, false, lim25);
-    if (lean) {
-      // ftok [2][Mp][25][128] as it is: sequence q of side 0 pairs with q + Mp
-      lf_encoder(ctx->finel[0], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 0, 0, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s, lim25, Mp);
-      lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 1, 1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s, lim25, Mp);
-      lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 1, 2, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s, lim25, Mp);
-    } else {
-    // sequences: index q in [0, 2 Mp); its cross partner must be q ^ 1 for k_lf_attn_apply -> windows are stored INTERLEAVED? No: the
-    // partner of window m of side 0 is window m of side 1, i.e. q + Mp.  The fine encoder therefore runs on a buffer re-ordered so that
-    // sequence 2 m = side 0, 2 m + 1 = side 1 (fine_reorder below does it in place through frows).
-    // (frows [2 Mp * 25][256] is free now: use its first half as the interleaved token buffer [2 Mp][25][128])
-    float* ft = ctx->frows;
-    for (int side = 0; side < 2; ++side)
-      LF_HIP(hipMemcpy2DAsync(ft + (size_t)side * kLfWW * 128, 2 * (size_t)kLfWW * 128 * sizeof(float), ctx->ftok + (size_t)side * Mp * kLfWW * 128, (size_t)kLfWW * 128 * sizeof(float),
-                              (size_t)kLfWW * 128 * sizeof(float), Mp, hipMemcpyDeviceToDevice, s));
-    for (int i = 0; i < 2; ++i) {
-      const LfLayer& ly = ctx->finel[i];
-      if (i == 0) {
-        lf_encoder(ly, ft, kLfWW, kLfWW, R, kLfFine, 0, 0, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s);
-      } else {
-        // cross: even sequences (side 0) first, then odd sequences (side 1) against the UPDATED side 0
-        lf_encoder(ly, ft, kLfWW, kLfWW, R, kLfFine, 1, 1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s);
-        lf_encoder(ly, ft, kLfWW, kLfWW, R, kLfFine, 1, 2, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, ctx->fkvpart, ctx->fkv, s);
-      }
-    }
-    // de-interleave into ftok: side 0 windows [Mp][25][128], side 1 behind them
-    for (int side = 0; side < 2; ++side)
-      LF_HIP(hipMemcpy2DAsync(ctx->ftok + (size_t)side * Mp * kLfWW * 128, (size_t)kLfWW * 128 * sizeof(float), ft + (size_t)side * kLfWW * 128, 2 * (size_t)kLfWW * 128 * sizeof(float),
-                              (size_t)kLfWW * 128 * sizeof(float), Mp, hipMemcpyDeviceToDevice, s));
-    }
+    lf_encoder(ctx->finel[0], ctx->ftok, kLfWW, kLfWW, R, kLfFine, -1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
+    lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 0, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
+    lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
     // (the refined points go into fc, dead since down_proj read it: [B][M][2]; in split arithmetic a result that is not finite raises its pair's guard word)
     hipLaunchKernelGGL(k_lf_fine_match, dim3((unsigned)(((long long)B * M + 3) / 4)), dim3(256), 0, s, ctx->ftok, ctx->ftok + (size_t)Mp * kLfWW * 128, ctx->n_tot, ctx->cat, M, ctx->k1c, ctx->fc,
                        ctx->arith == 1 ? ctx->ovf : (unsigned int*)nullptr);

@@ -221,20 +221,37 @@ def test_loftr_in_front_of_the_pose_solver(sd):
 @pytest.mark.gpu
 def test_loftr_no_matches_and_truncation(sd):
     """A featureless pair has no confident mutual maximum -> zero matches, empty (0, 2) tensors like kornia; `max_matches` below the number of
-    matches keeps the FIRST ones in ascending cell order of image0 (kornia returns all: the cap is this build's, documented in the header)."""
+    matches keeps the FIRST ones in ascending cell order of image0 (kornia returns all: the cap is this build's, documented in the header).  In
+    both arithmetics, at 128 x 160 and at 136 x 200 -- the smallest size whose convolution grids are ragged: there the capped context is called
+    twice (the second call replays the captured graph; the fine level's windows behind the cap are skipped) and the featureless pair leaves
+    every fine-level tile at once."""
     from gisnav_amd.loftr import LoFTR
     flat = torch.full((128, 160), 0.5)
-    m = LoFTR(state_dict=sd).to("cuda:0").eval()
-    out = m({"image0": flat.cuda(), "image1": flat.cuda()})
     ref = lf.loftr_forward(sd, flat, flat)
-    assert len(ref["i_ids"]) == out["keypoints0"].shape[0]
-    assert out["keypoints1"].shape == (out["keypoints0"].shape[0], 2) and out["confidence"].shape == (out["keypoints0"].shape[0],)
     i0, i1 = lf.synthetic_pair(1, 128, 160)
     full = lf.loftr_forward(sd, i0, i1)
     assert len(full["i_ids"]) > 40
-    capped = LoFTR(state_dict=sd, max_matches=40).to("cuda:0").eval()({"image0": i0.cuda(), "image1": i1.cuda()}, with_ids=True)
-    assert capped["keypoints0"].shape == (40, 2) and torch.equal(capped["i_ids"].cpu(), full["i_ids"][:40]) and torch.equal(capped["j_ids"].cpu(), full["j_ids"][:40])
-    assert (capped["keypoints1"].cpu() - full["keypoints1"][:40]).abs().max() < 2e-3
+    r0, r1 = lf.synthetic_pair(2, 136, 200)
+    ragged = lf.loftr_forward(sd, r0, r1)
+    assert len(ragged["i_ids"]) > 100
+    flat_r = torch.full((136, 200), 0.5)
+    for arithmetic in ("exact_f32", "split_fp16"):
+        m = LoFTR(state_dict=sd, arithmetic=arithmetic).to("cuda:0").eval()
+        out = m({"image0": flat.cuda(), "image1": flat.cuda()})
+        assert len(ref["i_ids"]) == out["keypoints0"].shape[0]
+        assert out["keypoints1"].shape == (out["keypoints0"].shape[0], 2) and out["confidence"].shape == (out["keypoints0"].shape[0],)
+        capped = LoFTR(state_dict=sd, arithmetic=arithmetic, max_matches=40).to("cuda:0").eval()({"image0": i0.cuda(), "image1": i1.cuda()}, with_ids=True)
+        assert capped["keypoints0"].shape == (40, 2) and torch.equal(capped["i_ids"].cpu(), full["i_ids"][:40]) and torch.equal(capped["j_ids"].cpu(), full["j_ids"][:40])
+        assert (capped["keypoints1"].cpu() - full["keypoints1"][:40]).abs().max() < 2e-3
+        m37 = LoFTR(state_dict=sd, arithmetic=arithmetic, max_matches=37).to("cuda:0").eval()
+        first, second = [m37({"image0": r0.cuda(), "image1": r1.cuda()}, with_ids=True) for _ in range(2)]
+        assert all(torch.equal(first[k], second[k]) for k in first)
+        assert second["keypoints0"].shape == (37, 2) and torch.equal(second["i_ids"].cpu(), ragged["i_ids"][:37]) and torch.equal(second["j_ids"].cpu(), ragged["j_ids"][:37])
+        assert torch.equal(second["keypoints0"].cpu(), ragged["keypoints0"][:37])
+        assert (second["confidence"].cpu() - ragged["confidence"][:37]).abs().max() < 2e-4
+        assert (second["keypoints1"].cpu() - ragged["keypoints1"][:37]).abs().max() < 2e-3
+        none = LoFTR(state_dict=sd, arithmetic=arithmetic).to("cuda:0").eval()({"image0": flat_r.cuda(), "image1": flat_r.cuda()}, with_ids=True)
+        assert none["keypoints0"].shape == (0, 2) and none["keypoints1"].shape == (0, 2) and none["confidence"].shape == (0,) and none["i_ids"].shape == (0,)
 
 
 @pytest.mark.gpu
@@ -273,36 +290,3 @@ def test_exact_f32_gemm_on_64_row_tiles_equals_the_128_row_kernel_bitwise():
             assert np.abs(outs[320][0] - ref).max() < 2e-6 * np.abs(ref).max() * np.sqrt(K)
     finally:
         eng.lib.gn_debug_set_variant(eng.ctx, 41, 320)
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("arithmetic", ["exact_f32", "split_fp16"])
-def test_loftr_round5_forms_equal_the_forms_they_replace_bitwise(arithmetic, sd):
-    """Round 5 changed HOW LoFTR's forward is computed, not what: the next channel slice's halo tile prefetched into registers, the rows-per-wave
-    choice re-fitted, the stem's weights transposed in LDS, the zero-padding channel steps of the 196-channel layers skipped, and the fine level
-    run only on the windows of the matches there are, sides one behind the other (a cross half computes the side it updates).  Developer knob 42
-    = 15 selects every old form: all outputs are identical -- at a size whose grids are ragged, with the match list capped below the number of
-    matches (windows behind the cap are skipped), and on a featureless pair (no match at all: every fine-level tile leaves at once)."""
-    from gisnav_amd.engine import PoseEngine
-    from gisnav_amd.loftr import LoFTR
-    eng = PoseEngine(0, max_batch=1, max_kpts=128, precision="f32")      # a gn_ctx to reach the process-wide developer knob
-    i0, i1 = lf.synthetic_pair(2, 136, 200)
-    flat = torch.full((136, 200), 0.5)
-    cases = [({"image0": i0.cuda(), "image1": i1.cuda()}, {}), ({"image0": i0.cuda(), "image1": i1.cuda()}, {"max_matches": 37}),
-             ({"image0": flat.cuda(), "image1": flat.cuda()}, {})]
-    try:
-        res = {}
-        for knob in (15, 0):
-            eng.lib.gn_debug_set_variant(eng.ctx, 42, knob)
-            res[knob] = []
-            for data, kw in cases:
-                m = LoFTR(state_dict=sd, arithmetic=arithmetic, **kw).to("cuda:0").eval()      # (a new context per knob: the graph is captured with it in force)
-                res[knob].append([m(data, with_ids=True) for _ in range(2)][-1])
-                del m
-    finally:
-        eng.lib.gn_debug_set_variant(eng.ctx, 42, 0)
-    assert res[0][0]["keypoints0"].shape[0] > 100 and res[0][1]["keypoints0"].shape[0] == 37 and res[0][2]["keypoints0"].shape[0] == 0
-    for old, new in zip(res[15], res[0]):
-        assert old.keys() == new.keys()
-        for k in old:
-            assert old[k].shape == new[k].shape and torch.equal(old[k], new[k]), k
