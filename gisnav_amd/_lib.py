@@ -43,6 +43,9 @@ SIGNATURES = {
                                     VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
     "gn_estimate_cov": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int,
                                   c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
+    "gn_set_distortion": (C.c_int, [VP, c_f64p, C.c_int]),
+    "gn_get_distortion": (C.c_int, [VP, c_f64p]),
+    "gn_undistort_points": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, c_f64p, C.c_int, VP, VP]),
     "gn_set_overlap": (C.c_int, [VP, C.c_int]),
     "gn_flush": (C.c_int, [VP, VP]),
     "gn_set_substreams": (C.c_int, [VP, C.c_int]),

@@ -44,6 +44,7 @@ struct Call {
   double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr; int64_t* idx = nullptr; float* score = nullptr;
   double *cov = nullptr, *sigma_hat = nullptr; uint8_t* cov_ok = nullptr; double sigma_px = 0.0;   // pose covariance (gn_estimate_cov): null = not asked for
   const double* K9 = nullptr; int min_matches = 0;
+  int dist = 0; double dk[5] = {0, 0, 0, 0, 0};   // lens distortion as the context held it when the call was issued (gn_set_distortion), by value
   int kw = 0, in_dim = 0; size_t km = 0;   // floats per keypoint, per descriptor; match-list stride (gn_kmax)
   Call() = default;
   Call(int feature, int npad, int B_, int kpt_format_, const float* desc_q_, const float* kpt_q_, const int32_t* n_q_, int stride_q_,
@@ -142,6 +143,7 @@ struct gn_ctx {
   bool cal_cols = false;
   int precision_api = 0;   // the gn_precision value gn_create was called with
   int feature = 0;         // GN_FEATURE_SIFT / GN_FEATURE_SUPERPOINT (gn_create_ex)
+  int dist_on = 0; double dist[5] = {0, 0, 0, 0, 0};      // gn_set_distortion: plumb-bob (k1, k2, p1, p2, k3) of the PnP stage; off = the pinhole kernels
   float size_q[2] = {0.f, 0.f}, size_r[2] = {0.f, 0.f};   // gn_set_image_size: (w, h) per side for the keypoint normalisation, 0 = keypoint extent
   int npad_run = 0;        // padded keypoint count the matcher runs at (<= npad, gn_set_active_kpts); buffers are laid out for it per call
   int n_layers = kMaxLayers;
@@ -1168,6 +1170,43 @@ int gn_set_image_size(gn_ctx* ctx, float w_q, float h_q, float w_r, float h_r) {
   return GN_OK;
 }
 
+int gn_set_distortion(gn_ctx* ctx, const double* d_host, int n) {
+  if (!ctx) return GN_ERR_ARG;
+  if (!d_host || n == 0) { ctx->dist_on = 0; return GN_OK; }
+  if (n == 8 || n == 12 || n == 14)
+    return fail(ctx, GN_ERR_ARG, "gn_set_distortion: the rational, thin-prism and tilted models (8, 12, 14 coefficients) are not built; plumb-bob (4 or 5) only");
+  if (n != 4 && n != 5) return fail(ctx, GN_ERR_ARG, "gn_set_distortion: n must be 0, 4 or 5 (k1, k2, p1, p2[, k3])");
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (!std::isfinite(d_host[i])) return fail(ctx, GN_ERR_ARG, "gn_set_distortion: non-finite coefficient");
+    any = any || d_host[i] != 0.0;
+  }
+  for (int i = 0; i < 5; ++i) ctx->dist[i] = i < n ? d_host[i] : 0.0;
+  ctx->dist_on = any ? 1 : 0;      // all zeros = off: the pinhole kernels run, bit for bit
+  return GN_OK;
+}
+
+int gn_get_distortion(const gn_ctx* ctx, double* d5_host) {
+  if (!ctx) return GN_ERR_ARG;
+  if (d5_host) for (int i = 0; i < 5; ++i) d5_host[i] = ctx->dist_on ? ctx->dist[i] : 0.0;
+  return ctx->dist_on;
+}
+
+int gn_undistort_points(gn_ctx* ctx, int B, const float* img, const int32_t* n_pts, int kstride, const double* K9, int to_pixels,
+                        float* out, void* stream) {
+  if (!ctx || !img || !n_pts || !K9 || !out || B < 1 || kstride < 1) return fail(ctx, GN_ERR_ARG, "bad gn_undistort_points argument");
+  GN_HIP(hipSetDevice(ctx->device));
+  UndistortArgs a;
+  a.img = img; a.n_pts = n_pts; a.kstride = kstride; a.B = B;
+  a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
+  a.dist = ctx->dist_on;
+  for (int i = 0; i < 5; ++i) a.dk[i] = ctx->dist[i];
+  a.to_pixels = to_pixels ? 1 : 0; a.out = out;
+  launch_undistort(a, (hipStream_t)stream);
+  GN_HIP(hipGetLastError());
+  return GN_OK;
+}
+
 int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int feature, gn_ctx** out) {
   gn_ctx* ctx = nullptr;
   if (!out || max_batch < 1 || max_kpts < 2) return fail(nullptr, GN_ERR_ARG, "bad gn_create argument");
@@ -1669,9 +1708,11 @@ int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int
 }
 
 namespace {
+// the context's coefficients (gn_set_distortion), null when off
+const double* dist_of(const gn_ctx* c) { return c && c->dist_on ? c->dist : nullptr; }
 // gn_pnp_ransac (cov, sigma_hat, cov_ok all null) and gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine)
 int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
-             const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
+             const double* K9, const double* dk, int iterations_count, float reproj_error_px, double confidence, int min_pts,
              double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!ctx || !obj || !img || !n_pts || !K9 || !R || !t || !n_inliers || !ok || B < 1 || B > ctx->max_batch)
     return fail(ctx, GN_ERR_ARG, "bad gn_pnp_ransac argument");
@@ -1686,6 +1727,7 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
   a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = ctx->mask_ws; a.hyp = ctx->hyp_ws; a.pts_ws = ctx->pts_ws;
   a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(ctx->sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
   a.sigma_px = sigma_px; a.cov = cov; a.sigma_hat = sigma_hat; a.cov_ok = cov_ok;
+  if (dk) { a.dist = 1; for (int i = 0; i < 5; ++i) a.dk[i] = dk[i]; }     // (null = off; the arguments travel by value, like fx .. cy)
   StageTimer tm(ctx, (hipStream_t)stream, ST_PNP);
   launch_pnp(a, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
@@ -1696,7 +1738,7 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
 int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
                   const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
                   double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream) {
-  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   0.0, nullptr, nullptr, nullptr, stream);
 }
 
@@ -1705,7 +1747,7 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_pnp_ransac_cov: null covariance output");
-  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
@@ -1784,7 +1826,7 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
     rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
                           ctx->e_mkp, ctx->e_obj, stream);
     if (rc != GN_OK) return rc;
-    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, 10, 8.0f, 0.99, v.min_matches,
                     v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream);
   }
   hipStream_t s = (hipStream_t)stream;
@@ -1797,7 +1839,7 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
   GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
-  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, 10, 8.0f, 0.99, v.min_matches,
+  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, v.dist ? v.dk : nullptr, 10, 8.0f, 0.99, v.min_matches,
                 v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp);
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
@@ -1839,6 +1881,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.dem = dem; v.H = H; v.W = W; v.K9 = K9; v.min_matches = min_matches;
   v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
   v.sigma_px = sigma_px; v.cov = cov; v.sigma_hat = sigma_hat; v.cov_ok = cov_ok;
+  v.dist = ctx->dist_on; memcpy(v.dk, ctx->dist, sizeof v.dk);      // captured now: a deferred re-run of this call (cert_pend) keeps them
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
     // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the un-shifted workspaces, on the
@@ -2043,7 +2086,7 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
   rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, nullptr, 0, 0,
                         ctx->e_mkp, ctx->e_obj, stream);
   if (rc != GN_OK) return rc;
-  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, 10, 8.0f, 0.99, min_matches,
+  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, dist_of(ctx), 10, 8.0f, 0.99, min_matches,
                   R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream);
 }
 }  // namespace

@@ -315,8 +315,18 @@ struct PnpArgs {
   double* cov = nullptr;     // [B][36]
   double* sigma_hat = nullptr;   // [B]
   uint8_t* cov_ok = nullptr;     // [B]
+  // lens distortion (gn_set_distortion): dist = 0 launches the pinhole kernels, which never read dk
+  int dist = 0;
+  double dk[5] = {0, 0, 0, 0, 0};   // plumb-bob k1, k2, p1, p2, k3
 };
 void launch_pnp(const PnpArgs& a, hipStream_t s);
+struct UndistortArgs {       // gn_undistort_points
+  const float* img; const int32_t* n_pts; int kstride; int B;
+  double fx, fy, cx, cy;
+  int dist; double dk[5];
+  int to_pixels; float* out;
+};
+void launch_undistort(const UndistortArgs& a, hipStream_t s);
 void launch_epnp_debug(const double* pws, const double* us, double* out, int n, hipStream_t s);
 
 // ---- visual-odometry matcher (TwistNode): brute-force 2-NN + ratio test ------------------------------------

@@ -457,7 +457,7 @@ __device__ int sym_eig_reg(double* A, double* V, int* ord, int lane) {   // retu
 // element a step needs from another lane is a v_readlane with compile-time lane and register.  Result: unit vector in column 0
 // of V, ord[0] = 0 (the layout sym_eig_reg's callers read).  Called by the whole (single-wave) block.
 template <int N>
-__device__ void smallest_eigvec_reg(const double* A, double* V, int* ord, int lane) {
+__device__ __forceinline__ void smallest_eigvec_reg(const double* A, double* V, int* ord, int lane) {
   const int k = lane < N ? lane : 0;
   double row[N];
 #pragma unroll
@@ -917,11 +917,57 @@ __device__ bool epnp5(Shared& sh, int lane, double Rb[3][3], double tb[3], doubl
 }
 
 // ------------------------------------------------------------------------------------------------
-struct Cam { double fx, fy, cx, cy; };
+// The camera as the kernels see it.  DIST = false is the pinhole camera every caller had before gn_set_distortion; DIST = true adds OpenCV's
+// plumb-bob coefficients (k1, k2, p1, p2, k3) [EXT: calib3d calibration.cpp / undistort.dispatch.cpp, restated, not checkable here].  Every
+// function below that touches an image point is a template on DIST: the `false` instantiations are the code this file had without distortion.
+template <bool DIST> struct CamT { double fx, fy, cx, cy; };
+template <> struct CamT<true> { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
+template <bool DIST> __device__ __forceinline__ CamT<DIST> make_cam(const PnpArgs& a) {
+  if constexpr (DIST) return {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
+  else return {a.fx, a.fy, a.cx, a.cy};
+}
+
+// cvProjectPoints2's distortion of a normalised point: xd = x c + 2 p1 x y + p2 (r2 + 2 x^2), yd = y c + p1 (r2 + 2 y^2) + 2 p2 x y with
+// c = 1 + k1 r2 + k2 r2^2 + k3 r2^3; with want_j also j = d(xd, yd) / d(x, y), row-major 2 x 2
+__device__ __forceinline__ void distort_fwd(const CamT<true>& c, double x, double y, double& xd, double& yd, bool want_j, double j[4]) {
+  const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+  const double a1 = 2.0 * x * y, a2 = r2 + 2.0 * x * x, a3 = r2 + 2.0 * y * y;
+  const double cd = 1.0 + c.k1 * r2 + c.k2 * r4 + c.k3 * r6;
+  xd = x * cd + c.p1 * a1 + c.p2 * a2;
+  yd = y * cd + c.p1 * a3 + c.p2 * a1;
+  if (want_j) {
+    const double cp = c.k1 + 2.0 * c.k2 * r2 + 3.0 * c.k3 * r4;      // dc / dr2
+    j[0] = cd + 2.0 * x * x * cp + 2.0 * c.p1 * y + 6.0 * c.p2 * x;
+    j[1] = 2.0 * x * y * cp + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    j[2] = 2.0 * x * y * cp + 2.0 * c.p1 * x + 2.0 * c.p2 * y;
+    j[3] = cd + 2.0 * y * y * cp + 6.0 * c.p1 * y + 2.0 * c.p2 * x;
+  }
+}
+// cv::undistortPoints' fixed-point iteration from (x0, y0) = K^-1 (u, v): exactly five steps (TermCriteria(COUNT, 5, 0.01)), NOT run to
+// convergence -- at the corners of a wide frame it stops short of the fixed point, and OpenCV's solvers read that value
+__device__ __forceinline__ void undistort5(const CamT<true>& c, double x0, double y0, double& x, double& y) {
+  x = x0; y = y0;
+#pragma unroll
+  for (int it = 0; it < 5; ++it) {
+    const double r2 = x * x + y * y;
+    const double icdist = 1.0 / (1.0 + ((c.k3 * r2 + c.k2) * r2 + c.k1) * r2);
+    const double dx = 2.0 * c.p1 * x * y + c.p2 * (r2 + 2.0 * x * x);
+    const double dy = c.p1 * (r2 + 2.0 * y * y) + 2.0 * c.p2 * x * y;
+    x = (x0 - dx) * icdist;
+    y = (y0 - dy) * icdist;
+  }
+}
+// normalised coordinates of image point (u, v), in double: K^-1 alone, or followed by the five undistortion steps
+template <bool DIST> __device__ __forceinline__ void normalise_pt(const CamT<DIST>& cam, float u, float v, double& x, double& y) {
+  x = ((double)u - cam.cx) / cam.fx;
+  y = ((double)v - cam.cy) / cam.fy;
+  if constexpr (DIST) { const double x0 = x, y0 = y; undistort5(cam, x0, y0, x, y); }
+}
 
 // point i's share of |e|^2 (acc[27]) and optionally of J^T J (upper, acc[0..20]) and J^T e (acc[21..26]) at the pose p = (rvec, tvec), R = R(rvec),
 // dR = dR / drvec: f32 inputs widened, everything else f64
-__device__ __forceinline__ void lm_point(const float* obj, const float* img, int i, const Cam& cam, const double p[6], const double R[3][3],
+template <bool DIST>
+__device__ __forceinline__ void lm_point(const float* obj, const float* img, int i, const CamT<DIST>& cam, const double p[6], const double R[3][3],
                                          const double dR[3][9], bool want_j, double acc[28]) {
     const double M0 = obj[3 * i], M1 = obj[3 * i + 1], M2 = obj[3 * i + 2];
     const double X = R[0][0] * M0 + R[0][1] * M1 + R[0][2] * M2 + p[3];
@@ -929,6 +975,37 @@ __device__ __forceinline__ void lm_point(const float* obj, const float* img, int
     const double Z = R[2][0] * M0 + R[2][1] * M1 + R[2][2] * M2 + p[5];
     const double z = Z != 0 ? 1.0 / Z : 1.0;
     const double x = X * z, y = Y * z;
+    if constexpr (DIST) {
+      // raw-pixel residual of the forward model with distortion; the Jacobian goes through d(xd, yd) / d(x, y)
+      double xd, yd, j4[4];
+      distort_fwd(cam, x, y, xd, yd, want_j, j4);
+      const double ex = xd * cam.fx + cam.cx - (double)img[2 * i], ey = yd * cam.fy + cam.cy - (double)img[2 * i + 1];
+      acc[27] += ex * ex + ey * ey;
+      if (want_j) {
+        double jx[6], jy[6];
+        // d(u, v) / d(X, Y, Z): x = X z, y = Y z
+        const double ax0 = cam.fx * j4[0] * z, ax1 = cam.fx * j4[1] * z, ax2 = -(ax0 * x + ax1 * y);
+        const double ay0 = cam.fy * j4[2] * z, ay1 = cam.fy * j4[3] * z, ay2 = -(ay0 * x + ay1 * y);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double dX = dR[k][0] * M0 + dR[k][1] * M1 + dR[k][2] * M2;
+          const double dY = dR[k][3] * M0 + dR[k][4] * M1 + dR[k][5] * M2;
+          const double dZ = dR[k][6] * M0 + dR[k][7] * M1 + dR[k][8] * M2;
+          jx[k] = ax0 * dX + ax1 * dY + ax2 * dZ;
+          jy[k] = ay0 * dX + ay1 * dY + ay2 * dZ;
+        }
+        jx[3] = ax0; jx[4] = ax1; jx[5] = ax2;
+        jy[3] = ay0; jy[4] = ay1; jy[5] = ay2;
+        int q = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+#pragma unroll
+          for (int c = r; c < 6; ++c) { acc[q] += jx[r] * jx[c] + jy[r] * jy[c]; ++q; }
+          acc[21 + r] += jx[r] * ex + jy[r] * ey;
+        }
+      }
+      return;
+    }
     const double ex = x * cam.fx + cam.cx - (double)img[2 * i], ey = y * cam.fy + cam.cy - (double)img[2 * i + 1];
     acc[27] += ex * ex + ey * ey;
     if (want_j) {
@@ -957,14 +1034,15 @@ __device__ __forceinline__ void lm_point(const float* obj, const float* img, int
 }
 
 // |e|^2, and optionally J^T J (upper, 21) and J^T e (6), over the n (compacted inlier) points
+template <bool DIST>
 __device__ inline double lm_accumulate(const float* obj, const float* img, int n, int lane,
-                                       const Cam& cam, const double p[6], bool want_j, double JtJ[21], double Jte[6]) {
+                                       const CamT<DIST>& cam, const double p[6], bool want_j, double JtJ[21], double Jte[6]) {
   double R[3][3], dR[3][9];
   rodrigues_v2m(p, R, dR, want_j);
   double acc[28];
 #pragma unroll
   for (int k = 0; k < 28; ++k) acc[k] = 0.0;
-  for (int i = lane; i < n; i += 64) lm_point(obj, img, i, cam, p, R, dR, want_j, acc);
+  for (int i = lane; i < n; i += 64) lm_point<DIST>(obj, img, i, cam, p, R, dR, want_j, acc);
   const int lo = want_j ? 0 : 27;
 #pragma unroll
   for (int k = 0; k < 28; ++k)
@@ -995,11 +1073,12 @@ __device__ inline void lm_step(const double JtJ[21], const double Jte[6], const 
 }
 
 // CvLevMarq(6, 2n, TermCriteria(20, FLT_EPSILON)) driven as in cvFindExtrinsicCameraParams2
-__device__ void levmarq_pose(const float* obj, const float* img, int n, int lane, const Cam& cam, double p[6]) {
+template <bool DIST>
+__device__ void levmarq_pose(const float* obj, const float* img, int n, int lane, const CamT<DIST>& cam, double p[6]) {
   double prev[6], JtJ[21], Jte[6];
   int lambda_lg10 = -3, iters = 0;
   double prev_err = 0.0;
-  double e2 = lm_accumulate(obj, img, n, lane, cam, p, true, JtJ, Jte);
+  double e2 = lm_accumulate<DIST>(obj, img, n, lane, cam, p, true, JtJ, Jte);
   for (;;) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) prev[k] = p[k];
@@ -1007,7 +1086,7 @@ __device__ void levmarq_pose(const float* obj, const float* img, int n, int lane
     if (iters == 0) prev_err = sqrt(e2);
     double err_norm;
     for (;;) {
-      err_norm = sqrt(lm_accumulate(obj, img, n, lane, cam, p, false, JtJ, Jte));
+      err_norm = sqrt(lm_accumulate<DIST>(obj, img, n, lane, cam, p, false, JtJ, Jte));
       if (err_norm > prev_err) {
         if (++lambda_lg10 <= 16) { lm_step(JtJ, Jte, prev, lambda_lg10, p); continue; }
       }
@@ -1021,7 +1100,7 @@ __device__ void levmarq_pose(const float* obj, const float* img, int n, int lane
     const double rel = sqrt(dn) / (pn > 0 ? sqrt(pn) : 1.0);
     if (iters >= 20 || rel < kFltEps) break;
     prev_err = err_norm;
-    e2 = lm_accumulate(obj, img, n, lane, cam, p, true, JtJ, Jte);
+    e2 = lm_accumulate<DIST>(obj, img, n, lane, cam, p, true, JtJ, Jte);
   }
 }
 
@@ -1059,7 +1138,8 @@ __device__ __forceinline__ int select_hypothesis(const HypResult* hyp, int nhyp,
 }
 
 // planar-structure initial guess of cvFindExtrinsicCameraParams2 (homography from the model plane)
-__device__ __noinline__ bool pnp_init_planar(Shared& sh, const float* obj, const float* img, int ninl, int lane, const Cam& cam, const double mc[3], const double Vc[3][3], double p[6]) {
+template <bool DIST>
+__device__ __noinline__ bool pnp_init_planar(Shared& sh, const float* obj, const float* img, int ninl, int lane, const CamT<DIST>& cam, const double mc[3], const double Vc[3][3], double p[6]) {
   bool init_ok = true;
     // planar structure: homography from the model plane to the normalised image
     double Rt[3][3];  // rows = principal axes (V^T)
@@ -1087,8 +1167,13 @@ __device__ __noinline__ bool pnp_init_planar(Shared& sh, const float* obj, const
       const double M0 = obj[3 * i], M1 = obj[3 * i + 1], M2 = obj[3 * i + 2];
       X = (double)(float)(Rt[0][0] * M0 + Rt[0][1] * M1 + Rt[0][2] * M2 + Tt[0]);
       Y = (double)(float)(Rt[1][0] * M0 + Rt[1][1] * M1 + Rt[1][2] * M2 + Tt[1]);
+      if constexpr (DIST) {   // the five-step undistorted point, in double; findHomography then takes its float32 copy
+        normalise_pt<true>(cam, img[2 * i], img[2 * i + 1], x, y);
+        x = (double)(float)x; y = (double)(float)y;
+      } else {
       x = (double)(float)(((double)img[2 * i] - cam.cx) / cam.fx);
       y = (double)(float)(((double)img[2 * i + 1] - cam.cy) / cam.fy);
+      }
     };
     double s4[4] = {0, 0, 0, 0};
     for (int i = lane; i < ninl; i += 64)
@@ -1321,7 +1406,8 @@ __device__ __noinline__ bool pnp_init_planar(Shared& sh, const float* obj, const
 }
 
 // non-planar initial guess of cvFindExtrinsicCameraParams2 (12 x 12 DLT)
-__device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const float* img, int ninl, int lane, const Cam& cam, const double mc[3], const double Vc[3][3], double p[6]) {
+template <bool DIST>
+__device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const float* img, int ninl, int lane, const CamT<DIST>& cam, const double mc[3], const double Vc[3][3], double p[6]) {
     // DLT: L^T L from 4 weighted sums of P P^T, P = [X Y Z 1]
     double s40[40];
 #pragma unroll
@@ -1329,7 +1415,9 @@ __device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const fl
     for (int i = lane; i < ninl; i += 64)
       {
         const double X = obj[3 * i], Y = obj[3 * i + 1], Z = obj[3 * i + 2];
-        const double x = -(((double)img[2 * i] - cam.cx) / cam.fx), y = -(((double)img[2 * i + 1] - cam.cy) / cam.fy);
+        double x, y;
+        if constexpr (DIST) { normalise_pt<true>(cam, img[2 * i], img[2 * i + 1], x, y); x = -x; y = -y; }
+        else { x = -(((double)img[2 * i] - cam.cx) / cam.fx); y = -(((double)img[2 * i + 1] - cam.cy) / cam.fy); }
         const double pp[10] = {X * X, X * Y, X * Z, X, Y * Y, Y * Z, Y, Z * Z, Z, 1.0};
         const double w = x * x + y * y;
 #pragma unroll
@@ -1394,6 +1482,7 @@ __device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const fl
 // the results in hypothesis order (hypotheses past the adapted iteration count are ignored, exactly as
 // the sequential loop would never have computed them) and refines the winner.
 constexpr int kHypPack = 8;
+template <bool DIST>
 __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
   __shared__ Shared shs[kHypPack];
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1406,7 +1495,7 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
   const float* img = a.img + (size_t)b * a.kstride * 2;
   uint8_t* mask_w = a.mask_ws + ((size_t)b * kMaxHyp + wave) * a.kstride;
   HypResult* hyp = a.hyp + (size_t)b * kMaxHyp;
-  const Cam cam = {a.fx, a.fy, a.cx, a.cy};
+  const CamT<DIST> cam = make_cam<DIST>(a);
   if (n < a.min_pts || n < 5) return;
   {
     unsigned long long rng = 0xFFFFFFFFFFFFFFFFull;
@@ -1432,8 +1521,15 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
       sh.pws[lane * 3 + 0] = obj[3 * id]; sh.pws[lane * 3 + 1] = obj[3 * id + 1]; sh.pws[lane * 3 + 2] = obj[3 * id + 2];
       // cv::undistortPoints output takes the input's depth (float32): computed in double, stored as float (oracle: solve_pnp_ransac)
       // ... and epnp::init_points re-applies the intrinsics to them: us = x fu + uc, in double
+      if constexpr (DIST) {
+        double xn, yn;
+        normalise_pt<true>(cam, img[2 * id], img[2 * id + 1], xn, yn);
+        sh.us[2 * lane] = (double)(float)xn * cam.fx + cam.cx;
+        sh.us[2 * lane + 1] = (double)(float)yn * cam.fy + cam.cy;
+      } else {
       sh.us[2 * lane] = (double)(float)(((double)img[2 * id] - cam.cx) / cam.fx) * cam.fx + cam.cx;
       sh.us[2 * lane + 1] = (double)(float)(((double)img[2 * id + 1] - cam.cy) / cam.fy) * cam.fy + cam.cy;
+      }
     }
     if (lane == 0) { sh.cam[0] = cam.fx; sh.cam[1] = cam.fy; sh.cam[2] = cam.cx; sh.cam[3] = cam.cy; }
     wave_sync();
@@ -1453,7 +1549,14 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
           const double Y = R[1][0] * M0 + R[1][1] * M1 + R[1][2] * M2 + t[1];
           const double Z = R[2][0] * M0 + R[2][1] * M1 + R[2][2] * M2 + t[2];
           const double z = Z != 0 ? 1.0 / Z : 1.0;
-          const float pu = (float)(X * z * cam.fx + cam.cx), pv = (float)(Y * z * cam.fy + cam.cy);
+          float pu, pv;
+          if constexpr (DIST) {   // PnPRansacCallback::computeError projects with the distortion and compares with the raw image points
+            double xd, yd;
+            distort_fwd(cam, X * z, Y * z, xd, yd, false, nullptr);
+            pu = (float)(xd * cam.fx + cam.cx); pv = (float)(yd * cam.fy + cam.cy);
+          } else {
+            pu = (float)(X * z * cam.fx + cam.cx); pv = (float)(Y * z * cam.fy + cam.cy);
+          }
           const float dx = img[2 * i] - pu, dy = img[2 * i + 1] - pv;
           const float e = dx * dx + dy * dy;   // float32 squared reprojection error, tested <= thr
           inl = e <= thr;
@@ -1542,13 +1645,19 @@ __device__ inline void triad3(const double p0[3], const double p1[3], const doub
   for (int i = 0; i < 3; ++i) { F[i][0] = e1[i]; F[i][1] = e2[i]; F[i][2] = e3[i]; }
 }
 
-__device__ __noinline__ bool p3p_gao(const float* obj, const float* img, const Cam& cam, double Rb[3][3], double tb[3]) {
+template <bool DIST>
+__device__ __noinline__ bool p3p_gao(const float* obj, const float* img, const CamT<DIST>& cam, double Rb[3][3], double tb[3]) {
   double X[4][3], u[4][2], f[3][3];
   for (int i = 0; i < 4; ++i) {
     for (int k = 0; k < 3; ++k) X[i][k] = (double)obj[3 * i + k];
     // cv::undistortPoints keeps the input's depth: normalised coordinates computed in double, stored as float32
+    if constexpr (DIST) {
+      normalise_pt<true>(cam, img[2 * i], img[2 * i + 1], u[i][0], u[i][1]);
+      u[i][0] = (double)(float)u[i][0]; u[i][1] = (double)(float)u[i][1];
+    } else {
     u[i][0] = (double)(float)(((double)img[2 * i] - cam.cx) / cam.fx);
     u[i][1] = (double)(float)(((double)img[2 * i + 1] - cam.cy) / cam.fy);
+    }
   }
   for (int i = 0; i < 3; ++i) {
     const double nn = sqrt(u[i][0] * u[i][0] + u[i][1] * u[i][1] + 1.0);
@@ -1614,6 +1723,7 @@ __device__ __noinline__ bool p3p_gao(const float* obj, const float* img, const C
 }
 
 constexpr int kLdsPts = 2048;   // inlier correspondences k_pnp_refine keeps in LDS (20 bytes each)
+template <bool DIST>
 __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   __shared__ Shared sh;
   __shared__ float cpts[5 * kLdsPts];
@@ -1623,14 +1733,14 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   const HypResult* hyp = a.hyp + (size_t)b * kMaxHyp;
   double* Rout = a.R + (size_t)b * 9;
   double* tout = a.t + (size_t)b * 3;
-  const Cam cam = {a.fx, a.fy, a.cx, a.cy};
+  const CamT<DIST> cam = make_cam<DIST>(a);
   long long ts[8];
   auto stamp = [&](int k) __attribute__((always_inline)) { if (a.dbg_ts) ts[k] = (long long)__builtin_amdgcn_s_memtime(); };
   stamp(0);
   if (n == 4 && a.min_pts <= 4) {   // solvePnPRansac's npoints == 4 branch: one P3P solve, every point an inlier, no refinement
     if (lane == 0) {
       double Rb[3][3], tb[3], rv[3], Rf[3][3], dummy[3][9];
-      bool ok4 = p3p_gao(a.obj + (size_t)b * a.kstride * 3, a.img + (size_t)b * a.kstride * 2, cam, Rb, tb);
+      bool ok4 = p3p_gao<DIST>(a.obj + (size_t)b * a.kstride * 3, a.img + (size_t)b * a.kstride * 2, cam, Rb, tb);
       if (ok4) {
         rodrigues_m2v(Rb, rv);                       // the reference applies cv2.Rodrigues to the returned rvec
         rodrigues_v2m(rv, Rf, dummy, false);
@@ -1737,9 +1847,9 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   stamp(2);
   bool init_ok = true;
   if (W[2] / W[1] < 1e-3) {
-    init_ok = pnp_init_planar(sh, obj, img, ninl, lane, cam, mc, Vc, p);
+    init_ok = pnp_init_planar<DIST>(sh, obj, img, ninl, lane, cam, mc, Vc, p);
   } else if (ninl >= 6) {
-    init_ok = pnp_init_dlt(sh, obj, img, ninl, lane, cam, mc, Vc, p);
+    init_ok = pnp_init_dlt<DIST>(sh, obj, img, ninl, lane, cam, mc, Vc, p);
   } else {
     init_ok = false;  // < 6 non-planar inliers: OpenCV >= 4.5 falls back to the RANSAC model
   }
@@ -1747,7 +1857,7 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   stamp(3);
   double Rf[3][3], dummy[3][9];
   if (init_ok) {
-    levmarq_pose(obj, img, ninl, lane, cam, p);
+    levmarq_pose<DIST>(obj, img, ninl, lane, cam, p);
     stamp(4);
     rodrigues_v2m(p, Rf, dummy, false);
   } else {
@@ -1784,6 +1894,7 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
 // (22 DPP reductions and a few hundred dependent f64 operations behind one pass over the points), and dealt out one wave to a workgroup they
 // would each hold a compute unit against a matcher workgroup of a concurrent stream.
 constexpr int kCovPack = 8;
+template <bool DIST>
 __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * kCovPack + slot;
@@ -1806,7 +1917,7 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   if (good) {
     const float* obj = a.obj + (size_t)b * a.kstride * 3;
     const float* img = a.img + (size_t)b * a.kstride * 2;
-    const Cam cam = {a.fx, a.fy, a.cx, a.cy};
+    const CamT<DIST> cam = make_cam<DIST>(a);
     double Rm[3][3], p[6], R[3][3], dR[3][9];
 #pragma unroll
     for (int i = 0; i < 3; ++i) { p[3 + i] = a.t[(size_t)b * 3 + i];
@@ -1818,7 +1929,7 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
 #pragma unroll
     for (int k = 0; k < 28; ++k) acc[k] = 0.0;
     for (int i = lane; i < n; i += 64)
-      if (!mask || mask[i]) lm_point(obj, img, i, cam, p, R, dR, true, acc);
+      if (!mask || mask[i]) lm_point<DIST>(obj, img, i, cam, p, R, dR, true, acc);
     double N[6][6];
     int q = 0;
 #pragma unroll
@@ -1883,6 +1994,26 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
     a.sigma_hat[b] = good ? sig : 0.0; a.cov_ok[b] = good ? 1 : 0;
   }
 }
+
+// cv2.undistortPoints(img, K, distCoeffs[, P = K]) for [B][kstride] f32 points, one thread per point; slots past a pair's n_pts are left alone.
+// Computed in double, stored as f32 (cv2's output takes the input's depth).  dist = 0: the plain (u - cx) / fx the solvers read without distortion.
+__global__ __launch_bounds__(256) void k_undistort_points(UndistortArgs a) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)a.B * a.kstride) return;
+  const int b = (int)(idx / a.kstride), i = (int)(idx - (long long)b * a.kstride);
+  if (i >= a.n_pts[b]) return;
+  const float u = a.img[2 * idx], v = a.img[2 * idx + 1];
+  double x, y;
+  if (a.dist) {
+    const CamT<true> cam = {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
+    normalise_pt<true>(cam, u, v, x, y);
+  } else {
+    const CamT<false> cam = {a.fx, a.fy, a.cx, a.cy};
+    normalise_pt<false>(cam, u, v, x, y);
+  }
+  if (a.to_pixels) { x = x * a.fx + a.cx; y = y * a.fy + a.cy; }
+  a.out[2 * idx] = (float)x; a.out[2 * idx + 1] = (float)y;
+}
 }  // namespace
 
 // test hook: EPnP on n independent 5-point sets (world points f64 [n][5][3], normalised image points
@@ -1916,9 +2047,21 @@ void launch_epnp_debug(const double* pws, const double* us, double* out, int n, 
 
 void launch_pnp(const PnpArgs& a, hipStream_t s) {
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
-  hipLaunchKernelGGL(k_pnp_hyp, dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, nh);
-  hipLaunchKernelGGL(k_pnp_refine, dim3(a.B), dim3(64), 0, s, a);
-  if (a.cov) hipLaunchKernelGGL(k_pnp_cov, dim3((a.B + kCovPack - 1) / kCovPack), dim3(64 * kCovPack), 0, s, a);
+  const dim3 gh((nh * a.B + kHypPack - 1) / kHypPack), gc((a.B + kCovPack - 1) / kCovPack);
+  if (a.dist) {      // gn_set_distortion: the plumb-bob instantiations; otherwise the pinhole code, untouched
+    hipLaunchKernelGGL(k_pnp_hyp<true>, gh, dim3(64 * kHypPack), 0, s, a, nh);
+    hipLaunchKernelGGL(k_pnp_refine<true>, dim3(a.B), dim3(64), 0, s, a);
+    if (a.cov) hipLaunchKernelGGL(k_pnp_cov<true>, gc, dim3(64 * kCovPack), 0, s, a);
+    return;
+  }
+  hipLaunchKernelGGL(k_pnp_hyp<false>, gh, dim3(64 * kHypPack), 0, s, a, nh);
+  hipLaunchKernelGGL(k_pnp_refine<false>, dim3(a.B), dim3(64), 0, s, a);
+  if (a.cov) hipLaunchKernelGGL(k_pnp_cov<false>, gc, dim3(64 * kCovPack), 0, s, a);
+}
+
+void launch_undistort(const UndistortArgs& a, hipStream_t s) {
+  const long long total = (long long)a.B * a.kstride;
+  hipLaunchKernelGGL(k_undistort_points, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
 }
 
 }  // namespace gn

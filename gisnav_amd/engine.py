@@ -357,6 +357,33 @@ class PoseEngine:
         q, r = wh_q or (0.0, 0.0), wh_r or (0.0, 0.0)
         _lib.check(self.ctx, self.lib.gn_set_image_size(self.ctx, float(q[0]), float(q[1]), float(r[0]), float(r[1])), "gn_set_image_size")
 
+    def set_distortion(self, d) -> None:
+        """cv2.solvePnPRansac's distCoeffs for the PnP stage of pnp_ransac / estimate / vo_estimate (gn_set_distortion): 4 or 5 plumb-bob
+        coefficients (k1, k2, p1, p2[, k3]); None, an empty sequence or all zeros switch it off (the default).  Sticky, captured per call."""
+        a = np.zeros(0, np.float64) if d is None else np.ascontiguousarray(np.asarray(d, np.float64).reshape(-1))
+        rc = self.lib.gn_set_distortion(self.ctx, a.ctypes.data_as(_lib.c_f64p) if a.size else None, int(a.size))
+        _lib.check(self.ctx, rc, "gn_set_distortion")
+
+    def distortion(self) -> Optional[np.ndarray]:
+        """The five coefficients in effect (gn_get_distortion), or None when distortion is off."""
+        d = np.zeros(5, np.float64)
+        rc = self.lib.gn_get_distortion(self.ctx, d.ctypes.data_as(_lib.c_f64p))
+        _lib.check(self.ctx, rc, "gn_get_distortion")
+        return d if rc == 1 else None
+
+    def undistort_points(self, img, n_pts, K: np.ndarray, to_pixels: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cv2.undistortPoints with this engine's coefficients (gn_undistort_points).  img [B,S,2] f32 pixels, n_pts [B] i32 (device) ->
+        [B,S,2] f32: normalised coordinates, or pixels again with to_pixels (cv2's P = K).  Slots past n_pts keep what `out` held (zeros
+        when it is allocated here)."""
+        B, S = img.shape[0], img.shape[1]
+        if out is None:
+            out = torch.zeros((B, S, 2), dtype=torch.float32, device=self.device)
+        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        rc = self.lib.gn_undistort_points(self.ctx, B, _ptr(img), _ptr(n_pts), S, K9.ctypes.data_as(_lib.c_f64p), int(bool(to_pixels)),
+                                          _ptr(out), self._stream())
+        _lib.check(self.ctx, rc, "gn_undistort_points")
+        return out
+
     def set_num_layers(self, n: int) -> None:
         self._n_layers = n
         _lib.check(self.ctx, self.lib.gn_set_num_layers(self.ctx, n), "gn_set_num_layers")
@@ -465,11 +492,19 @@ class PoseEngine:
 
     def pnp_ransac_host(self, obj: np.ndarray, img: np.ndarray, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
                         reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
-                        covariance: bool = False, sigma_px: float = 0.0):
+                        covariance: bool = False, sigma_px: float = 0.0, dist=None):
         """gn_pnp_ransac for ONE correspondence list given as host arrays (seam B2): obj (n, 3), img (n, 2) -> (R (3,3) f64, t (3,1) f64, n_inliers, ok)
         as host values.  One pinned staging block in ([n | pad | obj | img], one asynchronous copy), one 416-byte block out: pageable transfers of
         this size were measured to stall for ~90 ms every few dozen calls on the MI355X boxes (tools/bench_seams.py), pinned ones never.
-        covariance=True (gn_pnp_ransac_cov) appends (cov (6,6) f64, sigma, cov_ok) to the result."""
+        covariance=True (gn_pnp_ransac_cov) appends (cov (6,6) f64, sigma, cov_ok) to the result.  dist: distCoeffs for this call alone
+        (set_distortion around it, the engine's own state restored afterwards); None leaves the engine's state in charge."""
+        if dist is not None:
+            keep = self.distortion()
+            self.set_distortion(dist)
+            try:
+                return self.pnp_ransac_host(obj, img, K, iterations, reproj_px, confidence, min_pts, covariance, sigma_px)
+            finally:
+                self.set_distortion(keep)
         n = int(len(obj))
         if n > self.kmax:
             raise _lib.GnError(f"{n} correspondences exceed this context's max_kpts {self.kmax}")

@@ -6,6 +6,7 @@ host-side marshalling of the reference's `_compute_3d_points`; RANSAC, EPnP, the
 and Rodrigues run in `gn_pnp_ransac` on the GPU.  Returns None where the reference would fail
 (cv2 returning no model).  `return_covariance=True` adds the 6x6 covariance of (rvec, tvec) from the
 inliers (`gn_pnp_ransac_cov`, DESIGN.md "Pose covariance"), or None in its place when it is not defined.
+`use_distortion=True` passes `camera_info.d` as distCoeffs (`gn_set_distortion`); the default ignores it, as the reference does.
 """
 from __future__ import annotations
 
@@ -35,8 +36,20 @@ def init(device: int = 0, max_points: int = 4096) -> PoseEngine:
     return _default_engine
 
 
+def distortion_of(camera_info) -> np.ndarray:
+    """The plumb-bob coefficients of a CameraInfo-like object as distCoeffs: `d` (missing or empty = none: an empty array).  A
+    `distortion_model` other than "" or "plumb_bob" raises ValueError -- ignoring it would silently bias the pose."""
+    model = getattr(camera_info, "distortion_model", "") or ""
+    if model not in ("", "plumb_bob"):
+        raise ValueError(f"distortion model {model!r} is not supported (plumb_bob only)")
+    d = getattr(camera_info, "d", None)
+    return np.zeros(0, np.float64) if d is None else np.asarray(d, np.float64).reshape(-1)
+
+
 def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevation: Optional[np.ndarray],
-                 engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0) -> Optional[Tuple[np.ndarray, ...]]:
+                 engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0,
+                 use_distortion: bool = False) -> Optional[Tuple[np.ndarray, ...]]:
+    dist = distortion_of(camera_info) if use_distortion else None      # (checked before anything else: an unsupported model raises)
     n = len(mkp_qry)
     if n < 4:                     # cv2.solvePnPRansac asserts npoints >= 4 (the reference would raise); the shim reports "no pose"
         return None
@@ -51,7 +64,7 @@ def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevatio
     img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
     k_matrix = np.asarray(camera_info.k, dtype=np.float64).reshape((3, 3))
     res = eng.pnp_ransac_host(obj, img, k_matrix, RANSAC_ITERATIONS, min_pts=4,   # n == 4: OpenCV's P3P branch
-                              covariance=return_covariance, sigma_px=sigma_px)
+                              covariance=return_covariance, sigma_px=sigma_px, dist=dist)
     if not res[3]:
         return None
     if return_covariance:

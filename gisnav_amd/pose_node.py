@@ -29,7 +29,7 @@ class PoseNode:
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
-                 sigma_px: float = 0.0):
+                 sigma_px: float = 0.0, use_distortion: bool = False):
         from .matcher import _check_ladder
         ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
         self._engine = PoseEngine(device, max_batch=1, max_kpts=max_kpts, precision=precision, state_dict=state_dict,
@@ -56,6 +56,8 @@ class PoseNode:
         self._covariance, self._sigma_px = bool(covariance), float(sigma_px)
         self.last_covariance: Optional[np.ndarray] = None
         self.last_sigma_px = 0.0
+        # use_distortion=True: camera_info.d goes to the PnP stage as distCoeffs (gn_set_distortion); the default ignores it, like the reference
+        self._use_distortion = bool(use_distortion)
         # The DEM raster goes to the device with EVERY message, like in the reference (which never caches it): upstream re-stamps dem_msg with
         # the keypoint cloud's stamp on each message (stereo_node.py:272), so a cache keyed on the DEM's own stamp never hits on real traffic and
         # serves a stale raster to a caller that reuses a stamp.  cache_dem = True keys the device copy on the REFERENCE image's stamp instead --
@@ -74,6 +76,9 @@ class PoseNode:
     def estimate(self, camera_info: CameraInfo, msg: OrthoStereoImage) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         eng, dev = self._engine, self._engine.device
         self.last_covariance, self.last_sigma_px = None, 0.0
+        if self._use_distortion:
+            from .pose import distortion_of
+            eng.set_distortion(distortion_of(camera_info))      # (ValueError for a model other than plumb_bob)
         # pose_node.py:207-213 parses the 532-byte records with np.frombuffer and re-assembles keypoint / descriptor arrays on the host;
         # here the message bytes go to the device AS THEY ARE (GN_KPT_RECORD): k_prep reads x, y, size, angle and the descriptor
         # straight from the records

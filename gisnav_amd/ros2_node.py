@@ -62,7 +62,10 @@ def ortho_stereo_image_from_ros(msg: Any) -> OrthoStereoImage:
 
 
 def camera_info_from_ros(msg: Any) -> CameraInfo:
-    return CameraInfo(k=np.asarray(msg.k, np.float64).reshape(9), height=int(msg.height), width=int(msg.width))
+    """sensor_msgs/CameraInfo -> the wire dataclass, `d` and `distortion_model` included (read only with use_distortion=True)."""
+    d = getattr(msg, "d", None)
+    return CameraInfo(k=np.asarray(msg.k, np.float64).reshape(9), height=int(msg.height), width=int(msg.width),
+                      d=None if d is None else np.asarray(d, np.float64).reshape(-1), distortion_model=str(getattr(msg, "distortion_model", "") or ""))
 
 
 def pose_fields(r: np.ndarray, t: np.ndarray, crs: str, ref_shape, cov_rt: Optional[np.ndarray] = None) -> Optional[dict]:
@@ -106,9 +109,9 @@ def make_node_class():
     class GisnavAmdPoseNode(Node):
         """`~/pose_earth` from `/camera/camera_info` + StereoNode's pose image, computed by gisnav_amd (one message = one GPU call, ~1 ms)."""
 
-        def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", **kwargs):
+        def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", use_distortion: bool = False, **kwargs):
             super().__init__(*args, **kwargs)
-            self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True)
+            self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True, use_distortion=use_distortion)
             self._camera_info: Optional[CameraInfo] = None
             qos = QoSPresetProfiles.SENSOR_DATA.value
             self._pub = self.create_publisher(PoseWithCovarianceStamped, ROS_TOPIC_POSE_EARTH, qos)

@@ -57,10 +57,13 @@ class ImageMsg:
 
 @dataclass
 class CameraInfo:
-    """The subset of sensor_msgs/CameraInfo PoseNode touches: flat row-major 3x3 `k`."""
+    """The subset of sensor_msgs/CameraInfo PoseNode touches: flat row-major 3x3 `k`; `d` / `distortion_model` are read only by callers that
+    ask for it (`use_distortion=True`): the reference ignores them."""
     k: np.ndarray
     height: int = 0
     width: int = 0
+    d: Optional[np.ndarray] = None
+    distortion_model: str = ""
 
 
 @dataclass

@@ -296,6 +296,26 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
 
+/* Lens distortion of the PnP stage: cv2.solvePnPRansac's distCoeffs argument (the reference passes zeros, _shared.py:104-116; a real camera
+ * publishes CameraInfo.d).  d_host: HOST, n = 4 (k1, k2, p1, p2; k3 = 0) or 5 (k1, k2, p1, p2, k3) plumb-bob coefficients; NULL or n = 0
+ * switches it off, and so do coefficients that are all zero: every output is then bit for bit what it was before the call.  n = 8, 12, 14
+ * (rational, thin-prism, tilted) and non-finite values return GN_ERR_ARG (gn_last_error says why) and leave the state as it was.  Sticky
+ * host-side state like gn_set_image_size, off by default.  It applies to the PnP stage of gn_pnp_ransac(_cov), gn_estimate(_cov) and
+ * gn_vo_estimate(_cov) in every mode (gn_set_overlap, gn_set_substreams, gn_set_deferred_join, the certificate's re-runs); the coefficients
+ * are captured when a call is issued, as K9_host is: a change between two pipelined calls does not reach the earlier call.
+ * Semantics (OpenCV 4.x restated, DESIGN.md "Lens distortion"): the minimal solvers (EPnP, P3P) and the planar / DLT start read image points
+ * undistorted by cv::undistortPoints' FIVE fixed-point steps (not run to convergence); hypothesis scoring, the Levenberg-Marquardt residuals
+ * and Jacobian, and the covariance's e_i and J use the forward model with distortion against the raw image points. */
+int gn_set_distortion(gn_ctx* ctx, const double* d_host, int n);
+/* The coefficients in effect into d5_host (HOST, 5 doubles, zeros when off; may be NULL).  Returns 1 when distortion is on, 0 when off. */
+int gn_get_distortion(const gn_ctx* ctx, double* d5_host);
+/* cv2.undistortPoints(img, K, d) with the context's coefficients (gn_set_distortion) for B point lists.
+ *   img [B][kstride][2] f32 pixels, n_pts [B] int32, K9: HOST 3x3 row-major f64, out [B][kstride][2] f32 (device; slots past n_pts untouched).
+ * to_pixels = 0: normalised coordinates; 1: K re-applied (cv2's P = K).  Computed in double and stored as f32 (cv2's output takes the
+ * input's depth); five fixed-point steps, as above.  With distortion off the result is (float)((u - cx) / fx), (float)((v - cy) / fy). */
+int gn_undistort_points(gn_ctx* ctx, int B, const float* img, const int32_t* n_pts, int kstride,
+                        const double* K9_host, int to_pixels, float* out, void* stream);
+
 /* PoseNode._pose lines 246-308 for B pairs: match -> gather -> MIN_MATCHES gate -> PnP. */
 int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
                 const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
