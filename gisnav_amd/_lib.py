@@ -45,6 +45,9 @@ SIGNATURES = {
                                   c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
     "gn_set_distortion": (C.c_int, [VP, c_f64p, C.c_int]),
     "gn_get_distortion": (C.c_int, [VP, c_f64p]),
+    "gn_set_ransac": (C.c_int, [VP, C.c_int, C.c_float, C.c_double]),
+    "gn_get_ransac": (C.c_int, [VP, C.POINTER(C.c_int), c_f32p, c_f64p]),
+    "gn_ransac_last_counts": (C.c_int, [VP, C.c_int, c_i32p, c_i32p, VP]),
     "gn_undistort_points": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, c_f64p, C.c_int, VP, VP]),
     "gn_set_overlap": (C.c_int, [VP, C.c_int]),
     "gn_flush": (C.c_int, [VP, VP]),
@@ -126,6 +129,7 @@ GN_PREC_F16X2_F16_ATTN = 4
 GN_PREC_F16X2_F16X2_ATTN = 5
 GN_FEATURE_SIFT = 0
 GN_FEATURE_SUPERPOINT = 1
+GN_RANSAC_MAX_ITERATIONS = 4096
 GN_KPT_LAF = 0
 GN_KPT_XYSA = 1
 GN_KPT_RECORD = 2   # raw 532-byte KEYPOINT_DTYPE wire records (133 floats per keypoint)

@@ -45,6 +45,7 @@ struct Call {
   double *cov = nullptr, *sigma_hat = nullptr; uint8_t* cov_ok = nullptr; double sigma_px = 0.0;   // pose covariance (gn_estimate_cov): null = not asked for
   const double* K9 = nullptr; int min_matches = 0;
   int dist = 0; double dk[5] = {0, 0, 0, 0, 0};   // lens distortion as the context held it when the call was issued (gn_set_distortion), by value
+  int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac, captured the same way
   int kw = 0, in_dim = 0; size_t km = 0;   // floats per keypoint, per descriptor; match-list stride (gn_kmax)
   Call() = default;
   Call(int feature, int npad, int B_, int kpt_format_, const float* desc_q_, const float* kpt_q_, const int32_t* n_q_, int stride_q_,
@@ -99,6 +100,7 @@ struct gn_ctx {
   bool sp_enc_hm16 = false, sp_enc_fp16 = false;   // the last pass left the encoder output (sp_y) as hm16 records (gn_debug_read("sp_enc") converts)
   int head_fused = 1;      // match head: 1 = two fused sweeps that recompute the similarity tiles (no sim buffer); 0 = sim GEMM + five passes (developer knob 16)
   int head_stamps = 0;     // developer knob 17: k_head_fused writes s_memtime phase stamps into the sim buffer
+  int pnp_rounds = 0;      // developer knob 49: iterations_count <= 16 through the round path of the PnP stage too
   int pnp_stamps = 0;      // developer knob 15: k_pnp_* write s_memtime phase stamps into the sim buffer
   int ffn_compose = 1;     // with ffn_fused == 3 and ffn_fold: out_proj / to_out composed into ffn.0's weights (developer knob 28; 0 = the kernel computes the message)
   int ffn_fold = 1;        // with ffn_fused == 3: out_proj / to_out folded into the block-tail kernel (developer knob 13; 0 = separate GEMM launch)
@@ -143,6 +145,8 @@ struct gn_ctx {
   bool cal_cols = false;
   int precision_api = 0;   // the gn_precision value gn_create was called with
   int feature = 0;         // GN_FEATURE_SIFT / GN_FEATURE_SUPERPOINT (gn_create_ex)
+  int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac: what gn_estimate / gn_vo_estimate pass to the PnP stage
+  gn::PnpArgs last_pnp; bool last_pnp_valid = false; const int32_t* last_npts = nullptr;   // the most recent PnP stage (gn_ransac_last_counts)
   int dist_on = 0; double dist[5] = {0, 0, 0, 0, 0};      // gn_set_distortion: plumb-bob (k1, k2, p1, p2, k3) of the PnP stage; off = the pinhole kernels
   float size_q[2] = {0.f, 0.f}, size_r[2] = {0.f, 0.f};   // gn_set_image_size: (w, h) per side for the keypoint normalisation, 0 = keypoint extent
   int npad_run = 0;        // padded keypoint count the matcher runs at (<= npad, gn_set_active_kpts); buffers are laid out for it per call
@@ -247,6 +251,8 @@ struct gn_ctx {
   uint8_t* mask_ws = nullptr;
   float* pts_ws = nullptr;
   gn::HypResult* hyp_ws = nullptr;
+  uint8_t* rmask_ws = nullptr;             // round path of the PnP stage: [B][kRansacRound + 1][npad], whatever iterations_count
+  gn::RansacState *rstate_ws = nullptr, *rstate_base = nullptr;   // [B]; the base stays put under shift_workspaces
   std::vector<void*> allocs;
   std::vector<void*> ws_allocs;     // the max_kpts-dependent workspaces (alloc_workspace): replaced by gn_resize, weights stay
   // stage timing
@@ -829,6 +835,8 @@ int alloc_workspace(gn_ctx* ctx, int max_kpts) {
   GN_ALLOC(mask_ws, B * np * 16);
   GN_ALLOC(pts_ws, B * np * 5);
   GN_ALLOC(hyp_ws, B * 16);
+  GN_ALLOC(rmask_ws, B * np * (gn::kRansacRound + 1)); GN_ALLOC(rstate_ws, B);
+  ctx->rstate_base = ctx->rstate_ws; ctx->last_pnp_valid = false;
   GN_ALLOC(ovf_base, 16);
   ctx->ovf = ctx->ovf_base;
   ctx->lists_stride = gn::kTileListBase + 2 * (np / 128) + 8 * ((np + 255) / 256);
@@ -1190,6 +1198,24 @@ int gn_get_distortion(const gn_ctx* ctx, double* d5_host) {
   if (!ctx) return GN_ERR_ARG;
   if (d5_host) for (int i = 0; i < 5; ++i) d5_host[i] = ctx->dist_on ? ctx->dist[i] : 0.0;
   return ctx->dist_on;
+}
+
+int gn_set_ransac(gn_ctx* ctx, int iterations_count, float reproj_error_px, double confidence) {
+  if (!ctx) return GN_ERR_ARG;
+  if (iterations_count < 1 || iterations_count > GN_RANSAC_MAX_ITERATIONS)
+    return fail(ctx, GN_ERR_ARG, "gn_set_ransac: iterations_count must be in 1..4096 (GN_RANSAC_MAX_ITERATIONS)");
+  if (!(reproj_error_px > 0.0f) || !std::isfinite(reproj_error_px)) return fail(ctx, GN_ERR_ARG, "gn_set_ransac: reproj_error_px must be positive and finite");
+  if (!(confidence > 0.0 && confidence < 1.0)) return fail(ctx, GN_ERR_ARG, "gn_set_ransac: confidence must lie strictly between 0 and 1");
+  ctx->ransac_iters = iterations_count; ctx->ransac_reproj = reproj_error_px; ctx->ransac_conf = confidence;
+  return GN_OK;
+}
+
+int gn_get_ransac(const gn_ctx* ctx, int* iterations_count, float* reproj_error_px, double* confidence) {
+  if (!ctx) return GN_ERR_ARG;
+  if (iterations_count) *iterations_count = ctx->ransac_iters;
+  if (reproj_error_px) *reproj_error_px = ctx->ransac_reproj;
+  if (confidence) *confidence = ctx->ransac_conf;
+  return GN_OK;
 }
 
 int gn_undistort_points(gn_ctx* ctx, int B, const float* img, const int32_t* n_pts, int kstride, const double* K9, int to_pixels,
@@ -1718,7 +1744,8 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
     return fail(ctx, GN_ERR_ARG, "bad gn_pnp_ransac argument");
   if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
   if (kstride < 1 || kstride > ctx->npad) return fail(ctx, GN_ERR_ARG, "kstride exceeds max_kpts of this context");
-  if (iterations_count < 1 || iterations_count > 16) return fail(ctx, GN_ERR_ARG, "iterations_count must be in 1..16 (PoseNode uses 10)");
+  if (iterations_count < 1 || iterations_count > GN_RANSAC_MAX_ITERATIONS)
+    return fail(ctx, GN_ERR_ARG, "iterations_count must be in 1..4096 (GN_RANSAC_MAX_ITERATIONS; PoseNode uses 10)");
   GN_HIP(hipSetDevice(ctx->device));
   PnpArgs a;
   a.obj = obj; a.img = img; a.n_pts = n_pts; a.kstride = kstride; a.B = B;
@@ -1728,6 +1755,11 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
   a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(ctx->sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
   a.sigma_px = sigma_px; a.cov = cov; a.sigma_hat = sigma_hat; a.cov_ok = cov_ok;
   if (dk) { a.dist = 1; for (int i = 0; i < 5; ++i) a.dk[i] = dk[i]; }     // (null = off; the arguments travel by value, like fx .. cy)
+  a.rmask_ws = ctx->rmask_ws; a.rstate = ctx->rstate_ws; a.force_rounds = ctx->pnp_rounds;
+  {   // gn_ransac_last_counts: a sub-batch group's stage is the pairs [b0, b0 + B) of its call
+    const long long b0 = ctx->rstate_ws - ctx->rstate_base;
+    if (b0 == 0 || !ctx->last_pnp_valid) { ctx->last_pnp = a; ctx->last_npts = n_pts - b0; ctx->last_pnp_valid = true; }
+  }
   StageTimer tm(ctx, (hipStream_t)stream, ST_PNP);
   launch_pnp(a, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
@@ -1751,6 +1783,26 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                   sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
+int gn_ransac_last_counts(gn_ctx* ctx, int B, int32_t* niters_host, int32_t* evaluated_host, void* stream) {
+  if (!ctx || B < 1 || B > ctx->max_batch || !niters_host || !evaluated_host) return fail(ctx, GN_ERR_ARG, "bad gn_ransac_last_counts argument");
+  if (!ctx->last_pnp_valid) return fail(ctx, GN_ERR_ARG, "gn_ransac_last_counts: no PnP stage has run on this context");
+  GN_HIP(hipSetDevice(ctx->device));
+  GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+  GN_HIP(hipDeviceSynchronize());      // the stage may sit on the library's own streams (gn_set_overlap, gn_set_substreams)
+  if (ctx->last_pnp.iterations <= 16 && !ctx->last_pnp.force_rounds) {
+    // a classic stage keeps no RansacState: fold what k_pnp_hyp left, for all B pairs from the unshifted workspaces
+    PnpArgs a = ctx->last_pnp;
+    a.B = B; a.n_pts = ctx->last_npts; a.hyp = ctx->hyp_ws; a.rstate = ctx->rstate_base;
+    launch_pnp_counts(a, (hipStream_t)stream);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+  }
+  std::vector<RansacState> st((size_t)B);
+  GN_HIP(hipMemcpy(st.data(), ctx->rstate_base, (size_t)B * sizeof(RansacState), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) { niters_host[b] = st[b].niters; evaluated_host[b] = st[b].evaluated; }
+  return GN_OK;
+}
+
 namespace {
 // every per-pair workspace pointer of the context moved by `b0` pairs (sign = +1) and back (sign = -1): kernels capture
 // pointer values at launch, so a sub-batch group simply runs the ordinary path on its slice of the workspaces
@@ -1770,6 +1822,7 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   const long long km = c->npad;
   mv(c->e_idx, km * 2); mv(c->e_score, km); mv(c->e_mkp, km * 2); mv(c->e_obj, km * 3);
   mv(c->mask_ws, km * 16); mv(c->hyp_ws, 16); mv(c->pts_ws, km * 5);
+  mv(c->rmask_ws, km * (gn::kRansacRound + 1)); mv(c->rstate_ws, 1);
   for (int i = 0; i < 2; ++i) { mv(c->o_mkp[i], km * 2); mv(c->o_obj[i], km * 3); mv(c->o_nmatch[i], 1); }
   mv(c->lists, c->lists_stride);
 }
@@ -1826,7 +1879,7 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
     rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
                           ctx->e_mkp, ctx->e_obj, stream);
     if (rc != GN_OK) return rc;
-    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, 10, 8.0f, 0.99, v.min_matches,
+    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
                     v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream);
   }
   hipStream_t s = (hipStream_t)stream;
@@ -1839,7 +1892,7 @@ int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g
   GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
-  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, v.dist ? v.dk : nullptr, 10, 8.0f, 0.99, v.min_matches,
+  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
                 v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp);
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
@@ -1882,6 +1935,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
   v.sigma_px = sigma_px; v.cov = cov; v.sigma_hat = sigma_hat; v.cov_ok = cov_ok;
   v.dist = ctx->dist_on; memcpy(v.dk, ctx->dist, sizeof v.dk);      // captured now: a deferred re-run of this call (cert_pend) keeps them
+  v.ransac_iters = ctx->ransac_iters; v.ransac_reproj = ctx->ransac_reproj; v.ransac_conf = ctx->ransac_conf;
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
     // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the un-shifted workspaces, on the
@@ -2086,7 +2140,7 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
   rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, nullptr, 0, 0,
                         ctx->e_mkp, ctx->e_obj, stream);
   if (rc != GN_OK) return rc;
-  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, dist_of(ctx), 10, 8.0f, 0.99, min_matches,
+  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, dist_of(ctx), ctx->ransac_iters, ctx->ransac_reproj, ctx->ransac_conf, min_matches,
                   R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream);
 }
 }  // namespace
@@ -2463,6 +2517,7 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       {"extent", ctx->extent, B * 4}, {"nvalid", ctx->nvalid, B * 2}, {"e_mkp", ctx->e_mkp, B * np * 2},
       {"e_obj", ctx->e_obj, B * np * 3}, {"e_score", ctx->e_score, B * np},
       {"hyp", ctx->hyp_ws, B * 16 * (sizeof(gn::HypResult) / 4)},
+      {"ransac_state", ctx->rstate_ws, B * (sizeof(gn::RansacState) / 4)}, {"ransac_mask", ctx->rmask_ws, B * np * (gn::kRansacRound + 1) / 4},
       {"sp_enc", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * (ctx->sp_h / 8) * (ctx->sp_w / 8) * 128 : 0},          // SuperPoint: encoder output of the last pass, NHWC
       {"sp_scores", ctx->sp_maps[0], ctx->sp_maps[0] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},             // softmax + depth-to-space scores
       {"sp_nms", ctx->sp_maps[5], ctx->sp_maps[5] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},                // after simple_nms
@@ -2657,6 +2712,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 32) ctx->qkv_in_tail = value ? 1 : 0;
   else if (which == 33) ctx->skinny = value;
   else if (which == 48) ctx->prep_fused = value ? 1 : 0;
+  else if (which == 49) ctx->pnp_rounds = value ? 1 : 0;
   else if (which == 29) {   // CU shares for the sub-batch streams: takes effect for streams created afterwards
     GN_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 8; ++i) if (ctx->sub_s[i]) { hipStreamSynchronize(ctx->sub_s[i]); hipEventDestroy(ctx->ev_join[i]); hipStreamDestroy(ctx->sub_s[i]); ctx->sub_s[i] = nullptr; ctx->ev_join[i] = nullptr; }

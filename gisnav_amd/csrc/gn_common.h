@@ -301,6 +301,22 @@ void launch_gather(const GatherArgs& a, hipStream_t s);
 
 struct HypResult { double R[9]; double t[3]; int good; int valid; };   // one RANSAC hypothesis
 
+// Round path of the PnP stage (iterations_count > 16; DESIGN.md "RANSAC beyond 16 hypotheses"): hypotheses run kRansacRound at a time and
+// k_pnp_select folds each round into this per-pair state between two round kernels.
+#ifndef GN_RANSAC_ROUND
+#define GN_RANSAC_ROUND 64     // measured against 32 and 128 (tools/ransac_cost.py --round-lib; profiles/ransac_iters.json)
+#endif
+constexpr int kRansacRound = GN_RANSAC_ROUND;
+struct RansacState {
+  int niters;                  // the adapted iteration count so far (RANSACUpdateNumIters); starts at iterations_count
+  int max_good, best;          // the winner so far: its inlier count and hypothesis index (-1: none yet)
+  int evaluated;               // hypotheses whose EPnP and scoring were actually run
+  unsigned long long rng;      // cv::RNG state behind the subsets drawn so far
+  HypResult win;               // the winner's R, t (n == 5: hypothesis 0, whatever it scored)
+  int subs[kRansacRound][5];   // the next round's subsets, in hypothesis order
+  HypResult round[kRansacRound];   // the last round's results
+};
+
 struct PnpArgs {
   const float* obj; const float* img; const int32_t* n_pts; int kstride; int B;
   double fx, fy, cx, cy;
@@ -318,8 +334,14 @@ struct PnpArgs {
   // lens distortion (gn_set_distortion): dist = 0 launches the pinhole kernels, which never read dk
   int dist = 0;
   double dk[5] = {0, 0, 0, 0, 0};   // plumb-bob k1, k2, p1, p2, k3
+  // round path (iterations > 16, or forced by developer knob 49): the workspaces do not grow with `iterations`
+  uint8_t* rmask_ws = nullptr;   // [B][kRansacRound + 1][kstride]: one mask per hypothesis of the round in flight, then the winner's (kept by copy)
+  RansacState* rstate = nullptr; // [B]
+  int force_rounds = 0;          // developer: counts <= 16 through the round path too (same bits as the two classic launches)
 };
 void launch_pnp(const PnpArgs& a, hipStream_t s);
+// niters / evaluated of a classic (<= 16) stage into rstate[b], from the results k_pnp_hyp left in a.hyp (gn_ransac_last_counts)
+void launch_pnp_counts(const PnpArgs& a, hipStream_t s);
 struct UndistortArgs {       // gn_undistort_points
   const float* img; const int32_t* n_pts; int kstride; int B;
   double fx, fy, cx, cy;

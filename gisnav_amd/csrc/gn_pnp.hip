@@ -1472,6 +1472,77 @@ __device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const fl
   return true;
 }
 
+constexpr int kHypPack = 8;
+// One hypothesis, one wave: EPnP on the subset (lane i < 5 holds subset_of(i)), every point of the pair scored into mask_w, the result to *out.
+// k_pnp_hyp and k_pnp_round both run exactly this: `good` and the mask come from the same instructions on either path.
+template <bool DIST, class SubsetOf>
+__device__ __forceinline__ void hyp_eval(const PnpArgs& a, Shared& sh, int lane, SubsetOf subset_of, const float* obj, const float* img, int n,
+                                         const CamT<DIST>& cam, uint8_t* mask_w, HypResult* out, long long* dbg_ts) {
+  {
+    if (lane < 5) {
+      const int id = subset_of(lane);
+      sh.pws[lane * 3 + 0] = obj[3 * id]; sh.pws[lane * 3 + 1] = obj[3 * id + 1]; sh.pws[lane * 3 + 2] = obj[3 * id + 2];
+      // cv::undistortPoints output takes the input's depth (float32): computed in double, stored as float (oracle: solve_pnp_ransac)
+      // ... and epnp::init_points re-applies the intrinsics to them: us = x fu + uc, in double
+      if constexpr (DIST) {
+        double xn, yn;
+        normalise_pt<true>(cam, img[2 * id], img[2 * id + 1], xn, yn);
+        sh.us[2 * lane] = (double)(float)xn * cam.fx + cam.cx;
+        sh.us[2 * lane + 1] = (double)(float)yn * cam.fy + cam.cy;
+      } else {
+      sh.us[2 * lane] = (double)(float)(((double)img[2 * id] - cam.cx) / cam.fx) * cam.fx + cam.cx;
+      sh.us[2 * lane + 1] = (double)(float)(((double)img[2 * id + 1] - cam.cy) / cam.fy) * cam.fy + cam.cy;
+      }
+    }
+    if (lane == 0) { sh.cam[0] = cam.fx; sh.cam[1] = cam.fy; sh.cam[2] = cam.cx; sh.cam[3] = cam.cy; }
+    wave_sync();
+    double R[3][3], t[3];
+    long long ts[9];
+    if (dbg_ts) ts[0] = (long long)__builtin_amdgcn_s_memtime();
+    const bool okm = epnp5(sh, lane, R, t, nullptr, dbg_ts ? ts : nullptr);
+    int good = 0;
+    if (okm) {
+      const float thr = a.reproj * a.reproj;
+      for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        bool inl = false;
+        if (i < n) {
+          const double M0 = obj[3 * i], M1 = obj[3 * i + 1], M2 = obj[3 * i + 2];
+          const double X = R[0][0] * M0 + R[0][1] * M1 + R[0][2] * M2 + t[0];
+          const double Y = R[1][0] * M0 + R[1][1] * M1 + R[1][2] * M2 + t[1];
+          const double Z = R[2][0] * M0 + R[2][1] * M1 + R[2][2] * M2 + t[2];
+          const double z = Z != 0 ? 1.0 / Z : 1.0;
+          float pu, pv;
+          if constexpr (DIST) {   // PnPRansacCallback::computeError projects with the distortion and compares with the raw image points
+            double xd, yd;
+            distort_fwd(cam, X * z, Y * z, xd, yd, false, nullptr);
+            pu = (float)(xd * cam.fx + cam.cx); pv = (float)(yd * cam.fy + cam.cy);
+          } else {
+            pu = (float)(X * z * cam.fx + cam.cx); pv = (float)(Y * z * cam.fy + cam.cy);
+          }
+          const float dx = img[2 * i] - pu, dy = img[2 * i + 1] - pv;
+          const float e = dx * dx + dy * dy;   // float32 squared reprojection error, tested <= thr
+          inl = e <= thr;
+          mask_w[i] = inl ? 1 : 0;
+        }
+        good += __popcll(__ballot(inl));
+      }
+    }
+    if (dbg_ts && lane == 0) {   // developer: s_memtime phase stamps of this hypothesis
+      ts[7] = (long long)__builtin_amdgcn_s_memtime();
+      for (int k = 0; k < 9; ++k) dbg_ts[k] = ts[k];
+    }
+    if (lane == 0) {
+      HypResult& hr = *out;
+      hr.good = good; hr.valid = okm ? 1 : 0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { hr.t[i] = t[i];
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) hr.R[3 * i + jj] = R[i][jj]; }
+    }
+  }
+}
+
 // Two launches per batch.  k_pnp_hyp: one wave per (pair, RANSAC hypothesis) -- the RNG stream and therefore
 // the subsets do not depend on the models, so wave h replays cv::RNG to its own subset, runs EPnP and scores
 // it.  The waves are independent (own slice of LDS, no workgroup barrier) and are launched kHypPack to a
@@ -1481,7 +1552,6 @@ __device__ __noinline__ bool pnp_init_dlt(Shared& sh, const float* obj, const fl
 // one wave per pair replays the sequential `good > max(maxGood, 4)` / RANSACUpdateNumIters logic over
 // the results in hypothesis order (hypotheses past the adapted iteration count are ignored, exactly as
 // the sequential loop would never have computed them) and refines the winner.
-constexpr int kHypPack = 8;
 template <bool DIST>
 __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
   __shared__ Shared shs[kHypPack];
@@ -1514,70 +1584,122 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
         }
       }
     }
-    if (lane < 5) {
+    hyp_eval<DIST>(a, sh, lane, [&](int l) __attribute__((always_inline)) {
       int id = 0;
 #pragma unroll
-      for (int i = 0; i < 5; ++i) if (i == lane) id = idx[i];
-      sh.pws[lane * 3 + 0] = obj[3 * id]; sh.pws[lane * 3 + 1] = obj[3 * id + 1]; sh.pws[lane * 3 + 2] = obj[3 * id + 2];
-      // cv::undistortPoints output takes the input's depth (float32): computed in double, stored as float (oracle: solve_pnp_ransac)
-      // ... and epnp::init_points re-applies the intrinsics to them: us = x fu + uc, in double
-      if constexpr (DIST) {
-        double xn, yn;
-        normalise_pt<true>(cam, img[2 * id], img[2 * id + 1], xn, yn);
-        sh.us[2 * lane] = (double)(float)xn * cam.fx + cam.cx;
-        sh.us[2 * lane + 1] = (double)(float)yn * cam.fy + cam.cy;
-      } else {
-      sh.us[2 * lane] = (double)(float)(((double)img[2 * id] - cam.cx) / cam.fx) * cam.fx + cam.cx;
-      sh.us[2 * lane + 1] = (double)(float)(((double)img[2 * id + 1] - cam.cy) / cam.fy) * cam.fy + cam.cy;
-      }
-    }
-    if (lane == 0) { sh.cam[0] = cam.fx; sh.cam[1] = cam.fy; sh.cam[2] = cam.cx; sh.cam[3] = cam.cy; }
-    wave_sync();
-    double R[3][3], t[3];
-    long long ts[9];
-    if (a.dbg_ts) ts[0] = (long long)__builtin_amdgcn_s_memtime();
-    const bool okm = epnp5(sh, lane, R, t, nullptr, a.dbg_ts ? ts : nullptr);
-    int good = 0;
-    if (okm) {
-      const float thr = a.reproj * a.reproj;
-      for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        bool inl = false;
-        if (i < n) {
-          const double M0 = obj[3 * i], M1 = obj[3 * i + 1], M2 = obj[3 * i + 2];
-          const double X = R[0][0] * M0 + R[0][1] * M1 + R[0][2] * M2 + t[0];
-          const double Y = R[1][0] * M0 + R[1][1] * M1 + R[1][2] * M2 + t[1];
-          const double Z = R[2][0] * M0 + R[2][1] * M1 + R[2][2] * M2 + t[2];
-          const double z = Z != 0 ? 1.0 / Z : 1.0;
-          float pu, pv;
-          if constexpr (DIST) {   // PnPRansacCallback::computeError projects with the distortion and compares with the raw image points
-            double xd, yd;
-            distort_fwd(cam, X * z, Y * z, xd, yd, false, nullptr);
-            pu = (float)(xd * cam.fx + cam.cx); pv = (float)(yd * cam.fy + cam.cy);
-          } else {
-            pu = (float)(X * z * cam.fx + cam.cx); pv = (float)(Y * z * cam.fy + cam.cy);
-          }
-          const float dx = img[2 * i] - pu, dy = img[2 * i + 1] - pv;
-          const float e = dx * dx + dy * dy;   // float32 squared reprojection error, tested <= thr
-          inl = e <= thr;
-          mask_w[i] = inl ? 1 : 0;
-        }
-        good += __popcll(__ballot(inl));
-      }
-    }
-    if (a.dbg_ts && lane == 0) {   // developer: s_memtime phase stamps of this hypothesis
-      ts[7] = (long long)__builtin_amdgcn_s_memtime();
-      for (int k = 0; k < 9; ++k) a.dbg_ts[((size_t)b * kMaxHyp + wave) * 16 + k] = ts[k];
-    }
-    if (lane == 0) {
-      HypResult& hr = hyp[wave];
-      hr.good = good; hr.valid = okm ? 1 : 0;
+      for (int i = 0; i < 5; ++i) if (i == l) id = idx[i];
+      return id; }, obj, img, n, cam, mask_w, hyp + wave, a.dbg_ts ? a.dbg_ts + ((size_t)b * kMaxHyp + wave) * 16 : nullptr);
+  }
+}
+
+// ---- round path: iterations_count > 16 (DESIGN.md "RANSAC beyond 16 hypotheses") -----------------------------------------------------------
+// The same sequential loop, kRansacRound hypotheses at a time.  Per round: k_pnp_round (one wave per hypothesis of the round, hyp_eval on the
+// subset k_pnp_select left for it, scored into the round's own mask slot) and k_pnp_select (one wave per pair: folds the round's results in
+// hypothesis order into the pair's RansacState, keeps the round winner's mask by copy, draws the next round's subsets).  A round boundary is a
+// kernel boundary: no workgroup ever waits for another.  The host enqueues every round of the requested count; a wave whose hypothesis index
+// is at or past the pair's adapted count returns at once, so the work thrown away per pair is less than one round and no wave's cost depends
+// on its index (nothing replays cv::RNG from the seed: its state travels in RansacState).
+__device__ inline void draw_subset(unsigned long long& rng, int n, int idx[5]) {   // RANSACPointSetRegistrator::getSubset for 5 of n > 5
 #pragma unroll
-      for (int i = 0; i < 3; ++i) { hr.t[i] = t[i];
+  for (int i = 0; i < 5; ++i) {
+    for (;;) {
+      const int v = (int)(rng_next(rng) % (unsigned)n);
+      bool dup = false;
 #pragma unroll
-        for (int jj = 0; jj < 3; ++jj) hr.R[3 * i + jj] = R[i][jj]; }
+      for (int jj = 0; jj < 5; ++jj) if (jj < i && idx[jj] == v) dup = true;
+      if (!dup) { idx[i] = v; break; }
     }
   }
+}
+
+// `cnt` results, hypotheses first .. first + cnt - 1, folded in order into (niters, max_good): the `good > max(maxGood, 4)` rule with
+// RANSACUpdateNumIters after every improvement, hypotheses at or past the adapted count never counted.  Returns the last improvement (-1: none).
+__device__ inline int ransac_fold(const HypResult* res, int first, int cnt, int n, double confidence, int& niters, int& max_good) {
+  int win = -1;
+  for (int j = 0; j < cnt; ++j) {
+    if (first + j >= niters) break;
+    if (!res[j].valid) continue;
+    const int good = res[j].good;
+    if (good > (max_good > 4 ? max_good : 4)) {
+      win = j; max_good = good;
+      niters = ransac_update_iters(confidence, (double)(n - good) / n, 5, niters);
+    }
+  }
+  return win;
+}
+
+template <bool DIST>
+__global__ __launch_bounds__(64 * kHypPack) void k_pnp_round(PnpArgs a, int round, int nh) {
+  __shared__ Shared shs[kHypPack];
+  const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int id = blockIdx.x * kHypPack + slot;      // hypothesis round * kRansacRound + j of pair b
+  if (id >= nh * a.B) return;
+  const int b = id / nh, j = id - b * nh;
+  RansacState* st = a.rstate + b;
+  if (round * kRansacRound + j >= st->niters) return;   // the sequential loop stopped before this one (niters is 0 where it never starts)
+  const int n = a.n_pts[b];
+  const float* obj = a.obj + (size_t)b * a.kstride * 3;
+  const float* img = a.img + (size_t)b * a.kstride * 2;
+  uint8_t* mask_w = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + j) * a.kstride;
+  const CamT<DIST> cam = make_cam<DIST>(a);
+  const int* sub = st->subs[j];
+  hyp_eval<DIST>(a, shs[slot], lane, [&](int l) __attribute__((always_inline)) { return sub[l]; }, obj, img, n, cam, mask_w, st->round + j, nullptr);
+}
+
+// round < 0: the state before the first round.  Otherwise: behind k_pnp_round(round).
+constexpr int kSelPack = 8;
+__global__ __launch_bounds__(64 * kSelPack) void k_pnp_select(PnpArgs a, int round) {
+  const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int b = blockIdx.x * kSelPack + slot;
+  if (b >= a.B) return;
+  RansacState* st = a.rstate + b;
+  const int n = a.n_pts[b];
+  int niters, max_good = 0, best = -1, evaluated = 0;
+  unsigned long long rng = 0xFFFFFFFFFFFFFFFFull;
+  if (round < 0) {
+    // n == 5: the one EPnP solve on all five points is hypothesis 0; n == 4 (P3P) and n < min_pts run no hypothesis at all
+    niters = (n < a.min_pts || n < 5) ? 0 : (n == 5 ? 1 : a.iterations);
+  } else {
+    niters = st->niters;
+    const int first = round * kRansacRound;
+    if (first >= niters) return;
+    const int left = niters - first, cnt = left < kRansacRound ? left : kRansacRound;   // what k_pnp_round(round) ran
+    max_good = st->max_good; best = st->best; evaluated = st->evaluated + cnt; rng = st->rng;
+    int win = ransac_fold(st->round, first, cnt, n, a.confidence, niters, max_good);
+    if (n == 5) win = 0;
+    if (win >= 0) {
+      best = first + win;
+      if (lane < (int)(sizeof(HypResult) / 8))
+        reinterpret_cast<unsigned long long*>(&st->win)[lane] = reinterpret_cast<const unsigned long long*>(st->round + win)[lane];
+      const uint8_t* src = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + win) * a.kstride;
+      uint8_t* dst = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + kRansacRound) * a.kstride;
+      for (int i = lane; i < n; i += 64) dst[i] = src[i];
+    }
+  }
+  if (lane == 0) {
+    const int next = (round + 1) * kRansacRound;
+    if (next < niters) {
+      const int left = niters - next, cnt = left < kRansacRound ? left : kRansacRound;
+      int idx[5] = {0, 1, 2, 3, 4};
+      for (int j = 0; j < cnt; ++j) {
+        if (n > 5) draw_subset(rng, n, idx);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) st->subs[j][i] = idx[i];
+      }
+    }
+    st->niters = niters; st->max_good = max_good; st->best = best; st->evaluated = evaluated; st->rng = rng;
+  }
+}
+
+// gn_ransac_last_counts after a classic stage: the fold over what k_pnp_hyp left, one thread per pair
+__global__ __launch_bounds__(64) void k_pnp_counts(PnpArgs a, int nh) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= a.B) return;
+  const int n = a.n_pts[b];
+  int niters = 0, max_good = 0, evaluated = 0;
+  if (n == 5 && a.min_pts <= 5) { niters = 1; evaluated = 1; }
+  else if (!(n < a.min_pts || n < 5)) { niters = nh; evaluated = nh; ransac_fold(a.hyp + (size_t)b * kMaxHyp, 0, nh, n, a.confidence, niters, max_good); }
+  a.rstate[b].niters = niters; a.rstate[b].evaluated = evaluated;
 }
 
 // ---- P3P: cv::solvePnPRansac with npoints == 4 makes one solvePnP(SOLVEPNP_P3P) call (core/_shared.py:109-116 -> calib3d solvepnp.cpp): Gao's
@@ -1723,14 +1845,15 @@ __device__ __noinline__ bool p3p_gao(const float* obj, const float* img, const C
 }
 
 constexpr int kLdsPts = 2048;   // inlier correspondences k_pnp_refine keeps in LDS (20 bytes each)
-template <bool DIST>
+// ROUND: the winner (R, t, inlier count, mask) comes from the pair's RansacState instead of the replay over hyp_ws
+template <bool DIST, bool ROUND = false>
 __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   __shared__ Shared sh;
   __shared__ float cpts[5 * kLdsPts];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nhyp = a.iterations;
   const int n = a.n_pts[b];
-  const HypResult* hyp = a.hyp + (size_t)b * kMaxHyp;
+  const HypResult* hyp = ROUND ? &a.rstate[b].win : a.hyp + (size_t)b * kMaxHyp;
   double* Rout = a.R + (size_t)b * 9;
   double* tout = a.t + (size_t)b * 3;
   const CamT<DIST> cam = make_cam<DIST>(a);
@@ -1774,8 +1897,9 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   }
 
   // ---- sequential selection over the hypotheses ----------------------------------------------------
-  int max_good;
-  const int best = select_hypothesis(hyp, nhyp, n, a.confidence, max_good);
+  int max_good, best;
+  if constexpr (ROUND) { max_good = a.rstate[b].max_good; best = a.rstate[b].best < 0 ? -1 : 0; }
+  else best = select_hypothesis(hyp, nhyp, n, a.confidence, max_good);
   if (best < 0) {
     if (lane < 9) Rout[lane] = (lane % 4 == 0) ? 1.0 : 0.0;
     if (lane < 3) tout[lane] = 0.0;
@@ -1788,7 +1912,8 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   for (int i = 0; i < 3; ++i) { bestT[i] = hyp[best].t[i];
 #pragma unroll
     for (int jj = 0; jj < 3; ++jj) bestR[i][jj] = hyp[best].R[3 * i + jj]; }
-  const uint8_t* mask_best = a.mask_ws + ((size_t)b * kMaxHyp + best) * a.kstride;
+  const uint8_t* mask_best = ROUND ? a.rmask_ws + ((size_t)b * (kRansacRound + 1) + kRansacRound) * a.kstride
+                                   : a.mask_ws + ((size_t)b * kMaxHyp + best) * a.kstride;
 
   // ---- solvePnP(SOLVEPNP_ITERATIVE) on the inliers ---------------------------------------------
   // The inliers are compacted once (order kept) into LDS -- object points [k][3], image points [k][2] -- and every pass below (two for
@@ -1894,7 +2019,7 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
 // (22 DPP reductions and a few hundred dependent f64 operations behind one pass over the points), and dealt out one wave to a workgroup they
 // would each hold a compute unit against a matcher workgroup of a concurrent stream.
 constexpr int kCovPack = 8;
-template <bool DIST>
+template <bool DIST, bool ROUND = false>
 __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * kCovPack + slot;
@@ -1906,10 +2031,15 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   // the inlier set: every point in solvePnPRansac's `npoints == 4` / `model_points == npoints` branches (k_pnp_refine), else the winner's mask
   const uint8_t* mask = nullptr;
   if (good && !((n == 4 && a.min_pts <= 4) || (n == 5 && a.min_pts <= 5))) {
+    if constexpr (ROUND) {
+      good = a.rstate[b].best >= 0;
+      mask = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + kRansacRound) * a.kstride;
+    } else {
     int max_good;
     const int best = select_hypothesis(a.hyp + (size_t)b * kMaxHyp, a.iterations, n, a.confidence, max_good);
     good = best >= 0;
     mask = a.mask_ws + ((size_t)b * kMaxHyp + (best < 0 ? 0 : best)) * a.kstride;
+    }
   }
   double c36[36], sig = 0.0;
 #pragma unroll
@@ -2045,7 +2175,27 @@ void launch_epnp_debug(const double* pws, const double* us, double* out, int n, 
   hipLaunchKernelGGL(k_epnp_debug, dim3(n), dim3(64), 0, s, pws, us, out, (const double*)nullptr);
 }
 
+namespace {
+template <bool DIST>
+void launch_pnp_rounds(PnpArgs a, hipStream_t s) {
+  a.dbg_ts = nullptr;      // the phase stamps are laid out for the classic launches
+  const dim3 gs((a.B + kSelPack - 1) / kSelPack), gc((a.B + kCovPack - 1) / kCovPack);
+  hipLaunchKernelGGL(k_pnp_select, gs, dim3(64 * kSelPack), 0, s, a, -1);
+  for (int r = 0; r * kRansacRound < a.iterations; ++r) {
+    const int left = a.iterations - r * kRansacRound, nh = left < kRansacRound ? left : kRansacRound;
+    hipLaunchKernelGGL(k_pnp_round<DIST>, dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, r, nh);
+    hipLaunchKernelGGL(k_pnp_select, gs, dim3(64 * kSelPack), 0, s, a, r);
+  }
+  hipLaunchKernelGGL((k_pnp_refine<DIST, true>), dim3(a.B), dim3(64), 0, s, a);
+  if (a.cov) hipLaunchKernelGGL((k_pnp_cov<DIST, true>), gc, dim3(64 * kCovPack), 0, s, a);
+}
+}  // namespace
+
 void launch_pnp(const PnpArgs& a, hipStream_t s) {
+  if (a.iterations > kMaxHyp || a.force_rounds) {   // gn_api refuses counts outside 1..GN_RANSAC_MAX_ITERATIONS
+    if (a.dist) launch_pnp_rounds<true>(a, s); else launch_pnp_rounds<false>(a, s);
+    return;
+  }
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
   const dim3 gh((nh * a.B + kHypPack - 1) / kHypPack), gc((a.B + kCovPack - 1) / kCovPack);
   if (a.dist) {      // gn_set_distortion: the plumb-bob instantiations; otherwise the pinhole code, untouched
@@ -2057,6 +2207,11 @@ void launch_pnp(const PnpArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_pnp_hyp<false>, gh, dim3(64 * kHypPack), 0, s, a, nh);
   hipLaunchKernelGGL(k_pnp_refine<false>, dim3(a.B), dim3(64), 0, s, a);
   if (a.cov) hipLaunchKernelGGL(k_pnp_cov<false>, gc, dim3(64 * kCovPack), 0, s, a);
+}
+
+void launch_pnp_counts(const PnpArgs& a, hipStream_t s) {
+  const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
+  hipLaunchKernelGGL(k_pnp_counts, dim3((a.B + 63) / 64), dim3(64), 0, s, a, nh);
 }
 
 void launch_undistort(const UndistortArgs& a, hipStream_t s) {

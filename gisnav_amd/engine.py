@@ -25,6 +25,17 @@ RANSAC_ITERATIONS = 10    # _shared.py:115
 RANSAC_REPROJ_PX = 8.0    # cv2.solvePnPRansac default
 RANSAC_CONFIDENCE = 0.99  # cv2.solvePnPRansac default
 
+
+
+def check_ransac_iterations(iterations) -> int:
+    """iterationsCount as the library takes it: an integer in 1 .. GN_RANSAC_MAX_ITERATIONS (ValueError / TypeError otherwise, before any GPU call)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)):
+        raise TypeError(f"ransac iterations must be an integer, got {type(iterations).__name__}")
+    if not 1 <= int(iterations) <= _lib.GN_RANSAC_MAX_ITERATIONS:
+        raise ValueError(f"ransac iterations must be in 1..{_lib.GN_RANSAC_MAX_ITERATIONS}, got {int(iterations)}")
+    return int(iterations)
+
+
 _PRECISIONS = {"f32": _lib.GN_PREC_F32, "bf16_attn": _lib.GN_PREC_BF16_ATTN, "f32x3_bf16_attn": _lib.GN_PREC_F32X3_BF16_ATTN,
                "f16x2_bf16_attn": _lib.GN_PREC_F16X2_BF16_ATTN, "f16x2_f16_attn": _lib.GN_PREC_F16X2_F16_ATTN,
                "f16x2_f16x2_attn": _lib.GN_PREC_F16X2_F16X2_ATTN}
@@ -370,6 +381,27 @@ class PoseEngine:
         rc = self.lib.gn_get_distortion(self.ctx, d.ctypes.data_as(_lib.c_f64p))
         _lib.check(self.ctx, rc, "gn_get_distortion")
         return d if rc == 1 else None
+
+    def set_ransac(self, iterations: int = RANSAC_ITERATIONS, reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE) -> None:
+        """cv2.solvePnPRansac's iterationsCount / reprojectionError / confidence for the PnP stage inside estimate / vo_estimate and the
+        certificate's re-runs (gn_set_ransac): 1 .. 4096 hypotheses.  Sticky, captured per call; the default is the reference's (10, 8.0, 0.99).
+        pnp_ransac / pnp_ransac_host take theirs as arguments."""
+        iterations = check_ransac_iterations(iterations)
+        _lib.check(self.ctx, self.lib.gn_set_ransac(self.ctx, iterations, float(reproj_px), float(confidence)), "gn_set_ransac")
+
+    def ransac(self) -> Tuple[int, float, float]:
+        """(iterations, reproj_px, confidence) in effect (gn_get_ransac)."""
+        it, px, conf = C.c_int(0), C.c_float(0.0), C.c_double(0.0)
+        _lib.check(self.ctx, self.lib.gn_get_ransac(self.ctx, C.byref(it), C.byref(px), C.byref(conf)), "gn_get_ransac")
+        return int(it.value), float(px.value), float(conf.value)
+
+    def ransac_last_counts(self, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Per pair of the most recent PnP stage: (final adapted iteration count, hypotheses actually evaluated), int32 [B] each
+        (gn_ransac_last_counts).  Synchronises the device."""
+        niters, evaluated = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        rc = self.lib.gn_ransac_last_counts(self.ctx, int(B), niters.ctypes.data_as(_lib.c_i32p), evaluated.ctypes.data_as(_lib.c_i32p), self._stream())
+        _lib.check(self.ctx, rc, "gn_ransac_last_counts")
+        return niters, evaluated
 
     def undistort_points(self, img, n_pts, K: np.ndarray, to_pixels: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """cv2.undistortPoints with this engine's coefficients (gn_undistort_points).  img [B,S,2] f32 pixels, n_pts [B] i32 (device) ->

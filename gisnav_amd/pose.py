@@ -7,6 +7,8 @@ and Rodrigues run in `gn_pnp_ransac` on the GPU.  Returns None where the referen
 (cv2 returning no model).  `return_covariance=True` adds the 6x6 covariance of (rvec, tvec) from the
 inliers (`gn_pnp_ransac_cov`, DESIGN.md "Pose covariance"), or None in its place when it is not defined.
 `use_distortion=True` passes `camera_info.d` as distCoeffs (`gn_set_distortion`); the default ignores it, as the reference does.
+`ransac_iterations=N` (1 .. 4096) is cv2.solvePnPRansac's iterationsCount for this call; the default is the reference's 10, and the
+engine's own `set_ransac` state is neither read nor changed.
 """
 from __future__ import annotations
 
@@ -15,7 +17,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .engine import PoseEngine, RANSAC_ITERATIONS
+from .engine import PoseEngine, RANSAC_ITERATIONS, check_ransac_iterations
 
 _default_engine: Optional[PoseEngine] = None
 
@@ -48,7 +50,8 @@ def distortion_of(camera_info) -> np.ndarray:
 
 def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevation: Optional[np.ndarray],
                  engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0,
-                 use_distortion: bool = False) -> Optional[Tuple[np.ndarray, ...]]:
+                 use_distortion: bool = False, ransac_iterations: Optional[int] = None) -> Optional[Tuple[np.ndarray, ...]]:
+    iterations = RANSAC_ITERATIONS if ransac_iterations is None else check_ransac_iterations(ransac_iterations)
     dist = distortion_of(camera_info) if use_distortion else None      # (checked before anything else: an unsupported model raises)
     n = len(mkp_qry)
     if n < 4:                     # cv2.solvePnPRansac asserts npoints >= 4 (the reference would raise); the shim reports "no pose"
@@ -63,7 +66,7 @@ def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevatio
         obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
     img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
     k_matrix = np.asarray(camera_info.k, dtype=np.float64).reshape((3, 3))
-    res = eng.pnp_ransac_host(obj, img, k_matrix, RANSAC_ITERATIONS, min_pts=4,   # n == 4: OpenCV's P3P branch
+    res = eng.pnp_ransac_host(obj, img, k_matrix, iterations, min_pts=4,   # n == 4: OpenCV's P3P branch
                               covariance=return_covariance, sigma_px=sigma_px, dist=dist)
     if not res[3]:
         return None

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MIN_MATCHES, PoseEngine
+from .engine import MIN_MATCHES, RANSAC_ITERATIONS, PoseEngine, check_ransac_iterations
 from .wire import CameraInfo, OrthoStereoImage, pack_keypoints
 
 
@@ -29,8 +29,9 @@ class PoseNode:
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
-                 sigma_px: float = 0.0, use_distortion: bool = False):
+                 sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS):
         from .matcher import _check_ladder
+        ransac_iterations = check_ransac_iterations(ransac_iterations)      # (refused before any device work)
         ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
         self._engine = PoseEngine(device, max_batch=1, max_kpts=max_kpts, precision=precision, state_dict=state_dict,
                                   n_layers=9, filter_threshold=self.CONFIDENCE_THRESHOLD, guard="sync")
@@ -58,6 +59,10 @@ class PoseNode:
         self.last_sigma_px = 0.0
         # use_distortion=True: camera_info.d goes to the PnP stage as distCoeffs (gn_set_distortion); the default ignores it, like the reference
         self._use_distortion = bool(use_distortion)
+        # ransac_iterations: cv2.solvePnPRansac's iterationsCount (gn_set_ransac); the default is the reference's 10 and leaves the context untouched
+        self.ransac_iterations = ransac_iterations
+        if ransac_iterations != RANSAC_ITERATIONS:
+            self._engine.set_ransac(iterations=ransac_iterations)
         # The DEM raster goes to the device with EVERY message, like in the reference (which never caches it): upstream re-stamps dem_msg with
         # the keypoint cloud's stamp on each message (stereo_node.py:272), so a cache keyed on the DEM's own stamp never hits on real traffic and
         # serves a stale raster to a caller that reuses a stamp.  cache_dem = True keys the device copy on the REFERENCE image's stamp instead --

@@ -109,9 +109,11 @@ def make_node_class():
     class GisnavAmdPoseNode(Node):
         """`~/pose_earth` from `/camera/camera_info` + StereoNode's pose image, computed by gisnav_amd (one message = one GPU call, ~1 ms)."""
 
-        def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", use_distortion: bool = False, **kwargs):
+        def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", use_distortion: bool = False,
+                     ransac_iterations: int = 10, **kwargs):
             super().__init__(*args, **kwargs)
-            self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True, use_distortion=use_distortion)
+            self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True, use_distortion=use_distortion,
+                                  ransac_iterations=ransac_iterations)
             self._camera_info: Optional[CameraInfo] = None
             qos = QoSPresetProfiles.SENSOR_DATA.value
             self._pub = self.create_publisher(PoseWithCovarianceStamped, ROS_TOPIC_POSE_EARTH, qos)

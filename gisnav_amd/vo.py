@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import PoseEngine
+from .engine import PoseEngine, check_ransac_iterations
 
 CONFIDENCE_THRESHOLD = 0.7   # twist_node.py:54
 MIN_MATCHES = 30             # twist_node.py:57
@@ -71,8 +71,18 @@ class BFMatcher:
 
 def twist_pose(engine: PoseEngine, k_matrix: np.ndarray, kp_qry: np.ndarray, desc_qry: np.ndarray,
                kp_ref: np.ndarray, desc_ref: np.ndarray, ratio: float = CONFIDENCE_THRESHOLD,
-               min_matches: int = MIN_MATCHES) -> Optional[Tuple[np.ndarray, np.ndarray]]:
-    """`TwistNode._pose` from the descriptors on (twist_node.py:248-289): (r, t) or None.  kp: [N,2] pixel coordinates."""
+               min_matches: int = MIN_MATCHES, ransac_iterations: Optional[int] = None) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+    """`TwistNode._pose` from the descriptors on (twist_node.py:248-289): (r, t) or None.  kp: [N,2] pixel coordinates.
+    ransac_iterations: cv2.solvePnPRansac's iterationsCount for this call (PoseEngine.set_ransac around it, the engine's own state restored
+    afterwards); None leaves the engine's state in charge (the reference's 10 unless it was told otherwise)."""
+    if ransac_iterations is not None:
+        ransac_iterations = check_ransac_iterations(ransac_iterations)
+        keep = engine.ransac()
+        engine.set_ransac(ransac_iterations, keep[1], keep[2])
+        try:
+            return twist_pose(engine, k_matrix, kp_qry, desc_qry, kp_ref, desc_ref, ratio, min_matches)
+        finally:
+            engine.set_ransac(*keep)
     n_q, n_r = len(kp_qry), len(kp_ref)
     if n_q < min_matches or n_r < 2:      # `len(matches) < MIN_MATCHES` -> None (twist_node.py:256)
         return None

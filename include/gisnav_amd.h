@@ -13,6 +13,8 @@
  *   gn_gather_points             kp[idx] gathers, MIN_MATCHES gate, _compute_3d_points
  *                                                 pose_node.py:289-303, _shared.py:95-102
  *   gn_pnp_ransac                cv2.solvePnPRansac(..., iterationsCount=10) + cv2.Rodrigues
+ *   gn_set_ransac                iterationsCount / reprojectionError / confidence of the pose stage inside gn_estimate and gn_vo_estimate
+ *                                (1 .. GN_RANSAC_MAX_ITERATIONS hypotheses; the default stays the reference's 10, 8.0, 0.99)
  *                                                                       _shared.py:104-117
  *   gn_estimate                  the whole of PoseNode._pose lines 246-308 for a batch of pairs
  *                                (gn_set_active_kpts: padded size per call, for batches well below max_kpts)
@@ -276,7 +278,13 @@ int gn_gather_points(gn_ctx* ctx, int B, int kpt_format,
  *   obj [B][kstride][3] f32, img [B][kstride][2] f32, n_pts [B] int32, K9: HOST 3x3 row-major f64.
  * Outputs (device): R [B][9] f64 row-major, t [B][3] f64, n_inliers [B] int32,
  * ok [B] u8 (0 when n_pts < min_pts or RANSAC found no model with > 4 inliers).  n_pts == 4 with min_pts <= 4 takes OpenCV's
- * `npoints == 4` branch: one P3P solve (Gao) on the first three points, the fourth picks the pose, all four are inliers, no refinement. */
+ * `npoints == 4` branch: one P3P solve (Gao) on the first three points, the fourth picks the pose, all four are inliers, no refinement.
+ * iterations_count: 1 .. GN_RANSAC_MAX_ITERATIONS (GN_ERR_ARG outside; gn_last_error names the range).  For every count the result is that
+ * of OpenCV's sequential loop: the same cv::RNG stream and subsets, `good > max(maxGood, 4)`, RANSACUpdateNumIters after every improvement,
+ * hypotheses at or past the adapted count never counted, the same refinement on the winner's inliers.  Counts up to 16 evaluate all their
+ * hypotheses in one launch; above 16 they run in rounds of 64 with the adapted count checked between rounds, so a pair that stops early
+ * costs at most one round more than it needed, and the workspace does not grow with the count (DESIGN.md "RANSAC beyond 16 hypotheses"). */
+#define GN_RANSAC_MAX_ITERATIONS 4096
 int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
                   const double* K9_host, int iterations_count, float reproj_error_px, double confidence,
                   int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream);
@@ -295,6 +303,22 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       const double* K9_host, int iterations_count, float reproj_error_px, double confidence,
                       int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
+
+/* cv2.solvePnPRansac's iterationsCount, reprojectionError and confidence for the PnP stage that gn_estimate(_cov), gn_vo_estimate(_cov) and
+ * the certificate's re-runs issue themselves (gn_pnp_ransac(_cov) take theirs as arguments).  Sticky host-side state like gn_set_distortion;
+ * the default (10, 8.0, 0.99) is what the reference passes (_shared.py:115), and a context that is never told, or told the default, computes
+ * bit for bit what it always did.  Captured when a call is issued, as K9_host and the distortion coefficients are.  iterations_count outside
+ * 1 .. GN_RANSAC_MAX_ITERATIONS, reproj_error_px <= 0 or confidence outside (0, 1): GN_ERR_ARG, state unchanged. */
+int gn_set_ransac(gn_ctx* ctx, int iterations_count, float reproj_error_px, double confidence);
+/* The values in effect (each pointer may be NULL). */
+int gn_get_ransac(const gn_ctx* ctx, int* iterations_count, float* reproj_error_px, double* confidence);
+/* "How hard was this frame": for pairs 0 .. B-1 of the most recent PnP stage of this context, the final adapted iteration count (what
+ * RANSACUpdateNumIters left; 0 where the loop never ran: n_pts < min_pts, or the 4-point branch) and the number of hypotheses that were
+ * actually evaluated (above 16 requested: less than one round of 64 past the adapted count; up to 16: all that were requested, they run at
+ * once).  Synchronises the device.  niters_host /
+ * evaluated_host: HOST [B] int32.  The point counts of that stage (n_pts / n_match, device) must still be alive.  After a call that was split
+ * into sub-batch groups (gn_set_substreams) every group's pairs are reported; after a certificate re-run, the re-run's. */
+int gn_ransac_last_counts(gn_ctx* ctx, int B, int32_t* niters_host, int32_t* evaluated_host, void* stream);
 
 /* Lens distortion of the PnP stage: cv2.solvePnPRansac's distCoeffs argument (the reference passes zeros, _shared.py:104-116; a real camera
  * publishes CameraInfo.d).  d_host: HOST, n = 4 (k1, k2, p1, p2; k3 = 0) or 5 (k1, k2, p1, p2, k3) plumb-bob coefficients; NULL or n = 0
@@ -585,7 +609,8 @@ int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);
  * tiles (320; 0 = never), 42 bits 8 and up: the overhead term of the rows-per-wave cost model of LoFTR's convolutions x 100 (0 = the shipped 0.25; bits
  * 0-7 selected LoFTR's forms of rounds 3-4 and are retired), 43 exact-f32 attention of one or two pairs (bits 0-1: 0 = k_attn_f32_ks, 1 = k_attn_f32 always, 2 = k_attn_f32_ks
  * always; bit 2 its eight-wave form), 44 exact-f32 GEMM on 64 x 64 tiles (1 = for grids of at most 128 workgroups on 64 x 128 tiles, 0 = never,
- * 2 = the four-slot-ring kernel on 64 x 128 tiles everywhere).  All of them select between forms with identical results except 43 (f32 rounding). */
+ * 2 = the four-slot-ring kernel on 64 x 128 tiles everywhere).  All of them select between forms with identical results except 43 (f32 rounding).
+ * Knob 49 (per context): 1 sends iterations_count <= 16 through the round path of the PnP stage as well (same bits; tests). */
 int gn_debug_set_variant(gn_ctx* ctx, int which, int value);
 int gn_debug_mfma_probe(gn_ctx* ctx, int blocks, int iters, void* stream);
 /* LDS-DMA addressing probe (80 KB of LDS per block filled by global_load_lds, verified by ds_read):
