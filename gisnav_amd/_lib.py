@@ -43,6 +43,11 @@ SIGNATURES = {
                                     VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
     "gn_estimate_cov": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int,
                                   c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
+    # the *_report entry points: the *_cov lists (covariance trio nullable) + [idx, score,] inlier_mask, inlier_idx, reproj_err in front of the stream
+    "gn_pnp_ransac_report": (C.c_int, [VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_int, C.c_float, C.c_double, C.c_int,
+                                       VP, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP]),
+    "gn_estimate_report": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, C.c_int, C.c_int,
+                                     c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gn_set_distortion": (C.c_int, [VP, c_f64p, C.c_int]),
     "gn_get_distortion": (C.c_int, [VP, c_f64p]),
     "gn_set_ransac": (C.c_int, [VP, C.c_int, C.c_float, C.c_double]),
@@ -74,6 +79,8 @@ SIGNATURES = {
                                  VP, VP, VP, VP, VP, VP]),
     "gn_vo_estimate_cov": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_double, C.c_int,
                                      VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP]),
+    "gn_vo_estimate_report": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_double, C.c_int,
+                                        VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gn_rotate_crop_center": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, c_f64p, VP]),
     "gn_stereo_reference": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, VP, c_f64p, VP]),
     "gn_proj_to_affine": (C.c_int, [C.c_char_p, c_f64p]),

@@ -36,13 +36,15 @@ struct Block {       // one SelfBlock or CrossBlock
 enum Stage { ST_PREP = 0, ST_PROJ, ST_ATTN, ST_FFN, ST_HEAD, ST_GATHER, ST_PNP, ST_COUNT };
 
 // One matcher / estimate call: its per-pair arrays as pointers to the first pair, the strides that step from pair to pair, and the estimate's
-// call-wide inputs.  A per-pair array the call does not own stays null (the estimate path's idx / score live in the e_idx / e_score workspaces).
+// call-wide inputs.  A per-pair array the call does not own stays null (the estimate path's idx / score live in the e_idx / e_score workspaces
+// unless gn_estimate_report was given arrays for them).
 struct Call {
   int B = 0, kpt_format = 0, stride_q = 0, stride_r = 0;
   const float *desc_q = nullptr, *kpt_q = nullptr, *desc_r = nullptr, *kpt_r = nullptr; const int32_t *n_q = nullptr, *n_r = nullptr;
   const uint8_t* dem = nullptr; int H = 0, W = 0;
   double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr; int64_t* idx = nullptr; float* score = nullptr;
   double *cov = nullptr, *sigma_hat = nullptr; uint8_t* cov_ok = nullptr; double sigma_px = 0.0;   // pose covariance (gn_estimate_cov): null = not asked for
+  uint8_t* inlier_mask = nullptr; int32_t* inlier_idx = nullptr; float* reproj_err = nullptr;   // report of the pose stage (gn_estimate_report): each null = not asked for
   const double* K9 = nullptr; int min_matches = 0;
   int dist = 0; double dk[5] = {0, 0, 0, 0, 0};   // lens distortion as the context held it when the call was issued (gn_set_distortion), by value
   int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac, captured the same way
@@ -64,7 +66,11 @@ template <typename F, typename... C> void pair_arrays(const Call& h, F&& f, C&..
   f((size_t)72, true, c.R...); f((size_t)24, true, c.t...); f((size_t)4, true, c.n_match...); f((size_t)4, true, c.n_inliers...); f((size_t)1, true, c.ok...);
   f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...);
   f((size_t)288, true, c.cov...); f((size_t)8, true, c.sigma_hat...); f((size_t)1, true, c.cov_ok...);
+  f(h.km, true, c.inlier_mask...); f(h.km * 4, true, c.inlier_idx...); f(h.km * 4, true, c.reproj_err...);
 }
+// the report arrays of a PnP stage (gn_pnp_ransac_report), each null on its own
+struct Report { uint8_t* inlier_mask = nullptr; int32_t* inlier_idx = nullptr; float* reproj_err = nullptr; };
+Report report_of(const Call& v) { return {v.inlier_mask, v.inlier_idx, v.reproj_err}; }
 template <typename T> T* byte_offset(T* p, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes); }
 
 // pairs [b0, b0 + n) of a call
@@ -1736,10 +1742,12 @@ int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int
 namespace {
 // the context's coefficients (gn_set_distortion), null when off
 const double* dist_of(const gn_ctx* c) { return c && c->dist_on ? c->dist : nullptr; }
-// gn_pnp_ransac (cov, sigma_hat, cov_ok all null) and gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine)
+// gn_pnp_ransac (cov, sigma_hat, cov_ok all null), gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine) and
+// gn_pnp_ransac_report (any of rep given: k_pnp_report runs last)
 int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
              const double* K9, const double* dk, int iterations_count, float reproj_error_px, double confidence, int min_pts,
-             double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+             double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
+             const Report& rep = Report()) {
   if (!ctx || !obj || !img || !n_pts || !K9 || !R || !t || !n_inliers || !ok || B < 1 || B > ctx->max_batch)
     return fail(ctx, GN_ERR_ARG, "bad gn_pnp_ransac argument");
   if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
@@ -1754,6 +1762,7 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
   a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = ctx->mask_ws; a.hyp = ctx->hyp_ws; a.pts_ws = ctx->pts_ws;
   a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(ctx->sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
   a.sigma_px = sigma_px; a.cov = cov; a.sigma_hat = sigma_hat; a.cov_ok = cov_ok;
+  a.inlier_mask = rep.inlier_mask; a.inlier_idx = rep.inlier_idx; a.reproj_err = rep.reproj_err;
   if (dk) { a.dist = 1; for (int i = 0; i < 5; ++i) a.dk[i] = dk[i]; }     // (null = off; the arguments travel by value, like fx .. cy)
   a.rmask_ws = ctx->rmask_ws; a.rstate = ctx->rstate_ws; a.force_rounds = ctx->pnp_rounds;
   {   // gn_ransac_last_counts: a sub-batch group's stage is the pairs [b0, b0 + B) of its call
@@ -1781,6 +1790,15 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_pnp_ransac_cov: null covariance output");
   return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   sigma_px, cov_rt, sigma_hat, cov_ok, stream);
+}
+
+int gn_pnp_ransac_report(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+                         const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
+                         double* R, double* t, int32_t* n_inliers, uint8_t* ok,
+                         double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                         uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream) {
+  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+                  sigma_px, cov_rt, sigma_hat, cov_ok, stream, Report{inlier_mask, inlier_idx, reproj_err});
 }
 
 int gn_ransac_last_counts(gn_ctx* ctx, int B, int32_t* niters_host, int32_t* evaluated_host, void* stream) {
@@ -1872,28 +1890,31 @@ int join_internal(gn_ctx* ctx, hipStream_t s) {
 // that slot of the double-buffered PnP inputs, and `stream` is free for the next call's matcher once the gather is enqueued; R / t / n_inliers / ok
 // are complete behind ev_pnp[slot][g] (gn_flush, or the waits gn_estimate enqueues one call later).
 int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g = 0) {
+  // the match list: the caller's arrays when the call has them (gn_estimate_report), else the workspaces
+  int64_t* const m_idx = v.idx ? v.idx : ctx->e_idx;
+  float* const m_score = v.score ? v.score : ctx->e_score;
   int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
-                    ctx->e_idx, ctx->e_score, v.n_match, stream);
+                    m_idx, m_score, v.n_match, stream);
   if (rc != GN_OK) return rc;
   if (slot < 0) {
-    rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
+    rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
                           ctx->e_mkp, ctx->e_obj, stream);
     if (rc != GN_OK) return rc;
     return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
-                    v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream);
+                    v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream, report_of(v));
   }
   hipStream_t s = (hipStream_t)stream;
   GN_HIP(hipSetDevice(ctx->device));
   GN_HIP(hipEventRecord(ctx->ev_head[g], s));
   if (ctx->pnp_recorded[slot][g]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot][g], 0));   // the PnP that last read this slot (two calls ago)
-  rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, ctx->e_idx, v.n_match, v.dem, v.H, v.W,
+  rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
                         ctx->o_mkp[slot], ctx->o_obj[slot], stream);
   if (rc != GN_OK) return rc;
   GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
   rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
-                v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp);
+                v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp, report_of(v));
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
   ctx->pnp_pending[slot][g] = ctx->pnp_recorded[slot][g] = true;
@@ -1916,14 +1937,16 @@ int cert_resolve(gn_ctx* ctx, int slot, hipStream_t s) {
 }  // namespace
 
 namespace {
-// gn_estimate (covariance pointers null) and gn_estimate_cov
+// gn_estimate (covariance pointers null), gn_estimate_cov and gn_estimate_report (idx / score / rep: each null = not asked for)
 int estimate_call(gn_ctx* ctx, int B, int kpt_format,
                   const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
                   const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
                   const uint8_t* dem, int H, int W, const double* K9, int min_matches,
                   double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
-                  double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+                  double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
+                  int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
+  if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
   if (ctx->fused_proj_pending && ctx->npad > 0 && gn_missing_tensors(ctx) == 0) {      // (the sub-batch groups below skip it: their workspace pointers are shifted)
     GN_HIP(hipSetDevice(ctx->device));
     int rcs = ensure_composed(ctx);
@@ -1934,6 +1957,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.dem = dem; v.H = H; v.W = W; v.K9 = K9; v.min_matches = min_matches;
   v.R = R; v.t = t; v.n_match = n_match; v.n_inliers = n_inliers; v.ok = ok;
   v.sigma_px = sigma_px; v.cov = cov; v.sigma_hat = sigma_hat; v.cov_ok = cov_ok;
+  v.idx = idx; v.score = score; v.inlier_mask = rep.inlier_mask; v.inlier_idx = rep.inlier_idx; v.reproj_err = rep.reproj_err;
   v.dist = ctx->dist_on; memcpy(v.dk, ctx->dist, sizeof v.dk);      // captured now: a deferred re-run of this call (cert_pend) keeps them
   v.ransac_iters = ctx->ransac_iters; v.ransac_reproj = ctx->ransac_reproj; v.ransac_conf = ctx->ransac_conf;
   const int groups = std::min(ctx->n_sub, B);
@@ -2025,6 +2049,17 @@ int gn_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_estimate_cov: null covariance output");
   return estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, dem, H, W, K9, min_matches,
                        R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream);
+}
+
+int gn_estimate_report(gn_ctx* ctx, int B, int kpt_format,
+                       const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                       const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                       const uint8_t* dem, int H, int W, const double* K9, int min_matches,
+                       double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                       int64_t* idx, float* score, uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream) {
+  return estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, dem, H, W, K9, min_matches,
+                       R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream, idx, score, Report{inlier_mask, inlier_idx, reproj_err});
 }
 
 int gn_set_deferred_join(gn_ctx* ctx, int enable) {
@@ -2132,16 +2167,19 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
                      const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
                      const double* K9, double ratio, int min_matches,
                      double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
-                     double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream) {
+                     double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
+                     int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
-  int rc = gn_vo_match(ctx, B, desc_q, n_q, stride_q, desc_r, n_r, stride_r, ratio, ctx->e_idx, ctx->e_score, n_match,
+  int64_t* const m_idx = idx ? idx : ctx->e_idx;
+  float* const m_score = score ? score : ctx->e_score;
+  int rc = gn_vo_match(ctx, B, desc_q, n_q, stride_q, desc_r, n_r, stride_r, ratio, m_idx, m_score, n_match,
                        nullptr, nullptr, stream);
   if (rc != GN_OK) return rc;
-  rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, ctx->e_idx, n_match, nullptr, 0, 0,
+  rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, m_idx, n_match, nullptr, 0, 0,
                         ctx->e_mkp, ctx->e_obj, stream);
   if (rc != GN_OK) return rc;
   return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, dist_of(ctx), ctx->ransac_iters, ctx->ransac_reproj, ctx->ransac_conf, min_matches,
-                  R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream);
+                  R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream, rep);
 }
 }  // namespace
 
@@ -2163,6 +2201,17 @@ int gn_vo_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_vo_estimate_cov: null covariance output");
   return vo_estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, K9, ratio, min_matches,
                           R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream);
+}
+
+int gn_vo_estimate_report(gn_ctx* ctx, int B, int kpt_format,
+                          const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                          const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                          const double* K9, double ratio, int min_matches,
+                          double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                          double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                          int64_t* idx, float* score, uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream) {
+  return vo_estimate_call(ctx, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, K9, ratio, min_matches,
+                          R, t, n_match, n_inliers, ok, sigma_px, cov_rt, sigma_hat, cov_ok, stream, idx, score, Report{inlier_mask, inlier_idx, reproj_err});
 }
 
 namespace {

@@ -338,6 +338,10 @@ struct PnpArgs {
   uint8_t* rmask_ws = nullptr;   // [B][kRansacRound + 1][kstride]: one mask per hypothesis of the round in flight, then the winner's (kept by copy)
   RansacState* rstate = nullptr; // [B]
   int force_rounds = 0;          // developer: counts <= 16 through the round path too (same bits as the two classic launches)
+  // report of the stage (gn_pnp_ransac_report): each may be null on its own; all three null = not asked for, k_pnp_report is not launched
+  uint8_t* inlier_mask = nullptr;   // [B][kstride]
+  int32_t* inlier_idx = nullptr;    // [B][kstride]
+  float* reproj_err = nullptr;      // [B][kstride]
 };
 void launch_pnp(const PnpArgs& a, hipStream_t s);
 // niters / evaluated of a classic (<= 16) stage into rstate[b], from the results k_pnp_hyp left in a.hyp (gn_ransac_last_counts)

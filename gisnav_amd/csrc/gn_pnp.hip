@@ -1,7 +1,7 @@
 // Batched PnP + RANSAC + Rodrigues on gfx950: k_pnp_hyp = one wave per (pair, RANSAC hypothesis), eight independent waves to a workgroup, each on its
 // own slice of LDS and with no workgroup barrier -- the cv::RNG stream does not depend on the models, so the <= 10 hypotheses of a pair run
 // concurrently --, k_pnp_refine = one wave per pair (best-model replay, initial guess, LM, Rodrigues); on request k_pnp_cov = one wave per pair
-// (covariance of the returned pose from the winner's inliers).
+// (covariance of the returned pose from the winner's inliers) and k_pnp_report = one wave per pair (the winner's inlier set and per-point residuals).
 //
 // Stands in for `cv2.solvePnPRansac(obj, img, K, zeros(4,1), useExtrinsicGuess=False,
 // iterationsCount=10)` + `cv2.Rodrigues` as called by `compute_pose`
@@ -2125,6 +2125,72 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   }
 }
 
+// ---- report of the stage (gn_pnp_ransac_report; DESIGN.md "Report of the pose stage") ------------------------------------------------------
+// cv2.solvePnPRansac's fourth return value and a per-point residual: one wave per pair, launched behind k_pnp_refine (and k_pnp_cov) on the same
+// stream and only when asked for.  The wave finds the winner as k_pnp_cov does, then strides the pair's row 64 slots at a time, all lanes active in
+// every trip: slot i gets its mask byte (the winner's mask; every point in the 4- / 5-point branches; 0 past n_pts and when ok = 0) and its residual
+// at the RETURNED pose (lm_point's forward model without the Jacobian, f64 on the widened f32 inputs, stored as f32; -1 past n_pts and when
+// ok = 0), and an inlier writes its index at base + (inliers in lower lanes), the ballot / popcount prefix of k_pnp_refine's compaction with the
+// base carried from chunk to chunk.  The index tail [count, kstride) is filled with -1 afterwards: disjoint from what the loop wrote, so nothing
+// has to be waited for.  Every pointer may be null on its own.  No LDS, no barrier; kReportPack waves to a workgroup for the reason given at k_pnp_cov.
+constexpr int kReportPack = 8;
+template <bool DIST, bool ROUND = false>
+__global__ __launch_bounds__(64 * kReportPack) void k_pnp_report(PnpArgs a) {
+  const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int b = blockIdx.x * kReportPack + slot;
+  if (b >= a.B) return;
+  const int ks = a.kstride;
+  int n = a.n_pts[b];
+  n = n < 0 ? 0 : (n > ks ? ks : n);      // a corrupted count stays inside the row
+  bool good = a.ok[b] != 0;
+  const uint8_t* mask = nullptr;          // null with good: every point is an inlier
+  if (good && !((n == 4 && a.min_pts <= 4) || (n == 5 && a.min_pts <= 5))) {
+    if constexpr (ROUND) {
+      good = a.rstate[b].best >= 0;
+      mask = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + kRansacRound) * ks;
+    } else {
+      int max_good;
+      const int best = select_hypothesis(a.hyp + (size_t)b * kMaxHyp, a.iterations, n, a.confidence, max_good);
+      good = best >= 0;
+      mask = a.mask_ws + ((size_t)b * kMaxHyp + (best < 0 ? 0 : best)) * ks;
+    }
+  }
+  const float* obj = a.obj + (size_t)b * ks * 3;
+  const float* img = a.img + (size_t)b * ks * 2;
+  uint8_t* const omask = a.inlier_mask ? a.inlier_mask + (size_t)b * ks : nullptr;
+  int32_t* const oidx = a.inlier_idx ? a.inlier_idx + (size_t)b * ks : nullptr;
+  float* const oerr = a.reproj_err ? a.reproj_err + (size_t)b * ks : nullptr;
+  const CamT<DIST> cam = make_cam<DIST>(a);
+  double R[3][3], p[6] = {0, 0, 0, 0, 0, 0}, dR[3][9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { p[3 + i] = a.t[(size_t)b * 3 + i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[i][j] = a.R[(size_t)b * 9 + 3 * i + j]; }
+  int base = 0;
+  for (int i0 = 0; i0 < ks; i0 += 64) {
+    const int i = i0 + lane;
+    const bool pt = good && i < n;        // (i < n implies i < ks)
+    const bool inl = pt && (!mask || mask[i] != 0);
+    float err = -1.0f;
+    if (pt && oerr) {
+      double acc[28];
+      acc[27] = 0.0;
+      lm_point<DIST>(obj, img, i, cam, p, R, dR, false, acc);
+      err = (float)sqrt(acc[27]);
+    }
+    const unsigned long long bal = __ballot(inl);
+    const int k = base + __popcll(bal & ((1ull << lane) - 1ull));
+    if (i < ks) {
+      if (omask) omask[i] = inl ? 1 : 0;
+      if (oerr) oerr[i] = err;
+    }
+    if (inl && oidx) oidx[k] = i;         // k <= i < ks
+    base += __popcll(bal);
+  }
+  if (oidx)
+    for (int k = base + lane; k < ks; k += 64) oidx[k] = -1;
+}
+
 // cv2.undistortPoints(img, K, distCoeffs[, P = K]) for [B][kstride] f32 points, one thread per point; slots past a pair's n_pts are left alone.
 // Computed in double, stored as f32 (cv2's output takes the input's depth).  dist = 0: the plain (u - cx) / fx the solvers read without distortion.
 __global__ __launch_bounds__(256) void k_undistort_points(UndistortArgs a) {
@@ -2176,6 +2242,7 @@ void launch_epnp_debug(const double* pws, const double* us, double* out, int n, 
 }
 
 namespace {
+inline bool wants_report(const PnpArgs& a) { return a.inlier_mask || a.inlier_idx || a.reproj_err; }
 template <bool DIST>
 void launch_pnp_rounds(PnpArgs a, hipStream_t s) {
   a.dbg_ts = nullptr;      // the phase stamps are laid out for the classic launches
@@ -2188,6 +2255,7 @@ void launch_pnp_rounds(PnpArgs a, hipStream_t s) {
   }
   hipLaunchKernelGGL((k_pnp_refine<DIST, true>), dim3(a.B), dim3(64), 0, s, a);
   if (a.cov) hipLaunchKernelGGL((k_pnp_cov<DIST, true>), gc, dim3(64 * kCovPack), 0, s, a);
+  if (wants_report(a)) hipLaunchKernelGGL((k_pnp_report<DIST, true>), dim3((a.B + kReportPack - 1) / kReportPack), dim3(64 * kReportPack), 0, s, a);
 }
 }  // namespace
 
@@ -2197,16 +2265,18 @@ void launch_pnp(const PnpArgs& a, hipStream_t s) {
     return;
   }
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
-  const dim3 gh((nh * a.B + kHypPack - 1) / kHypPack), gc((a.B + kCovPack - 1) / kCovPack);
+  const dim3 gh((nh * a.B + kHypPack - 1) / kHypPack), gc((a.B + kCovPack - 1) / kCovPack), gr((a.B + kReportPack - 1) / kReportPack);
   if (a.dist) {      // gn_set_distortion: the plumb-bob instantiations; otherwise the pinhole code, untouched
     hipLaunchKernelGGL(k_pnp_hyp<true>, gh, dim3(64 * kHypPack), 0, s, a, nh);
     hipLaunchKernelGGL(k_pnp_refine<true>, dim3(a.B), dim3(64), 0, s, a);
     if (a.cov) hipLaunchKernelGGL(k_pnp_cov<true>, gc, dim3(64 * kCovPack), 0, s, a);
+    if (wants_report(a)) hipLaunchKernelGGL(k_pnp_report<true>, gr, dim3(64 * kReportPack), 0, s, a);
     return;
   }
   hipLaunchKernelGGL(k_pnp_hyp<false>, gh, dim3(64 * kHypPack), 0, s, a, nh);
   hipLaunchKernelGGL(k_pnp_refine<false>, dim3(a.B), dim3(64), 0, s, a);
   if (a.cov) hipLaunchKernelGGL(k_pnp_cov<false>, gc, dim3(64 * kCovPack), 0, s, a);
+  if (wants_report(a)) hipLaunchKernelGGL(k_pnp_report<false>, gr, dim3(64 * kReportPack), 0, s, a);
 }
 
 void launch_pnp_counts(const PnpArgs& a, hipStream_t s) {

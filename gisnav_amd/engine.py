@@ -480,13 +480,38 @@ class PoseEngine:
         return dict(cov=torch.empty((B, 6, 6), dtype=torch.float64, device=d), sigma=torch.empty((B,), dtype=torch.float64, device=d),
                     cov_ok=torch.empty((B,), dtype=torch.uint8, device=d))
 
+    def _alloc_report(self, B: int, stride: int, matches: bool = False) -> dict:
+        d = self.device
+        out = dict(inlier_mask=torch.empty((B, stride), dtype=torch.uint8, device=d), inlier_idx=torch.empty((B, stride), dtype=torch.int32, device=d),
+                   reproj_err=torch.empty((B, stride), dtype=torch.float32, device=d))
+        if matches:
+            out.update(idx=torch.empty((B, stride, 2), dtype=torch.int64, device=d), score=torch.empty((B, stride), dtype=torch.float32, device=d))
+        return out
+
     def pnp_ransac(self, obj, img, n_pts, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
                    reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
-                   covariance: bool = False, sigma_px: float = 0.0):
+                   covariance: bool = False, sigma_px: float = 0.0, report: bool = False, report_out: Optional[dict] = None):
         """gn_pnp_ransac.  obj [B,S,3] f32, img [B,S,2] f32, n_pts [B] i32 (device).  Returns (R, t, n_inliers, ok); with covariance=True
         (gn_pnp_ransac_cov) also cov [B,6,6] f64 of (rvec, tvec), sigma [B] f64 (a-posteriori pixel sigma) and cov_ok [B] u8.  sigma_px > 0
-        states the pixel noise; 0 scales the covariance with the residuals' own sigma."""
+        states the pixel noise; 0 scales the covariance with the residuals' own sigma.  report=True (gn_pnp_ransac_report) appends
+        inlier_mask [B,S] u8, inlier_idx [B,S] i32 (cv2's `inliers`: the first n_inliers entries, then -1) and reproj_err [B,S] f32 (pixels at
+        the returned pose, -1 past n_pts and where ok = 0); report_out: a dict of those three to write into instead of fresh tensors."""
         B = obj.shape[0]
+        if report:
+            R = torch.empty((B, 3, 3), dtype=torch.float64, device=self.device)
+            t = torch.empty((B, 3, 1), dtype=torch.float64, device=self.device)
+            n_inl = torch.empty((B,), dtype=torch.int32, device=self.device)
+            ok = torch.empty((B,), dtype=torch.uint8, device=self.device)
+            K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+            c = self._alloc_cov(B) if covariance else {}
+            r = report_out if report_out is not None else self._alloc_report(B, obj.shape[1])
+            rc = self.lib.gn_pnp_ransac_report(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
+                                               K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                                               _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), float(sigma_px), _ptr(c.get("cov")), _ptr(c.get("sigma")), _ptr(c.get("cov_ok")),
+                                               _ptr(r.get("inlier_mask")), _ptr(r.get("inlier_idx")), _ptr(r.get("reproj_err")), self._stream())
+            _lib.check(self.ctx, rc, "gn_pnp_ransac_report")
+            res = (R, t, n_inl, ok) + ((c["cov"], c["sigma"], c["cov_ok"]) if covariance else ())
+            return res + (r.get("inlier_mask"), r.get("inlier_idx"), r.get("reproj_err"))
         R = torch.empty((B, 3, 3), dtype=torch.float64, device=self.device)
         t = torch.empty((B, 3, 1), dtype=torch.float64, device=self.device)
         n_inl = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -524,17 +549,19 @@ class PoseEngine:
 
     def pnp_ransac_host(self, obj: np.ndarray, img: np.ndarray, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
                         reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
-                        covariance: bool = False, sigma_px: float = 0.0, dist=None):
+                        covariance: bool = False, sigma_px: float = 0.0, dist=None, report: bool = False):
         """gn_pnp_ransac for ONE correspondence list given as host arrays (seam B2): obj (n, 3), img (n, 2) -> (R (3,3) f64, t (3,1) f64, n_inliers, ok)
         as host values.  One pinned staging block in ([n | pad | obj | img], one asynchronous copy), one 416-byte block out: pageable transfers of
         this size were measured to stall for ~90 ms every few dozen calls on the MI355X boxes (tools/bench_seams.py), pinned ones never.
         covariance=True (gn_pnp_ransac_cov) appends (cov (6,6) f64, sigma, cov_ok) to the result.  dist: distCoeffs for this call alone
-        (set_distortion around it, the engine's own state restored afterwards); None leaves the engine's state in charge."""
+        (set_distortion around it, the engine's own state restored afterwards); None leaves the engine's state in charge.  report=True
+        (gn_pnp_ransac_report) appends (inliers (n_inliers, 1) int32 as cv2 returns them, reproj_err (n,) f32) -- the output block grows by 8 n
+        bytes, and only then."""
         if dist is not None:
             keep = self.distortion()
             self.set_distortion(dist)
             try:
-                return self.pnp_ransac_host(obj, img, K, iterations, reproj_px, confidence, min_pts, covariance, sigma_px)
+                return self.pnp_ransac_host(obj, img, K, iterations, reproj_px, confidence, min_pts, covariance, sigma_px, report=report)
             finally:
                 self.set_distortion(keep)
         n = int(len(obj))
@@ -544,9 +571,10 @@ class PoseEngine:
         if io is None or io["cap"] != self.kmax:
             cap = self.kmax
             pin = torch.empty(8 + 5 * cap, dtype=torch.float32, pin_memory=True)
-            out = torch.zeros(416, dtype=torch.uint8, device=self.device)      # R 72 | t 24 | pad 4 | n_inliers 4 | ok 1 | pad 7 | cov 288 | sigma 8 | cov_ok 1 (+ pad)
+            # R 72 | t 24 | pad 4 | n_inliers 4 | ok 1 | pad 7 | cov 288 | sigma 8 | cov_ok 1 (+ pad) | report: inlier_idx 4 n | reproj_err 4 n
+            out = torch.zeros(416 + 8 * cap, dtype=torch.uint8, device=self.device)
             io = self._pnp_io = dict(cap=cap, pin=pin, pin_np=pin.numpy(), dev=torch.empty(8 + 5 * cap, dtype=torch.float32, device=self.device), out=out,
-                                     host=torch.empty(416, dtype=torch.uint8, pin_memory=True))
+                                     host=torch.empty(416 + 8 * cap, dtype=torch.uint8, pin_memory=True))
             io["host_np"] = io["host"].numpy()
         h = io["pin_np"]
         h[:1].view(np.int32)[0] = n
@@ -559,18 +587,24 @@ class PoseEngine:
         args = (self.ctx, 1, _ptr(d[4:4 + 3 * n]), _ptr(d[i0:i0 + 2 * n]), _ptr(d[:1].view(torch.int32)), n,
                 K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
                 _ptr(o[0:72]), _ptr(o[72:96]), _ptr(o[100:104]), _ptr(o[104:105]))
-        if covariance:
-            rc = self.lib.gn_pnp_ransac_cov(*args, float(sigma_px), _ptr(o[112:400]), _ptr(o[400:408]), _ptr(o[408:409]), self._stream())
+        cov3 = (_ptr(o[112:400]), _ptr(o[400:408]), _ptr(o[408:409])) if covariance else (None, None, None)
+        if report:
+            rc = self.lib.gn_pnp_ransac_report(*args, float(sigma_px), *cov3, None, _ptr(o[416:416 + 4 * n]), _ptr(o[416 + 4 * n:416 + 8 * n]), self._stream())
+        elif covariance:
+            rc = self.lib.gn_pnp_ransac_cov(*args, float(sigma_px), *cov3, self._stream())
         else:
             rc = self.lib.gn_pnp_ransac(*args, self._stream())
-        _lib.check(self.ctx, rc, "gn_pnp_ransac_cov" if covariance else "gn_pnp_ransac")
-        nb = 416 if covariance else 112
+        _lib.check(self.ctx, rc, "gn_pnp_ransac_report" if report else "gn_pnp_ransac_cov" if covariance else "gn_pnp_ransac")
+        nb = 416 + 8 * n if report else 416 if covariance else 112
         io["host"][:nb].copy_(o[:nb], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         r = io["host_np"]
         res = (r[0:72].view(np.float64).reshape(3, 3).copy(), r[72:96].view(np.float64).reshape(3, 1).copy(), int(r[100:104].view(np.int32)[0]), bool(r[104]))
         if covariance:
             res += (r[112:400].view(np.float64).reshape(6, 6).copy(), float(r[400:408].view(np.float64)[0]), bool(r[408]))
+        if report:
+            ninl = res[2] if res[3] else 0
+            res += (r[416:416 + 4 * n].view(np.int32)[:ninl].reshape(-1, 1).copy(), r[416 + 4 * n:416 + 8 * n].view(np.float32).copy())
         return res
 
     def set_ragged(self, ragged: Optional[bool]) -> None:
@@ -603,13 +637,18 @@ class PoseEngine:
         _lib.check(self.ctx, self.lib.gn_flush(self.ctx, self._stream()), "gn_flush")
         self._last_out_ptr = None
 
+    def _report_ptrs(self, out: dict):
+        return tuple(_ptr(out.get(k)) for k in ("idx", "score", "inlier_mask", "inlier_idx", "reproj_err"))
+
     def estimate(self, inputs: dict, K: np.ndarray, min_matches: int = MIN_MATCHES, out: Optional[dict] = None,
-                 covariance: bool = False, sigma_px: float = 0.0):
+                 covariance: bool = False, sigma_px: float = 0.0, report: bool = False):
         """gn_estimate on staged inputs: PoseNode._pose lines 246-308 for the whole batch.  covariance=True (gn_estimate_cov): `out` also
-        carries cov [B,6,6], sigma [B], cov_ok [B] (alloc_outputs(B, covariance=True)), complete when R / t / ok are."""
+        carries cov [B,6,6], sigma [B], cov_ok [B] (alloc_outputs(B, covariance=True)), complete when R / t / ok are.  report=True
+        (gn_estimate_report): `out` also carries the match list idx [B,kmax,2], score [B,kmax] and inlier_mask / inlier_idx / reproj_err
+        [B,kmax] of its rows (alloc_outputs(B, report=True)), complete when R / t / ok are."""
         B = inputs["kpt_q"].shape[0]
         if out is None:
-            out = self.alloc_outputs(B, covariance)
+            out = self.alloc_outputs(B, covariance, report)
         if getattr(self, "_certify_mode", 0) == 3:
             if self._last_out_ptr == out["R"].data_ptr():
                 raise _lib.GnError("deferred certificate: this call would write the outputs of the previous call, whose flagged pairs may still be re-run -- "
@@ -624,15 +663,18 @@ class PoseEngine:
                 _ptr(inputs.get("desc_r")), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["kpt_r"].shape[1],
                 _ptr(dem), H, W, K9.ctypes.data_as(_lib.c_f64p), min_matches,
                 _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
-        if covariance:
+        if report:
+            cov3 = (_ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"])) if covariance else (None, None, None)
+            rc = self.lib.gn_estimate_report(*args, float(sigma_px), *cov3, *self._report_ptrs(out), self._stream())
+        elif covariance:
             rc = self.lib.gn_estimate_cov(*args, float(sigma_px), _ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"]), self._stream())
         else:
             rc = self.lib.gn_estimate(*args, self._stream())
-        _lib.check(self.ctx, rc, "gn_estimate_cov" if covariance else "gn_estimate")
+        _lib.check(self.ctx, rc, "gn_estimate_report" if report else "gn_estimate_cov" if covariance else "gn_estimate")
         return out
 
     def estimate_bucketed(self, inputs: dict, K: np.ndarray, n_q_host, n_r_host, bucket_pairs: int = 8, min_matches: int = MIN_MATCHES,
-                          out: Optional[dict] = None):
+                          out: Optional[dict] = None, report: bool = False):
         """Length-bucketing scheduler for ragged batches: `cv2.SIFT_create()` is unbounded (pose_node.py:122), so the keypoint counts of a
         batch of messages spread widely, and one gn_estimate call pads every pair to the batch maximum (attention cost grows with the
         SQUARE of the padded length).  The pairs are sorted by max(n_q, n_r) (host-side counts: no device read), run as groups of
@@ -641,17 +683,18 @@ class PoseEngine:
         two pairs (and sub-stream groups of that size) run the small-grid kernel family, whose summation order differs from the bulk kernels' -- a
         remainder bucket of one or two pairs therefore gives the same matches and poses up to rounding, not the same bits, as one padded call
         (tests/test_gpu_round6.py).  With the certificate on (set_certify) the correspondence indices are the exact arithmetic's either
-        way.  Returns (out, stats)."""
+        way.  report=True: every bucket runs gn_estimate_report, and the match lists and reports come back in the caller's order with the rest.
+        Returns (out, stats)."""
         n_q_host = np.asarray(n_q_host).astype(np.int64)
         n_r_host = np.asarray(n_r_host).astype(np.int64)
         B = len(n_q_host)
         if out is None:
-            out = self.alloc_outputs(B)
+            out = self.alloc_outputs(B, report=report)
         need = np.maximum(np.maximum(n_q_host, n_r_host), 1)
         order = np.argsort(-need, kind="stable")
         perm = torch.as_tensor(order, device=self.device)
         srt = {k: (v.index_select(0, perm) if isinstance(v, torch.Tensor) else v) for k, v in inputs.items()}
-        tmp = self.alloc_outputs(B)
+        tmp = self.alloc_outputs(B, report=report)
         pad_tokens = 0
         try:
             for a in range(0, B, bucket_pairs):
@@ -659,7 +702,7 @@ class PoseEngine:
                 pad = self.set_active_kpts(int(need[order[a:b]].max()))
                 pad_tokens += 2 * pad * (b - a)
                 grp = {k: (v[a:b] if isinstance(v, torch.Tensor) else v) for k, v in srt.items()}
-                self.estimate(grp, K, min_matches, out={k: v[a:b] for k, v in tmp.items()})
+                self.estimate(grp, K, min_matches, out={k: v[a:b] for k, v in tmp.items()}, report=report)
         finally:
             self.set_active_kpts(self.kmax)
         # with set_overlap / set_substreams(deferred_join=True) the PnP stage or the groups may still run on the library's internal streams:
@@ -672,11 +715,13 @@ class PoseEngine:
         return out, {"real_tokens": real, "padded_tokens_bucketed": int(pad_tokens), "padded_tokens_one_call": int(one_call_pad),
                      "groups": (B + bucket_pairs - 1) // bucket_pairs}
 
-    def estimate_images(self, frames, tiles, K: np.ndarray, dem=None, sift=None, min_matches: int = MIN_MATCHES, out: Optional[dict] = None):
+    def estimate_images(self, frames, tiles, K: np.ndarray, dem=None, sift=None, min_matches: int = MIN_MATCHES, out: Optional[dict] = None,
+                        report: bool = False):
         """Frames -> pose from pixels for B pairs, everything in HBM: one batched SIFT pass over the B camera frames and the
         B map tiles (`gn_sift_detect_and_compute_batch`), the matcher padded to what the batch needs (`gn_set_active_kpts`),
         then `gn_estimate`.  frames / tiles: (B, H, W) uint8 (numpy or device tensors, one size); dem: (B, H, W) uint8 or
-        None (flat).  Returns (estimate outputs, n_keypoints [2B] int32 on the host: frames first)."""
+        None (flat).  report=True: as estimate; `kpt_q` / `kpt_r` [B,S,4] of the extraction are then added to the outputs, so that idx can be
+        resolved to pixel coordinates.  Returns (estimate outputs, n_keypoints [2B] int32 on the host: frames first)."""
         from .sift import SIFT
         if sift is None:
             if getattr(self, "_sift", None) is None:
@@ -700,7 +745,9 @@ class PoseEngine:
         inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], dem=to_dev(dem), kpt_format=_lib.GN_KPT_XYSA)
         self.set_active_kpts(max(int(n.max()), 1))
         try:
-            res = self.estimate(inputs, K, min_matches, out=out)
+            res = self.estimate(inputs, K, min_matches, out=out, report=report)
+            if report:
+                res = dict(res, kpt_q=inputs["kpt_q"], kpt_r=inputs["kpt_r"])
             self.flush()                                       # sub-stream groups read the temporaries above: join before they are released
         finally:
             self.set_active_kpts(self.kmax)                    # the active size is sticky context state: do not leak it to later calls
@@ -722,28 +769,33 @@ class PoseEngine:
         return (idx, dist, n_good, nn_idx, nn_dist) if want_knn else (idx, dist, n_good)
 
     def vo_estimate(self, inputs: dict, K: np.ndarray, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None,
-                    covariance: bool = False, sigma_px: float = 0.0):
-        """gn_vo_estimate on staged inputs: TwistNode._pose lines 227-289 for the whole batch (covariance=True: gn_vo_estimate_cov, as estimate)."""
+                    covariance: bool = False, sigma_px: float = 0.0, report: bool = False):
+        """gn_vo_estimate on staged inputs: TwistNode._pose lines 227-289 for the whole batch (covariance=True: gn_vo_estimate_cov, report=True:
+        gn_vo_estimate_report, both as estimate; `score` is then the matches' distance)."""
         B = inputs["desc_q"].shape[0]
         if out is None:
-            out = self.alloc_outputs(B, covariance)
+            out = self.alloc_outputs(B, covariance, report)
         K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
         args = (self.ctx, B, inputs["kpt_format"],
                 _ptr(inputs["desc_q"]), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["desc_q"].shape[1],
                 _ptr(inputs["desc_r"]), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["desc_r"].shape[1],
                 K9.ctypes.data_as(_lib.c_f64p), float(ratio), min_matches,
                 _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
-        if covariance:
+        if report:
+            cov3 = (_ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"])) if covariance else (None, None, None)
+            rc = self.lib.gn_vo_estimate_report(*args, float(sigma_px), *cov3, *self._report_ptrs(out), self._stream())
+        elif covariance:
             rc = self.lib.gn_vo_estimate_cov(*args, float(sigma_px), _ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"]), self._stream())
         else:
             rc = self.lib.gn_vo_estimate(*args, self._stream())
-        _lib.check(self.ctx, rc, "gn_vo_estimate_cov" if covariance else "gn_vo_estimate")
+        _lib.check(self.ctx, rc, "gn_vo_estimate_report" if report else "gn_vo_estimate_cov" if covariance else "gn_vo_estimate")
         return out
 
-    def vo_estimate_images(self, frames_q, frames_r, K: np.ndarray, sift=None, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None):
+    def vo_estimate_images(self, frames_q, frames_r, K: np.ndarray, sift=None, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None,
+                           report: bool = False):
         """TwistNode._pose from pixels for B frame pairs (twist_node.py:227-289), everything in HBM: one batched SIFT pass over
         the B query frames and the B reference (previous) frames, then brute-force 2-NN + ratio test + planar PnP
-        (`gn_vo_estimate`).  Returns (outputs, n_keypoints [2B] int32 on the host: query frames first)."""
+        (`gn_vo_estimate`).  report=True: as estimate_images.  Returns (outputs, n_keypoints [2B] int32 on the host: query frames first)."""
         from .sift import SIFT
         if sift is None:
             if getattr(self, "_sift", None) is None:
@@ -756,15 +808,20 @@ class PoseEngine:
         kpt, _, _, desc, n = sift.detect_and_compute_batch_device(torch.cat([q, r], 0))
         nd = torch.as_tensor(n, device=self.device)
         inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], kpt_format=_lib.GN_KPT_XYSA)
-        return self.vo_estimate(inputs, K, ratio, min_matches, out=out), n
+        res = self.vo_estimate(inputs, K, ratio, min_matches, out=out, report=report)
+        if report:
+            res = dict(res, kpt_q=inputs["kpt_q"], kpt_r=inputs["kpt_r"])
+        return res, n
 
-    def alloc_outputs(self, B: int, covariance: bool = False) -> dict:
+    def alloc_outputs(self, B: int, covariance: bool = False, report: bool = False) -> dict:
         d = self.device
         out = dict(R=torch.empty((B, 3, 3), dtype=torch.float64, device=d), t=torch.empty((B, 3, 1), dtype=torch.float64, device=d),
                    n_match=torch.empty((B,), dtype=torch.int32, device=d), n_inliers=torch.empty((B,), dtype=torch.int32, device=d),
                    ok=torch.empty((B,), dtype=torch.uint8, device=d))
         if covariance:
             out.update(self._alloc_cov(B))
+        if report:
+            out.update(self._alloc_report(B, self.kmax, matches=True))
         return out
 
     # ------------------------------------------------------------------ test hooks

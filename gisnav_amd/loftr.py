@@ -235,14 +235,16 @@ class LoFTR:
 
 
 def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Tensor, dem, K, min_matches: int = 15, conf_threshold: float = 0.0,
-               return_covariance: bool = False, dist=None, ransac_iterations=None):
+               return_covariance: bool = False, dist=None, ransac_iterations=None, return_inliers: bool = False):
     """Camera frame <-> map tile pose with the detector-free matcher in front of the SAME solver as the SIFT / LightGlue path: LoFTR matches
     (`keypoints0` in the frame, `keypoints1` in the tile) -> DEM lift of the tile points (`_shared.py:95-102`) -> solvePnPRansac + Rodrigues
     (`gn_gather_points`, `gn_pnp_ransac`; seam B2).  Everything stays on the device.  frame01 / tile01: (H, W) float in [0, 1];
     dem: (H, W) uint8 or None.  Returns (R (3,3), t (3,1), n_matches) or None below `min_matches` / when RANSAC finds no model;
     with return_covariance also the 6x6 covariance of (rvec, tvec) from the inliers (None when it is not defined) as a fourth entry.
     dist: distCoeffs of the frame's camera for the solver (PoseEngine.set_distortion for this call; None = the engine's state).
-    ransac_iterations: cv2.solvePnPRansac's iterationsCount for this call, 1 .. 4096 (None = the reference's 10)."""
+    ransac_iterations: cv2.solvePnPRansac's iterationsCount for this call, 1 .. 4096 (None = the reference's 10).
+    return_inliers: append cv2.solvePnPRansac's `inliers`, (n_inliers, 1) int32, indexing the matches that passed `conf_threshold` in their order
+    (`gn_pnp_ransac_report`)."""
     out = matcher({"image0": frame01, "image1": tile01})
     keep = out["confidence"] > conf_threshold
     k0, k1 = out["keypoints0"][keep], out["keypoints1"][keep]
@@ -261,13 +263,14 @@ def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Te
     d = None if dem is None else torch.as_tensor(np.ascontiguousarray(dem, np.uint8), device=dev)[None]
     mkp, obj = engine.gather_points(pad(k0), pad(k1), idx_full, nm, d, _lib.GN_KPT_XYSA)
     res = _pnp_with_dist(engine, dist, obj, mkp, nm, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance,
-                         **_iterations_kw(ransac_iterations))
+                         **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
     R, t, ok = res[0], res[1], res[3]
     if not bool(ok.cpu()[0]):
         return None
+    tail = (res[-2][0, :int(res[2].cpu()[0])].cpu().numpy().reshape(-1, 1),) if return_inliers else ()
     if return_covariance:
-        return R[0].cpu().numpy(), t[0].cpu().numpy(), n, (res[4][0].cpu().numpy() if bool(res[6].cpu()[0]) else None)
-    return R[0].cpu().numpy(), t[0].cpu().numpy(), n
+        return (R[0].cpu().numpy(), t[0].cpu().numpy(), n, (res[4][0].cpu().numpy() if bool(res[6].cpu()[0]) else None)) + tail
+    return (R[0].cpu().numpy(), t[0].cpu().numpy(), n) + tail
 
 
 def _iterations_kw(ransac_iterations) -> dict:
@@ -276,6 +279,11 @@ def _iterations_kw(ransac_iterations) -> dict:
         return {}
     from .engine import check_ransac_iterations
     return {"iterations": check_ransac_iterations(ransac_iterations)}
+
+
+def _report_kw(return_inliers: bool) -> dict:
+    """The `report` keyword of engine.pnp_ransac (none at all when off: the call is then the one it always was)."""
+    return {"report": True} if return_inliers else {}
 
 
 def _pnp_with_dist(engine, dist, *args, **kwargs):
@@ -291,12 +299,13 @@ def _pnp_with_dist(engine, dist, *args, **kwargs):
 
 
 def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_matches: int = 15, conf_threshold: float = 0.0, return_covariance: bool = False,
-                     dist=None, ransac_iterations=None):
+                     dist=None, ransac_iterations=None, return_inliers: bool = False):
     """`loftr_pose` for B pairs at once: frames01 / tiles01 (B, H, W) (or sequences of B (H, W) images), dems (B, H, W) uint8 (or a sequence of
     B) or None.  ONE batched match (the counts stay on the device), the confidence filter as a stable per-pair compaction on the device, ONE
     gn_gather_points, ONE gn_pnp_ransac over the B pairs and ONE read-back.  Returns a list of B entries, each what `loftr_pose` returns for that
     pair (None below `min_matches` / without a model).  The engine must have been created with max_batch >= B; it is grown to the matcher's
-    per-pair cap when that exceeds its keypoint capacity.  dist, ransac_iterations: as for `loftr_pose`."""
+    per-pair cap when that exceeds its keypoint capacity.  dist, ransac_iterations, return_inliers: as for `loftr_pose` (the inlier indices
+    ride in the one read-back)."""
     stack = lambda x: x if isinstance(x, torch.Tensor) else torch.stack([torch.as_tensor(v) for v in x])  # noqa: E731
     frames01, tiles01 = stack(frames01), stack(tiles01)
     B, H, W = matcher._batch_shape(frames01, tiles01)
@@ -321,17 +330,18 @@ def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_m
         d = d.to(torch.uint8).contiguous()
     mkp, obj = engine.gather_points(g(k0), g(k1), idx, cnt, d, _lib.GN_KPT_XYSA)
     res = _pnp_with_dist(engine, dist, obj, mkp, cnt, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance,
-                         **_iterations_kw(ransac_iterations))
-    back = [res[0], res[1], res[3], cnt] + ([res[4], res[6]] if return_covariance else [])
+                         **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
+    back = [res[0], res[1], res[3], cnt] + ([res[4], res[6]] if return_covariance else []) + ([res[2], res[-2]] if return_inliers else [])
     host = engine.to_host(*back)
     R, t, ok, cn = host[:4]
     out = []
     for b in range(B):
         nb = int(cn[b])
+        tail = (np.array(host[-1][b][:int(host[-2][b])], np.int32).reshape(-1, 1),) if return_inliers else ()
         if nb < min_matches or not bool(ok[b]):
             out.append(None)
         elif return_covariance:
-            out.append((np.array(R[b]), np.array(t[b]), nb, np.array(host[4][b]) if bool(host[5][b]) else None))
+            out.append((np.array(R[b]), np.array(t[b]), nb, np.array(host[4][b]) if bool(host[5][b]) else None) + tail)
         else:
-            out.append((np.array(R[b]), np.array(t[b]), nb))
+            out.append((np.array(R[b]), np.array(t[b]), nb) + tail)
     return out

@@ -9,6 +9,8 @@ inliers (`gn_pnp_ransac_cov`, DESIGN.md "Pose covariance"), or None in its place
 `use_distortion=True` passes `camera_info.d` as distCoeffs (`gn_set_distortion`); the default ignores it, as the reference does.
 `ransac_iterations=N` (1 .. 4096) is cv2.solvePnPRansac's iterationsCount for this call; the default is the reference's 10, and the
 engine's own `set_ransac` state is neither read nor changed.
+`return_inliers=True` appends cv2.solvePnPRansac's fourth return value: `inliers`, an (n_inliers, 1) int32 array of ascending indices into
+`mkp_qry` / `mkp_ref` (`gn_pnp_ransac_report`); `return_residuals=True` after it the per-point pixel residual (n,) f32 at the returned pose.
 """
 from __future__ import annotations
 
@@ -50,7 +52,8 @@ def distortion_of(camera_info) -> np.ndarray:
 
 def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevation: Optional[np.ndarray],
                  engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0,
-                 use_distortion: bool = False, ransac_iterations: Optional[int] = None) -> Optional[Tuple[np.ndarray, ...]]:
+                 use_distortion: bool = False, ransac_iterations: Optional[int] = None, return_inliers: bool = False,
+                 return_residuals: bool = False) -> Optional[Tuple[np.ndarray, ...]]:
     iterations = RANSAC_ITERATIONS if ransac_iterations is None else check_ransac_iterations(ransac_iterations)
     dist = distortion_of(camera_info) if use_distortion else None      # (checked before anything else: an unsupported model raises)
     n = len(mkp_qry)
@@ -66,10 +69,14 @@ def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevatio
         obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
     img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
     k_matrix = np.asarray(camera_info.k, dtype=np.float64).reshape((3, 3))
+    report = return_inliers or return_residuals
     res = eng.pnp_ransac_host(obj, img, k_matrix, iterations, min_pts=4,   # n == 4: OpenCV's P3P branch
-                              covariance=return_covariance, sigma_px=sigma_px, dist=dist)
+                              covariance=return_covariance, sigma_px=sigma_px, dist=dist, **({"report": True} if report else {}))
     if not res[3]:
         return None
-    if return_covariance:
-        return res[0], res[1], (res[4] if res[6] else None)
-    return res[0], res[1]
+    out = (res[0], res[1]) + (((res[4] if res[6] else None),) if return_covariance else ())
+    if return_inliers:
+        out += (res[-2],)
+    if return_residuals:
+        out += (res[-1],)
+    return out

@@ -29,7 +29,7 @@ class PoseNode:
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
-                 sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS):
+                 sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS, report: bool = False):
         from .matcher import _check_ladder
         ransac_iterations = check_ransac_iterations(ransac_iterations)      # (refused before any device work)
         ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
@@ -57,6 +57,13 @@ class PoseNode:
         self._covariance, self._sigma_px = bool(covariance), float(sigma_px)
         self.last_covariance: Optional[np.ndarray] = None
         self.last_sigma_px = 0.0
+        # report=True: every estimate() also asks for the match list and the PnP stage's report (gn_estimate_report) and leaves
+        # last_report = dict(mkp_qry (n,2), mkp_ref (n,2), score (n,), inliers (n_inliers,1) int32 as cv2.solvePnPRansac returns them, reproj_err (n,))
+        # of the most recent message that returned a pose (None otherwise) -- what the reference's visualize_matches_and_pose takes.  The arrays
+        # ride in the message's one device-to-host transfer, which grows only when the flag is set.
+        self._report = bool(report)
+        self.last_report: Optional[dict] = None
+        self._kp_q_host = self._kp_r_host = None
         # use_distortion=True: camera_info.d goes to the PnP stage as distCoeffs (gn_set_distortion); the default ignores it, like the reference
         self._use_distortion = bool(use_distortion)
         # ransac_iterations: cv2.solvePnPRansac's iterationsCount (gn_set_ransac); the default is the reference's 10 and leaves the context untouched
@@ -81,6 +88,7 @@ class PoseNode:
     def estimate(self, camera_info: CameraInfo, msg: OrthoStereoImage) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         eng, dev = self._engine, self._engine.device
         self.last_covariance, self.last_sigma_px = None, 0.0
+        self.last_report = None
         if self._use_distortion:
             from .pose import distortion_of
             eng.set_distortion(distortion_of(camera_info))      # (ValueError for a model other than plumb_bob)
@@ -98,6 +106,7 @@ class PoseNode:
             cached = (torch.from_numpy(rec_r.reshape(1, -1, 133).copy()).to(dev), torch.tensor([len(kp_r)], dtype=torch.int32, device=dev))
             self._cached_stamp_kps_desc = (stamp, cached)
             self._cached_n_r = len(kp_r)
+            self._kp_r_host = np.asarray(kp_r, np.float32).reshape(-1, 2).copy() if self._report else None
         rec_r_t, n_r_t = self._cached_stamp_kps_desc[1]
         if n == 0:
             self.last_num_matches = 0
@@ -138,10 +147,10 @@ class PoseNode:
                 except _lib.GnError:      # (a sample that cannot calibrate -- it left the fp16 range -- : the next message tries again)
                     pass
             eng.estimate(inputs, np.asarray(camera_info.k, np.float64).reshape(3, 3), self.MIN_MATCHES, out=self._out,
-                         covariance=self._covariance, sigma_px=self._sigma_px)
+                         covariance=self._covariance, sigma_px=self._sigma_px, report=self._report)
         finally:
             eng.set_active_kpts(eng.kmax)                   # sticky context state: restore
-        nb = 416 if self._covariance else 112
+        nb = self.out_bytes(self._covariance, self._report, eng.kmax)
         self._out_host[:nb].copy_(self._out_flat[:nb], non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
         h = self._out_host_np
@@ -153,7 +162,29 @@ class PoseNode:
         if self._covariance and h[408]:
             self.last_covariance = h[112:400].view(np.float64).reshape(6, 6).copy()
             self.last_sigma_px = float(h[400:408].view(np.float64)[0])
+        if self._report:
+            kp_q = np.frombuffer(msg.query_sift, dtype=np.float32, count=n * 133).reshape(n, 133)[:, :2]
+            self.last_report = self.report_from_block(h, eng.kmax, kp_q, self._kp_r_host)
         return h[0:72].view(np.float64).reshape(3, 3).copy(), h[72:96].view(np.float64).reshape(3, 1).copy()
+
+    @staticmethod
+    def out_bytes(covariance: bool, report: bool, kmax: int) -> int:
+        """Bytes of the output block one message reads back: the pose head, the covariance when asked for, and -- only with report -- the
+        match list and the report rows behind it (28 bytes per match slot)."""
+        return 416 + 28 * kmax if report else 416 if covariance else 112
+
+    @staticmethod
+    def report_from_block(h: np.ndarray, kmax: int, kp_q: np.ndarray, kp_r: np.ndarray) -> dict:
+        """last_report from the host copy of the output block: idx [kmax][2] i64 | score [kmax] f32 | inlier_idx [kmax] i32 | reproj_err [kmax] f32
+        behind byte 416, resolved against the two keypoint lists the matcher saw."""
+        n_match, n_inl = int(h[96:100].view(np.int32)[0]), int(h[100:104].view(np.int32)[0])
+        o = 416
+        idx = h[o:o + 16 * kmax].view(np.int64).reshape(kmax, 2)[:n_match]
+        score = h[o + 16 * kmax:o + 20 * kmax].view(np.float32)[:n_match]
+        inl = h[o + 20 * kmax:o + 24 * kmax].view(np.int32)[:n_inl]
+        err = h[o + 24 * kmax:o + 28 * kmax].view(np.float32)[:n_match]
+        return dict(mkp_qry=np.asarray(kp_q, np.float32)[idx[:, 0]].copy(), mkp_ref=np.asarray(kp_r, np.float32)[idx[:, 1]].copy(), score=score.copy(),
+                    inliers=inl.reshape(-1, 1).copy(), reproj_err=err.copy())
 
     def _ensure_io(self, kmax: int) -> None:
         """Pinned staging block, its device mirror and the output block (re-made when the engine grew)."""
@@ -164,11 +195,18 @@ class PoseNode:
         self._pin_np = self._pin.numpy()
         self._dev_in = torch.empty(4 + kmax * 133, dtype=torch.float32, device=dev)
         # R 72 B | t 24 B | n_match 4 | n_inliers 4 | ok 1 (+ pad to 112) | cov 288 B | sigma 8 B | cov_ok 1 (+ pad)
-        self._out_flat = torch.zeros(416, dtype=torch.uint8, device=dev)
+        # with report: | idx 16 kmax | score 4 kmax | inlier_idx 4 kmax | reproj_err 4 kmax (the mask is not read back: inlier_idx says the same)
+        total = self.out_bytes(True, self._report, kmax)
+        self._out_flat = torch.zeros(total, dtype=torch.uint8, device=dev)
         f = self._out_flat
         self._out = dict(R=f[0:72].view(torch.float64).view(1, 3, 3), t=f[72:96].view(torch.float64).view(1, 3, 1), n_match=f[96:100].view(torch.int32),
                          n_inliers=f[100:104].view(torch.int32), ok=f[104:105], cov=f[112:400].view(torch.float64).view(1, 6, 6),
                          sigma=f[400:408].view(torch.float64), cov_ok=f[408:409])
-        self._out_host = torch.empty(416, dtype=torch.uint8, pin_memory=True)
+        if self._report:
+            o = 416
+            self._out.update(idx=f[o:o + 16 * kmax].view(torch.int64).view(1, kmax, 2), score=f[o + 16 * kmax:o + 20 * kmax].view(torch.float32).view(1, kmax),
+                             inlier_idx=f[o + 20 * kmax:o + 24 * kmax].view(torch.int32).view(1, kmax),
+                             reproj_err=f[o + 24 * kmax:o + 28 * kmax].view(torch.float32).view(1, kmax))
+        self._out_host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         self._out_host_np = self._out_host.numpy()
         self._io_kmax = kmax

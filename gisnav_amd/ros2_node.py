@@ -110,15 +110,20 @@ def make_node_class():
         """`~/pose_earth` from `/camera/camera_info` + StereoNode's pose image, computed by gisnav_amd (one message = one GPU call, ~1 ms)."""
 
         def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", use_distortion: bool = False,
-                     ransac_iterations: int = 10, **kwargs):
+                     ransac_iterations: int = 10, report: bool = False, **kwargs):
             super().__init__(*args, **kwargs)
+            # report=True: `last_report` holds the matches, cv2-style inliers and residuals of the most recent message (PoseNode.last_report)
             self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True, use_distortion=use_distortion,
-                                  ransac_iterations=ransac_iterations)
+                                  ransac_iterations=ransac_iterations, report=report)
             self._camera_info: Optional[CameraInfo] = None
             qos = QoSPresetProfiles.SENSOR_DATA.value
             self._pub = self.create_publisher(PoseWithCovarianceStamped, ROS_TOPIC_POSE_EARTH, qos)
             self.create_subscription(RosCameraInfo, ROS_TOPIC_CAMERA_INFO, self._camera_info_cb, qos)
             self.create_subscription(RosOrthoStereoImage, ROS_TOPIC_POSE_IMAGE, self._pose_image_cb, qos)
+
+        @property
+        def last_report(self) -> Optional[dict]:
+            return self._impl.last_report
 
         def _camera_info_cb(self, msg) -> None:
             self._camera_info = camera_info_from_ros(msg)

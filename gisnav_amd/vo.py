@@ -71,16 +71,19 @@ class BFMatcher:
 
 def twist_pose(engine: PoseEngine, k_matrix: np.ndarray, kp_qry: np.ndarray, desc_qry: np.ndarray,
                kp_ref: np.ndarray, desc_ref: np.ndarray, ratio: float = CONFIDENCE_THRESHOLD,
-               min_matches: int = MIN_MATCHES, ransac_iterations: Optional[int] = None) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+               min_matches: int = MIN_MATCHES, ransac_iterations: Optional[int] = None,
+               return_inliers: bool = False) -> Optional[Tuple[np.ndarray, ...]]:
     """`TwistNode._pose` from the descriptors on (twist_node.py:248-289): (r, t) or None.  kp: [N,2] pixel coordinates.
     ransac_iterations: cv2.solvePnPRansac's iterationsCount for this call (PoseEngine.set_ransac around it, the engine's own state restored
-    afterwards); None leaves the engine's state in charge (the reference's 10 unless it was told otherwise)."""
+    afterwards); None leaves the engine's state in charge (the reference's 10 unless it was told otherwise).
+    return_inliers=True (gn_vo_estimate_report): (r, t, inliers) with inliers an (n_inliers, 1) int32 array as cv2.solvePnPRansac returns it, indexing
+    the ratio-test survivors in query order (BFMatcher.ratio_matches gives the same list)."""
     if ransac_iterations is not None:
         ransac_iterations = check_ransac_iterations(ransac_iterations)
         keep = engine.ransac()
         engine.set_ransac(ransac_iterations, keep[1], keep[2])
         try:
-            return twist_pose(engine, k_matrix, kp_qry, desc_qry, kp_ref, desc_ref, ratio, min_matches)
+            return twist_pose(engine, k_matrix, kp_qry, desc_qry, kp_ref, desc_ref, ratio, min_matches, return_inliers=return_inliers)
         finally:
             engine.set_ransac(*keep)
     n_q, n_r = len(kp_qry), len(kp_ref)
@@ -96,8 +99,14 @@ def twist_pose(engine: PoseEngine, k_matrix: np.ndarray, kp_qry: np.ndarray, des
 
     dq, kq, nq = pack(kp_qry, desc_qry, "q")
     dr, kr, nr = pack(kp_ref, desc_ref, "r")
-    out = engine.vo_estimate(dict(desc_q=dq, kpt_q=kq, n_q=nq, desc_r=dr, kpt_r=kr, n_r=nr, kpt_format=_lib.GN_KPT_XYSA),
-                             k_matrix, ratio, min_matches)
+    inputs = dict(desc_q=dq, kpt_q=kq, n_q=nq, desc_r=dr, kpt_r=kr, n_r=nr, kpt_format=_lib.GN_KPT_XYSA)
+    if return_inliers:
+        out = engine.vo_estimate(inputs, k_matrix, ratio, min_matches, report=True)
+        ok, R, t, n_inl, inl = engine.to_host(out["ok"], out["R"], out["t"], out["n_inliers"], out["inlier_idx"])
+        if not bool(ok[0]):
+            return None
+        return R[0], t[0], inl[0, :int(n_inl[0])].reshape(-1, 1).astype(np.int32)
+    out = engine.vo_estimate(inputs, k_matrix, ratio, min_matches)
     ok, R, t = engine.to_host(out["ok"], out["R"], out["t"])
     if not bool(ok[0]):
         return None

@@ -304,6 +304,25 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
 
+/* gn_pnp_ransac(_cov) + a report of the stage: cv2.solvePnPRansac's fourth return value `inliers`, and a per-point residual (DESIGN.md "Report
+ * of the pose stage").  R / t / n_inliers / ok are bit for bit gn_pnp_ransac's.  cov_rt / sigma_hat / cov_ok: all three given (then as
+ * gn_pnp_ransac_cov) or all three NULL.  The report arrays are device outputs, row stride kstride, each may be NULL on its own; with all three
+ * NULL nothing more is launched than without this call.
+ *   inlier_mask [B][kstride] u8     1 where point i is an inlier of the winning RANSAC hypothesis -- the set the refinement and the covariance
+ *                                   sum over; every point when n_pts is 4 or 5 --, 0 elsewhere: slots >= n_pts, and the whole row when ok = 0
+ *   inlier_idx  [B][kstride] int32  the indices of the inliers, ascending (cv2's `inliers`): the first n_inliers[b] entries, the rest -1;
+ *                                   the whole row -1 when ok = 0
+ *   reproj_err  [B][kstride] f32    |project(R, t; X_i) - u_i| in pixels at the RETURNED (refined) pose for every i < n_pts, inlier or not,
+ *                                   through the forward model the stage uses (lens distortion included when gn_set_distortion is on), in f64
+ *                                   on the widened f32 inputs, stored as f32; -1 in slots >= n_pts, and in every slot when ok = 0
+ * As in OpenCV the mask comes from the hypothesis model (f32 squared error <= reproj_error_px^2 at the minimal solver's pose) and reproj_err
+ * from the refined pose: an inlier may sit above reproj_error_px in reproj_err, and a point below it may be no inlier. */
+int gn_pnp_ransac_report(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+                         const double* K9_host, int iterations_count, float reproj_error_px, double confidence,
+                         int min_pts, double* R, double* t, int32_t* n_inliers, uint8_t* ok,
+                         double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                         uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream);
+
 /* cv2.solvePnPRansac's iterationsCount, reprojectionError and confidence for the PnP stage that gn_estimate(_cov), gn_vo_estimate(_cov) and
  * the certificate's re-runs issue themselves (gn_pnp_ransac(_cov) take theirs as arguments).  Sticky host-side state like gn_set_distortion;
  * the default (10, 8.0, 0.99) is what the reference passes (_shared.py:115), and a context that is never told, or told the default, computes
@@ -355,6 +374,20 @@ int gn_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
                     const uint8_t* dem, int H, int W, const double* K9_host, int min_matches,
                     double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
                     double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
+
+/* gn_estimate(_cov) + the match list the pose was computed from and gn_pnp_ransac_report's report of its PnP stage.  cov_rt / sigma_hat / cov_ok:
+ * all three or none.  idx [B][kmax][2] int64 and score [B][kmax] f32 are exactly gn_match's outputs (with idx given the matcher writes into it
+ * and the gather reads it there); inlier_mask / inlier_idx / reproj_err are [B][kmax], kmax = gn_kmax(ctx), and their row k refers to row k of
+ * idx (the gather keeps row order); a pair below min_matches has an all-sentinel report.  Each of the five may be NULL on its own; with all
+ * NULL this is gn_estimate(_cov).  They are per-pair outputs like R / t / ok: complete when those are, in every mode (gn_set_overlap,
+ * gn_set_substreams, gn_set_deferred_join, gn_set_certify 2 and 3 and the ladder -- a re-run pair gets the re-run's matches and report). */
+int gn_estimate_report(gn_ctx* ctx, int B, int kpt_format,
+                       const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                       const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                       const uint8_t* dem, int H, int W, const double* K9_host, int min_matches,
+                       double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                       int64_t* idx, float* score, uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream);
 
 /* Throughput option for back-to-back gn_estimate calls (batch serving): with overlap enabled the PnP stage of a call
  * runs on an internal stream beside the matcher of the NEXT call (its inputs are double-buffered).  R / t /
@@ -412,6 +445,15 @@ int gn_vo_estimate_cov(gn_ctx* ctx, int B, int kpt_format,
                        const double* K9_host, double ratio, int min_matches,
                        double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
                        double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream);
+
+/* gn_vo_estimate(_cov) + the match list (gn_vo_match's idx and dist, as `score`) and the report, as gn_estimate_report. */
+int gn_vo_estimate_report(gn_ctx* ctx, int B, int kpt_format,
+                          const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+                          const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+                          const double* K9_host, double ratio, int min_matches,
+                          double* R, double* t, int32_t* n_match, int32_t* n_inliers, uint8_t* ok,
+                          double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
+                          int64_t* idx, float* score, uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream);
 
 /* ---- StereoNode reference-raster preparation ----------------------- */
 /* StereoNode._rotate_and_crop_center(image, angle_degrees, shape) -- ros/gisnav/gisnav/core/stereo_node.py:292-335:
