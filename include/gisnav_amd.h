@@ -157,7 +157,9 @@ int gn_set_certify(gn_ctx* ctx, int mode, float eps, float eps_f32);
 /* Arithmetic of the block tail (ffn.0 -> LayerNorm -> GELU -> ffn.3 with out_proj folded in; kornia `x + ffn(cat[x, msg])`) on bulk grids in the f16x2
  * modes: 3 (default) = every operand as two fp16 terms, three partial products, f32-accurate; 2 = the activations' fp16 HIGH term only (22-bit weights x
  * 11-bit activations, f32 accumulation: the arithmetic of the attention input projections, and the rounding the fp16 attention applies to q, k, v anyway) --
- * a third less matrix-pipe work.  The error of the assignment scores grows (gn_calibrate_certify measures it), so this setting is meant to run under the
+ * a third less matrix-pipe work.  On this level the GELU's erf is a degree-4 polynomial inside exp2 (6.7e-7 absolute; GELU error <= 3.7e-7 |y|, far
+ * below the fp16 rounding step, 2^-12 |h|, applied to the same value in the next instruction) instead of level 3's degree-7 one (2.2e-8): 12 instead of 17
+ * vector instructions per hidden value.  The error of the assignment scores grows (gn_calibrate_certify measures it), so this setting is meant to run under the
  * margin certificate (gn_set_certify(2 / 3)), which makes the returned correspondence indices independent of the fast pass's arithmetic.  Small grids
  * (fewer than 256 tiles of 128 tokens) keep three products.
  * 0 = the level FOLLOWS THE CERTIFICATE (needs gn_set_certify(2 / 3) and a gn_calibrate_certify made under this setting, which measures eps for both
