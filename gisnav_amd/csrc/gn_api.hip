@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cctype>
 #include <algorithm>
+#include <memory>
 #include <tuple>
 
 using namespace gn;
@@ -129,13 +130,13 @@ struct gn_ctx {
   int cert_eps_src = 0;        // where cert_eps comes from: 0 the built-in default, 1 stated (gn_set_certify), 2 measured (gn_calibrate_certify),
                                // 3 measured on weights since replaced (gn_load_tensor; cert_eps is then +inf: every pair goes to exact f32)
   float cert_eps_f32 = 1.0e-4f;   // the same for the exact-f32 kernels (GPU f32 against the torch-CPU f32 oracle: summation order only)
-  float* max0b = nullptr; float* rpart_c = nullptr; int32_t* uncert = nullptr; int32_t* uncert_alt = nullptr; int32_t* uncert_host = nullptr;   // uncert_host: pinned [2 * max_batch] (flags | the other level's flags)
+  float* max0b = nullptr; float* rpart_c = nullptr; int32_t* uncert = nullptr; int32_t* uncert_alt = nullptr; int32_t* uncert_alt2 = nullptr; int32_t* uncert_host = nullptr;   // uncert_host: pinned [3 * max_batch] (flags | the two other levels' flags)
   bool cert_inner = false;     // a certificate re-run is being enqueued (no nested certification)
   void* cert_stage = nullptr; size_t cert_stage_bytes = 0;      // staging block of the gathered re-run (certify_rerun), grown on demand
   // mode 3 (deferred): gn_estimate leaves the flags of call n in a pinned slot behind an event and resolves them -- reads them, re-runs the flagged
   // pairs from the SAVED arguments -- after call n + 1 has been enqueued (or in gn_flush), so the host never waits for an idle GPU
   struct CertPending {
-    bool active = false; hipEvent_t ev = nullptr; int32_t* flags = nullptr;   // flags: pinned [max_batch]
+    bool active = false; hipEvent_t ev = nullptr; int32_t* flags = nullptr;   // flags: pinned [3 * max_batch] (own level | the two alternates, as uncert_host)
     int npad_run = 0, level = 0;
     Call call; double K9[9] = {0};      // call.K9 points at K9, the saved copy of the caller's matrix
   } cert_pend[2];
@@ -223,7 +224,11 @@ struct gn_ctx {
   // calibrated) every head launch also evaluates the OTHER level's certificate on the same scores (uncert_alt); over windows of >= 64 certified pairs the
   // context counts the pairs each level flags and runs the next window on two products only when that flags at most 1 pair in 64 more than three products
   // would (a re-run in exact f32 costs ~4 block-tail passes of the pair, the two-product pass saves ~7 % of one).  Starts on three products.
-  int auto_level = 3; float cert_eps_lvl[2] = {-1.f, -1.f}; long long auto_pairs = 0, auto_wide = 0, auto_narrow = 0, auto_calls_lvl[2] = {0, 0}, auto_switches = 0;
+  // Third level (one product, W_h X_h: cert_eps_one): the head evaluates all three eps on every automatic call (own level, uncert_alt, uncert_alt2); from two
+  // products the context goes down to one only after two consecutive windows, evaluated on level 2, in each of which one product would have flagged at most
+  // 1 pair in 64 more than three; on level 1 one window that fails that test goes back to 2 (or to 3 when level 2 fails its own test too).
+  int auto_level = 3; float cert_eps_lvl[2] = {-1.f, -1.f}, cert_eps_one = -1.f; long long auto_pairs = 0, auto_wide = 0, auto_narrow = 0, auto_one = 0, auto_calls_lvl[2] = {0, 0}, auto_calls_one = 0, auto_switches = 0;
+  int auto_ok1 = 0;        // consecutive level-2 windows that passed level 1's test
   int ffn_products = 3;    // gn_set_ffn_products: fp16 partial products of the block tail's two GEMMs on bulk grids (k_ffn128, composed form): 3 = f32-accurate split,
                            // 2 = the activations' fp16 high term only (meant to run under the margin certificate)
   int qkv_products = 2;    // knob 27: fp16 partial products of the attention input projections (2 or 3), per context
@@ -594,7 +599,11 @@ bool tail_should_walk(const gn_ctx* c) {
 
 inline bool ffn_auto(const gn_ctx* c) { return c->ffn_products == 0 && c->cert_eps_lvl[0] >= 0.f && c->cert_eps_lvl[1] >= 0.f && c->certify >= 2; }
 inline int ffn_level(const gn_ctx* c) { return c->attn_f16 == 2 ? 3 : c->ffn_products == 0 ? (ffn_auto(c) ? c->auto_level : 3) : c->ffn_products; }
-inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? c->cert_eps_lvl[c->auto_level - 2] : c->cert_eps; }
+inline float ffn_level_eps(const gn_ctx* c, int lvl) { return lvl == 1 ? c->cert_eps_one : c->cert_eps_lvl[lvl - 2]; }
+inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? ffn_level_eps(c, c->auto_level) : c->cert_eps; }
+// the two levels whose certificates a call on level lvl evaluates beside its own (HeadArgs::uncert_alt, uncert_alt2): the other of {2, 3} and 1; on level 1: 2 and 3
+inline int ffn_alt_level(int lvl, int k) { return lvl == 1 ? 2 + k : (k == 0 ? 5 - lvl : 1); }
+inline void ffn_window_reset(gn_ctx* c, int level) { c->auto_level = level; c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = 0; c->auto_ok1 = 0; }
 
 // x += ffn3(gelu(ln(ffn0([x | msg]))))
 // next / next_cross: the block whose attention input projection follows this tail (nullptr: none) -- when the tail runs as the composed k_ffn128 and that
@@ -624,7 +633,7 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     f.walk = c->use_lists == 2 || (c->use_lists == 1 && tail_should_walk(c));
     f.ncu = c->ncu;
     f.composed = comp ? 1 : 0;
-    f.products = (comp && ffn_level(c) == 2) ? 2 : 3;
+    f.products = (comp && ffn_level(c) <= 2) ? ffn_level(c) : 3;
     const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_stamps == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
                           c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
@@ -791,7 +800,10 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     hd.ovf = (c->planes_mode && c->guard) ? c->ovf : nullptr;
     hd.max0b = c->max0b; hd.rpart_c = c->rpart_c; hd.uncert = c->certify ? c->uncert : nullptr;
     hd.cert_eps = (c->precision == GN_PREC_F32) ? c->cert_eps_f32 : cert_eps_now(c);
-    if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) { hd.uncert_alt = c->uncert_alt; hd.cert_eps_alt = c->cert_eps_lvl[3 - c->auto_level]; }
+    if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) {
+      hd.uncert_alt = c->uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
+      hd.uncert_alt2 = c->uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
+    }
     hd.idx = v.idx; hd.score = v.score; hd.n_match = v.n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
     hd.md = c->planes_mode ? (const void*)c->md_p : (const void*)c->md; hd.md_f32 = c->planes_mode ? 0 : 1;
     hd.cpart_m = c->cpart_m; hd.cpart_s = c->cpart_s; hd.cpart_i = c->cpart_i; hd.rpart_a = c->rpart_a; hd.rpart_b = c->rpart_b; hd.tickets = c->tickets;
@@ -833,7 +845,7 @@ int alloc_workspace(gn_ctx* ctx, int max_kpts) {
   }
   if (ctx->precision != GN_PREC_F32) { GN_ALLOC(qkb, T * 2 * kDim); GN_ALLOC(vtb, T * kDim); GN_ALLOC(attn_part, (size_t)256 * 4 * 34 * 64); GN_ALLOC(attn_tickets, 256); }
   GN_ALLOC(rowmax, B * np); GN_ALLOC(rowlog, B * np); GN_ALLOC(colmax, B * np); GN_ALLOC(collog, B * np);
-  GN_ALLOC(max0, B * np); GN_ALLOC(m0, B * np); GN_ALLOC(m1, B * np); GN_ALLOC(max0b, B * np); GN_ALLOC(rpart_c, B * 8 * np); GN_ALLOC(uncert, B); GN_ALLOC(uncert_alt, B);
+  GN_ALLOC(max0, B * np); GN_ALLOC(m0, B * np); GN_ALLOC(m1, B * np); GN_ALLOC(max0b, B * np); GN_ALLOC(rpart_c, B * 8 * np); GN_ALLOC(uncert, B); GN_ALLOC(uncert_alt, B); GN_ALLOC(uncert_alt2, B);
   GN_ALLOC(colbest, B * np); GN_ALLOC(col2, B * np);
   GN_ALLOC(cpart_m, B * (np / 32) * np); GN_ALLOC(cpart_s, B * (np / 32) * np); GN_ALLOC(cpart_i, B * (np / 32) * np); GN_ALLOC(rpart_a, B * 8 * np); GN_ALLOC(rpart_b, B * 8 * np); GN_ALLOC(tickets, B * 2);
   GN_ALLOC(e_idx, B * np * 2); GN_ALLOC(e_score, B * np); GN_ALLOC(e_mkp, B * np * 2); GN_ALLOC(e_obj, B * np * 3);
@@ -869,7 +881,7 @@ __global__ void k_count_diff(const uint4* a, const uint4* b, size_t n, unsigned 
 // k_qkv launches on ITS weights before it is used: the first forward call after a weight (re)load runs, on pseudo-random token rows in the context's own
 // workspaces, the block tail with the projection fused (self and cross form, one-tile and walking form) and tail + k_qkv separately, and compares the
 // q | k rows and V^T panels bit for bit.  Any difference switches the fusion off for this context (gn_fused_projection_status).  ~60 ms, once.
-// Every block-tail level the context can select is proved: three products, and two when gn_set_ffn_products is 2 or 0 (automatic).  The check runs
+// Every block-tail level the context can select is proved: three products, two when gn_set_ffn_products is 2 or 0 (automatic), one when it is 1 or 0.  The check runs
 // at the full padded size (the smallest bulk grid there) whatever gn_set_active_kpts has set: ffn() lays the rows out at npad_run.
 int selfcheck_fused_projection(gn_ctx* c) {
   gn_ctx* ctx = c;
@@ -914,11 +926,12 @@ int selfcheck_fused_projection(gn_ctx* c) {
     const int prod0 = c->ffn_products;
     c->ktiming = false; c->stop_after = 0; c->guard = 0; c->npad_run = np;
     const int nblk = c->n_layers > 1 ? 1 : 0;
-    const int n_lv = (prod0 == 0 || prod0 == 2) ? 2 : 1;     // levels: 3, then 2 when the context can select it
+    const int lvs[3] = {3, prod0 == 1 ? 1 : 2, 1};
+    const int n_lv = prod0 == 0 ? 3 : (prod0 == 2 || prod0 == 1) ? 2 : 1;     // levels: 3, then 2 and / or 1 when the context can select them
     for (int lv = 0; lv < n_lv && applicable; ++lv)
     for (int cross = 0; cross < 2 && applicable; ++cross)
       for (int walk = 0; walk < 2 && applicable; ++walk) {
-        c->ffn_products = lv == 0 ? 3 : 2;
+        c->ffn_products = lvs[lv];
         const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
         const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
         c->use_lists = walk ? 2 : 3;
@@ -954,18 +967,34 @@ int selfcheck_fused_projection(gn_ctx* c) {
   return GN_OK;
 }
 
-// gn_set_ffn_products(0): one certified call's flags (those of the level it ran on, and the other level's from the same scores) into the window
-void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt, int lvl) {      // lvl: the level the call ran on (a deferred call's: saved with it)
-  if (!ffn_auto(c) || c->precision == GN_PREC_F32 || lvl < 2 || lvl > 3) return;
-  ++c->auto_calls_lvl[lvl - 2];
-  int nf = 0, na = 0;
-  for (int b = 0; b < B; ++b) { nf += flags[b] == 1; na += alt[b] == 1; }
-  c->auto_pairs += B; c->auto_wide += lvl == 2 ? nf : na; c->auto_narrow += lvl == 2 ? na : nf;
+// gn_set_ffn_products(0): the window rule, on plain numbers.  level: the level in
+// force; ok1_run: consecutive level-2 windows that passed level 1's test so far; n1 / n2 / n3: pairs of the window each level's certificate flags; have1: level
+// 1 has an eps.  Between 3 and 2 the rule of round 6; down to 1 after two consecutive windows on 2 that pass level 1's test, back up after one that fails.
+int ffn_level_next(int level, int* ok1_run, long long pairs, long long n1, long long n2, long long n3, bool have1) {
+  const bool ok2 = (n2 - n3) * 64 <= pairs, ok1 = have1 && (n1 - n3) * 64 <= pairs;
+  int next = level;
+  if (level == 3) next = ok2 ? 2 : 3;
+  else if (level == 2) {
+    if (!ok2) next = 3;
+    else { *ok1_run = ok1 ? *ok1_run + 1 : 0; next = *ok1_run >= 2 ? 1 : 2; }
+  } else next = ok1 ? 1 : (ok2 ? 2 : 3);
+  if (next != 2) *ok1_run = 0;
+  return next;
+}
+
+// one certified call's flags (those of the level it ran on, and the two other levels' from the same scores) into the window
+void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt, const int32_t* alt2, int lvl) {      // lvl: the level the call ran on (a deferred call's: saved with it)
+  if (!ffn_auto(c) || c->precision == GN_PREC_F32 || lvl < 1 || lvl > 3) return;
+  ++(lvl == 1 ? c->auto_calls_one : c->auto_calls_lvl[lvl - 2]);
+  int n[4] = {0, 0, 0, 0};
+  const int la = ffn_alt_level(lvl, 0), lb = ffn_alt_level(lvl, 1);
+  for (int b = 0; b < B; ++b) { n[lvl] += flags[b] == 1; n[la] += alt[b] == 1; n[lb] += alt2[b] == 1; }
+  c->auto_pairs += B; c->auto_one += n[1]; c->auto_wide += n[2]; c->auto_narrow += n[3];
   if (c->auto_pairs < 64) return;
-  const int next = (c->auto_wide - c->auto_narrow) * 64 <= c->auto_pairs ? 2 : 3;
+  const int next = ffn_level_next(c->auto_level, &c->auto_ok1, c->auto_pairs, c->auto_one, c->auto_wide, c->auto_narrow, c->cert_eps_one >= 0.f);
   if (next != c->auto_level) ++c->auto_switches;
   c->auto_level = next;
-  c->auto_pairs = c->auto_wide = c->auto_narrow = 0;
+  c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = 0;
 }
 
 // The arithmetics a call is run again in, each for the duration of a scope (counters and statistics are never part of one):
@@ -1063,11 +1092,14 @@ template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& 
   const int B = v.B;
   if (!flags_ready) {
     GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (ffn_auto(ctx)) {
+      GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(ctx->uncert_host + 2 * ctx->max_batch, ctx->uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
     GN_HIP(hipStreamSynchronize(s));
     flags_ready = ctx->uncert_host;
   }
-  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_level ? flags_level : ctx->auto_level);     // (both callers lay the other level's flags max_batch entries behind)
+  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_ready + 2 * ctx->max_batch, flags_level ? flags_level : ctx->auto_level);     // (both callers lay the other levels' flags max_batch and 2 max_batch entries behind)
   ++ctx->cert_calls; ctx->cert_pairs += B;
   std::vector<int> flagged, margin;
   for (int b = 0; b < B; ++b) {
@@ -1104,9 +1136,9 @@ template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& 
 }
 
 // gn_calibrate_certify: one pass of the sample w (the whole sample, its first pair, or its first pair with the reference side cut) in arithmetic
-// `arith` -- 2 / 3 = the context's own on that block-tail level, kCalExactF32, kCalMid = the ladder's middle level -- and the host copies of every row's
+// `arith` -- 1 / 2 / 3 = the context's own on that block-tail level, kCalExactF32, kCalMid = the ladder's middle level -- and the host copies of every row's
 // best score and runner-up, of every column's when `cols`, of the per-slot counts when `nv`, and the guard word's trip bit (not read in exact f32)
-enum { kCalExactF32 = 0, kCalMid = 1 };
+enum { kCalExactF32 = 0, kCalMid = -1 };
 struct CalPass { std::vector<float> best, second, colbest, col2; unsigned int trip = 0u; };
 int cal_pass(gn_ctx* ctx, const Call& w, int arith, bool cols, std::vector<int32_t>* nv, CalPass& out, hipStream_t s) {
   int rc = GN_OK;
@@ -1264,10 +1296,10 @@ int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int fea
   if (hipHostMalloc((void**)&ctx->ovf_host, (16 + 4096 + 16) * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
   memset(ctx->ovf_host, 0, (16 + 4096 + 16) * sizeof(unsigned int));
   ctx->tile_feedback = reinterpret_cast<unsigned long long*>(ctx->ovf_host + 16 + 4096);   // [8] x 8 bytes behind the counters (8-byte aligned)
-  if (hipHostMalloc((void**)&ctx->uncert_host, (size_t)2 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
-  memset(ctx->uncert_host, 0, (size_t)2 * max_batch * sizeof(int32_t));
+  if (hipHostMalloc((void**)&ctx->uncert_host, (size_t)3 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
+  memset(ctx->uncert_host, 0, (size_t)3 * max_batch * sizeof(int32_t));
   for (auto& pd : ctx->cert_pend) {
-    if (hipHostMalloc((void**)&pd.flags, (size_t)2 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+    if (hipHostMalloc((void**)&pd.flags, (size_t)3 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "certificate slots: allocation failed"); }
   }
   ctx->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -1465,7 +1497,7 @@ int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int
   if (rc == GN_OK) {
     ctx->loaded[name] = true; ctx->fused_proj_pending = true;
     // a calibration belongs to the weights it was measured on: the automatic block-tail level goes back to "not calibrated" (three products, cert_eps)
-    ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = -1.f; ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+    ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = ctx->cert_eps_one = -1.f; ffn_window_reset(ctx, 3);
     ctx->cert_eps_mid = -1.f;   // (the ladder sends flagged pairs straight to exact f32 until the next calibration)
     // and so does the single eps when it was measured (a stated one is the caller's to keep): every pair is flagged -- exact f32 -- until
     // gn_calibrate_certify runs again or gn_set_certify states an eps
@@ -1555,9 +1587,9 @@ int gn_device_numa_node(int device) {
 int gn_fused_projection_status(const gn_ctx* ctx) { return ctx ? ctx->fused_proj_status : GN_ERR_ARG; }
 
 int gn_set_ffn_products(gn_ctx* ctx, int products) {
-  if (!ctx || (products != 0 && products != 2 && products != 3)) return GN_ERR_ARG;
+  if (!ctx || products < 0 || products > 3) return GN_ERR_ARG;
   if (products != ctx->ffn_products) {
-    ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+    ffn_window_reset(ctx, 3);
     ctx->fused_proj_pending = true;        // the fused projection is proved on every level the new setting can select
   }
   ctx->ffn_products = products;
@@ -1565,9 +1597,40 @@ int gn_set_ffn_products(gn_ctx* ctx, int products) {
 }
 
 int gn_set_ffn_level_eps(gn_ctx* ctx, float eps2, float eps3, int level) {
-  if (!ctx || !(eps2 >= 0.f) || !(eps3 >= 0.f) || (level != 2 && level != 3)) return GN_ERR_ARG;
+  if (!ctx || !(eps2 >= 0.f) || !(eps3 >= 0.f) || level < 1 || level > 3) return GN_ERR_ARG;
   ctx->cert_eps_lvl[0] = std::max(eps2, eps3); ctx->cert_eps_lvl[1] = eps3;
-  ctx->auto_level = level; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+  if (ctx->cert_eps_one >= 0.f) ctx->cert_eps_one = std::max(ctx->cert_eps_one, ctx->cert_eps_lvl[0]);
+  ffn_window_reset(ctx, (level == 1 && !(ctx->cert_eps_one >= 0.f)) ? 2 : level);      // (level 1 without an eps of its own -- gn_set_ffn_level_eps1 -- starts on two products)
+  return GN_OK;
+}
+
+int gn_set_ffn_level_eps1(gn_ctx* ctx, float eps1) {
+  if (!ctx || !(eps1 >= 0.f)) return GN_ERR_ARG;
+  ctx->cert_eps_one = std::max(eps1, std::max(ctx->cert_eps_lvl[0], ctx->cert_eps_lvl[1]));      // eps_one >= eps_two >= eps_three, as gn_calibrate_certify stores them
+  return GN_OK;
+}
+
+int gn_get_ffn_level1(gn_ctx* ctx, float* eps1, int64_t* calls1) {
+  if (!ctx) return GN_ERR_ARG;
+  if (eps1) *eps1 = ctx->cert_eps_one;
+  if (calls1) *calls1 = ctx->auto_calls_one;
+  return GN_OK;
+}
+
+int gn_debug_ffn_level_sim(int n_calls, int B, const int32_t* f1, const int32_t* f2, const int32_t* f3, int have1, int32_t* levels_out, int64_t* out4) {
+  if (n_calls < 0 || B < 1 || !f1 || !f2 || !f3) return GN_ERR_ARG;
+  // a context that owns nothing on the device: only the automatic level's state is touched (ffn_level_update reads no other field)
+  std::unique_ptr<gn_ctx> c(new gn_ctx);
+  c->ffn_products = 0; c->certify = 2; c->precision = GN_PREC_F16X2_BF16_ATTN;
+  c->cert_eps_lvl[0] = 2.f; c->cert_eps_lvl[1] = 1.f; c->cert_eps_one = have1 ? 3.f : -1.f;
+  const int32_t* f[4] = {nullptr, f1, f2, f3};
+  for (int i = 0; i < n_calls; ++i) {
+    const int lvl = c->auto_level;
+    if (levels_out) levels_out[i] = lvl;
+    const size_t o = (size_t)i * B;
+    ffn_level_update(c.get(), B, f[lvl] + o, f[ffn_alt_level(lvl, 0)] + o, f[ffn_alt_level(lvl, 1)] + o, lvl);
+  }
+  if (out4) { out4[0] = c->auto_level; out4[1] = c->auto_switches; out4[2] = c->auto_calls_lvl[0]; out4[3] = c->auto_calls_one; }
   return GN_OK;
 }
 
@@ -1605,12 +1668,12 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   GN_HIP(hipMalloc((void**)&nm, (size_t)B * sizeof(int32_t)));
   Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
   v.idx = ctx->e_idx; v.score = ctx->e_score; v.n_match = nm;
-  // passes: the context's arithmetic -- on BOTH block-tail levels under gn_set_ffn_products(0) -- then the exact-f32 kernels
+  // passes: the context's arithmetic -- on ALL THREE block-tail levels under gn_set_ffn_products(0) -- then the exact-f32 kernels
   const int setting = ctx->ffn_products;
-  const int n_lv = setting == 0 ? 2 : 1;
-  const int lv[2] = {setting == 0 ? 2 : setting, 3};
+  const int n_lv = setting == 0 ? 3 : 1;
+  const int lv[3] = {setting == 0 ? 1 : setting, 2, 3};
   const float L = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
-  CalPass whole[3];
+  CalPass whole[4];
   std::vector<int32_t> nv(2 * (size_t)B);
   unsigned int tripped = 0u;
   const bool lad = ctx->ladder && ctx->planes_mode && ctx->attn_f16 != 2;   // (gn_set_certify_ladder refuses every other context)
@@ -1631,7 +1694,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   // the sample's first pair alone, and with its reference side cut to 128 and to 2 keypoints: the one-pair grid of bucket remainders, and the
   // few-keypoint sides of a ragged stream, where the fp16 attention's rounding averages over few keys (measured against fp64 on a ragged bulk
   // batch: 1.7x the eps of a 16 x 1024 sample alone, tests/test_gpu_fp64_parity.py).  Each level's eps is taken over these passes too.
-  double var_mx[2] = {0.0, 0.0};
+  double var_mx[3] = {0.0, 0.0, 0.0};
   int32_t* nr1 = nullptr;
   if (rc == GN_OK && !tripped && nv[0] >= 2 && nv[1] >= 2 && hipMalloc((void**)&nr1, sizeof(int32_t)) != hipSuccess) rc = GN_ERR_HIP;
   Call v1 = slice(v, 0, 1);
@@ -1639,7 +1702,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   for (int var = 0; nr1 && rc == GN_OK && var < 3; ++var) {
     const int32_t nr_cut = var == 0 ? nv[1] : std::min(nv[1], var == 1 ? 128 : 2);
     if (hipMemcpy(nr1, &nr_cut, sizeof nr_cut, hipMemcpyHostToDevice) != hipSuccess) { rc = GN_ERR_HIP; break; }
-    CalPass p[3];
+    CalPass p[4];
     unsigned int trip = 0u;
     for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
       rc = cal_pass(ctx, v1, pass == n_lv ? kCalExactF32 : lv[pass], false, nullptr, p[pass], s);
@@ -1653,7 +1716,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
   if (tripped) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample left the fp16 range of this precision mode (nothing to calibrate: such calls are re-run as a whole)");
   // largest difference between the two arithmetics over every valid row's best score and runner-up (max_diff)
-  float eps_of[2] = {0.f, 0.f}, mx_of[2] = {0.f, 0.f};
+  float eps_of[3] = {0.f, 0.f, 0.f}, mx_of[3] = {0.f, 0.f, 0.f};
   for (int k = 0; k < n_lv; ++k) {
     long long rows = 0;
     double mx = max_diff(whole[k], whole[n_lv], nv, B, np, false, L, &rows);
@@ -1665,8 +1728,8 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   }
   if (setting == 0) {
     // the wider level's bound is never stated tighter than the narrower one's (a sample can happen to show the opposite)
-    ctx->cert_eps_lvl[1] = eps_of[1]; ctx->cert_eps_lvl[0] = std::max(eps_of[0], eps_of[1]);
-    ctx->auto_level = 3; ctx->auto_pairs = ctx->auto_wide = ctx->auto_narrow = 0;
+    ctx->cert_eps_lvl[1] = eps_of[2]; ctx->cert_eps_lvl[0] = std::max(eps_of[1], eps_of[2]); ctx->cert_eps_one = std::max(eps_of[0], ctx->cert_eps_lvl[0]);
+    ffn_window_reset(ctx, 3);
   }
   if (lad && mid_mx >= 0.0) {
     if (!std::isfinite(mid_mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the middle level's pass");
@@ -1709,7 +1772,7 @@ int gn_reset_certify_stats(gn_ctx* ctx) {
   if (!ctx) return GN_ERR_ARG;
   ctx->cert_calls = ctx->cert_pairs = ctx->cert_flag_margin = ctx->cert_flag_range = ctx->cert_rerun = ctx->cert_f32_marginal = 0;
   ctx->mid_rerun = ctx->mid_certified = ctx->mid_passed = 0;
-  ctx->auto_calls_lvl[0] = ctx->auto_calls_lvl[1] = ctx->auto_switches = 0;
+  ctx->auto_calls_lvl[0] = ctx->auto_calls_lvl[1] = ctx->auto_calls_one = ctx->auto_switches = 0;
   return GN_OK;
 }
 
@@ -1835,7 +1898,7 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   mv(c->qkb, T2 * 2 * kDim); mv(c->vtb, T2 * kDim);
   mv(c->rowmax, np); mv(c->rowlog, np); mv(c->colmax, np); mv(c->collog, np); mv(c->max0, np); mv(c->m0, np); mv(c->m1, np);
   mv(c->cpart_m, (np / 32) * np); mv(c->cpart_s, (np / 32) * np); mv(c->cpart_i, (np / 32) * np); mv(c->rpart_a, 8 * np); mv(c->rpart_b, 8 * np); mv(c->tickets, 2);
-  mv(c->max0b, np); mv(c->rpart_c, 8 * np); mv(c->uncert, 1); mv(c->uncert_alt, 1); mv(c->colbest, np); mv(c->col2, np);
+  mv(c->max0b, np); mv(c->rpart_c, 8 * np); mv(c->uncert, 1); mv(c->uncert_alt, 1); mv(c->uncert_alt2, 1); mv(c->colbest, np); mv(c->col2, np);
   // match lists and the PnP masks are strided by the context's padded maximum (gn_kmax), whatever the active size
   const long long km = c->npad;
   mv(c->e_idx, km * 2); mv(c->e_score, km); mv(c->e_mkp, km * 2); mv(c->e_obj, km * 3);
@@ -2014,8 +2077,10 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     gn_ctx::CertPending& p = ctx->cert_pend[slot];
     if (p.active) { const int rcr = cert_resolve(ctx, slot, s); if (rcr != GN_OK) return rcr; }     // (cannot happen in the alternating order; kept for safety)
     GN_HIP(hipMemcpyAsync(p.flags, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (ffn_auto(ctx)) GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    else memset(p.flags + ctx->max_batch, 0, (size_t)B * sizeof(int32_t));
+    if (ffn_auto(ctx)) {
+      GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(p.flags + 2 * ctx->max_batch, ctx->uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    } else memset(p.flags + ctx->max_batch, 0, (size_t)2 * ctx->max_batch * sizeof(int32_t));
     GN_HIP(hipEventRecord(p.ev, s));
     p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.npad_run = ctx->npad_run;
     p.call = v; memcpy(p.K9, K9, sizeof p.K9); p.call.K9 = p.K9;

@@ -285,6 +285,8 @@ struct HeadArgs {
   float cert_eps;           // bound on |P_this mode - P_exact| the certificate is stated for
   int32_t* uncert_alt = nullptr;   // [B] out (optional): the same test for cert_eps_alt -- what the OTHER block-tail level's certificate would say about these
   float cert_eps_alt = -1.f;       // scores (gn_set_ffn_products(0): the context weighs the two levels' re-run fractions against each other); 0 / 1
+  int32_t* uncert_alt2 = nullptr;  // [B] out (optional): and for a third eps, cert_eps_alt2 (the automatic block-tail level weighs three levels: own + two alternates)
+  float cert_eps_alt2 = -1.f;
   float* colbest = nullptr;        // [B][npad] out (optional, fused head): best score and runner-up of every column (gn_calibrate_certify's middle
   float* col2 = nullptr;           // level measures its eps over row AND column decisions)
 };

@@ -66,9 +66,14 @@ constexpr float kErf2Clamp = 5.75f;
 // projections since round 4, one rounding of the GEMM inputs to fp16, which the fp16 attention beside it applies to q, k, v and the probabilities anyway.
 // A third of the matrix-pipe work of both GEMMs, half of the token-fragment reads, no residual split of the hidden tile, the degree-4 erf.  Meant to run under the margin
 // certificate (gn_set_certify), which makes the correspondence indices independent of the fast pass's arithmetic; composed form only.
+// 1 = the weights' fp16 high term only as well (W_h X_h: plane 0 of every fragment pair, p == 2 of the product loops): one MFMA per k-step instead of two and
+// half the weight bytes in GEMM 1 and GEMM 2 -- a second rounding of the GEMM inputs, independent of the activations' and of the same relative size.  The bias
+// through the accumulators, the LayerNorm statistics, the degree-4 erf, the fp16 publish, the epilogue, the range guard and the padding-tile exit are level 2's;
+// the fused next-block projection (QKV) stays on two products, expression for expression.  Under the certificate and composed form only, as 2.
 template <int ABL, bool COMP, bool LOOP = false, int QKV = 0, int PROD = 3>   // LOOP: the workgroup walks the work list (one workgroup per CU); ABL: 0, or 8 = s_memtime stamps per phase into a.dbg_ts, + 128 = per k-tile stamps too (results stay valid)
 __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
-  static_assert(PROD == 3 || (PROD == 2 && COMP), "two partial products: composed form only");
+  static_assert(PROD == 3 || ((PROD == 2 || PROD == 1) && COMP), "two partial products / one: composed form only");
+  constexpr bool HI = PROD != 3;          // the GEMMs read the activations' fp16 high term only (levels 2 and 1)
   constexpr int NJ = 4, NI = 4, NO = 2, NW = 4, TM = 128;
   constexpr int KT = TM * 128;            // bytes of one 32-wide k-tile of 128 token rows (hm16: 128 B per row)
   constexpr int RING = 8 * KT;            // two staging slots behind the message tile
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
   auto read_b = [&](int g, int tile_off, int ks, int j) __attribute__((always_inline)) {
     const int off = tile_off + (j >> 1) * 8192;
 #pragma unroll
-    for (int pl = 0; pl < (PROD == 2 ? 1 : 2); ++pl) bq[g % 3][pl] = *reinterpret_cast<const f16x8*>(smem + bo[off >> 16][j & 1][2 * ks + pl] + (off & 65535));
+    for (int pl = 0; pl < (HI ? 1 : 2); ++pl) bq[g % 3][pl] = *reinterpret_cast<const f16x8*>(smem + bo[off >> 16][j & 1][2 * ks + pl] + (off & 65535));
   };
   // a lane's accumulator registers 8 ks' .. 8 ks' + 7 of tile (., j) ARE one 16-byte B-operand fragment of a following transposed
   // GEMM (whose weight columns are permuted to this order in the re-layout): publishing costs two ds_write_b128 per fragment.
@@ -221,8 +226,11 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 
   // GEMM 1's weight ring is requested now: its latency hides behind the message publish
   const __amdgpu_buffer_rsrc_t w1b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.w1s) + (size_t)(NI * wave) * 32 * 2 * 512, 0, NI * 32 * 2 * 1024, 0x00020000);
-  constexpr int RA = 4;     // ring slots (8 KB per wave each); k-step n2 uses slot n2 % RA and refills slot (n2 - 1) % RA
-  f16x8 fa[RA][NI][2];
+  // ring slots (8 KB per wave each; one product: the W_h fragments only, 4 KB, and twice the slots in the same registers -- stamps: GEMM 1 32.4 k cycles
+  // against 33.3 k with four, inside the +-1.7 k two processes differ by; kept because it costs nothing); k-step n2 uses slot n2 % RA and refills slot (n2 - 1) % RA
+  constexpr int RA = PROD == 1 ? 8 : 4;
+  constexpr int NPL = PROD == 1 ? 1 : 2;      // weight terms a GEMM of the tail reads: W_h alone (plane 0 of every fragment pair), or W_h and W_m
+  f16x8 fa[RA][NI][NPL];
   // GEMM 1 visits the k-tiles in the order 8..15 (message), 0..7 (x): sequence number n2 (k-steps) -> weight k-step (n2 + 16) & 31
   auto load_a = [&](int slot, int n2, int i, int pl) __attribute__((always_inline)) {
     fa[slot][i][pl] = ldw(w1b, ((i * 32 + (COMP ? n2 : ((n2 + 16) & 31))) * 2 + pl) * 1024);
@@ -239,7 +247,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
       for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) load_a(q, q, i, pl);
+        for (int pl = 0; pl < NPL; ++pl) load_a(q, q, i, pl);
     if (tid < 128) *reinterpret_cast<f32x4*>(smem + B1OFF + 16 * tid) = b1q * (1.0f / s1);
 #pragma unroll
     for (int q = 0; q < 4; ++q) stage_write(0, q);
@@ -377,13 +385,15 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
         for (int pl = 0; pl < 2; ++pl) load_a(q, q, i, pl);
   }
   uint4 cst_a;      // the thread's share of the LayerNorm weight / bias arrays on their way to LDS
+  constexpr int LA1 = PROD == 1 ? 2 : 1;      // j-steps a token fragment is read ahead of its MFMAs (one product: 4 MFMAs per j-step, so two)
   read_b(0, COMP ? RING : 0, 0, 0);
+  if constexpr (PROD == 1) read_b(1, RING, 0, 1);
   GN_PIN();
   auto gemm1_kstep = [&](int n2) __attribute__((always_inline)) {       // k-tile n = n2 >> 1: n < 8: message k-tile n; n >= 8: staged tile n (x k-tile n - 8) in ring slot n & 1
     const int n = n2 >> 1, ks = n2 & 1;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int g = 4 * n2 + j, g1 = g + 1, m2 = g1 >> 2, nn = m2 >> 1;
+      const int g = 4 * n2 + j, g1 = g + LA1, m2 = g1 >> 2, nn = m2 >> 1;
       if (m2 < 32) read_b(g1, (!COMP && nn < 8) ? nn * KT : RING + (nn & 1) * KT, m2 & 1, g1 & 3);
       // products: W_m X_h, W_h X_m, W_h X_h (small terms first), the four hidden tiles round-robin
 #pragma unroll
@@ -391,13 +401,15 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           if (PROD == 2 && p == 1) continue;            // (W_h X_m: not in the two-product form)
-          const int mj = 4 * p + i;       // MFMA number inside the j-step
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[n2 % RA][i][p == 0 ? 1 : 0], bq[g % 3][p == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
-          // the memory instructions of the k-step, one per MFMA gap: three products: gaps 2 | 5, 10 | 7 of the j-step's 12; two products: 2 | 1, 9 | 3 of its 8 (mj 4..7 do not exist)
-          constexpr int kLa0 = PROD == 3 ? 5 : 1, kLa1 = PROD == 3 ? 10 : 9, kSl = PROD == 3 ? 7 : 3;
+          if (PROD == 1 && p != 2) continue;            // (one product: W_h X_h alone)
+          const int mj = PROD == 1 ? i : 4 * p + i;       // MFMA number inside the j-step
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[n2 % RA][i][(p == 0 && NPL == 2) ? 1 : 0], bq[g % 3][p == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
+          // the memory instructions of the k-step, one per MFMA gap: three products: gaps 2 | 5, 10 | 7 of the j-step's 12; two products: 2 | 1, 9 | 3 of its 8 (mj 4..7 do not exist);
+          // one product: 2 | 1 | 3 of its 4 (one weight fragment per j-step: hidden tile j's)
+          constexpr int kLa0 = PROD == 3 ? 5 : 1, kLa1 = PROD == 3 ? 10 : (PROD == 2 ? 9 : -1), kSl = PROD == 3 ? 7 : 3;
           if ((COMP || n >= 8) && ks == 0 && n + 1 < 16 && mj == 2) stage_write(n + 1, j);
           if ((mj == kLa0 || mj == kLa1) && n2 >= 1 && n2 + RA - 1 < 32) {
-            const int u = 2 * j + (mj == kLa1 ? 1 : 0);   // 0..7 -> (i, term)
+            const int u = PROD == 1 ? 2 * j : 2 * j + (mj == kLa1 ? 1 : 0);   // 0..7 -> (i, term)
             load_a((n2 - 1) % RA, n2 + RA - 1, u >> 1, u & 1);
           }
           if (ks == 0 && (COMP || n + 3 >= 9) && n + 3 < 16 && mj == kSl) stage_load(n + 3, j);     // (x tiles 9, 10 are requested during the last message k-tiles)
@@ -430,9 +442,9 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 
   // wave w: output features 64 w ..; k-steps are visited quarter by quarter: sequence number c = 8 q + 2 w' + ks -> weight k-step 8 w' + 2 q + ks
   const __amdgpu_buffer_rsrc_t w2b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.w2s) + (size_t)(NO * wave) * 32 * 2 * 512, 0, NO * 32 * 2 * 1024, 0x00020000);        // output tile NO w + o: 1 KB block ((tile * 32 + kstep) * 2 + term)
-  constexpr int RG = 5;      // W2 k-tiles in flight.  (Six cost 16 more registers: the LayerNorm constants of the last two quarters then went to scratch and their
+  constexpr int RG = PROD == 1 ? 10 : 5;      // W2 k-tiles in flight (one product: W_h fragments only, twice the k-tiles in the same registers).  (Six cost 16 more registers: the LayerNorm constants of the last two quarters then went to scratch and their
                              // reload in the middle of GEMM 2 drained the ring: 164 -> 162 us with five, same bits.)
-  f16x8 ga[RG][NO][2];
+  f16x8 ga[RG][NO][NPL];
   auto load_g = [&](int slot, int c, int o, int pl) __attribute__((always_inline)) {
     const int kstep = 8 * ((c >> 1) & 3) + 2 * (c >> 3) + (c & 1);
     ga[slot][o][pl] = ldw(w2b, ((o * 32 + kstep) * 2 + pl) * 1024);
@@ -491,7 +503,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
     for (int o = 0; o < NO; ++o)
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) load_g(q, q, o, pl);
+      for (int pl = 0; pl < NPL; ++pl) load_g(q, q, o, pl);
 
   // ---------------------------------------------------------------- normalise + erf GELU + split + publish of one fragment, as 22 stages
   // wave w's hidden units 32 (NI w + q) .. of quarter q -> k-tile w of buffer q & 1 (the message tile's space: GEMM 1 is done with it)
@@ -509,8 +521,8 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     } else if (st == 2) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) gy[e] = gy[e] * c2[e >> 2][e & 3] + c3[e >> 2][e & 3];
-    } else if constexpr (PROD == 2) {
-      // the two-product level: 15 stages (10 instructions per value from here; kErf2C above).  t = min(|y|, C) and the last fma's |0.5 y| are source
+    } else if constexpr (HI) {
+      // the two-product level (and the one-product level, which shares it): 15 stages (10 instructions per value from here; kErf2C above).  t = min(|y|, C) and the last fma's |0.5 y| are source
       // modifiers: no scale by 1 / sqrt 2, no copysign (|hy| u + hy == hy copysign(u, y) + hy bit for bit)
       if (st == 3) {
 #pragma unroll
@@ -602,7 +614,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     for (int k = 0; k < 8; ++k) y[k] = pair(acc[q][j], 2 * k) * splat2(rs[j]) + splat2(nmr[j]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) y[k] = y[k] * (f32x2v){w4[k >> 1][2 * (k & 1)], w4[k >> 1][2 * (k & 1) + 1]} + (f32x2v){b4[k >> 1][2 * (k & 1)], b4[k >> 1][2 * (k & 1) + 1]};
-    if constexpr (PROD == 2) {
+    if constexpr (HI) {
       // the two-product level's erf (kErf2C above; the same operations, hence the same bits, as gelu_stage's): the clamp and the last fma carry the
       // abs source modifier, which packed arithmetic does not have -- two scalar instructions each, as the clamp and the copysign were
 #pragma unroll
@@ -717,13 +729,25 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
           for (int o = 0; o < NO; ++o) {
             if (PROD == 2 && p == 1) continue;            // (W_h H_m: not in the two-product form)
-            acc2[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[c % RG][o][p == 0 ? 1 : 0], bq[g % 3][p == 1 ? 1 : 0], acc2[o][j], 0, 0, 0);
+            if (PROD == 1 && p != 2) continue;            // (one product: W_h H_h alone)
+            acc2[o][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[c % RG][o][(p == 0 && NPL == 2) ? 1 : 0], bq[g % 3][p == 1 ? 1 : 0], acc2[o][j], 0, 0, 0);
             if constexpr (PROD == 3) {
               const int m = 6 * j + 2 * p + o;
               // the VALU stage of the next quarter's fragment (token tile w4, k-step ks) that shares this MFMA's gap
               if (fill && m < 22) gelu_stage(m, q + 1, w4, ks);
               if (q == 3 && m == 2 && !LOOP) res_load(cc);      // (walking form: the registers are not there, all residual rows are requested in the epilogue)
               if (m % 6 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, (m / 6) >> 1, (m / 6) & 1);
+            } else if constexpr (PROD == 1) {
+              // eight MFMA gaps per (quarter, k-step) for the same fifteen stages: two per gap, the last gap -- which carries the second of the k-step's
+              // two weight loads -- the publish alone.  The MFMA of a gap lasts as long as ~5 VALU instructions of the wave: this loop runs at the
+              // stages' pace (phase table), the matrix pipe waits.
+              const int m = 2 * j + o;
+              if (fill) {
+                gelu_stage(2 * m, q + 1, w4, ks);
+                if (m < 7) gelu_stage(2 * m + 1, q + 1, w4, ks);
+              }
+              if (q == 3 && m == 2 && !LOOP) res_load(cc);
+              if (m % 4 == 3 && c >= 1 && c + RG - 1 < 32) load_g((c - 1) % RG, c + RG - 1, m / 4, 0);
             } else {
               // sixteen MFMA gaps per (quarter, k-step) for the fragment's fifteen stages (degree-4 erf, no residual split): one stage per gap, no
               // gap shared.  The gap left empty is the last one, which also carries a weight load (m % 4 == 3: each load holds the wave's issue ~30
@@ -996,6 +1020,23 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #undef GN_PIN
 }  // namespace
 
+#ifdef GN_FFN128_LEVEL1_TU
+// The one-product forms (PROD == 1) are compiled in a translation unit of their own, gn_ffn128_l1.hip, which includes this file with GN_FFN128_LEVEL1_TU
+// defined: seven more instantiations of a ~17 k-instruction kernel would lengthen this file's (serial) compile by half.  b, grid, walk: as launch_ffn128
+// has prepared them; qv: the fused projection (0 with stamps).
+void launch_ffn128_level1(const FfnArgs& b, dim3 grid, bool walk, int stamps, int qv, hipStream_t s) {
+  const dim3 block(256);
+#define GN_F1(Q) do { if (stamps == 8) hipLaunchKernelGGL((k_ffn128<8, true, false, 0, 1>), grid, block, 0, s, b); \
+                      else if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true, Q, 1>), grid, block, 0, s, b); \
+                      else hipLaunchKernelGGL((k_ffn128<0, true, false, Q, 1>), grid, block, 0, s, b); } while (0)
+  if (qv == 1) { GN_F1(1); g_last_kernel = walk ? "k_ffn128<0, true, true, 1, 1>" : "k_ffn128<0, true, false, 1, 1>"; }
+  else if (qv == 2) { GN_F1(2); g_last_kernel = walk ? "k_ffn128<0, true, true, 2, 1>" : "k_ffn128<0, true, false, 2, 1>"; }
+  else { GN_F1(0); g_last_kernel = walk ? "k_ffn128<0, true, true, 0, 1>" : "k_ffn128<0, true, false, 0, 1>"; }
+#undef GN_F1
+}
+#else
+void launch_ffn128_level1(const FfnArgs& b, dim3 grid, bool walk, int stamps, int qv, hipStream_t s);      // gn_ffn128_l1.hip
+
 void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s) {
   const int ncu = a.ncu > 0 ? a.ncu : device_cu_count();
   const bool walk = a.tiles != nullptr && a.walk && stamps == 0;
@@ -1003,6 +1044,10 @@ void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s) {
   FfnArgs b = a;
   if (!walk) b.tiles = nullptr;
   if (walk || stamps != 0) b.nvalid = nullptr;
+  if (a.composed && a.products == 1 && (stamps == 0 || stamps == 8)) {      // one product (W_h X_h): composed form only
+    launch_ffn128_level1(b, grid, walk, stamps, stamps == 0 ? a.qkv : 0, s);
+    return;
+  }
   if (a.composed && a.products == 2 && (stamps == 0 || stamps == 8)) {      // two partial products (round 6): composed form only
 #define GN_F2(Q) do { if (stamps == 8) hipLaunchKernelGGL((k_ffn128<8, true, false, Q, 2>), grid, block, 0, s, b); \
                       else if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true, Q, 2>), grid, block, 0, s, b); \
@@ -1040,5 +1085,7 @@ void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s) {
   }
   g_last_kernel = walk ? "k_ffn128<0, false, true, 0, 3>" : "k_ffn128<0, false, false, 0, 3>";
 }
+
+#endif
 
 }  // namespace gn

@@ -162,23 +162,39 @@ int gn_set_certify(gn_ctx* ctx, int mode, float eps, float eps_f32);
  * vector instructions per hidden value.  The error of the assignment scores grows (gn_calibrate_certify measures it), so this setting is meant to run under the
  * margin certificate (gn_set_certify(2 / 3)), which makes the returned correspondence indices independent of the fast pass's arithmetic.  Small grids
  * (fewer than 256 tiles of 128 tokens) keep three products.
+ * 1 = the weights' fp16 HIGH term only as well (W_h X_h: one product per k-step, 11-bit weights x 11-bit activations -- a second, independent rounding of the
+ * size of the activations'; half of level 2's matrix-pipe work and weight bytes in both GEMMs; LayerNorm, the degree-4 erf, the fp16-range guard and the fused
+ * next-block projection, which stays on two products, are level 2's).  Composed form on bulk grids only, and under the certificate, as 2.
  * 0 = the level FOLLOWS THE CERTIFICATE (needs gn_set_certify(2 / 3) and a gn_calibrate_certify made under this setting, which measures eps for both
  * levels; three products otherwise): every matcher call also evaluates the other level's certificate on its scores, the context counts over windows
  * of >= 64 certified pairs how many pairs each level flags, and runs the next window on two products only when that would flag at most 1 pair in 64
  * more than three products (a flagged pair costs an exact-f32 re-run, ~4 fast passes; the two-product pass saves ~7 % of one).  Starts on three
  * products.  The returned indices do not depend on the level (both are certified against the same exact arithmetic); scores differ within eps.
- * gn_load_tensor discards the two levels' calibration (three products until gn_calibrate_certify / gn_set_ffn_level_eps is called again). */
+ * Under 0 gn_calibrate_certify also measures eps_one_product (same passes, same extra grids; stored so that eps_one >= eps_two >= eps_three) and every call
+ * evaluates all three certificates.  From two products the context goes down to one only after TWO consecutive windows on level 2 in each of which one product
+ * would have flagged at most 1 pair in 64 more than three products; on level 1 a single window that fails that test goes back to 2 (to 3 when level 2 fails
+ * its own test as well).  The first 128 certified pairs of a context therefore behave as before the third level existed.
+ * gn_load_tensor discards the levels' calibration (three products until gn_calibrate_certify / gn_set_ffn_level_eps is called again). */
 int gn_set_ffn_products(gn_ctx* ctx, int products);
-/* The level the next call runs on (2 / 3), the eps calibrated for each (< 0: not calibrated), and out4 = {certified calls that ran on two products, on three
+/* The level the next call runs on (1 / 2 / 3), the eps calibrated for each (< 0: not calibrated), and out4 = {certified calls that ran on two products, on three
  * products, level switches, 1 when the automatic setting is in effect} since gn_reset_certify_stats.  Any pointer may be NULL. */
 int gn_get_ffn_level(gn_ctx* ctx, int32_t* level, float* eps2, float* eps3, int64_t* out4);
 /* The two levels' eps and the level to start on, stated by the caller instead of measured (values a gn_calibrate_certify of the same weights and
  * batch size returned earlier: a process that restarts need not repeat the calibration's exact-f32 pass). */
 int gn_set_ffn_level_eps(gn_ctx* ctx, float eps2, float eps3, int level);
+/* The one-product level's share of the two calls above (their ABI is unchanged): its eps (< 0: not calibrated -- the level is then never selected) and the
+ * certified calls that ran on it.  gn_set_ffn_level_eps1 states eps_one (stored as max(eps_one, eps_two)); call it BEFORE gn_set_ffn_level_eps when the
+ * context is to start on level 1: gn_set_ffn_level_eps(e2, e3, 1) without a stated eps_one starts on level 2. */
+int gn_get_ffn_level1(gn_ctx* ctx, float* eps1, int64_t* calls1);
+int gn_set_ffn_level_eps1(gn_ctx* ctx, float eps1);
+/* Developer / test entry, no device: the automatic level's rule run over n_calls synthetic calls of B pairs, starting on three products.  f1, f2, f3:
+ * [n_calls][B] flags (0 / 1) the one-, two- and three-product certificates would raise on each call's scores; have1: level 1 has an eps.  levels_out
+ * [n_calls] (may be NULL): the level each call ran on; out4 (may be NULL) = {level after the last call, switches, calls on two products, calls on one}. */
+int gn_debug_ffn_level_sim(int n_calls, int B, const int32_t* f1, const int32_t* f2, const int32_t* f3, int have1, int32_t* levels_out, int64_t* out4);
 /* On bulk grids the block-tail kernel also computes the next block's attention input projection (one launch and one pass over the residual rows
  * less).  Every context proves that fused form against the separate launches on its own weights before using it: at the first forward call after
  * a weight (re)load or a change of gn_set_ffn_products both forms run on pseudo-random rows, at the full padded size whatever gn_set_active_kpts
- * has set, on every block-tail level the setting can select (three products; also two under 2 or 0), and their outputs are compared bit for bit
+ * has set, on every block-tail level the setting can select (three products; also two under 2 or 0, one under 1 or 0), and their outputs are compared bit for bit
  * (~60 ms per level, once); a difference switches the fusion off for the context until the next check passes.  Returns 1 = checked equal, 0 = differed (fusion off), -1 = not run yet / not applicable (small contexts, other modes). */
 int gn_fused_projection_status(const gn_ctx* ctx);
 /* NUMA node of HIP device `device` (its PCI function's /sys/bus/pci/devices/<bus id>/numa_node), or -1 when the platform does not say.  The host side pins

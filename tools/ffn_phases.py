@@ -12,7 +12,7 @@ from gisnav_amd.weights import synthetic_state_dict  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 if len(sys.argv) > 2:
-    # ffn_phases.py <batch> <products>: the stamps of k_ffn128<8, true, false, ., products> (one-tile composed form of the headline mode; tools/ffn128_ab.py
+    # ffn_phases.py <batch> <products>: the stamps of k_ffn128<8, true, false, ., products>, products = 3 / 2 / 1 (one-tile composed form of the headline mode; tools/ffn128_ab.py
     # prints the same table for three products next to its A/B) from the first block-tail launch of a bench-sized call
     products = int(sys.argv[2])
     eng = PoseEngine(0, max_batch=B, max_kpts=1024, precision="f16x2_f16_attn", state_dict=synthetic_state_dict(0))
