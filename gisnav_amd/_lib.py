@@ -31,6 +31,9 @@ SIGNATURES = {
     "gn_missing_tensors": (C.c_int, [VP]),
     "gn_set_num_layers": (C.c_int, [VP, C.c_int]),
     "gn_set_filter_threshold": (C.c_int, [VP, C.c_float]),
+    "gn_set_width_pruning": (C.c_int, [VP, C.c_float, C.c_int]),
+    "gn_get_width_pruning": (C.c_int, [VP, c_f32p, C.POINTER(C.c_int)]),
+    "gn_get_prune": (C.c_int, [VP, C.c_int, c_i32p, c_i32p]),
     "gn_match": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, VP]),
     "gn_kmax": (C.c_int, [VP]),
     "gn_gather_points": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),

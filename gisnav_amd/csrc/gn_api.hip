@@ -159,6 +159,11 @@ struct gn_ctx {
   int npad_run = 0;        // padded keypoint count the matcher runs at (<= npad, gn_set_active_kpts); buffers are laid out for it per call
   int n_layers = kMaxLayers;
   float threshold = 0.5f;
+  // point pruning (gn_set_width_pruning; gn_prune.hip): off unless width_conf > 0.  pr_*: [B * 2][npad_run] per call, sliced by shift_workspaces
+  float width_conf = -1.f; int prune_min_kpts = 1536;
+  int32_t *pr_ind = nullptr, *pr_prune = nullptr, *pr_dst = nullptr, *pr_counts = nullptr;   // pr_counts: [B * 2][kMaxLayers] a slot's count after every layer
+  int32_t* pr_nin = nullptr; float* pr_z = nullptr;      // [B * 2] the call's input counts (the head's no-match rule); [B * 2][npad_run] z of the last pruning layer
+  bool prune_last_on = false; int prune_last_np = 0, prune_last_layers = 0, prune_last_B = 0;                  // the most recent matcher call (gn_get_prune)
   std::string err;
   // weights
   Linear input_proj;
@@ -718,6 +723,11 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     const int g = (int)(c->ovf - c->ovf_base);
     launch_tile_lists(c->nvalid, BS, np, c->lists, (c->tile_feedback && g >= 0 && g < 8) ? c->tile_feedback + g : nullptr, s);
   }
+  // point pruning: ind = arange, prune = ones behind k_prep's counts; then one k_prune + list rebuild behind every cross block but the last
+  const bool pruning = c->width_conf > 0.f && c->pr_ind != nullptr;
+  c->prune_last_on = pruning; c->prune_last_np = np; c->prune_last_layers = c->n_layers;
+  if (!c->in_group) c->prune_last_B = B;      // (a sub-batch group sees its own share: estimate_call records the call's)
+  if (pruning) launch_prune_init(c->pr_ind, c->pr_prune, c->pr_nin, c->nvalid, BS, np, s);
   bool qkv_done = false;      // the previous tail has already computed this block's attention input projection
   for (int i = 0; i < c->n_layers; ++i) {
     {  // SelfBlock on both sides at once
@@ -783,7 +793,20 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
         GemmArgs g = gemm_args(c->ctx, kDim, blk.proj_out, c->msg, kDim, T);
         gemm(c, EPI_BIAS, g, s);
       }
-      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, blk, T, s, i == c->n_layers - 1, (bf16v2 && i + 1 < c->n_layers) ? &c->self_blk[i + 1] : nullptr, false, np, vt_perm); }   // the last block leaves f32 x for the match head
+      // (pruning: the next self block's projection must see the pruned rows, so the cross tail does not fuse it)
+      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, blk, T, s, i == c->n_layers - 1, (bf16v2 && i + 1 < c->n_layers && !pruning) ? &c->self_blk[i + 1] : nullptr, false, np, vt_perm); }   // the last block leaves f32 x for the match head
+      if (pruning && i + 1 < c->n_layers && !(c->stop_after && c->launch_count >= c->stop_after)) {
+        StageTimer tm(c, s, ST_PREP);
+        const bool planes_only = c->planes_mode && c->x_planes_only;
+        PruneArgs pa;
+        pa.x = planes_only ? nullptr : c->x; pa.xp = c->planes_mode ? c->x_p : nullptr; pa.z_from_planes = planes_only ? 1 : 0;
+        pa.cos_t = c->cos_t; pa.sin_t = c->sin_t; pa.rot4 = c->rot4; pa.rot_stride = (long long)c->Tmax;
+        pa.ind = c->pr_ind; pa.prune = c->pr_prune; pa.dst = c->pr_dst; pa.nvalid = c->nvalid; pa.counts = c->pr_counts; pa.layer = i; pa.z = c->pr_z;
+        pa.w = c->matchability[i].w; pa.b = c->matchability[i].b; pa.thresh = 1.0f - c->width_conf; pa.min_kpts = c->prune_min_kpts; pa.BS = BS; pa.npad = np;
+        // (bytes: every row read once for z; the moved rows are counted as all of them, read and written)
+        timed_launch(c, s, 0, 2.0 * T * kDim, (double)T * (pa.x ? 3.0 : 0.0) * 4.0 * kDim + (double)T * (pa.xp ? 3.0 : 0.0) * 4.0 * kDim, "k_prune", [&] { launch_prune(pa, s); });
+        if (c->use_lists && c->lists) launch_tile_lists(c->nvalid, BS, np, c->lists, nullptr, s);
+      }
     }
   }
   {
@@ -794,6 +817,7 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     gemm(c, EPI_SCALE_COLS, g, s);
     launch_matchability(c->x, c->matchability[li].w, c->matchability[li].b, c->ls, T, s);
     HeadArgs hd;
+    hd.n_in = pruning ? c->pr_nin : nullptr;
     hd.sim = c->sim; hd.ls = c->ls; hd.nvalid = c->nvalid; hd.B = B; hd.npad = np; hd.threshold = c->threshold;
     hd.rowmax = c->rowmax; hd.rowlog = c->rowlog; hd.colmax = c->colmax; hd.collog = c->collog;
     hd.m0 = c->m0; hd.max0 = c->max0; hd.m1 = c->m1;
@@ -813,6 +837,7 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
       timed_launch(c, s, 0, 2.0 * 2.0 * B * (double)np * np * kDim,                         // the similarity tiles are computed twice
                    2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0,            // descriptors once per sweep, per-row / per-column statistics, matches
                    "k_head_fused (2 sweeps)", [&] { launch_match_head_fused(hd, s); });
+      if (pruning) launch_unprune_idx(v.idx, v.n_match, c->pr_ind, B, np, c->npad, s);
       return GN_OK;
     }
     GemmArgs gs;
@@ -822,6 +847,7 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     gs.strideA = gs.strideW = 2LL * np * kDim; gs.strideY = (long long)np * np;
     timed_gemm(c, EPI_PLAIN, gs, B, s);
     launch_match_head(hd, s);
+    if (pruning) launch_unprune_idx(v.idx, v.n_match, c->pr_ind, B, np, c->npad, s);
   }
   return GN_OK;
 }
@@ -859,6 +885,8 @@ int alloc_workspace(gn_ctx* ctx, int max_kpts) {
   ctx->ovf = ctx->ovf_base;
   ctx->lists_stride = gn::kTileListBase + 2 * (np / 128) + 8 * ((np + 255) / 256);
   GN_ALLOC(lists, B * (size_t)ctx->lists_stride);
+  GN_ALLOC(pr_ind, T); GN_ALLOC(pr_prune, T); GN_ALLOC(pr_dst, T); GN_ALLOC(pr_counts, B * 2 * kMaxLayers); GN_ALLOC(pr_nin, B * 2); GN_ALLOC(pr_z, T);
+  ctx->prune_last_np = 0; ctx->prune_last_B = 0; ctx->prune_last_on = false;      // gn_get_prune: no matcher call yet on these workspaces
 #undef GN_ALLOC
   return GN_OK;
 }
@@ -1399,6 +1427,47 @@ int gn_set_filter_threshold(gn_ctx* ctx, float th) {
   return GN_OK;
 }
 
+int gn_set_width_pruning(gn_ctx* ctx, float width_confidence, int min_kpts) {
+  if (!ctx) return GN_ERR_ARG;
+  if (!std::isfinite(width_confidence) || width_confidence >= 1.f)
+    return fail(ctx, GN_ERR_ARG, "gn_set_width_pruning: width_confidence must be finite and < 1 (<= 0 turns pruning off)");
+  if (width_confidence > 0.f && ctx->certify > 0)
+    return fail(ctx, GN_ERR_ARG, "gn_set_width_pruning: point pruning cannot run under the margin certificate (gn_set_certify mode > 0): the certificate's eps bounds "
+                                 "|P - P_f32| on the same token set, and a fast mode may prune a different set -- gn_set_certify(ctx, 0, ...) first");
+  ctx->width_conf = width_confidence > 0.f ? width_confidence : -1.f;
+  ctx->prune_min_kpts = min_kpts < 0 ? 1536 : min_kpts;
+  return GN_OK;
+}
+
+int gn_get_width_pruning(const gn_ctx* ctx, float* width_confidence, int* min_kpts) {
+  if (!ctx) return GN_ERR_ARG;
+  if (width_confidence) *width_confidence = ctx->width_conf;
+  if (min_kpts) *min_kpts = ctx->prune_min_kpts;
+  return GN_OK;
+}
+
+int gn_get_prune(gn_ctx* ctx, int B, int32_t* prune_q, int32_t* prune_r) {
+  if (!ctx || !prune_q || !prune_r) return fail(ctx, GN_ERR_ARG, "gn_get_prune: null pointer");
+  if (ctx->prune_last_np <= 0 || ctx->prune_last_np > ctx->npad || ctx->prune_last_B < 1 || !ctx->nvalid) return fail(ctx, GN_ERR_ARG, "gn_get_prune: no matcher call yet on these workspaces");
+  if (B < 1 || B > ctx->prune_last_B) return fail(ctx, GN_ERR_ARG, "gn_get_prune: B exceeds the pairs of the most recent matcher call");
+  GN_HIP(hipSetDevice(ctx->device));
+  GN_HIP(hipDeviceSynchronize());
+  const size_t np = (size_t)ctx->prune_last_np, km = (size_t)ctx->npad;
+  int32_t* out[2] = {prune_q, prune_r};
+  memset(prune_q, 0, (size_t)B * km * sizeof(int32_t)); memset(prune_r, 0, (size_t)B * km * sizeof(int32_t));
+  if (ctx->prune_last_on) {
+    std::vector<int32_t> host((size_t)B * 2 * np);
+    GN_HIP(hipMemcpy(host.data(), ctx->pr_prune, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int bs = 0; bs < 2 * B; ++bs) memcpy(out[bs & 1] + (size_t)(bs >> 1) * km, host.data() + (size_t)bs * np, np * sizeof(int32_t));
+  } else {      // kornia without pruning: every keypoint took part in every layer
+    std::vector<int32_t> nv((size_t)B * 2);
+    GN_HIP(hipMemcpy(nv.data(), ctx->nvalid, nv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int bs = 0; bs < 2 * B; ++bs)
+      for (int i = 0; i < std::min(std::max(nv[bs], 0), (int)np); ++i) out[bs & 1][(size_t)(bs >> 1) * km + i] = ctx->prune_last_layers;
+  }
+  return GN_OK;
+}
+
 int gn_kmax(const gn_ctx* ctx) { return ctx ? ctx->npad : GN_ERR_ARG; }
 
 int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int64_t* shape, int ndim) {
@@ -1647,6 +1716,9 @@ int gn_set_certify(gn_ctx* ctx, int mode, float eps, float eps_f32) {
   if (!ctx || mode < 0 || mode > 3) return GN_ERR_ARG;
   if (ctx->certify == 3 && mode != 3 && (ctx->cert_pend[0].active || ctx->cert_pend[1].active))
     return fail(ctx, GN_ERR_ARG, "gn_set_certify: deferred certificates are still open -- gn_flush first");
+  if (mode > 0 && ctx->width_conf > 0.f)
+    return fail(ctx, GN_ERR_ARG, "gn_set_certify: the margin certificate cannot run with point pruning on (gn_set_width_pruning): its eps bounds |P - P_f32| on the same "
+                                 "token set, and a fast mode may prune a different set -- gn_set_width_pruning(ctx, -1, -1) first");
   ctx->certify = mode;
   if (eps >= 0.f) { ctx->cert_eps = eps; ctx->cert_eps_src = 1; }
   if (eps_f32 >= 0.f) ctx->cert_eps_f32 = eps_f32;
@@ -1661,6 +1733,9 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   if (rc != GN_OK) return rc;
   if (!(safety >= 1.f) || !(floor_eps >= 0.f)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: safety must be >= 1, floor_eps >= 0");
   if (ctx->precision == GN_PREC_F32) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: this context already computes in exact f32");
+  if (ctx->width_conf > 0.f)
+    return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: point pruning is on (gn_set_width_pruning): the measured eps would compare scores of different token sets -- "
+                                 "gn_set_width_pruning(ctx, -1, -1) first");
   if (ctx->n_sub > 1 || ctx->overlap) { const int rcf = gn_flush(ctx, stream); if (rcf != GN_OK) return rcf; }
   hipStream_t s = (hipStream_t)stream;
   const size_t np = (size_t)ctx->npad_run;
@@ -1906,6 +1981,7 @@ void shift_workspaces(gn_ctx* c, long long b0, int sign) {
   mv(c->rmask_ws, km * (gn::kRansacRound + 1)); mv(c->rstate_ws, 1);
   for (int i = 0; i < 2; ++i) { mv(c->o_mkp[i], km * 2); mv(c->o_obj[i], km * 3); mv(c->o_nmatch[i], 1); }
   mv(c->lists, c->lists_stride);
+  mv(c->pr_ind, T2); mv(c->pr_prune, T2); mv(c->pr_dst, T2); mv(c->pr_counts, 2 * kMaxLayers); mv(c->pr_nin, 2); mv(c->pr_z, T2);
 }
 
 // The PnP stream, its events and the double-buffered PnP inputs (gn_set_overlap, gn_set_substreams).
@@ -2043,6 +2119,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     if (rcj != GN_OK) return rcj;
   }
   ctx->sub_last_B = B; ctx->sub_last_np = ctx->npad_run;
+  ctx->prune_last_B = B;
   ctx->ovf_groups_last = groups;
   GN_HIP(hipEventRecord(ctx->ev_fork, s));
   // Every group runs matcher and gather on its own stream and hands its PnP to the PnP stream (slot = parity of the call), so the group's stream is
@@ -2628,6 +2705,9 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       {"h", ctx->h, T * 2 * kDim}, {"md", ctx->md, T * kDim}, {"ls", ctx->ls, T}, {"sim", ctx->sim, ctx->sim ? B * np * np : 0},
       {"rowmax", ctx->rowmax, B * np}, {"rowlog", ctx->rowlog, B * np}, {"colmax", ctx->colmax, B * np},
       {"collog", ctx->collog, B * np}, {"max0", ctx->max0, B * np}, {"max0b", ctx->max0b, B * np}, {"uncert", ctx->uncert, B}, {"m0", ctx->m0, B * np}, {"m1", ctx->m1, B * np},
+      {"prune_counts", ctx->pr_counts, B * 2 * kMaxLayers}, {"prune_ind", ctx->pr_ind, T}, {"prune_z", ctx->pr_z, T},      // (prune_z: f32 z of the last pruning layer's rows)
+      {"lists", ctx->lists, ctx->lists ? B * (size_t)ctx->lists_stride : 0},      // work lists of the last call as they stand (int32: [0] tiles, [1] attention items, ...)
+           // point pruning: [slot][layer] counts after each layer; [slot][npad_run] original indices
       {"extent", ctx->extent, B * 4}, {"nvalid", ctx->nvalid, B * 2}, {"e_mkp", ctx->e_mkp, B * np * 2},
       {"e_obj", ctx->e_obj, B * np * 3}, {"e_score", ctx->e_score, B * np},
       {"hyp", ctx->hyp_ws, B * 16 * (sizeof(gn::HypResult) / 4)},

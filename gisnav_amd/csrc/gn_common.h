@@ -228,6 +228,29 @@ struct AttnArgs {
 // zero-initialised), and no valid token reads them (keys are masked, everything else is row-wise).
 constexpr int kTileListBase = 16;
 void launch_tile_lists(const int32_t* nvalid, int BS, int npad, int* lists, unsigned long long* feedback /* pinned host word or nullptr */, hipStream_t s);
+// ---- point pruning (gn_prune.hip, gn_set_width_pruning): after the cross block of a layer, every (pair, side) slot with more than min_kpts tokens keeps
+// the rows whose matchability passes sigmoid(z) > thresh, compacted to the front of the slot in ascending order; nvalid shrinks, the work lists are
+// rebuilt behind it, and every later launch of the call is smaller
+struct PruneArgs {
+  float* x = nullptr;                  // [T][256] f32 residual stream, or nullptr when the mode keeps none between layers
+  uint16_t* xp = nullptr;              // [T][256] hm16 residual stream, or nullptr
+  int z_from_planes = 0;               // 1: z from h + m of xp (the residual stream lives in hm16 only); 0: from x
+  float* cos_t = nullptr; float* sin_t = nullptr;          // [T][32]
+  float* rot4 = nullptr; long long rot_stride = 0;         // [16][rot_stride] float4, or nullptr
+  int32_t* ind = nullptr;              // [BS][npad] original index of every current row
+  int32_t* prune = nullptr;            // [BS][npad] kornia's prune0 / prune1, by ORIGINAL index
+  int32_t* dst = nullptr;              // [BS][npad] scratch: destination row of every current row, -1 = dropped
+  int32_t* nvalid = nullptr;           // [BS] in / out
+  int32_t* counts = nullptr;           // [BS][kMaxLayers] out: the slot's count after this layer
+  float* z = nullptr;                  // [BS][npad] out: z of every row k_prune_z looked at in this layer (gn_debug_read("prune_z"))
+  int layer = 0;
+  const float* w = nullptr; const float* b = nullptr;      // log_assignment.{layer}.matchability
+  float thresh = 0.f;                  // 1 - width_confidence
+  int min_kpts = 0; int BS = 0; int npad = 0;
+};
+void launch_prune_init(int32_t* ind, int32_t* prune, int32_t* n_in, const int32_t* nvalid, int BS, int npad, hipStream_t s);
+void launch_prune(const PruneArgs& a, hipStream_t s);
+void launch_unprune_idx(int64_t* idx, const int32_t* n_match, const int32_t* ind, int B, int npad, int kmax, hipStream_t s);
 void launch_attention_f32(const AttnArgs& a, hipStream_t s);
 void launch_attention_bf16(const AttnArgs& a, hipStream_t s);
 void launch_attention_f16x2(const AttnArgs& a, hipStream_t s);   // k_attn_f16x2 (gn_attention_f16x2.hip): f32 rows in, split-fp16 operands, f32-accurate
@@ -289,6 +312,8 @@ struct HeadArgs {
   float cert_eps_alt2 = -1.f;
   float* colbest = nullptr;        // [B][npad] out (optional, fused head): best score and runner-up of every column (gn_calibrate_certify's middle
   float* col2 = nullptr;           // level measures its eps over row AND column decisions)
+  const int32_t* n_in = nullptr;   // [B*2] the call's INPUT counts while point pruning is on (gn_prune.hip), nullptr = nvalid: kornia's _no_match looks at the
+                                   // input counts, so a side pruned down to ONE keypoint still runs; a side with none left reports no match
 };
 void launch_match_head(const HeadArgs& a, hipStream_t s);
 void launch_match_head_fused(const HeadArgs& a, hipStream_t s);

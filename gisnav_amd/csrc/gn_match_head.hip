@@ -151,8 +151,10 @@ __global__ __launch_bounds__(256) void k_compact(HeadArgs a) {
   if (tid == 0) base_s = 0;
   __syncthreads();
   // (the five-pass developer form keeps no runner-ups: with a certificate requested every pair that has matches to decide reports "uncertain")
-  if (n0 < 2 || n1 < 2 || (a.ovf != nullptr && *a.ovf != 0u)) {  // kornia LightGlueMatcher._no_match; or the f16x2 domain guard tripped (gn_common.h)
-    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = (n0 < 2 || n1 < 2) ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; }
+  // (point pruning: the rule looks at the call's input counts; a pruned side needs one row to run)
+  const bool nomatch = (a.n_in ? a.n_in[2 * b] : n0) < 2 || (a.n_in ? a.n_in[2 * b + 1] : n1) < 2 || n0 < 1 || n1 < 1;
+  if (nomatch || (a.ovf != nullptr && *a.ovf != 0u)) {  // kornia LightGlueMatcher._no_match; or the f16x2 domain guard tripped (gn_common.h)
+    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = nomatch ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; }
     return;
   }
   if (tid == 0 && a.uncert) a.uncert[b] = 1;
@@ -275,7 +277,8 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
     b = v / per; const int w_ = v - b * per; sp = w_ / gridDim.x; rb = w_ - sp * gridDim.x;
   }
   const int n0 = a.nvalid[2 * b], n1 = a.nvalid[2 * b + 1];
-  const bool nomatch = n0 < 2 || n1 < 2;                 // kornia LightGlueMatcher._no_match
+  // kornia LightGlueMatcher._no_match (point pruning: on the call's input counts; a pruned side needs one row to run)
+  const bool nomatch = (a.n_in ? a.n_in[2 * b] : n0) < 2 || (a.n_in ? a.n_in[2 * b + 1] : n1) < 2 || n0 < 1 || n1 < 1;
   const int nact = nomatch ? 1 : (n0 + kHeadRows - 1) / kHeadRows;   // row blocks of this pair that hold valid rows (block 0 always reports)
   if (rb >= nact) return;
   const int i0 = rb * kHeadRows;

@@ -36,6 +36,20 @@ def check_ransac_iterations(iterations) -> int:
     return int(iterations)
 
 
+def check_width_pruning(width_confidence, min_kpts=None) -> None:
+    """The library's argument rules for gn_set_width_pruning, before any GPU call: width_confidence finite and < 1 (<= 0 = off), min_kpts None or
+    an integer >= 0 (ValueError / TypeError otherwise)."""
+    if isinstance(width_confidence, bool) or not isinstance(width_confidence, (int, float, np.integer, np.floating)):
+        raise TypeError(f"width_confidence must be a number, got {type(width_confidence).__name__}")
+    if not np.isfinite(width_confidence) or float(width_confidence) >= 1.0:
+        raise ValueError(f"width_confidence must be finite and < 1 (<= 0 switches pruning off), got {width_confidence}")
+    if min_kpts is not None:
+        if isinstance(min_kpts, bool) or not isinstance(min_kpts, (int, np.integer)):
+            raise TypeError(f"pruning min_kpts must be an integer or None, got {type(min_kpts).__name__}")
+        if int(min_kpts) < 0:
+            raise ValueError(f"pruning min_kpts must be >= 0 (None = the default 1536), got {int(min_kpts)}")
+
+
 _PRECISIONS = {"f32": _lib.GN_PREC_F32, "bf16_attn": _lib.GN_PREC_BF16_ATTN, "f32x3_bf16_attn": _lib.GN_PREC_F32X3_BF16_ATTN,
                "f16x2_bf16_attn": _lib.GN_PREC_F16X2_BF16_ATTN, "f16x2_f16_attn": _lib.GN_PREC_F16X2_F16_ATTN,
                "f16x2_f16x2_attn": _lib.GN_PREC_F16X2_F16X2_ATTN}
@@ -427,6 +441,30 @@ class PoseEngine:
     def set_num_layers(self, n: int) -> None:
         self._n_layers = n
         _lib.check(self.ctx, self.lib.gn_set_num_layers(self.ctx, n), "gn_set_num_layers")
+
+    # ------------------------------------------------------------------ point pruning (gn_set_width_pruning)
+    def set_width_pruning(self, width_confidence: float, min_kpts: Optional[int] = None) -> None:
+        """kornia's width_confidence with early exit off: after every layer but the last, a side that still holds more than `min_kpts` keypoints
+        (None: 1536, recalled from kornia's pruning_keypoint_thresholds) keeps those with sigmoid(matchability) > 1 - width_confidence; the rest of
+        the call runs on what is left and the match indices stay ORIGINAL keypoint indices.  <= 0 switches it off (the default).  Refused (GnError)
+        while the margin certificate is on, and for width_confidence >= 1 or not finite."""
+        check_width_pruning(width_confidence, min_kpts)
+        rc = self.lib.gn_set_width_pruning(self.ctx, float(width_confidence), -1 if min_kpts is None else int(min_kpts))
+        _lib.check(self.ctx, rc, "gn_set_width_pruning")
+
+    def width_pruning(self) -> Tuple[float, int]:
+        """(width_confidence, min_kpts) in effect; width_confidence is -1.0 when pruning is off."""
+        w, m = C.c_float(0.0), C.c_int(0)
+        _lib.check(self.ctx, self.lib.gn_get_width_pruning(self.ctx, C.byref(w), C.byref(m)), "gn_get_width_pruning")
+        return float(w.value), int(m.value)
+
+    def last_prune(self, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """kornia's (prune0, prune1) of the most recent matcher call, int32 [B, kmax] each (gn_get_prune): the number of layers every original
+        keypoint took part in -- n_layers everywhere with pruning off, 1 where pruning is on and never fired, 0 past a side's count.
+        Synchronises the device."""
+        p0, p1 = np.zeros((B, self.kmax), np.int32), np.zeros((B, self.kmax), np.int32)
+        _lib.check(self.ctx, self.lib.gn_get_prune(self.ctx, int(B), p0.ctypes.data_as(_lib.c_i32p), p1.ctypes.data_as(_lib.c_i32p)), "gn_get_prune")
+        return p0, p1
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> C.c_void_p:

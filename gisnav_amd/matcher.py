@@ -14,7 +14,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from .engine import PoseEngine
+from .engine import PoseEngine, check_width_pruning
 from .weights import N_LAYERS
 
 _DEFAULTS = {"n_layers": N_LAYERS, "filter_threshold": 0.1, "depth_confidence": 0.95, "width_confidence": 0.99}
@@ -44,10 +44,17 @@ class LightGlueMatcher:
         self.feature_name = feature_name
         p = dict(_DEFAULTS)
         p.update(params or {})
-        if p["depth_confidence"] > 0 or p["width_confidence"] > 0:
-            # the adaptive depth/width branch is dead code in the reference (torch.device == str is
-            # always False, pose_node.py:88); only the exhaustive configuration is implemented
-            raise NotImplementedError("only depth_confidence = width_confidence = -1 is supported")
+        if p["depth_confidence"] > 0:
+            # the adaptive branch is dead code in the reference (torch.device == str is always False, pose_node.py:88); adaptive DEPTH (per-pair
+            # early exit) is not built -- point pruning (width_confidence > 0 with depth_confidence <= 0) is
+            raise NotImplementedError("depth_confidence > 0 (early exit) is not supported: pass depth_confidence = -1; width_confidence > 0 (point pruning) is")
+        self._prune_min_kpts = p.pop("pruning_min_kpts", None)      # this mirror's own parameter: kornia picks its threshold from the device / flash table
+        check_width_pruning(p["width_confidence"], self._prune_min_kpts)
+        self._width_conf = float(p["width_confidence"]) if p["width_confidence"] > 0 else -1.0
+        if self._width_conf > 0:
+            if bool(certify) and precision != "f32":
+                raise ValueError("width_confidence > 0 (point pruning) cannot run under the margin certificate of the fast precision modes: its eps bounds the "
+                                 "scores on the same token set, and a fast mode may prune a different set -- pass certify=False")
         self.params = p
         if state_dict is None:
             state_dict = self._find_pretrained(feature_name)    # kornia loads the pretrained checkpoint in its constructor (pose_node.py:109-121 passes none)
@@ -95,6 +102,8 @@ class LightGlueMatcher:
                                   filter_threshold=self.params["filter_threshold"], guard="sync", feature=self.feature_name)
         if self._ladder:
             self._engine.set_certify_ladder(True)
+        if self._width_conf > 0:
+            self._engine.set_width_pruning(self._width_conf, self._prune_min_kpts)
         return self
 
     def eval(self):

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MIN_MATCHES, RANSAC_ITERATIONS, PoseEngine, check_ransac_iterations
+from .engine import MIN_MATCHES, RANSAC_ITERATIONS, PoseEngine, check_ransac_iterations, check_width_pruning
 from .wire import CameraInfo, OrthoStereoImage, pack_keypoints
 
 
@@ -29,12 +29,21 @@ class PoseNode:
 
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
-                 sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS, report: bool = False):
+                 sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS, report: bool = False,
+                 width_confidence: float = -1.0, pruning_min_kpts: Optional[int] = None):
         from .matcher import _check_ladder
         ransac_iterations = check_ransac_iterations(ransac_iterations)      # (refused before any device work)
+        # width_confidence > 0: LightGlue's point pruning (gn_set_width_pruning; the reference asks for 0.99 at pose_node.py:88-107 behind a
+        # comparison that is never true).  Not under the margin certificate: certify=False for the fast precision modes.
+        check_width_pruning(width_confidence, pruning_min_kpts)
+        if width_confidence > 0 and bool(certify) and precision != "f32":
+            raise ValueError("width_confidence > 0 (point pruning) cannot run under the margin certificate of the fast precision modes -- pass certify=False")
         ladder = _check_ladder(certify_ladder, precision, "sift", bool(certify) and precision != "f32")   # (refused before any device work)
         self._engine = PoseEngine(device, max_batch=1, max_kpts=max_kpts, precision=precision, state_dict=state_dict,
                                   n_layers=9, filter_threshold=self.CONFIDENCE_THRESHOLD, guard="sync")
+        self.width_confidence, self.pruning_min_kpts = float(width_confidence), pruning_min_kpts
+        if width_confidence > 0:
+            self._engine.set_width_pruning(width_confidence, pruning_min_kpts)
         if extractor is None:
             from .sift import SIFT
             extractor = SIFT(engine=self._engine, max_keypoints=max_kpts).as_extractor()

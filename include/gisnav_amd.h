@@ -271,6 +271,30 @@ int gn_missing_tensors(const gn_ctx* ctx);
 int gn_set_num_layers(gn_ctx* ctx, int n_layers);
 int gn_set_filter_threshold(gn_ctx* ctx, float th);
 
+/* LightGlue point pruning (kornia's width_confidence with early exit off; adaptive depth is not built).  After the cross block of every layer
+ * but the last, each side of each pair whose CURRENT keypoint count is > min_kpts keeps the keypoints with
+ * sigmoid(log_assignment.{i}.matchability(x)) > 1 - width_confidence (f32), compacted in ascending order; the count shrinks on the device, the work
+ * lists are rebuilt, and every later kernel of the call runs on what is left.  Match indices are mapped back to the ORIGINAL keypoint indices
+ * (a pruned query simply has no match), so every output keeps its meaning and the match list stays in ascending query index.
+ *   width_confidence <= 0     off (the default): no extra launch, no extra buffer read, the same bits as a build without the feature
+ *   width_confidence >= 1, or not finite: GN_ERR_ARG, the previous setting stays
+ *   min_kpts < 0              the default, 1536
+ * Restated from the public kornia 0.7.2 / cvg LightGlue source; kornia is not in this project's oracle environment, so parity with it is UNPINNED.
+ * min_kpts' default is RECALLED from that source (pruning_keypoint_thresholds: 1536 for CUDA with flash attention, 1024 without), not verified.
+ * This build's own behaviour: a side left with NO keypoint makes its pair report n_match = 0 (kornia would raise in a max over an empty dimension).
+ * A side left with one keypoint runs on, as in kornia: gn_match's fewer-than-two rule looks at the call's input counts.
+ * Pruning and the margin certificate exclude each other: the calibrated eps bounds |P - P_f32| on the SAME token set, and a fast mode may prune a
+ * different set.  With gn_set_certify mode > 0 this call returns GN_ERR_ARG; with pruning on, gn_set_certify(mode > 0) and gn_calibrate_certify do.
+ * Works through gn_match / gn_estimate / gn_estimate_cov / gn_estimate_report, both feature types, every precision, sub-batch streams, deferred
+ * joins and the overlapped pose stage (the new per-slot buffers are sliced like the others). */
+int gn_set_width_pruning(gn_ctx* ctx, float width_confidence, int min_kpts);
+int gn_get_width_pruning(const gn_ctx* ctx, float* width_confidence, int* min_kpts);
+/* kornia's prune0 / prune1 of the most recent matcher call, into HOST buffers [B][gn_kmax] each, after a device synchronisation: how many layers
+ * every original keypoint took part in.  Pruning off: n_layers for every keypoint; on but never fired: 1.  Rows past a side's count are 0.
+ * B may not exceed the pairs of that call (GN_ERR_ARG; also before the first call on the context's current workspaces).
+ * (With deferred joins or deferred certificates open, gn_flush first.) */
+int gn_get_prune(gn_ctx* ctx, int B, int32_t* prune_q, int32_t* prune_r);
+
 /* Batched LightGlueMatcher.forward on RAW (un-normalised) SIFT descriptors.
  *   desc_q  [B][stride_q][128] f32     kpt_q [B][stride_q][6 or 4] f32     n_q [B] int32
  *   desc_r  [B][stride_r][128] f32     kpt_r [B][stride_r][6 or 4] f32     n_r [B] int32
