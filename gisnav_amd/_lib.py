@@ -97,6 +97,8 @@ SIGNATURES = {
     "gn_sift_detect_and_compute": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_sift_detect_and_compute_batch": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_sift_last_totals": (C.c_int, [VP, C.c_int, C.POINTER(C.c_int32)]),
+    "gn_sift_set_params": (C.c_int, [VP, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "gn_sift_get_params": (C.c_int, [VP, C.POINTER(C.c_int), c_f64p, c_f64p, c_f64p]),
     "gn_sp_load_tensor": (C.c_int, [VP, C.c_char_p, VP, c_i64p, C.c_int]),
     "gn_sp_detect_and_describe": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_sp_set_arithmetic": (C.c_int, [VP, C.c_int]),

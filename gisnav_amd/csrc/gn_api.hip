@@ -251,7 +251,9 @@ struct gn_ctx {
                            // 0: the separate k_split_hm16 / k_rot_table launches behind it (same bits; tests)
   // SIFT workspace (gn_sift_detect_and_compute), sized for the last image shape seen
   int sift_h = 0, sift_w = 0; std::vector<void*> sift_allocs; SiftPyramid sift_py; float* sift_tmp = nullptr;
-  float* sift_dk = nullptr; std::vector<std::vector<float>> sift_kernels; std::vector<int> sift_koff;   // [0] = initial blur, [1..5] = layer blurs
+  float* sift_dk = nullptr; std::vector<std::vector<float>> sift_kernels; std::vector<int> sift_koff;   // [0] = initial blur, [1..nOctaveLayers + 2] = layer blurs
+  int sift_layers = 3; double sift_contrast = 0.04, sift_edge = 10.0, sift_sigma = 1.6;   // gn_sift_set_params (cv2.SIFT_create's defaults)
+  int sift_ws_layers = 0; double sift_ws_sigma = 0.0;                                     // what the workspace above was built for
   int4* sift_cand = nullptr; int* sift_counts = nullptr; SiftKeypoint* sift_kp = nullptr;
   int sift_max_cand = 0, sift_max_kp = 0, sift_raw_cap = 0, sift_batch = 0; long long sift_kp_stride = 0;
   std::vector<int32_t> sift_totals;   // distinct keypoints found per image by the last call (before the max_kpts cap)
@@ -2416,7 +2418,9 @@ int gn_stereo_reference(gn_ctx* ctx, const uint8_t* bgr, const uint8_t* dem, int
 
 namespace {
 int sift_prepare(gn_ctx* ctx, int B, int H, int W, int max_kp) {
-  if (ctx->sift_h == H && ctx->sift_w == W && ctx->sift_max_kp >= max_kp && ctx->sift_batch >= B) return GN_OK;
+  const int nl = ctx->sift_layers, n_g = nl + 3, n_d = nl + 2;     // Gaussian / DoG planes per octave
+  const bool same_params = ctx->sift_ws_layers == nl && ctx->sift_ws_sigma == ctx->sift_sigma;
+  if (ctx->sift_h == H && ctx->sift_w == W && ctx->sift_max_kp >= max_kp && ctx->sift_batch >= B && same_params) return GN_OK;
   B = std::max(B, ctx->sift_h == H && ctx->sift_w == W ? ctx->sift_batch : 1);
   for (void* p : ctx->sift_allocs) hipFree(p);
   ctx->sift_allocs.clear();
@@ -2427,34 +2431,33 @@ int sift_prepare(gn_ctx* ctx, int B, int H, int W, int max_kp) {
   if (n_oct < 1) n_oct = 1;
   if (n_oct > kSiftMaxOctaves) n_oct = kSiftMaxOctaves;
   SiftPyramid& py = ctx->sift_py;
-  py.n_oct = n_oct;
+  py.n_oct = n_oct; py.n_layers = nl;
   int w = bw, h = bh;
   for (int o = 0; o < n_oct; ++o) {
     py.oct[o].w = w; py.oct[o].h = h;
     const size_t n = (size_t)w * h;
-    py.oct[o].stride = (long long)(11 * n);            // per image: 6 Gaussian + 5 DoG levels, images back to back
-    float* block = (float*)alloc((size_t)B * 11 * n * sizeof(float));
+    py.oct[o].stride = (long long)((n_g + n_d) * n);   // per image: nOctaveLayers + 3 Gaussian + nOctaveLayers + 2 DoG levels (6 + 5 by default), images back to back
+    float* block = (float*)alloc((size_t)B * (n_g + n_d) * n * sizeof(float));
     if (!block) return fail(ctx, GN_ERR_HIP, "SIFT pyramid allocation failed");
-    for (int i = 0; i < 6; ++i) py.oct[o].gauss[i] = block + i * n;
-    for (int i = 0; i < 5; ++i) py.oct[o].dog[i] = block + (6 + i) * n;
+    for (int i = 0; i < kSiftMaxLayers + 3; ++i) py.oct[o].gauss[i] = i < n_g ? block + i * n : nullptr;
+    for (int i = 0; i < kSiftMaxLayers + 2; ++i) py.oct[o].dog[i] = i < n_d ? block + (n_g + i) * n : nullptr;
     w /= 2; h /= 2;
     if (w < 1 || h < 1) { py.n_oct = o + 1; break; }
   }
   ctx->sift_tmp = (float*)alloc((size_t)bw * bh * sizeof(float));
   // blur kernels: sigma differences of createInitialImage / buildGaussianPyramid (f64 on the host, libm exp)
-  const double sigma = 1.6;
-  std::vector<double> sig(6);
-  ctx->sift_kernels.assign(6, {});
+  const double sigma = ctx->sift_sigma;
+  ctx->sift_kernels.assign(n_g, {});
   { const float sf = (float)sigma; sift_gaussian_kernel((double)sqrtf(std::max(sf * sf - 0.5f * 0.5f * 4, 0.01f)), ctx->sift_kernels[0]); }   // createInitialImage: float arithmetic
-  const double k = std::pow(2.0, 1.0 / 3.0);
-  for (int i = 1; i < 6; ++i) {
+  const double k = std::pow(2.0, 1.0 / nl);
+  for (int i = 1; i < n_g; ++i) {
     const double sp = std::pow(k, (double)(i - 1)) * sigma, st = sp * k;
     sift_gaussian_kernel(std::sqrt(st * st - sp * sp), ctx->sift_kernels[i]);
   }
-  size_t tot = 0; ctx->sift_koff.assign(6, 0);
-  for (int i = 0; i < 6; ++i) { ctx->sift_koff[i] = (int)tot; tot += ctx->sift_kernels[i].size(); }
+  size_t tot = 0; ctx->sift_koff.assign(n_g, 0);
+  for (int i = 0; i < n_g; ++i) { ctx->sift_koff[i] = (int)tot; tot += ctx->sift_kernels[i].size(); }
   ctx->sift_dk = (float*)alloc(tot * sizeof(float));
-  for (int i = 0; i < 6; ++i)
+  for (int i = 0; i < n_g; ++i)
     if (hipMemcpy(ctx->sift_dk + ctx->sift_koff[i], ctx->sift_kernels[i].data(), ctx->sift_kernels[i].size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       return fail(ctx, GN_ERR_HIP, "SIFT kernel upload failed");
   ctx->sift_max_cand = std::max(65536, 16 * max_kp);
@@ -2468,6 +2471,7 @@ int sift_prepare(gn_ctx* ctx, int B, int H, int W, int max_kp) {
   if (!ctx->sift_tmp || !ctx->sift_dk || !ctx->sift_cand || !ctx->sift_counts || !ctx->sift_kp)
     return fail(ctx, GN_ERR_HIP, "SIFT workspace allocation failed");
   ctx->sift_h = H; ctx->sift_w = W; ctx->sift_batch = B;
+  ctx->sift_ws_layers = nl; ctx->sift_ws_sigma = ctx->sift_sigma;
   return GN_OK;
 }
 }  // namespace
@@ -2487,24 +2491,27 @@ int gn_sift_detect_and_compute_batch(gn_ctx* ctx, const uint8_t* gray, int B, in
     sift_blur(B, py.oct[o_in].stride, py.oct[o_out].stride, in, ctx->sift_tmp, out, py.oct[o_out].w, py.oct[o_out].h, ctx->sift_dk + ctx->sift_koff[ki],
               (int)ctx->sift_kernels[ki].size(), s, dog, in_step, py.oct[o_in].w, half_scratch);
   };
-  // createInitialImage: 2x bilinear, blur to sigma 1.6; then the Gaussian and DoG pyramids
-  sift_base_blur(gray, B, H, W, py.oct[0].gauss[5], ctx->sift_tmp, py.oct[0].gauss[0], py.oct[0].stride, ctx->sift_dk + ctx->sift_koff[0],
-                 (int)ctx->sift_kernels[0].size(), ctx->sift_counts, s);   // (scratch = level 5, overwritten later); also zeroes the counters
-  int ksize[6];
-  for (int i = 0; i < 6; ++i) ksize[i] = (int)ctx->sift_kernels[i].size();
+  // createInitialImage: 2x bilinear, blur to sigma; then the Gaussian and DoG pyramids
+  const int nl = py.n_layers, n_g = nl + 3;
+  sift_base_blur(gray, B, H, W, py.oct[0].gauss[n_g - 1], ctx->sift_tmp, py.oct[0].gauss[0], py.oct[0].stride, ctx->sift_dk + ctx->sift_koff[0],
+                 (int)ctx->sift_kernels[0].size(), ctx->sift_counts, s);   // (scratch = the last level, overwritten later); also zeroes the counters
+  int ksize[kSiftMaxLayers + 3] = {};
+  for (int i = 0; i < n_g; ++i) ksize[i] = (int)ctx->sift_kernels[i].size();
   const int o_tail = sift_tail_first(py, ksize);                     // octaves from here on: one single-workgroup launch per image
   for (int o = 0; o < o_tail; ++o) {
     const SiftOctave& oc = py.oct[o];
-    // level 1 of octave o > 0 samples level 3 of the octave above directly (its level 0 is never stored)
-    if (o > 0) blur(o - 1, py.oct[o - 1].gauss[3], o, oc.gauss[1], 1, oc.dog[0], 2, oc.gauss[0]);
-    for (int i = o > 0 ? 2 : 1; i < 6; ++i) blur(o, oc.gauss[i - 1], o, oc.gauss[i], i, oc.dog[i - 1]);   // row + column pass + DoG level in one launch
+    // level 1 of octave o > 0 samples level nOctaveLayers of the octave above directly (its level 0 is never stored)
+    if (o > 0) blur(o - 1, py.oct[o - 1].gauss[nl], o, oc.gauss[1], 1, oc.dog[0], 2, oc.gauss[0]);
+    for (int i = o > 0 ? 2 : 1; i < n_g; ++i) blur(o, oc.gauss[i - 1], o, oc.gauss[i], i, oc.dog[i - 1]);   // row + column pass + DoG level in one launch
   }
   sift_tail(py, B, o_tail, ctx->sift_dk, ctx->sift_koff.data(), ksize, s);
-  const float threshold = (float)(int)std::floor(0.5 * 0.04 / 3 * 255);
+  const float threshold = (float)(int)std::floor(0.5 * ctx->sift_contrast / nl * 255);
+  SiftParams prm;
+  prm.n_layers = nl; prm.contrast_thr = (float)ctx->sift_contrast; prm.edge_thr = (float)ctx->sift_edge; prm.edge1 = (float)(ctx->sift_edge + 1.0); prm.sigma = (float)ctx->sift_sigma;
   sift_find(py, B, threshold, ctx->sift_cand, ctx->sift_counts, ctx->sift_max_cand, s);
   // raw keypoints, their sorted copy and the final list of an image live back to back in one allocation
   const int max_raw = ctx->sift_raw_cap;
-  sift_refine(py, B, ctx->sift_cand, ctx->sift_counts, ctx->sift_max_cand, ctx->sift_kp, ctx->sift_kp_stride, max_raw, s);
+  sift_refine(py, prm, B, ctx->sift_cand, ctx->sift_counts, ctx->sift_max_cand, ctx->sift_kp, ctx->sift_kp_stride, max_raw, s);
   // sort / de-duplicate / rescale on the device, then descriptors for the final keypoints; one sync at the very end
   const int max_out = std::min(max_kpts, ctx->sift_max_kp);
   sift_sort_dedup(B, ctx->sift_kp, ctx->sift_kp_stride, ctx->sift_counts, max_raw, max_out, kpt_xysa, response, octave, max_kpts, s);
@@ -2528,6 +2535,26 @@ int gn_sift_detect_and_compute_batch(gn_ctx* ctx, const uint8_t* gray, int B, in
 int gn_sift_detect_and_compute(gn_ctx* ctx, const uint8_t* gray, int H, int W, int max_kpts,
                                float* kpt_xysa, float* response, int32_t* octave, float* desc, int32_t* n_out_host, void* stream) {
   return gn_sift_detect_and_compute_batch(ctx, gray, 1, H, W, max_kpts, kpt_xysa, response, octave, desc, n_out_host, stream);
+}
+
+// cv2.SIFT_create(nOctaveLayers, contrastThreshold, edgeThreshold, sigma): sticky host-side state, like gn_set_ransac
+int gn_sift_set_params(gn_ctx* ctx, int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma) {
+  if (!ctx) return GN_ERR_ARG;
+  if (n_octave_layers < 1 || n_octave_layers > kSiftMaxLayers) return fail(ctx, GN_ERR_ARG, "gn_sift_set_params: n_octave_layers must be in 1..5");
+  if (!std::isfinite(contrast_threshold) || contrast_threshold < 0.0) return fail(ctx, GN_ERR_ARG, "gn_sift_set_params: contrast_threshold must be finite and >= 0");
+  if (!std::isfinite(edge_threshold) || !(edge_threshold > 0.0)) return fail(ctx, GN_ERR_ARG, "gn_sift_set_params: edge_threshold must be finite and > 0");
+  if (!(sigma >= 1.0 && sigma <= 2.4)) return fail(ctx, GN_ERR_ARG, "gn_sift_set_params: sigma must be in [1.0, 2.4]");
+  ctx->sift_layers = n_octave_layers; ctx->sift_contrast = contrast_threshold; ctx->sift_edge = edge_threshold; ctx->sift_sigma = sigma;
+  return GN_OK;   // the workspace follows n_octave_layers / sigma at the next gn_sift_detect_and_compute(_batch) (sift_prepare)
+}
+
+int gn_sift_get_params(const gn_ctx* ctx, int* n_octave_layers, double* contrast_threshold, double* edge_threshold, double* sigma) {
+  if (!ctx) return GN_ERR_ARG;
+  if (n_octave_layers) *n_octave_layers = ctx->sift_layers;
+  if (contrast_threshold) *contrast_threshold = ctx->sift_contrast;
+  if (edge_threshold) *edge_threshold = ctx->sift_edge;
+  if (sigma) *sigma = ctx->sift_sigma;
+  return GN_OK;
 }
 
 int gn_sift_last_totals(gn_ctx* ctx, int B, int32_t* totals_host) {
@@ -2907,6 +2934,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 33) ctx->skinny = value;
   else if (which == 48) ctx->prep_fused = value ? 1 : 0;
   else if (which == 49) ctx->pnp_rounds = value ? 1 : 0;
+  else if (which == 50) gn::g_sift_general_blur = value ? 1 : 0;   // SIFT scale space through k_blur_row + k_blur_col only (the cost table of DESIGN.md 18)
   else if (which == 29) {   // CU shares for the sub-batch streams: takes effect for streams created afterwards
     GN_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 8; ++i) if (ctx->sub_s[i]) { hipStreamSynchronize(ctx->sub_s[i]); hipEventDestroy(ctx->ev_join[i]); hipStreamDestroy(ctx->sub_s[i]); ctx->sub_s[i] = nullptr; ctx->ev_join[i] = nullptr; }

@@ -410,19 +410,24 @@ void launch_rotate_crop(const WarpArgs& a, bool fused_gray, hipStream_t s);
 
 // ---- SIFT (cv2.SIFT_create().detectAndCompute) -------------------------------------------------------------
 constexpr int kSiftMaxOctaves = 12;
-struct SiftOctave { float* gauss[6]; float* dog[5]; int w, h; long long stride; };   // stride: floats between consecutive images of a batch
-struct SiftPyramid { SiftOctave oct[kSiftMaxOctaves]; int n_oct; };
+constexpr int kSiftMaxLayers = 5;             // nOctaveLayers 1 .. 5: at most 8 Gaussian + 7 DoG planes per octave
+struct SiftOctave { float* gauss[kSiftMaxLayers + 3]; float* dog[kSiftMaxLayers + 2]; int w, h; long long stride; };   // stride: floats between consecutive images of a batch
+struct SiftPyramid { SiftOctave oct[kSiftMaxOctaves]; int n_oct; int n_layers; };   // n_layers + 3 Gaussian and n_layers + 2 DoG planes are in use
 struct SiftKeypoint { float x, y, size, angle, response; int octave; };
+// cv2.SIFT_create's nOctaveLayers / contrastThreshold / edgeThreshold / sigma as the kernels take them (by value): the floats the oracle
+// rounds them to -- edge1 = (float)(edgeThreshold + 1), the sum formed in double as oracle/sift.py writes it
+struct SiftParams { int n_layers; float contrast_thr, edge_thr, edge1, sigma; };
 void sift_gaussian_kernel(double sigma, std::vector<float>& k);
 void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int* counters, hipStream_t s);
-// dog = out - in; in_step 2 reads every second pixel of a source image of row stride in_w (half_scratch: only used for non-stock kernel sizes)
+// dog = out - in; in_step 2 reads every second pixel of a source image of row stride in_w (half_scratch: only used by the two-launch form)
 void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, hipStream_t s,
                float* dog = nullptr, int in_step = 1, int in_w = 0, float* half_scratch = nullptr);
+extern int g_sift_general_blur;   // developer switch (gn_debug_set_variant 50): every level through k_blur_row + k_blur_col, no fused launch, no tail
 int sift_tail_first(const SiftPyramid& py, const int* ksize);
 void sift_tail(const SiftPyramid& py, int B, int o_first, const float* dk, const int* koff, const int* ksize, hipStream_t s);
 void sift_find(const SiftPyramid& py, int B, float threshold, int4* cand, int* counters, int max_cand, hipStream_t s);
 // counters: int[4] per image = {candidates, raw keypoints, final keypoints, -}; kp: per image [max_raw raw | max_raw sorted | final], kp_stride records apart
-void sift_refine(const SiftPyramid& py, int B, const int4* cand, int* counters, int max_cand, SiftKeypoint* kp, long long kp_stride, int max_raw, hipStream_t s);
+void sift_refine(const SiftPyramid& py, const SiftParams& prm, int B, const int4* cand, int* counters, int max_cand, SiftKeypoint* kp, long long kp_stride, int max_raw, hipStream_t s);
 void sift_descriptors(const SiftPyramid& py, int B, const SiftKeypoint* kp_final, long long kp_stride, const int* counters, int max_n, float* desc, long long out_stride, hipStream_t s);
 void sift_sort_dedup(int B, SiftKeypoint* kp, long long kp_stride, int* counters, int max_raw, int max_out,
                      float* kpt_xysa, float* response, int32_t* octave, long long out_stride, hipStream_t s);

@@ -1,12 +1,13 @@
 // SIFT detector + descriptor on the device: stands in for `cv2.SIFT_create().detectAndCompute(img, None)`
 // as GISNav calls it for the reference tile (ros/gisnav/gisnav/core/pose_node.py:122,230-232) and for every camera frame
-// (core/twist_node.py:93,227-245).  Follows OpenCV 4.x sift.dispatch.cpp / sift.simd.hpp with the defaults (3 octave
-// layers, contrast 0.04, edge 10, sigma 1.6, first octave -1, float descriptors), restated in oracle/sift.py.
+// (core/twist_node.py:93,227-245).  Follows OpenCV 4.x sift.dispatch.cpp / sift.simd.hpp (first octave -1, float descriptors), restated
+// in oracle/sift.py; nOctaveLayers (1 .. 5), contrastThreshold, edgeThreshold and sigma are run-time values (SiftPyramid::n_layers,
+// SiftParams), 3 / 0.04 / 10 / 1.6 by default.
 //
 // Compiled with -ffp-contract=off: every float operation below is a separate IEEE multiply / add / divide in the order the
 // oracle writes them, so scale space, keypoints and descriptors agree with it bit for bit.  Stages:
 //   k_sift_base (u8 -> f32, 2x bilinear) -> separable Gaussian with BORDER_REFLECT_101, both passes and the DoG level in one
-//   launch per level (k_blur_fused: LDS tiles, register windows); the first level of an octave samples level 3 of the
+//   launch per level (k_blur_fused: LDS tiles, register windows); the first level of an octave samples level nOctaveLayers of the
 //   octave above directly; every octave of <= 4800 pixels is finished by ONE workgroup in LDS (k_sift_tail) ->
 //   k_sift_find (26-neighbour extrema, all octaves and layers in one launch) ->
 //   k_sift_refine (quadratic fit, contrast / edge tests, orientation histogram; one wave per candidate) ->
@@ -20,7 +21,7 @@
 namespace gn {
 
 namespace {
-constexpr int kBorder = 5, kMaxInterp = 5, kOriBins = 36, kLayers = 3;
+constexpr int kBorder = 5, kMaxInterp = 5, kOriBins = 36;
 constexpr float kFltEps = 1.1920929e-07f;
 
 __device__ __forceinline__ int reflect101(int p, int n) {
@@ -87,9 +88,11 @@ __global__ __launch_bounds__(256) void k_blur_col(const float* in, float* out, i
 // (+ R columns/rows of BORDER_REFLECT_101 halo) in LDS, row-filters the 32 + 2R rows it needs into a second LDS tile and
 // column-filters those.  Every output is the same expression, in the same order, as k_blur_row followed by k_blur_col;
 // a thread produces 4 adjacent outputs of a row (8 of a column) from one register window, so an LDS word is read once per
-// 4 (8) outputs instead of once per tap.  N (taps) is a template parameter: the pyramid only has 11/13/17/21/27.
-// The first level of an octave reads its input straight from level 3 of the octave above (in_step = 2), so the
+// 4 (8) outputs instead of once per tap.  N (taps) is a template parameter: the default pyramid has 11/13/17/21/27, other
+// nOctaveLayers / sigma give other odd counts -- every odd N from 3 to kFusedMaxTaps is instantiated (sift_blur), wider kernels
+// take the two launches.  The first level of an octave reads its input straight from level nOctaveLayers of the octave above (in_step = 2), so the
 // half-size base image is never materialised.
+constexpr int kFusedMaxTaps = 37;     // LDS of the widest instantiation: 68 x 100 + 68 x 64 floats = 44.6 KB
 constexpr int kFtW = 64, kFtH = 32;   // (64-row tiles -- 1.4x instead of 1.8x halo work in the row pass -- measured 10 % SLOWER on batches: half the blocks per CU)
 // BASE: `in` is the u8 camera image [h / 2][w / 2] (images stride_in BYTES apart) and the tile is sampled from its 2x bilinear
 // upsampling on the fly -- the initial blur of createInitialImage without ever storing the doubled image; `counters` are zeroed.
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(256) void k_blur_fused(const float* in, float* out,
 // halos hold the BORDER_REFLECT_101 samples, so the tap loops are branch-free and fully unrolled -- and only the results
 // (Gaussian levels, DoG levels) go to global memory.  Same expressions, same order, as k_blur_row / k_blur_col.
 constexpr int kTailPx = 4800, kTailSide = 128, kTailPad = 13, kTailBuf = kTailPx + 2 * kTailPad * kTailSide;
-struct SiftBlurPlan { int off[6], n[6]; };
+struct SiftBlurPlan { int off[kSiftMaxLayers + 3], n[kSiftMaxLayers + 3]; };
 
 template <int N>
 __device__ __forceinline__ void tail_level(const float* cur, float* tmp, float* nxt, int w, int h, const float* kg, float* g_out, float* d_out) {
@@ -223,34 +226,46 @@ __device__ __forceinline__ void tail_pad_x(float* buf, int w, int h) {
   __syncthreads();
 }
 
+// STOCK: the default pyramid (three layers, 11 / 13 / 17 / 21 / 27 taps) with its level count and tap set as constants -- the kernel the extractor had
+// before the parameters became run-time values; a single workgroup on the critical path of a one-image call, it lost 5 us of 71 when the general
+// form's eleven tap counts shared its switch.  Every other pyramid the tail can hold takes the general form.
+template <bool STOCK>
 __global__ __launch_bounds__(1024) void k_sift_tail(SiftPyramid py, int o_first, const float* dk, SiftBlurPlan plan) {
   extern __shared__ __attribute__((aligned(16))) float s_tail[];
   float* cur = s_tail; float* nxt = s_tail + kTailBuf; float* tmp = s_tail + 2 * kTailBuf;
   const int tid = threadIdx.x;
   const int b = blockIdx.x;                            // one workgroup per image
+  const int n_layers = STOCK ? 3 : py.n_layers;
   for (int o = o_first; o < py.n_oct; ++o) {
     const SiftOctave& oc = py.oct[o];
     const long long boff = (long long)b * oc.stride;   // image b of the batch (a by-value copy of the octave record would go to scratch)
     const int w = oc.w, h = oc.h, px = w * h, wp = w + 2 * kTailPad;
-    {   // base level: every second pixel of level 3 of the octave above (written by an earlier launch or by this workgroup)
-      const float* src = py.oct[o - 1].gauss[3] + (long long)b * py.oct[o - 1].stride;
+    {   // base level: every second pixel of level nOctaveLayers of the octave above (written by an earlier launch or by this workgroup)
+      const float* src = py.oct[o - 1].gauss[n_layers] + (long long)b * py.oct[o - 1].stride;
       const int ws = py.oct[o - 1].w;
       for (int i = tid; i < px; i += 1024) { const int y = i / w, x = i - y * w; const float v = src[(size_t)(2 * y) * ws + 2 * x]; cur[y * wp + kTailPad + x] = v; oc.gauss[0][boff + i] = v; }
     }
     __syncthreads();
-    for (int lvl = 1; lvl < 6; ++lvl) {
+    for (int lvl = 1; lvl < n_layers + 3; ++lvl) {
       tail_pad_x(cur, w, h);
       const float* kg = dk + plan.off[lvl];
-      switch (plan.n[lvl]) {
-        case 11: tail_level<11>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
-        case 13: tail_level<13>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
-        case 17: tail_level<17>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
-        case 21: tail_level<21>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
-        default: tail_level<27>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
+#define GN_TAIL_CASE(N) case N: tail_level<N>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
+      if (STOCK) {
+        switch (plan.n[lvl]) {
+          GN_TAIL_CASE(11) GN_TAIL_CASE(13) GN_TAIL_CASE(17) GN_TAIL_CASE(21)
+          default: tail_level<27>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
+        }
+      } else {
+        switch (plan.n[lvl]) {                         // every odd tap count the halo holds (sift_tail_taps); the host sends nothing else here
+          GN_TAIL_CASE(7) GN_TAIL_CASE(9) GN_TAIL_CASE(11) GN_TAIL_CASE(13) GN_TAIL_CASE(15) GN_TAIL_CASE(17)
+          GN_TAIL_CASE(19) GN_TAIL_CASE(21) GN_TAIL_CASE(23) GN_TAIL_CASE(25)
+          default: tail_level<27>(cur, tmp, nxt, w, h, kg, oc.gauss[lvl] + boff, oc.dog[lvl - 1] + boff); break;
+        }
       }
+#undef GN_TAIL_CASE
       float* t2 = cur; cur = nxt; nxt = t2;
     }
-    __syncthreads();                                   // level 3 of this octave is read back from global memory by the next one
+    __syncthreads();                                   // level nOctaveLayers of this octave is read back from global memory by the next one
   }
 }
 
@@ -320,6 +335,8 @@ __device__ bool lu_solve3(float A[3][3], float x[3]) {
 // one launch for all octaves and layers: blockIdx.x runs over the 64 x 32 tiles of every octave back to back
 constexpr int kFindRows = 32;
 struct SiftFindPlan { int first_tile[kSiftMaxOctaves + 1]; int tiles_x[kSiftMaxOctaves]; };
+// NL = nOctaveLayers is a template parameter (1 .. 5, sift_find): the window lives in registers and the layer loop is unrolled over it
+template <int NL>
 __global__ __launch_bounds__(256) void k_sift_find(SiftPyramid py, SiftFindPlan plan, float threshold, int4* cand, int* n_cand, int max_cand) {
   const int b = blockIdx.z;
   cand += (size_t)b * max_cand; n_cand += 4 * b;
@@ -333,16 +350,16 @@ __global__ __launch_bounds__(256) void k_sift_find(SiftPyramid py, SiftFindPlan 
   const int rbeg = kBorder + (tile / plan.tiles_x[octave]) * kFindRows + wave * (kFindRows / 4);
   const int rend = min(rbeg + kFindRows / 4, oc.h - kBorder);
   if (c >= oc.w - kBorder || rbeg >= rend) return;
-  // a thread walks down a column strip with the 5 x 3 x 3 DoG neighbourhood in registers: 15 loads per row serve the three
+  // a thread walks down a column strip with the (NL + 2) x 3 x 3 DoG neighbourhood in registers: at NL = 3, 15 loads per row serve the three
   // layers (5 per tested value instead of 1 + 27 from L1 -- this kernel was bound by L1 request rate, not by HBM).
   // (Fetching the left / right neighbours from adjacent lanes with DPP wave shifts instead -- 5 full loads + 10 one-lane edge
   // loads per row -- was 2x SLOWER: the texture path is charged per load instruction, not per lane; four-column strips per
   // thread with one unaligned 16-byte load + two 4-byte loads per row and layer were 1.4x slower as well.)
   const int w = oc.w;
-  float win[5][3][3];
+  float win[NL + 2][3][3];
   auto load_row = [&](int r, int slot) __attribute__((always_inline)) {
 #pragma unroll
-    for (int l = 0; l < 5; ++l) {
+    for (int l = 0; l < NL + 2; ++l) {
       const float* p = oc.dog[l] + boff + (size_t)r * w + c;
       win[l][slot][0] = p[-1]; win[l][slot][1] = p[0]; win[l][slot][2] = p[1];
     }
@@ -352,7 +369,7 @@ __global__ __launch_bounds__(256) void k_sift_find(SiftPyramid py, SiftFindPlan 
   for (int r = rbeg; r < rend; ++r) {
     load_row(r + 1, 2);
 #pragma unroll
-    for (int layer = 1; layer <= kLayers; ++layer) {
+    for (int layer = 1; layer <= NL; ++layer) {
       const float val = win[layer][1][1];
       if (fabsf(val) > threshold && val != 0.f) {
         bool is_max = val > 0, is_min = val < 0;
@@ -373,7 +390,7 @@ __global__ __launch_bounds__(256) void k_sift_find(SiftPyramid py, SiftFindPlan 
       }
     }
 #pragma unroll
-    for (int l = 0; l < 5; ++l)
+    for (int l = 0; l < NL + 2; ++l)
 #pragma unroll
       for (int dx = 0; dx < 3; ++dx) { win[l][0][dx] = win[l][1][dx]; win[l][1][dx] = win[l][2][dx]; }
   }
@@ -383,7 +400,7 @@ __global__ __launch_bounds__(256) void k_sift_find(SiftPyramid py, SiftFindPlan 
 // The quadratic refinement is scalar work (every lane computes it redundantly); the orientation histogram evaluates 64
 // raster positions per step in parallel and commits them in raster order -- bin b of the histogram lives in a register of
 // lane b, each sample is broadcast with v_readlane and added by its owner lane -- so the float sums keep OpenCV's order.
-__global__ __launch_bounds__(64) void k_sift_refine(SiftPyramid py, const int4* cand, int* counters, int max_cand,
+__global__ __launch_bounds__(64) void k_sift_refine(SiftPyramid py, SiftParams prm, const int4* cand, int* counters, int max_cand,
                                                      SiftKeypoint* kp, long long kp_stride, int max_kp) {
   const int lane = threadIdx.x, b = blockIdx.y;
   cand += (size_t)b * max_cand; kp += (long long)b * kp_stride;
@@ -418,7 +435,7 @@ __global__ __launch_bounds__(64) void k_sift_refine(SiftPyramid py, const int4* 
       if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) break;
       if ((double)fabsf(xi) > 715827882.0 || (double)fabsf(xr) > 715827882.0 || (double)fabsf(xc) > 715827882.0) { dead = true; break; }
       c += (int)rintf(xc); r += (int)rintf(xr); layer += (int)rintf(xi);
-      if (layer < 1 || layer > kLayers || c < kBorder || c >= cols - kBorder || r < kBorder || r >= rows - kBorder) { dead = true; break; }
+      if (layer < 1 || layer > prm.n_layers || c < kBorder || c >= cols - kBorder || r < kBorder || r >= rows - kBorder) { dead = true; break; }
     }
     if (dead || i >= kMaxInterp) continue;
     float contr;
@@ -428,20 +445,20 @@ __global__ __launch_bounds__(64) void k_sift_refine(SiftPyramid py, const int4* 
                   d2 = (AT(nxt, r, c) - AT(prv, r, c)) * deriv_scale;
       const float t = (d0 * xc + d1 * xr) + d2 * xi;
       contr = AT(img, r, c) * img_scale + t * 0.5f;
-      if (fabsf(contr) * (float)kLayers < 0.04f) continue;
+      if (fabsf(contr) * (float)prm.n_layers < prm.contrast_thr) continue;
       const float v2 = AT(img, r, c) * 2.0f;
       const float dxx = (AT(img, r, c + 1) + AT(img, r, c - 1) - v2) * second_scale;
       const float dyy = (AT(img, r + 1, c) + AT(img, r - 1, c) - v2) * second_scale;
       const float dxy = (AT(img, r + 1, c + 1) - AT(img, r + 1, c - 1) - AT(img, r - 1, c + 1) + AT(img, r - 1, c - 1)) * cross_scale;
       const float tr = dxx + dyy;
       const float det = dxx * dyy - dxy * dxy;
-      if (det <= 0.f || (tr * tr) * 10.0f >= (11.0f * 11.0f) * det) continue;
+      if (det <= 0.f || (tr * tr) * prm.edge_thr >= (prm.edge1 * prm.edge1) * det) continue;
     }
     const float scale = (float)(1 << octv);
     const float kx = ((float)c + xc) * scale, ky = ((float)r + xr) * scale;
     const int octave = octv + (layer << 8) + ((int)rintf((xi + 0.5f) * 255.0f) << 16);
-    const float e = ((float)layer + xi) / (float)kLayers;
-    const float size = ((1.6f * (float)pow(2.0, (double)e)) * scale) * 2.0f;
+    const float e = ((float)layer + xi) / (float)prm.n_layers;
+    const float size = ((prm.sigma * (float)pow(2.0, (double)e)) * scale) * 2.0f;
     const float response = fabsf(contr);
 
     // orientation histogram on the Gaussian level of the refined layer
@@ -979,20 +996,22 @@ void sift_gaussian_kernel(double sigma, std::vector<float>& k) {
 
 static inline dim3 grid2d(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 
-static inline bool sift_fused_taps(int n) { return n == 11 || n == 13 || n == 17 || n == 21 || n == 27; }
+int g_sift_general_blur = 0;
+// tap counts k_sift_tail has a level for: odd, and no wider than its halo (2 kTailPad + 1 = 27)
+static inline bool sift_tail_taps(int n) { return (n & 1) && n >= 7 && n <= 2 * kTailPad + 1; }
 void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, hipStream_t s,
                float* dog, int in_step, int in_w, float* half_scratch) {
   if (in_w <= 0) in_w = w;
   const dim3 g((w + kFtW - 1) / kFtW, (h + kFtH - 1) / kFtH, B);
-  switch (n) {
-    case 11: hipLaunchKernelGGL(k_blur_fused<11>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
-    case 13: hipLaunchKernelGGL(k_blur_fused<13>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
-    case 17: hipLaunchKernelGGL(k_blur_fused<17>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
-    case 21: hipLaunchKernelGGL(k_blur_fused<21>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
-    case 27: hipLaunchKernelGGL(k_blur_fused<27>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
+#define GN_FUSED_CASE(N) case N: hipLaunchKernelGGL(k_blur_fused<N>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
+  if (!g_sift_general_blur) switch (n) {      // every odd tap count up to kFusedMaxTaps
+    GN_FUSED_CASE(3) GN_FUSED_CASE(5) GN_FUSED_CASE(7) GN_FUSED_CASE(9) GN_FUSED_CASE(11) GN_FUSED_CASE(13) GN_FUSED_CASE(15) GN_FUSED_CASE(17) GN_FUSED_CASE(19)
+    GN_FUSED_CASE(21) GN_FUSED_CASE(23) GN_FUSED_CASE(25) GN_FUSED_CASE(27) GN_FUSED_CASE(29) GN_FUSED_CASE(31) GN_FUSED_CASE(33) GN_FUSED_CASE(35) GN_FUSED_CASE(37)
     default: break;
   }
-  // other sigma: image by image, materialise the half-size image if needed, then two plain passes
+#undef GN_FUSED_CASE
+  static_assert(kFusedMaxTaps == 37, "sift_blur's switch lists the instantiations");
+  // wider kernels: image by image, materialise the half-size image if needed, then two plain passes
   for (int b = 0; b < B; ++b) {
     const float* src = in + (long long)b * stride_in;
     float* dst = out + (long long)b * stride_out;
@@ -1006,9 +1025,11 @@ void sift_blur(int B, long long stride_in, long long stride_out, const float* in
     hipLaunchKernelGGL(k_blur_col, grid2d(w, h), dim3(256), 0, s, tmp, dst, w, h, dk, n, src, dg);
   }
 }
-// octaves [o_first, n_oct) in one launch; o_first = sift_tail_first(py) (>= 1; n_oct when the kernel sizes are not the stock ones)
+// octaves [o_first, n_oct) in one launch; o_first = sift_tail_first(py) (>= 1; n_oct when a level's kernel is wider than the tail's halo:
+// those pyramids run every octave level by level, through the same expressions)
 int sift_tail_first(const SiftPyramid& py, const int* ksize) {
-  for (int i = 1; i < 6; ++i) if (!sift_fused_taps(ksize[i])) return py.n_oct;
+  if (g_sift_general_blur) return py.n_oct;
+  for (int i = 1; i < py.n_layers + 3; ++i) if (!sift_tail_taps(ksize[i])) return py.n_oct;
   int o = 1;
   while (o < py.n_oct && (py.oct[o].w * py.oct[o].h > kTailPx || py.oct[o].w > kTailSide || py.oct[o].h > kTailSide)) ++o;
   return o;
@@ -1016,16 +1037,21 @@ int sift_tail_first(const SiftPyramid& py, const int* ksize) {
 void sift_tail(const SiftPyramid& py, int B, int o_first, const float* dk, const int* koff, const int* ksize, hipStream_t s) {
   if (o_first >= py.n_oct) return;
   SiftBlurPlan plan;
-  for (int i = 0; i < 6; ++i) { plan.off[i] = koff[i]; plan.n[i] = ksize[i]; }
+  for (int i = 0; i < kSiftMaxLayers + 3; ++i) { const bool used = i < py.n_layers + 3; plan.off[i] = used ? koff[i] : 0; plan.n[i] = used ? ksize[i] : 0; }
   constexpr int lds = 3 * kTailBuf * (int)sizeof(float);
-  static const bool attr_set = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_sift_tail), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess);
+  static const bool attr_set = (hipFuncSetAttribute(reinterpret_cast<const void*>(k_sift_tail<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess) &&
+                               (hipFuncSetAttribute(reinterpret_cast<const void*>(k_sift_tail<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess);
   (void)attr_set;
-  hipLaunchKernelGGL(k_sift_tail, dim3(B), dim3(1024), lds, s, py, o_first, dk, plan);
+  bool stock = py.n_layers == 3;
+  for (int i = 1; i < 6 && stock; ++i) stock = ksize[i] == 11 || ksize[i] == 13 || ksize[i] == 17 || ksize[i] == 21 || ksize[i] == 27;
+  if (stock) hipLaunchKernelGGL(k_sift_tail<true>, dim3(B), dim3(1024), lds, s, py, o_first, dk, plan);
+  else hipLaunchKernelGGL(k_sift_tail<false>, dim3(B), dim3(1024), lds, s, py, o_first, dk, plan);
 }
-// createInitialImage for B images: gray [B][h][w] u8 -> level 0 of octave 0 (2h x 2w, blurred to sigma 1.6); zeroes counters[4b + 0..2].
-// Stock kernel (11 taps): one launch, the doubled image is sampled on the fly; otherwise k_sift_base into `scratch` + the generic blur.
+// createInitialImage for B images: gray [B][h][w] u8 -> level 0 of octave 0 (2h x 2w, blurred to sigma); zeroes counters[4b + 0..2].
+// Stock kernel (11 taps, sigma 1.6): one launch, the doubled image is sampled on the fly; any other sigma: k_sift_base into `scratch` + sift_blur
+// (one fused launch up to kFusedMaxTaps; sigma <= 2.4 needs 19).
 void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int* counters, hipStream_t s) {
-  if (n == 11) {
+  if (n == 11 && !g_sift_general_blur) {
     const dim3 g((2 * w + kFtW - 1) / kFtW, (2 * h + kFtH - 1) / kFtH, B);
     hipLaunchKernelGGL((k_blur_fused<11, true>), g, dim3(256), 0, s, reinterpret_cast<const float*>(gray), out, 2 * w, 2 * h, dk, (float*)nullptr, 1, 2 * w,
                        (long long)h * w, out_stride, counters);
@@ -1048,10 +1074,17 @@ void sift_find(const SiftPyramid& py, int B, float threshold, int4* cand, int* n
     total += gx * gy;
   }
   plan.first_tile[kSiftMaxOctaves] = total;
-  if (total > 0) hipLaunchKernelGGL(k_sift_find, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand);
+  if (total <= 0) return;
+  switch (py.n_layers) {
+    case 1: hipLaunchKernelGGL(k_sift_find<1>, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand); break;
+    case 2: hipLaunchKernelGGL(k_sift_find<2>, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand); break;
+    case 3: hipLaunchKernelGGL(k_sift_find<3>, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand); break;
+    case 4: hipLaunchKernelGGL(k_sift_find<4>, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand); break;
+    default: hipLaunchKernelGGL(k_sift_find<5>, dim3(total, 1, B), dim3(256), 0, s, py, plan, threshold, cand, n_cand, max_cand); break;
+  }
 }
-void sift_refine(const SiftPyramid& py, int B, const int4* cand, int* counters, int max_cand, SiftKeypoint* kp, long long kp_stride, int max_raw, hipStream_t s) {
-  hipLaunchKernelGGL(k_sift_refine, dim3(std::min(max_cand, 4096), B), dim3(64), 0, s, py, cand, counters, max_cand, kp, kp_stride, max_raw);
+void sift_refine(const SiftPyramid& py, const SiftParams& prm, int B, const int4* cand, int* counters, int max_cand, SiftKeypoint* kp, long long kp_stride, int max_raw, hipStream_t s) {
+  hipLaunchKernelGGL(k_sift_refine, dim3(std::min(max_cand, 4096), B), dim3(64), 0, s, py, prm, cand, counters, max_cand, kp, kp_stride, max_raw);
 }
 void sift_descriptors(const SiftPyramid& py, int B, const SiftKeypoint* kp_final, long long kp_stride, const int* counters, int max_n, float* desc, long long out_stride, hipStream_t s) {
   // blocks beyond an image's keypoint count exit at once.  One image: latency matters (producer waves + atomic committer);

@@ -30,8 +30,18 @@ class PoseNode:
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
                  sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS, report: bool = False,
-                 width_confidence: float = -1.0, pruning_min_kpts: Optional[int] = None):
+                 width_confidence: float = -1.0, pruning_min_kpts: Optional[int] = None, sift_params: Optional[dict] = None):
         from .matcher import _check_ladder
+        from .sift import SIFT, check_sift_params
+        # sift_params: cv2.SIFT_create's keywords (nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma) for the tile extractor this
+        # node builds; refused before any device work, and meaningless next to an injected extractor
+        sift_params = dict(sift_params or {})
+        if sift_params and extractor is not None:
+            raise ValueError("sift_params configures the node's own SIFT extractor; it cannot be combined with extractor=")
+        try:
+            check_sift_params(**sift_params)
+        except TypeError as e:
+            raise ValueError(f"sift_params: {e}") from None
         ransac_iterations = check_ransac_iterations(ransac_iterations)      # (refused before any device work)
         # width_confidence > 0: LightGlue's point pruning (gn_set_width_pruning; the reference asks for 0.99 at pose_node.py:88-107 behind a
         # comparison that is never true).  Not under the margin certificate: certify=False for the fast precision modes.
@@ -45,8 +55,7 @@ class PoseNode:
         if width_confidence > 0:
             self._engine.set_width_pruning(width_confidence, pruning_min_kpts)
         if extractor is None:
-            from .sift import SIFT
-            extractor = SIFT(engine=self._engine, max_keypoints=max_kpts).as_extractor()
+            extractor = SIFT(engine=self._engine, max_keypoints=max_kpts, **sift_params).as_extractor()
         self._extractor = extractor
         # fast precision modes: the correspondence indices are certified against the exact-f32 arithmetic (gn_set_certify(2)); eps is calibrated on
         # the first messages' own inputs (each is matched a second time in f32), 4 x the largest difference seen, then frozen

@@ -532,7 +532,8 @@ int gn_pose_cov_to_earth(const double* R9, const double* t3, const double* cov_r
                          double* cov_earth36);
 
 /* ---- SIFT feature extraction ------------------------------------------ */
-/* cv2.SIFT_create().detectAndCompute(gray, None) with OpenCV's defaults -- the tile extractor of PoseNode
+/* cv2.SIFT_create(nOctaveLayers, contrastThreshold, edgeThreshold, sigma).detectAndCompute(gray, None) with the parameters of
+ * gn_sift_set_params (OpenCV's defaults 3, 0.04, 10, 1.6 until it is called) -- the tile extractor of PoseNode
  * (pose_node.py:122,230-232) and the frame extractor of TwistNode (twist_node.py:93,227-245).
  *   gray [H][W] u8 (device).  Outputs (device): kpt_xysa [max_kpts][4] f32 = (x, y, size, angle_deg) -- the
  *   GN_KPT_XYSA keypoint format of gn_match / gn_estimate; response [max_kpts] f32 and octave [max_kpts] int32
@@ -552,6 +553,16 @@ int gn_sift_detect_and_compute(gn_ctx* ctx, const uint8_t* gray, int H, int W, i
  * (gn_estimate) already takes batches of pairs in this keypoint format. */
 int gn_sift_detect_and_compute_batch(gn_ctx* ctx, const uint8_t* gray, int B, int H, int W, int max_kpts,
                                      float* kpt_xysa, float* response, int32_t* octave, float* desc, int32_t* n_out_host, void* stream);
+
+/* cv2.SIFT_create's nOctaveLayers, contrastThreshold, edgeThreshold and sigma for the gn_sift_detect_and_compute(_batch) calls that follow:
+ * sticky host-side state like gn_set_ransac, (3, 0.04, 10, 1.6) by default -- with those values a context computes exactly what it computes
+ * when never told.  Accepted: n_octave_layers 1 .. 5, contrast_threshold finite and >= 0, edge_threshold finite and > 0, sigma in [1.0, 2.4];
+ * anything else returns GN_ERR_ARG (gn_last_error names the range) and leaves the state as it was.  The ranges are this build's own (cv2 accepts
+ * more): they bound an octave at 8 Gaussian + 7 DoG planes and the widest blur kernel at 135 taps.  A change of n_octave_layers or sigma
+ * replaces the SIFT workspace (pyramid planes, blur kernels) at the next call; the thresholds cost nothing to change.  nfeatures is the
+ * max_kpts argument of the call (order and tie rule above).  gn_sift_get_params: any pointer may be NULL. */
+int gn_sift_set_params(gn_ctx* ctx, int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma);
+int gn_sift_get_params(const gn_ctx* ctx, int* n_octave_layers, double* contrast_threshold, double* edge_threshold, double* sigma);
 
 /* Distinct keypoints each image of the LAST gn_sift_detect_and_compute(_batch) call had before the max_kpts cap (HOST int32 [B]). */
 int gn_sift_last_totals(gn_ctx* ctx, int B, int32_t* totals_host);
