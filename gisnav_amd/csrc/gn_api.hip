@@ -91,6 +91,71 @@ template <typename... T> struct Restore {
   Restore& operator=(const Restore&) = delete;
 };
 
+// The per-pair device workspaces of the matcher, the PnP stage and point pruning, each declared ONCE, here:
+//   X(element type, field, elements per pair, when it exists, gn_debug_read name or nullptr)
+// Allocation is max_batch x (elements per pair at np = npad); a view of the pairs from b0 on starts b0 x (elements per pair at np = npad_run)
+// into every buffer -- the buffers are laid out per call, at the padded size the call runs at.  Nothing else states a workspace's size.
+// T2 = 2 np (tokens per pair); km = npad = gn_kmax(): the match lists, the PnP masks and the work lists are strided by the context's padded
+// maximum whatever the active size.  uint16_t buffers count uint16 elements (hm16 rows: 2 T C).  A buffer that is not per pair (attn_part,
+// attn_tickets, vo_*, the guard words, tile_feedback, the pinned mirrors, cert_stage) is never sliced and stays a plain member of the context.
+enum { kWsAlways = 1, kWsF16x2 = 2 /* f16x2 contexts */, kWsNotF32 = 4 /* every precision but f32 */, kWsFirstUse = 8 /* ensure_sim */, kWsPnpStage = 16 /* ensure_pnp_stage */ };
+inline long long lists_stride_of(long long km) { return gn::kTileListBase + 2 * (km / 128) + 8 * ((km + 255) / 256); }   // ints per pair (launch_tile_lists)
+#define GN_WORKSPACES(X)                                                                                                         \
+  X(float, desc, T2 * kInDim, kWsAlways, "desc") X(float, cos_t, T2 * kFreq, kWsAlways, "cos") X(float, sin_t, T2 * kFreq, kWsAlways, "sin") \
+  X(float, extent, 4, kWsAlways, "extent") X(int32_t, nvalid, 2, kWsAlways, "nvalid")                                            \
+  X(float, x, T2 * kDim, kWsAlways, "x") X(float, qkv, T2 * 3 * kDim, kWsAlways, "qkv") X(float, ctx, T2 * kDim, kWsAlways, "ctx") \
+  X(float, msg, T2 * kDim, kWsAlways, "msg") X(float, h, T2 * 2 * kDim, kWsAlways, "h") X(float, md, T2 * kDim, kWsAlways, "md") \
+  X(float, ls, T2, kWsAlways, "ls")                                                                                              \
+  /* f16x2 mode: the hm16 rows that shadow the f32 activations feeding GEMMs (planes_of), written by their producers */          \
+  X(uint16_t, desc_p, 2 * T2 * kInDim, kWsF16x2, "desc_p") X(uint16_t, x_p, 2 * T2 * kDim, kWsF16x2, "x_p")                      \
+  X(uint16_t, ctx_p, 2 * T2 * kDim, kWsF16x2, nullptr) X(uint16_t, msg_p, 2 * T2 * kDim, kWsF16x2, "msg_p")                      \
+  X(uint16_t, h_p, 2 * T2 * 2 * kDim, kWsF16x2, nullptr) X(uint16_t, md_p, 2 * T2 * kDim, kWsF16x2, nullptr)                     \
+  /* rotary table of k_qkv: [16][Tmax] float4, plane-strided by Tmax (rot_stride) -- a pair is 2 np float4 further on in every plane */ \
+  X(float, rot4, slicing ? T2 * 4 : T2 * 2 * kFreq, kWsF16x2, "rot4")                                                            \
+  X(uint16_t, qkb, T2 * 2 * kDim, kWsNotF32, "qkb") X(uint16_t, vtb, T2 * kDim, kWsNotF32, "vtb") /* 16-bit q | k rows, V^T panels */ \
+  /* match head: per-row / per-column statistics, the certificate's runner-ups and per-pair flags, the calibration's column scores */ \
+  X(float, rowmax, np, kWsAlways, "rowmax") X(float, rowlog, np, kWsAlways, "rowlog") X(float, colmax, np, kWsAlways, "colmax")  \
+  X(float, collog, np, kWsAlways, "collog") X(float, max0, np, kWsAlways, "max0") X(int32_t, m0, np, kWsAlways, "m0")            \
+  X(int32_t, m1, np, kWsAlways, "m1") X(float, max0b, np, kWsAlways, "max0b") X(float, rpart_c, 8 * np, kWsAlways, nullptr)      \
+  X(int32_t, uncert, 1, kWsAlways, "uncert") X(int32_t, uncert_alt, 1, kWsAlways, nullptr) X(int32_t, uncert_alt2, 1, kWsAlways, nullptr) \
+  X(float, colbest, np, kWsAlways, nullptr) X(float, col2, np, kWsAlways, nullptr)                                               \
+  /* fused head: column partials [np / 32][np], row partials [8][np], two arrival counters (zero between calls) */               \
+  X(float, cpart_m, (np / 32) * np, kWsAlways, nullptr) X(float, cpart_s, (np / 32) * np, kWsAlways, nullptr)                    \
+  X(int32_t, cpart_i, (np / 32) * np, kWsAlways, nullptr) X(float, rpart_a, 8 * np, kWsAlways, nullptr)                          \
+  X(float, rpart_b, 8 * np, kWsAlways, nullptr) X(unsigned int, tickets, 2, kWsAlways, nullptr)                                  \
+  /* gn_estimate's match list, gathered points and PnP scratch (e_idx has 8-byte elements: gn_debug_read serves it by hand) */   \
+  X(int64_t, e_idx, km * 2, kWsAlways, nullptr) X(float, e_score, km, kWsAlways, "e_score") X(float, e_mkp, km * 2, kWsAlways, "e_mkp") \
+  X(float, e_obj, km * 3, kWsAlways, "e_obj") X(uint8_t, mask_ws, km * 16, kWsAlways, nullptr) X(float, pts_ws, km * 5, kWsAlways, nullptr) \
+  X(gn::HypResult, hyp_ws, 16, kWsAlways, "hyp")                                                                                 \
+  /* round path of the PnP stage: [kRansacRound + 1][km] masks whatever iterations_count, one state */                           \
+  X(uint8_t, rmask_ws, km * (gn::kRansacRound + 1), kWsAlways, "ransac_mask") X(gn::RansacState, rstate_ws, 1, kWsAlways, "ransac_state") \
+  X(int, lists, lists_stride_of(km), kWsAlways, "lists") /* work lists of the call as they stand ([0] tiles, [1] attention items, ...) */ \
+  /* point pruning (gn_prune.hip), [2][np] per pair: original indices, prune counts, move targets, z of the last pruning layer;   \
+     pr_counts: [2][kMaxLayers] a slot's count after every layer; pr_nin: [2] the call's input counts (the head's no-match rule) */ \
+  X(int32_t, pr_ind, T2, kWsAlways, "prune_ind") X(int32_t, pr_prune, T2, kWsAlways, nullptr) X(int32_t, pr_dst, T2, kWsAlways, nullptr) \
+  X(int32_t, pr_counts, 2 * kMaxLayers, kWsAlways, "prune_counts") X(int32_t, pr_nin, 2, kWsAlways, nullptr) X(float, pr_z, T2, kWsAlways, "prune_z") \
+  /* [np][np] similarity buffer: TwistNode's brute-force matcher, the unfused developer path and the phase-stamp tools only */   \
+  X(float, sim, np * np, kWsFirstUse, "sim")                                                                                     \
+  /* PnP inputs of the overlapped pose stage, double-buffered by call parity */                                                  \
+  X(float, o_mkp0, km * 2, kWsPnpStage, nullptr) X(float, o_obj0, km * 3, kWsPnpStage, nullptr) X(int32_t, o_nmatch0, 1, kWsPnpStage, nullptr) \
+  X(float, o_mkp1, km * 2, kWsPnpStage, nullptr) X(float, o_obj1, km * 3, kWsPnpStage, nullptr) X(int32_t, o_nmatch1, 1, kWsPnpStage, nullptr)
+
+struct Workspace {
+#define X(type, field, per_pair, when, name) type* field = nullptr;
+  GN_WORKSPACES(X)
+#undef X
+};
+// f(field, elements per pair, when it exists, debug name) for every workspace of w, in table order
+template <typename F> void for_each_workspace(Workspace& w, long long np, long long km, bool slicing, F&& f) {
+  const long long T2 = 2 * np;
+#define X(type, field, per_pair, when, name) f(w.field, (long long)(per_pair), (int)(when), (const char*)(name));
+  GN_WORKSPACES(X)
+#undef X
+}
+// The workspaces of the pairs from b0 on (view_of): what a sub-batch group, or the certificate's re-run of a run of pairs, works in.  The code
+// that enqueues work reads workspaces from the view it is given, never from the context.  g: the sub-batch group, ovf: its guard word.
+struct View : Workspace { long long b0 = 0; int g = 0; unsigned int* ovf = nullptr; };
+
 }  // namespace
 
 struct gn_ctx {
@@ -115,8 +180,8 @@ struct gn_ctx {
                            // (k_gemm_p2ln) when the grid fills the chip, 2 = always; 0 = separate k_ln_gelu (developer knob 10)
   // f16x2 domain guard (gn_set_guard): device word raised by any hm16 writer whose value does not fit fp16
   // ovf_base: [0..7] one word per sub-batch group of the matcher (groups run concurrently on their own streams and each clears / reads its own
-  // word), [8] the SuperPoint extractor's; ovf = the word of the group that is being enqueued (ovf_base + g); ovf_host: pinned mirror of all 16
-  unsigned int* ovf_base = nullptr; unsigned int* ovf = nullptr; unsigned int* ovf_host = nullptr;
+  // word: View::ovf), [8] the SuperPoint extractor's, [12] selfcheck_fused_projection's counter; ovf_host: pinned mirror of all 16
+  unsigned int* ovf_base = nullptr; unsigned int* ovf_host = nullptr;
   int dbg_trip_group = 0;  // developer knob 25: g + 1 = the matcher starts group g's guard word RAISED instead of cleared (tests of the per-group words)
   bool in_group = false;   // gn_estimate is enqueuing one of its sub-batch groups (gn_match then leaves ovf_groups_last alone)
   int ovf_groups_last = 1; // number of group words the most recent matcher call used (gn_get_guard_status ORs exactly those)
@@ -130,7 +195,7 @@ struct gn_ctx {
   int cert_eps_src = 0;        // where cert_eps comes from: 0 the built-in default, 1 stated (gn_set_certify), 2 measured (gn_calibrate_certify),
                                // 3 measured on weights since replaced (gn_load_tensor; cert_eps is then +inf: every pair goes to exact f32)
   float cert_eps_f32 = 1.0e-4f;   // the same for the exact-f32 kernels (GPU f32 against the torch-CPU f32 oracle: summation order only)
-  float* max0b = nullptr; float* rpart_c = nullptr; int32_t* uncert = nullptr; int32_t* uncert_alt = nullptr; int32_t* uncert_alt2 = nullptr; int32_t* uncert_host = nullptr;   // uncert_host: pinned [3 * max_batch] (flags | the two other levels' flags)
+  int32_t* uncert_host = nullptr;   // pinned [3 * max_batch] (flags | the two other levels' flags)
   bool cert_inner = false;     // a certificate re-run is being enqueued (no nested certification)
   void* cert_stage = nullptr; size_t cert_stage_bytes = 0;      // staging block of the gathered re-run (certify_rerun), grown on demand
   // mode 3 (deferred): gn_estimate leaves the flags of call n in a pinned slot behind an event and resolves them -- reads them, re-runs the flagged
@@ -148,8 +213,7 @@ struct gn_ctx {
   // cert_eps_mid (< 0 = not calibrated: straight to exact f32); only the pairs still flagged go on to exact f32
   int ladder = 0; float cert_eps_mid = -1.f, cert_mid_measured = -1.f;
   long long mid_rerun = 0, mid_certified = 0, mid_passed = 0;
-  float *colbest = nullptr, *col2 = nullptr;   // [B][npad] best score / runner-up of every column (written by the fused head while cal_cols is set)
-  bool cal_cols = false;
+  bool cal_cols = false;   // the fused head also writes colbest / col2: best score / runner-up of every column
   int precision_api = 0;   // the gn_precision value gn_create was called with
   int feature = 0;         // GN_FEATURE_SIFT / GN_FEATURE_SUPERPOINT (gn_create_ex)
   int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac: what gn_estimate / gn_vo_estimate pass to the PnP stage
@@ -159,10 +223,8 @@ struct gn_ctx {
   int npad_run = 0;        // padded keypoint count the matcher runs at (<= npad, gn_set_active_kpts); buffers are laid out for it per call
   int n_layers = kMaxLayers;
   float threshold = 0.5f;
-  // point pruning (gn_set_width_pruning; gn_prune.hip): off unless width_conf > 0.  pr_*: [B * 2][npad_run] per call, sliced by shift_workspaces
+  // point pruning (gn_set_width_pruning; gn_prune.hip): off unless width_conf > 0 (workspaces: pr_*)
   float width_conf = -1.f; int prune_min_kpts = 1536;
-  int32_t *pr_ind = nullptr, *pr_prune = nullptr, *pr_dst = nullptr, *pr_counts = nullptr;   // pr_counts: [B * 2][kMaxLayers] a slot's count after every layer
-  int32_t* pr_nin = nullptr; float* pr_z = nullptr;      // [B * 2] the call's input counts (the head's no-match rule); [B * 2][npad_run] z of the last pruning layer
   bool prune_last_on = false; int prune_last_np = 0, prune_last_layers = 0, prune_last_B = 0;                  // the most recent matcher call (gn_get_prune)
   std::string err;
   // weights
@@ -172,16 +234,9 @@ struct gn_ctx {
   Linear final_proj[kMaxLayers], matchability[kMaxLayers];
   std::map<std::string, bool> loaded;
   std::vector<std::string> required;
-  // workspace
-  float *desc = nullptr, *cos_t = nullptr, *sin_t = nullptr, *extent = nullptr;
-  int32_t* nvalid = nullptr;
-  float *x = nullptr, *qkv = nullptr, *ctx = nullptr, *msg = nullptr, *h = nullptr, *md = nullptr, *ls = nullptr;
-  // f16x2 mode: fp16 plane pairs [2][Tmax][C] of the activations that feed GEMMs (written by their producers)
-  uint16_t *desc_p = nullptr, *x_p = nullptr, *ctx_p = nullptr, *msg_p = nullptr, *h_p = nullptr, *md_p = nullptr;
+  Workspace ws;            // the per-pair workspaces as allocated (GN_WORKSPACES): changes in alloc_workspaces only; work is enqueued on a view_of it
   size_t Tmax = 0;         // token slots allocated (max_batch * 2 * npad) = plane stride in rows
   int planes_mode = 0;     // 1: activations travel as fp16 planes and GEMMs run k_gemm_p2 (default in f16x2 mode)
-  float* sim = nullptr;
-  uint16_t *qkb = nullptr, *vtb = nullptr;   // bf16 q|k rows and V^T panels (GN_PREC_BF16_ATTN)
   float* attn_part = nullptr; unsigned int* attn_tickets = nullptr;   // split-keys attention of small batches: <= 256 partial results, their tickets
   int attn_split = 1;      // developer knob 23: largest number of key ranges the attention of a small batch is split into (default 1 = never: the
                            // split changes the rounding of the probabilities, and results would then depend on batch size / padding / sub-streams)
@@ -197,15 +252,6 @@ struct gn_ctx {
   int dbg_reuse = 0;       // gn_debug_gemm: keep the operand planes of the previous call (micro-benchmarks time the GEMM alone)
   uint16_t* dbg_ap = nullptr; size_t dbg_ap_n = 0;   // gn_debug_gemm, variant 7: A planes for k_gemm_p2
   int gemm_variant = -1;   // -1: library default (f32 MFMA, LDS-DMA); 5: f32x3 (GN_PREC_F32X3_BF16_ATTN)
-  float *rowmax = nullptr, *rowlog = nullptr, *colmax = nullptr, *collog = nullptr, *max0 = nullptr;
-  int32_t *m0 = nullptr, *m1 = nullptr;
-  float *cpart_m = nullptr, *cpart_s = nullptr;   // fused head: column partials [B][2 npad / 64][npad]
-  int32_t* cpart_i = nullptr;
-  float* rot4 = nullptr;                          // [16][T] float4 rotary table for k_qkv (re-laid-out after every prep)
-  float *rpart_a = nullptr, *rpart_b = nullptr;   // fused head: row partials [B][8][npad]
-  unsigned int* tickets = nullptr;                // fused head: [B][2] arrival counters, zero between calls
-  // pipeline scratch for gn_estimate
-  int64_t* e_idx = nullptr; float* e_score = nullptr; float* e_mkp = nullptr; float* e_obj = nullptr;
   // sub-batch streams (gn_set_substreams): the pairs of one call are split into groups that run the whole path on
   // internal streams, out of phase with each other (fork / join events around them on the caller's stream)
   int defer_join = 0, sub_last_B = 0, sub_last_np = 0;   // gn_set_deferred_join; shape of the last unjoined sub-stream call
@@ -238,15 +284,13 @@ struct gn_ctx {
                            // 2 = the activations' fp16 high term only (meant to run under the margin certificate)
   int qkv_products = 2;    // knob 27: fp16 partial products of the attention input projections (2 or 3), per context
   unsigned long long* tile_feedback = nullptr;   // pinned host [8]: (all tiles << 32 | valid tiles) written by k_tile_lists of sub-batch group g's last call
-  int* lists = nullptr; long long lists_stride = 0;   // work lists (launch_tile_lists), lists_stride ints per pair
   int n_sub = 1; hipStream_t sub_s[8] = {}; hipEvent_t ev_fork = nullptr; hipEvent_t ev_join[8] = {}; bool sub_pending[8] = {};
   // overlapped pose stage (gn_set_overlap): PnP of call n runs on an internal stream beside the matcher of call n+1
   // and the pose stage of the sub-batch groups: every group of call n hands its PnP to the ONE PnP stream and its own stream goes on with call n + 1.
-  // The PnP inputs (o_*) are double-buffered by call parity; [slot][g] = group g's PnP of the call that used that slot (g = 0 without sub-batch groups)
+  // The PnP inputs (o_mkp0 / 1 ...) are double-buffered by call parity; [slot][g] = group g's PnP of the call that used that slot (g = 0 without sub-batch groups)
   int overlap = 0; unsigned long long calls = 0;
   hipStream_t s_pnp = nullptr; hipEvent_t ev_gather[2][8] = {}, ev_pnp[2][8] = {}; bool pnp_pending[2][8] = {}, pnp_recorded[2][8] = {};
   hipEvent_t ev_head[8] = {};      // group g's match head is done: the certificate's flags of the call exist (deferred certificate)
-  float* o_mkp[2] = {nullptr, nullptr}; float* o_obj[2] = {nullptr, nullptr}; int32_t* o_nmatch[2] = {nullptr, nullptr};
   int prep_fused = 1;      // knob 48.  1 (default): k_prep writes the hm16 descriptor rows and the rot4 table itself and k_extent clears the guard word;
                            // 0: the separate k_split_hm16 / k_rot_table launches behind it (same bits; tests)
   // SIFT workspace (gn_sift_detect_and_compute), sized for the last image shape seen
@@ -266,11 +310,6 @@ struct gn_ctx {
   int *sp_cand = nullptr, *sp_counts = nullptr, *sp_index = nullptr;
   // visual-odometry matcher workspace (gn_vo_match)
   float* vo_norm2 = nullptr; int32_t* vo_nn_idx = nullptr; float* vo_nn_dist = nullptr; uint8_t* vo_good = nullptr;
-  uint8_t* mask_ws = nullptr;
-  float* pts_ws = nullptr;
-  gn::HypResult* hyp_ws = nullptr;
-  uint8_t* rmask_ws = nullptr;             // round path of the PnP stage: [B][kRansacRound + 1][npad], whatever iterations_count
-  gn::RansacState *rstate_ws = nullptr, *rstate_base = nullptr;   // [B]; the base stays put under shift_workspaces
   std::vector<void*> allocs;
   std::vector<void*> ws_allocs;     // the max_kpts-dependent workspaces (alloc_workspace): replaced by gn_resize, weights stay
   // stage timing
@@ -329,12 +368,6 @@ int ws_alloc(gn_ctx* ctx, T_** p, size_t count) {
   *p = reinterpret_cast<T_*>(q);
   return GN_OK;
 }
-// The [B][npad][npad] similarity buffer is no longer part of the matcher (fused match head): it exists only for TwistNode's
-// brute-force matcher, the unfused developer path and the phase-stamp tools, and is allocated on their first use.
-int ensure_sim(gn_ctx* ctx) {
-  if (ctx->sim) return GN_OK;
-  return ws_alloc(ctx, &ctx->sim, (size_t)ctx->max_batch * ctx->npad * ctx->npad);
-}
 
 std::string canonical(const std::string& k) {
   for (const char* kind : {"self_attn.", "cross_attn."}) {
@@ -360,10 +393,10 @@ struct StageTimer {
 
 // f16x2 planes mode: the hm16 buffer that shadows an f32 activation buffer.  hm16 rows have the byte pitch of the
 // f32 rows, so an element offset into the f32 buffer (whole rows) maps to twice that many fp16 elements.
-bool planes_of(gn_ctx* c, const float* p, uint16_t** planes) {
+bool planes_of(const gn_ctx* c, const View& w, const float* p, uint16_t** planes) {
   struct { const float* f; uint16_t* q; size_t cols; } tab[] = {
-    {c->desc, c->desc_p, (size_t)kInDim}, {c->x, c->x_p, (size_t)kDim}, {c->ctx, c->ctx_p, (size_t)kDim},
-    {c->msg, c->msg_p, (size_t)kDim}, {c->h, c->h_p, (size_t)2 * kDim}, {c->md, c->md_p, (size_t)kDim}};
+    {w.desc, w.desc_p, (size_t)kInDim}, {w.x, w.x_p, (size_t)kDim}, {w.ctx, w.ctx_p, (size_t)kDim},
+    {w.msg, w.msg_p, (size_t)kDim}, {w.h, w.h_p, (size_t)2 * kDim}, {w.md, w.md_p, (size_t)kDim}};
   for (auto& e : tab) {
     if (e.f && p >= e.f && p < e.f + c->Tmax * e.cols && (size_t)(p - e.f) % e.cols == 0) {
       *planes = e.q + 2 * (p - e.f);
@@ -390,29 +423,29 @@ template <typename F> bool timed_launch(gn_ctx* c, hipStream_t s, int kclass, do
   return true;
 }
 
-void timed_gemm(gn_ctx* c, int epi, const GemmArgs& g_in, int batch, hipStream_t s) {
+void timed_gemm(gn_ctx* c, const View& w, int epi, const GemmArgs& g_in, int batch, hipStream_t s) {
   if (c->gemm_variant >= 0) gn::g_gemm_variant = c->gemm_variant;
   GemmArgs g = g_in;
   if (c->no_planes) g.Wp = nullptr;
   bool p2 = false;
   if (c->planes_mode) {
     uint16_t* q = nullptr;
-    p2 = planes_of(c, g.A, &q);
+    p2 = planes_of(c, w, g.A, &q);
     if (p2) {
       g.Ap = q;
-      if (g.A2) { uint16_t* q2 = nullptr; p2 = planes_of(c, g.A2, &q2) && g.lda2 == g.lda; g.A2p = q2; }
+      if (g.A2) { uint16_t* q2 = nullptr; p2 = planes_of(c, w, g.A2, &q2) && g.lda2 == g.lda; g.A2p = q2; }
     }
     if (p2 && !g.Wp) {   // similarity GEMM: the B operand is an activation too
       uint16_t* qw = nullptr;
-      p2 = planes_of(c, g.W, &qw);
+      p2 = planes_of(c, w, g.W, &qw);
       g.Wp = qw; g.acc_scale = 1.f;
     }
-    if (p2) g.ovf = c->guard ? c->ovf : nullptr;
+    if (p2) g.ovf = c->guard ? w.ovf : nullptr;
     if (p2) {   // outputs that feed later GEMMs leave in hm16; f32 is kept only where something reads it
       uint16_t* qy = nullptr;
-      if (g.Y == c->x) { planes_of(c, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; if (g.drop_f32) g.Y = nullptr; }
-      else if (g.Y == c->msg || g.Y == c->md) { planes_of(c, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; g.Y = nullptr; }
-      else if (epi == EPI_LN_GELU && g.Y == c->h) { planes_of(c, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; g.Y = nullptr; }
+      if (g.Y == w.x) { planes_of(c, w, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; if (g.drop_f32) g.Y = nullptr; }
+      else if (g.Y == w.msg || g.Y == w.md) { planes_of(c, w, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; g.Y = nullptr; }
+      else if (epi == EPI_LN_GELU && g.Y == w.h) { planes_of(c, w, g.Y, &qy); g.Yp = qy; g.ldyp = g.ldy; g.Y = nullptr; }
     }
   }
   // compulsory bytes: A and W once (4 B per element as f32 or as an hm16 pair), every output array once, residual rows and rotary tables once
@@ -426,9 +459,9 @@ void timed_gemm(gn_ctx* c, int epi, const GemmArgs& g_in, int batch, hipStream_t
   timed_launch(c, s, 0, 2.0 * g.M * (double)g.N * g.K * batch, by, nullptr, [&] { if (p2) launch_gemm_p2(epi, g, batch, s); else launch_gemm_f32(epi, g, batch, s); });
 }
 
-void gemm(gn_ctx* c, int epi, GemmArgs& g, hipStream_t s) {
+void gemm(gn_ctx* c, const View& w, int epi, GemmArgs& g, hipStream_t s) {
   g.strideA = g.strideW = g.strideY = 0;
-  timed_gemm(c, epi, g, 1, s);
+  timed_gemm(c, w, epi, g, 1, s);
 }
 
 // (re)build the three bf16 planes of a weight matrix (w = wh + wm + wl exactly) for the f32x3 GEMM
@@ -508,9 +541,9 @@ void timed_attention(gn_ctx* c, const AttnArgs& a, bool bf16v2, hipStream_t s) {
 
 // q | k | v (or qk | v) projection of one block straight into the attention kernel's bf16 layouts; false when the shape / mode
 // needs the general GEMM
-bool qkv_projection_applies(const gn_ctx* c, const Block& blk, int T, int np, int vt_perm) {
+bool qkv_projection_applies(const gn_ctx* c, const View& w, const Block& blk, int T, int np, int vt_perm) {
   // (small batches keep the tiled GEMM: T / 128 workgroups would leave most of the chip idle)
-  return c->planes_mode && c->qkv_fused && blk.proj_in.wf && c->x_p && c->qkb && c->vtb && c->rot4 && T % 128 == 0 && np % 128 == 0 && (vt_perm & 1) &&
+  return c->planes_mode && c->qkv_fused && blk.proj_in.wf && w.x_p && w.qkb && w.vtb && w.rot4 && T % 128 == 0 && np % 128 == 0 && (vt_perm & 1) &&
          (T / 128 >= 128 || c->qkv_fused == 2);
 }
 // The choice depends on the number of pairs of the call only (at most two), never on the padded length: gn_set_active_kpts must not change a result
@@ -518,17 +551,17 @@ bool qkv_projection_applies(const gn_ctx* c, const Block& blk, int T, int np, in
 bool skinny_applies(const gn_ctx* c, int T, int np) {
   return (c->skinny & 3) && c->planes_mode && c->x_planes_only && T % 32 == 0 && np > 0 && ((c->skinny & 3) == 2 || T / np <= 4);
 }
-bool qkv_projection(gn_ctx* c, const Block& blk, bool cross, int T, int np, int vt_perm, hipStream_t s) {
-  const bool skinny = skinny_applies(c, T, np) && !(c->skinny & 4) && c->qkv_fused && blk.proj_in.wf && c->x_p && c->qkb && c->vtb && c->rot4 && np % 32 == 0 && vt_perm == 1 && !c->qkv_stamps;
-  if (!skinny && !qkv_projection_applies(c, blk, T, np, vt_perm)) return false;
+bool qkv_projection(gn_ctx* c, const View& w, const Block& blk, bool cross, int T, int np, int vt_perm, hipStream_t s) {
+  const bool skinny = skinny_applies(c, T, np) && !(c->skinny & 4) && c->qkv_fused && blk.proj_in.wf && w.x_p && w.qkb && w.vtb && w.rot4 && np % 32 == 0 && vt_perm == 1 && !c->qkv_stamps;
+  if (!skinny && !qkv_projection_applies(c, w, blk, T, np, vt_perm)) return false;
   QkvArgs q;
-  q.xp = c->x_p; q.wf = blk.proj_in.wf; q.acc_scale = blk.proj_in.acc_scale; q.bias = blk.proj_in.b;
-  q.rot4 = c->rot4; q.rot_stride = (long long)c->Tmax; q.qkb = c->qkb; q.ldyb = cross ? kDim : 2 * kDim; q.vt = c->vtb; q.npad = np;
+  q.xp = w.x_p; q.wf = blk.proj_in.wf; q.acc_scale = blk.proj_in.acc_scale; q.bias = blk.proj_in.b;
+  q.rot4 = w.rot4; q.rot_stride = (long long)c->Tmax; q.qkb = w.qkb; q.ldyb = cross ? kDim : 2 * kDim; q.vt = w.vtb; q.npad = np;
   q.qscale = 0.125f; q.scale = 0.35355339059327373f; q.vt_perm = vt_perm; q.T = T;
-  q.half_fmt = c->attn_f16; q.ovf = (c->attn_f16 && c->guard) ? c->ovf : nullptr;
-  q.tiles = (c->use_lists && c->lists && !c->qkv_stamps) ? c->lists : nullptr;
+  q.half_fmt = c->attn_f16; q.ovf = (c->attn_f16 && c->guard) ? w.ovf : nullptr;
+  q.tiles = (c->use_lists && w.lists && !c->qkv_stamps) ? w.lists : nullptr;
   q.products = c->qkv_products == 3 ? 3 : 2; q.ncu = c->ncu;
-  q.dbg_ts = (c->qkv_stamps && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer knob 20
+  q.dbg_ts = (c->qkv_stamps && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 20
   const double N = cross ? 2.0 * kDim : 3.0 * kDim;
   timed_launch(c, s, 0, 2.0 * T * N * kDim, 4.0 * T * kDim + 2.0 * T * N + 4.0 * N * kDim + (cross ? 0.0 : 2.0 * 4.0 * T * kFreq),   // x in (hm16), bf16 out, weights once, rotary tables
                nullptr, [&] { if (skinny) launch_skinny_qkv(q, cross, s); else launch_qkv(q, cross, s); });
@@ -595,12 +628,10 @@ bool tail_folds_out_proj(const gn_ctx* c, const Block& blk, int T) {
 
 // The block tail's form on this call, predicted from the same sub-batch group's previous call (k_tile_lists leaves (all tiles, valid tiles) in pinned
 // host memory; read without synchronisation, so the word is from some earlier call -- workloads are stationary, and both forms give the same bits).
-bool tail_should_walk(const gn_ctx* c) {
+bool tail_should_walk(const gn_ctx* c, int g) {
   if (!c->tile_feedback) return false;
-  const int g = (int)(c->ovf - c->ovf_base);
-  if (g < 0 || g >= 8) return false;
-  const unsigned long long w = __atomic_load_n(&c->tile_feedback[g], __ATOMIC_RELAXED);
-  const unsigned all = (unsigned)(w >> 32), valid = (unsigned)w;
+  const unsigned long long word = __atomic_load_n(&c->tile_feedback[g], __ATOMIC_RELAXED);
+  const unsigned all = (unsigned)(word >> 32), valid = (unsigned)word;
   return all > 0 && (unsigned long long)valid * 10u < (unsigned long long)all * 9u;
 }
 
@@ -615,14 +646,14 @@ inline void ffn_window_reset(gn_ctx* c, int level) { c->auto_level = level; c->a
 // x += ffn3(gelu(ln(ffn0([x | msg]))))
 // next / next_cross: the block whose attention input projection follows this tail (nullptr: none) -- when the tail runs as the composed k_ffn128 and that
 // projection is a k_qkv<., true, 2> launch, it is computed inside the tail instead; returns true when it was (the caller then skips the projection)
-bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
+bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
   if (skinny_applies(c, T, np) && !(c->skinny & 8) && c->ffn_fused == 3 && c->ffn_compose && tail_folds_out_proj(c, blk, T) && blk.wfc && blk.b1c && !blk.comp_dirty && blk.ffn3.wfn &&
-      c->h && c->ctx_p && gn::g_ffn_stamps == 0 && gn::g_ffn_shape == 0) {
+      w.h && w.ctx_p && gn::g_ffn_stamps == 0 && gn::g_ffn_shape == 0) {
     // small grid: the weight stream split across CUs -- two launches (gn_skinny.hip)
     SkinnyTailArgs a;
-    a.xp = c->x_p; a.cp = c->ctx_p; a.w1 = blk.wfc; a.w1_scale = blk.wfc_scale; a.b1 = blk.b1c; a.h = c->h; a.ln_g = blk.ln_g; a.ln_b = blk.ln_b;
-    a.w2 = blk.ffn3.wfn; a.w2_scale = blk.ffn3.acc_scale; a.b2 = blk.ffn3.b; a.xp_out = c->x_p; a.y = keep_f32 ? c->x : nullptr;
-    a.ovf = c->guard ? c->ovf : nullptr; a.T = T;
+    a.xp = w.x_p; a.cp = w.ctx_p; a.w1 = blk.wfc; a.w1_scale = blk.wfc_scale; a.b1 = blk.b1c; a.h = w.h; a.ln_g = blk.ln_g; a.ln_b = blk.ln_b;
+    a.w2 = blk.ffn3.wfn; a.w2_scale = blk.ffn3.acc_scale; a.b2 = blk.ffn3.b; a.xp_out = w.x_p; a.y = keep_f32 ? w.x : nullptr;
+    a.ovf = c->guard ? w.ovf : nullptr; a.T = T;
     if (!timed_launch(c, s, 0, 2.0 * T * 512.0 * 512.0, 4.0 * T * (256.0 + 256.0 + 512.0) + 4.0 * 512.0 * 512.0, nullptr, [&] { launch_skinny_h(a, s, c->skinny >> 4); })) return false;
     timed_launch(c, s, 0, 2.0 * T * 256.0 * 512.0, 4.0 * T * (512.0 + 256.0 + 256.0) + 4.0 * 256.0 * 512.0, nullptr, [&] { launch_skinny_out(a, s, c->skinny >> 4); });
     return false;
@@ -630,28 +661,28 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
   if (c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && blk.ffn0.wf && blk.ffn3.wf && T % 64 == 0) {   // the whole tail in one launch
     FfnArgs f;
     const bool fold = tail_folds_out_proj(c, blk, T);                     // out_proj computed inside the kernel from the attention output
-    f.cp = fold ? c->ctx_p : nullptr; f.wos = blk.proj_out.wf; f.wo_scale = blk.proj_out.acc_scale; f.bo = blk.proj_out.b;
-    f.xp = c->x_p; f.mp = c->msg_p; f.w1s = fold ? blk.ffn0.wf2 : blk.ffn0.wf; f.w1_scale = blk.ffn0.acc_scale; f.b1 = blk.ffn0.b; f.ln_g = blk.ln_g; f.ln_b = blk.ln_b;
-    f.w2s = blk.ffn3.wf; f.w2_scale = blk.ffn3.acc_scale; f.b2 = blk.ffn3.b; f.yp = c->x_p; f.y = keep_f32 ? c->x : nullptr; f.T = T;
+    f.cp = fold ? w.ctx_p : nullptr; f.wos = blk.proj_out.wf; f.wo_scale = blk.proj_out.acc_scale; f.bo = blk.proj_out.b;
+    f.xp = w.x_p; f.mp = w.msg_p; f.w1s = fold ? blk.ffn0.wf2 : blk.ffn0.wf; f.w1_scale = blk.ffn0.acc_scale; f.b1 = blk.ffn0.b; f.ln_g = blk.ln_g; f.ln_b = blk.ln_b;
+    f.w2s = blk.ffn3.wf; f.w2_scale = blk.ffn3.acc_scale; f.b2 = blk.ffn3.b; f.yp = w.x_p; f.y = keep_f32 ? w.x : nullptr; f.T = T;
     const bool comp = fold && c->ffn_compose && blk.wfc && blk.b1c && !blk.comp_dirty;
     if (comp) { f.composed = 1; f.w1s = blk.wfc; f.w1_scale = blk.wfc_scale; f.b1 = blk.b1c; }
-    f.ovf = c->guard ? c->ovf : nullptr;
-    f.tiles = (c->use_lists && c->lists && gn::g_ffn_stamps == 0) ? c->lists : nullptr;
-    f.walk = c->use_lists == 2 || (c->use_lists == 1 && tail_should_walk(c));
+    f.ovf = c->guard ? w.ovf : nullptr;
+    f.tiles = (c->use_lists && w.lists && gn::g_ffn_stamps == 0) ? w.lists : nullptr;
+    f.walk = c->use_lists == 2 || (c->use_lists == 1 && tail_should_walk(c, w.g));
     f.ncu = c->ncu;
     f.composed = comp ? 1 : 0;
     f.products = (comp && ffn_level(c) <= 2) ? ffn_level(c) : 3;
     const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_stamps == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
-                          c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, *next, T, np, vt_perm) && !(vt_perm & 2);
+                          c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, w, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
       f.qkv = next_cross ? 2 : 1;
       f.q_wf = next->proj_in.wf; f.q_acc_scale = next->proj_in.acc_scale; f.q_bias = next->proj_in.b;
-      f.q_rot4 = c->rot4; f.q_rot_stride = (long long)c->Tmax; f.q_qkb = c->qkb; f.q_vt = c->vtb;
+      f.q_rot4 = w.rot4; f.q_rot_stride = (long long)c->Tmax; f.q_qkb = w.qkb; f.q_vt = w.vtb;
       f.q_qscale = 0.125f; f.q_scale = 0.35355339059327373f;
       f.npad = np;
     }
-    if (c->use_lists) { f.nvalid = c->nvalid; f.npad = c->npad_run; }
-    f.dbg_ts = gn::g_ffn_stamps ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
+    if (c->use_lists) { f.nvalid = w.nvalid; f.npad = c->npad_run; }
+    f.dbg_ts = gn::g_ffn_stamps ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
     double flops = 2.0 * T * (512.0 * 512.0 + 256.0 * 512.0 + ((fold && !comp) ? 256.0 * 256.0 : 0.0));   // composed: the flops the kernel's own formulation needs (algorithmic: whatever the number of partial products)
     double bytes = 4.0 * T * (256.0 + 256.0 + 256.0 + 256.0) + 4.0 * (512.0 * 512.0 + 256.0 * 512.0);   // x, msg, residual rows in; x out; weights once
     if (fuse_qkv) {     // + the projection (k_qkv's figures without its read of the rows)
@@ -661,32 +692,32 @@ bool ffn(gn_ctx* c, const Block& blk, int T, hipStream_t s, bool keep_f32, const
     }
     return timed_launch(c, s, 0, flops, bytes, nullptr, [&] { launch_ffn_fused(f, s); }) && fuse_qkv;
   }
-  GemmArgs g = gemm_args(c->x, kDim, blk.ffn0, c->h, 2 * kDim, T);
-  g.A2 = c->msg; g.lda2 = kDim; g.K1 = kDim;
+  GemmArgs g = gemm_args(w.x, kDim, blk.ffn0, w.h, 2 * kDim, T);
+  g.A2 = w.msg; g.lda2 = kDim; g.K1 = kDim;
   // LayerNorm + GELU in the GEMM's epilogue (the hidden tensor leaves once, as hm16) when there are enough 128-row tiles to fill the chip:
   // measured 9.64 vs 9.86 ms at 512 tiles (32 pairs), 5.68 vs 5.90 at 256, but 3.95 vs 3.73 ms at 128 tiles and 3.00 vs 2.40 ms at 16 (knob 10: 2 = always)
   if (c->planes_mode && T % 128 == 0 && (c->ffn_fused == 2 || (c->ffn_fused == 1 && T / 128 >= 256))) {
     g.ln_g = blk.ln_g; g.ln_b = blk.ln_b;
-    gemm(c, EPI_LN_GELU, g, s);
+    gemm(c, w, EPI_LN_GELU, g, s);
   } else {
-    gemm(c, EPI_BIAS, g, s);
-    launch_ln_gelu(c->h, blk.ln_g, blk.ln_b, T, s, c->planes_mode ? c->h_p : nullptr, c->planes_mode && c->guard ? c->ovf : nullptr);
+    gemm(c, w, EPI_BIAS, g, s);
+    launch_ln_gelu(w.h, blk.ln_g, blk.ln_b, T, s, c->planes_mode ? w.h_p : nullptr, c->planes_mode && c->guard ? w.ovf : nullptr);
   }
-  GemmArgs g3 = gemm_args(c->h, 2 * kDim, blk.ffn3, c->x, kDim, T);
-  g3.resid = c->x; g3.ldr = kDim;
+  GemmArgs g3 = gemm_args(w.h, 2 * kDim, blk.ffn3, w.x, kDim, T);
+  g3.resid = w.x; g3.ldr = kDim;
   if (c->planes_mode && c->x_planes_only) {   // the residual stream between layers lives in hm16 only (f32 x is written by the last block, for the head)
     uint16_t* xp = nullptr;
-    if (planes_of(c, c->x, &xp)) { g3.residp = xp; g3.ldrp = kDim; g3.resid = nullptr; g3.drop_f32 = keep_f32 ? 0 : 1; }
+    if (planes_of(c, w, w.x, &xp)) { g3.residp = xp; g3.ldrp = kDim; g3.resid = nullptr; g3.drop_f32 = keep_f32 ? 0 : 1; }
   }
-  gemm(c, EPI_RESIDUAL, g3, s);
+  gemm(c, w, EPI_RESIDUAL, g3, s);
   return false;
 }
 
-int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
+int run_matcher(gn_ctx* c, const View& w, const Call& v, hipStream_t s) {
   const int B = v.B, np = c->npad_run, T = B * 2 * np, BS = B * 2;
   const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
   gn::g_attn_variant = c->attn_variant;
-  gn::g_attn_stamps = (c->attn_variant == 73 && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;
+  gn::g_attn_stamps = (c->attn_variant == 73 && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;
   const int vt_perm = (bf16v2 ? 1 : 0) | (c->dbg_vt_skip ? 2 : 0);   // k_attn_bf16_v5 reads V^T with keys permuted inside 16-groups   // k_attn_bf16_v4 reads permuted V^T
   const bool attn_planes = c->planes_mode && (bf16v2 || c->attn_f16 == 2);   // k_attn_bf16_v5 / k_attn_f16x2 write the hm16 rows themselves
   c->launch_count = 0;
@@ -696,204 +727,207 @@ int run_matcher(gn_ctx* c, const Call& v, hipStream_t s) {
     p.desc_q = v.desc_q; p.kpt_q = v.kpt_q; p.n_q = v.n_q; p.stride_q = v.stride_q;
     p.desc_r = v.desc_r; p.kpt_r = v.kpt_r; p.n_r = v.n_r; p.stride_r = v.stride_r;
     p.kpt_format = v.kpt_format; p.B = B; p.npad = np; p.wr = c->wr;
-    p.desc = c->desc; p.kxy = nullptr; p.cos_t = c->cos_t; p.sin_t = c->sin_t; p.nvalid = c->nvalid; p.extent = c->extent;
+    p.desc = w.desc; p.kxy = nullptr; p.cos_t = w.cos_t; p.sin_t = w.sin_t; p.nvalid = w.nvalid; p.extent = w.extent;
     p.size_q[0] = c->size_q[0]; p.size_q[1] = c->size_q[1]; p.size_r[0] = c->size_r[0]; p.size_r[1] = c->size_r[1];
     p.feature = c->feature; p.x = nullptr; p.xp = nullptr;
     // the call's guard word starts clear -- or RAISED, developer knob 25 -- by k_extent, the call's first launch
-    p.ovf_clear = (c->planes_mode && c->guard) ? c->ovf : nullptr;
-    p.ovf_init = (c->dbg_trip_group && c->ovf == c->ovf_base + (c->dbg_trip_group - 1)) ? 1u : 0u;
+    p.ovf_clear = (c->planes_mode && c->guard) ? w.ovf : nullptr;
+    p.ovf_init = (c->dbg_trip_group && w.g == c->dbg_trip_group - 1) ? 1u : 0u;
     p.desc_p = nullptr; p.rot4 = nullptr; p.rot_stride = (long long)c->Tmax;
     const bool planes_only = c->planes_mode && c->x_planes_only && c->n_layers > 0;
     if (c->feature == 1) {   // 256-d descriptors ARE the initial residual stream (no input_proj)
-      p.x = planes_only ? nullptr : c->x; p.xp = c->planes_mode ? c->x_p : nullptr;
+      p.x = planes_only ? nullptr : w.x; p.xp = c->planes_mode ? w.x_p : nullptr;
       launch_prep(p, s);
-      if (c->rot4 && c->qkv_fused) launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, s);
+      if (w.rot4 && c->qkv_fused) launch_rot_table(w.cos_t, w.sin_t, w.rot4, T, (long long)c->Tmax, s);
     } else {
       // k_prep also writes what k_rot_table and k_split_hm16 would make of its f32 outputs (which stay, for the modes that read them)
-      const bool rot = c->rot4 && c->qkv_fused, split = c->planes_mode != 0;
-      if (c->prep_fused) { p.rot4 = rot ? c->rot4 : nullptr; p.desc_p = split ? c->desc_p : nullptr; }
+      const bool rot = w.rot4 && c->qkv_fused, split = c->planes_mode != 0;
+      if (c->prep_fused) { p.rot4 = rot ? w.rot4 : nullptr; p.desc_p = split ? w.desc_p : nullptr; }
       launch_prep(p, s);
-      if (rot && !p.rot4) launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, s);
-      if (split && !p.desc_p) launch_split_hm16(c->desc, c->desc_p, T, kInDim, 1.0f, s);
-      GemmArgs g = gemm_args(c->desc, kInDim, c->input_proj, c->x, kDim, T);
+      if (rot && !p.rot4) launch_rot_table(w.cos_t, w.sin_t, w.rot4, T, (long long)c->Tmax, s);
+      if (split && !p.desc_p) launch_split_hm16(w.desc, w.desc_p, T, kInDim, 1.0f, s);
+      GemmArgs g = gemm_args(w.desc, kInDim, c->input_proj, w.x, kDim, T);
       g.drop_f32 = planes_only ? 1 : 0;
-      gemm(c, EPI_BIAS, g, s);
+      gemm(c, w, EPI_BIAS, g, s);
     }
   }
   // the call's lists of tiles / query blocks that hold valid tokens (k_prep has written the per-slot counts)
-  if (c->use_lists && c->lists) {
-    const int g = (int)(c->ovf - c->ovf_base);
-    launch_tile_lists(c->nvalid, BS, np, c->lists, (c->tile_feedback && g >= 0 && g < 8) ? c->tile_feedback + g : nullptr, s);
+  if (c->use_lists && w.lists) {
+    launch_tile_lists(w.nvalid, BS, np, w.lists, c->tile_feedback ? c->tile_feedback + w.g : nullptr, s);
   }
   // point pruning: ind = arange, prune = ones behind k_prep's counts; then one k_prune + list rebuild behind every cross block but the last
-  const bool pruning = c->width_conf > 0.f && c->pr_ind != nullptr;
+  const bool pruning = c->width_conf > 0.f && w.pr_ind != nullptr;
   c->prune_last_on = pruning; c->prune_last_np = np; c->prune_last_layers = c->n_layers;
   if (!c->in_group) c->prune_last_B = B;      // (a sub-batch group sees its own share: estimate_call records the call's)
-  if (pruning) launch_prune_init(c->pr_ind, c->pr_prune, c->pr_nin, c->nvalid, BS, np, s);
+  if (pruning) launch_prune_init(w.pr_ind, w.pr_prune, w.pr_nin, w.nvalid, BS, np, s);
   bool qkv_done = false;      // the previous tail has already computed this block's attention input projection
   for (int i = 0; i < c->n_layers; ++i) {
     {  // SelfBlock on both sides at once
       const Block& blk = c->self_blk[i];
       if (!qkv_done) {
         StageTimer tm(c, s, ST_PROJ);
-        GemmArgs g = gemm_args(c->x, kDim, blk.proj_in, c->qkv, 3 * kDim, T);
-        g.cos_t = c->cos_t; g.sin_t = c->sin_t; g.rot_cols = 2 * kDim;
-        if (bf16v2 && qkv_projection(c, blk, false, T, np, vt_perm, s)) {
+        GemmArgs g = gemm_args(w.x, kDim, blk.proj_in, w.qkv, 3 * kDim, T);
+        g.cos_t = w.cos_t; g.sin_t = w.sin_t; g.rot_cols = 2 * kDim;
+        if (bf16v2 && qkv_projection(c, w, blk, false, T, np, vt_perm, s)) {
         } else if (bf16v2) {
-          g.Yb = c->qkb; g.ldyb = 2 * kDim; g.Vt = c->vtb; g.vt_start = 2 * kDim; g.q_cols = kDim; g.qscale = 0.125f; g.npad = np; g.vt_perm = vt_perm; g.half_fmt = c->attn_f16;
-          gemm(c, EPI_ROTARY_BF16, g, s);
+          g.Yb = w.qkb; g.ldyb = 2 * kDim; g.Vt = w.vtb; g.vt_start = 2 * kDim; g.q_cols = kDim; g.qscale = 0.125f; g.npad = np; g.vt_perm = vt_perm; g.half_fmt = c->attn_f16;
+          gemm(c, w, EPI_ROTARY_BF16, g, s);
         } else {
-          gemm(c, EPI_ROTARY, g, s);
+          gemm(c, w, EPI_ROTARY, g, s);
         }
       }
       {
         StageTimer tm(c, s, ST_ATTN);
         AttnArgs a; a.ovf = nullptr;
-        a.q = c->qkv; a.ldq = 3 * kDim; a.k = c->qkv + kDim; a.ldk = 3 * kDim; a.v = c->qkv + 2 * kDim; a.ldv = 3 * kDim;
-        a.out = c->ctx; a.ldo = kDim; a.nvalid = c->nvalid; a.npad = np; a.cross = 0; a.qscale = 0.125f; a.BS = BS;
-        a.outp = attn_planes ? c->ctx_p : nullptr; a.ovf = (attn_planes && c->guard) ? c->ovf : nullptr;
-        a.qb = c->qkb; a.ldqb = 2 * kDim; a.kb = c->qkb + kDim; a.ldkb = 2 * kDim; a.vt = c->vtb; a.half_fmt = c->attn_f16; a.tiles = (c->use_lists && c->lists) ? c->lists : nullptr; a.ncu = c->ncu;
+        a.q = w.qkv; a.ldq = 3 * kDim; a.k = w.qkv + kDim; a.ldk = 3 * kDim; a.v = w.qkv + 2 * kDim; a.ldv = 3 * kDim;
+        a.out = w.ctx; a.ldo = kDim; a.nvalid = w.nvalid; a.npad = np; a.cross = 0; a.qscale = 0.125f; a.BS = BS;
+        a.outp = attn_planes ? w.ctx_p : nullptr; a.ovf = (attn_planes && c->guard) ? w.ovf : nullptr;
+        a.qb = w.qkb; a.ldqb = 2 * kDim; a.kb = w.qkb + kDim; a.ldkb = 2 * kDim; a.vt = w.vtb; a.half_fmt = c->attn_f16; a.tiles = (c->use_lists && w.lists) ? w.lists : nullptr; a.ncu = c->ncu;
         if (bf16v2) attn_split(c, a);
         timed_attention(c, a, bf16v2, s);
-        if (c->planes_mode && !attn_planes) launch_split_hm16(c->ctx, c->ctx_p, T, kDim, 1.0f, s);
+        if (c->planes_mode && !attn_planes) launch_split_hm16(w.ctx, w.ctx_p, T, kDim, 1.0f, s);
       }
       if (!tail_folds_out_proj(c, blk, T)) {
         StageTimer tm(c, s, ST_PROJ);
-        GemmArgs g = gemm_args(c->ctx, kDim, blk.proj_out, c->msg, kDim, T);
-        gemm(c, EPI_BIAS, g, s);
+        GemmArgs g = gemm_args(w.ctx, kDim, blk.proj_out, w.msg, kDim, T);
+        gemm(c, w, EPI_BIAS, g, s);
       }
-      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, blk, T, s, false, bf16v2 ? &c->cross_blk[i] : nullptr, true, np, vt_perm); }
+      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, w, blk, T, s, false, bf16v2 ? &c->cross_blk[i] : nullptr, true, np, vt_perm); }
     }
     {  // CrossBlock
       const Block& blk = c->cross_blk[i];
       if (!qkv_done) {
         StageTimer tm(c, s, ST_PROJ);
-        GemmArgs g = gemm_args(c->x, kDim, blk.proj_in, c->qkv, 2 * kDim, T);
+        GemmArgs g = gemm_args(w.x, kDim, blk.proj_in, w.qkv, 2 * kDim, T);
         g.scale = 0.35355339059327373f;  // (dim_head ** -0.5) ** 0.5 applied to both qk sides
         g.scale_cols = kDim;
-        if (bf16v2 && qkv_projection(c, blk, true, T, np, vt_perm, s)) {
+        if (bf16v2 && qkv_projection(c, w, blk, true, T, np, vt_perm, s)) {
         } else if (bf16v2) {
-          g.Yb = c->qkb; g.ldyb = kDim; g.Vt = c->vtb; g.vt_start = kDim; g.q_cols = 0; g.qscale = 1.0f; g.npad = np; g.vt_perm = vt_perm; g.half_fmt = c->attn_f16;
-          gemm(c, EPI_SCALE_BF16, g, s);
+          g.Yb = w.qkb; g.ldyb = kDim; g.Vt = w.vtb; g.vt_start = kDim; g.q_cols = 0; g.qscale = 1.0f; g.npad = np; g.vt_perm = vt_perm; g.half_fmt = c->attn_f16;
+          gemm(c, w, EPI_SCALE_BF16, g, s);
         } else {
-          gemm(c, EPI_SCALE_COLS, g, s);
+          gemm(c, w, EPI_SCALE_COLS, g, s);
         }
       }
       {
         StageTimer tm(c, s, ST_ATTN);
         AttnArgs a; a.ovf = nullptr;
-        a.q = c->qkv; a.ldq = 2 * kDim; a.k = c->qkv; a.ldk = 2 * kDim; a.v = c->qkv + kDim; a.ldv = 2 * kDim;
-        a.out = c->ctx; a.ldo = kDim; a.nvalid = c->nvalid; a.npad = np; a.cross = 1; a.qscale = 1.0f; a.BS = BS;
-        a.outp = attn_planes ? c->ctx_p : nullptr; a.ovf = (attn_planes && c->guard) ? c->ovf : nullptr;
-        a.qb = c->qkb; a.ldqb = kDim; a.kb = c->qkb; a.ldkb = kDim; a.vt = c->vtb; a.half_fmt = c->attn_f16; a.tiles = (c->use_lists && c->lists) ? c->lists : nullptr; a.ncu = c->ncu;
+        a.q = w.qkv; a.ldq = 2 * kDim; a.k = w.qkv; a.ldk = 2 * kDim; a.v = w.qkv + kDim; a.ldv = 2 * kDim;
+        a.out = w.ctx; a.ldo = kDim; a.nvalid = w.nvalid; a.npad = np; a.cross = 1; a.qscale = 1.0f; a.BS = BS;
+        a.outp = attn_planes ? w.ctx_p : nullptr; a.ovf = (attn_planes && c->guard) ? w.ovf : nullptr;
+        a.qb = w.qkb; a.ldqb = kDim; a.kb = w.qkb; a.ldkb = kDim; a.vt = w.vtb; a.half_fmt = c->attn_f16; a.tiles = (c->use_lists && w.lists) ? w.lists : nullptr; a.ncu = c->ncu;
         if (bf16v2) attn_split(c, a);
         timed_attention(c, a, bf16v2, s);
-        if (c->planes_mode && !attn_planes) launch_split_hm16(c->ctx, c->ctx_p, T, kDim, 1.0f, s);
+        if (c->planes_mode && !attn_planes) launch_split_hm16(w.ctx, w.ctx_p, T, kDim, 1.0f, s);
       }
       if (!tail_folds_out_proj(c, blk, T)) {
         StageTimer tm(c, s, ST_PROJ);
-        GemmArgs g = gemm_args(c->ctx, kDim, blk.proj_out, c->msg, kDim, T);
-        gemm(c, EPI_BIAS, g, s);
+        GemmArgs g = gemm_args(w.ctx, kDim, blk.proj_out, w.msg, kDim, T);
+        gemm(c, w, EPI_BIAS, g, s);
       }
       // (pruning: the next self block's projection must see the pruned rows, so the cross tail does not fuse it)
-      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, blk, T, s, i == c->n_layers - 1, (bf16v2 && i + 1 < c->n_layers && !pruning) ? &c->self_blk[i + 1] : nullptr, false, np, vt_perm); }   // the last block leaves f32 x for the match head
+      { StageTimer tm(c, s, ST_FFN); qkv_done = ffn(c, w, blk, T, s, i == c->n_layers - 1, (bf16v2 && i + 1 < c->n_layers && !pruning) ? &c->self_blk[i + 1] : nullptr, false, np, vt_perm); }   // the last block leaves f32 x for the match head
       if (pruning && i + 1 < c->n_layers && !(c->stop_after && c->launch_count >= c->stop_after)) {
         StageTimer tm(c, s, ST_PREP);
         const bool planes_only = c->planes_mode && c->x_planes_only;
         PruneArgs pa;
-        pa.x = planes_only ? nullptr : c->x; pa.xp = c->planes_mode ? c->x_p : nullptr; pa.z_from_planes = planes_only ? 1 : 0;
-        pa.cos_t = c->cos_t; pa.sin_t = c->sin_t; pa.rot4 = c->rot4; pa.rot_stride = (long long)c->Tmax;
-        pa.ind = c->pr_ind; pa.prune = c->pr_prune; pa.dst = c->pr_dst; pa.nvalid = c->nvalid; pa.counts = c->pr_counts; pa.layer = i; pa.z = c->pr_z;
+        pa.x = planes_only ? nullptr : w.x; pa.xp = c->planes_mode ? w.x_p : nullptr; pa.z_from_planes = planes_only ? 1 : 0;
+        pa.cos_t = w.cos_t; pa.sin_t = w.sin_t; pa.rot4 = w.rot4; pa.rot_stride = (long long)c->Tmax;
+        pa.ind = w.pr_ind; pa.prune = w.pr_prune; pa.dst = w.pr_dst; pa.nvalid = w.nvalid; pa.counts = w.pr_counts; pa.layer = i; pa.z = w.pr_z;
         pa.w = c->matchability[i].w; pa.b = c->matchability[i].b; pa.thresh = 1.0f - c->width_conf; pa.min_kpts = c->prune_min_kpts; pa.BS = BS; pa.npad = np;
         // (bytes: every row read once for z; the moved rows are counted as all of them, read and written)
         timed_launch(c, s, 0, 2.0 * T * kDim, (double)T * (pa.x ? 3.0 : 0.0) * 4.0 * kDim + (double)T * (pa.xp ? 3.0 : 0.0) * 4.0 * kDim, "k_prune", [&] { launch_prune(pa, s); });
-        if (c->use_lists && c->lists) launch_tile_lists(c->nvalid, BS, np, c->lists, nullptr, s);
+        if (c->use_lists && w.lists) launch_tile_lists(w.nvalid, BS, np, w.lists, nullptr, s);
       }
     }
   }
   {
     StageTimer tm(c, s, ST_HEAD);
     const int li = c->n_layers - 1;
-    GemmArgs g = gemm_args(c->x, kDim, c->final_proj[li], c->md, kDim, T);
+    GemmArgs g = gemm_args(w.x, kDim, c->final_proj[li], w.md, kDim, T);
     g.scale = 0.25f; g.scale_cols = kDim;  // / d ** 0.25
-    gemm(c, EPI_SCALE_COLS, g, s);
-    launch_matchability(c->x, c->matchability[li].w, c->matchability[li].b, c->ls, T, s);
+    gemm(c, w, EPI_SCALE_COLS, g, s);
+    launch_matchability(w.x, c->matchability[li].w, c->matchability[li].b, w.ls, T, s);
     HeadArgs hd;
-    hd.n_in = pruning ? c->pr_nin : nullptr;
-    hd.sim = c->sim; hd.ls = c->ls; hd.nvalid = c->nvalid; hd.B = B; hd.npad = np; hd.threshold = c->threshold;
-    hd.rowmax = c->rowmax; hd.rowlog = c->rowlog; hd.colmax = c->colmax; hd.collog = c->collog;
-    hd.m0 = c->m0; hd.max0 = c->max0; hd.m1 = c->m1;
-    hd.ovf = (c->planes_mode && c->guard) ? c->ovf : nullptr;
-    hd.max0b = c->max0b; hd.rpart_c = c->rpart_c; hd.uncert = c->certify ? c->uncert : nullptr;
+    hd.n_in = pruning ? w.pr_nin : nullptr;
+    hd.sim = w.sim; hd.ls = w.ls; hd.nvalid = w.nvalid; hd.B = B; hd.npad = np; hd.threshold = c->threshold;
+    hd.rowmax = w.rowmax; hd.rowlog = w.rowlog; hd.colmax = w.colmax; hd.collog = w.collog;
+    hd.m0 = w.m0; hd.max0 = w.max0; hd.m1 = w.m1;
+    hd.ovf = (c->planes_mode && c->guard) ? w.ovf : nullptr;
+    hd.max0b = w.max0b; hd.rpart_c = w.rpart_c; hd.uncert = c->certify ? w.uncert : nullptr;
     hd.cert_eps = (c->precision == GN_PREC_F32) ? c->cert_eps_f32 : cert_eps_now(c);
     if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) {
-      hd.uncert_alt = c->uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
-      hd.uncert_alt2 = c->uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
+      hd.uncert_alt = w.uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
+      hd.uncert_alt2 = w.uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
     }
     hd.idx = v.idx; hd.score = v.score; hd.n_match = v.n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
-    hd.md = c->planes_mode ? (const void*)c->md_p : (const void*)c->md; hd.md_f32 = c->planes_mode ? 0 : 1;
-    hd.cpart_m = c->cpart_m; hd.cpart_s = c->cpart_s; hd.cpart_i = c->cpart_i; hd.rpart_a = c->rpart_a; hd.rpart_b = c->rpart_b; hd.tickets = c->tickets;
-    hd.dbg_ts = (c->head_stamps && c->sim) ? reinterpret_cast<long long*>(c->sim) : nullptr;   // developer knob 17
-    if (c->cal_cols) { hd.colbest = c->colbest; hd.col2 = c->col2; }
-    if (c->head_fused || !c->sim) {   // both sweeps as one entry
+    hd.md = c->planes_mode ? (const void*)w.md_p : (const void*)w.md; hd.md_f32 = c->planes_mode ? 0 : 1;
+    hd.cpart_m = w.cpart_m; hd.cpart_s = w.cpart_s; hd.cpart_i = w.cpart_i; hd.rpart_a = w.rpart_a; hd.rpart_b = w.rpart_b; hd.tickets = w.tickets;
+    hd.dbg_ts = (c->head_stamps && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 17
+    if (c->cal_cols) { hd.colbest = w.colbest; hd.col2 = w.col2; }
+    if (c->head_fused || !w.sim) {   // both sweeps as one entry
       timed_launch(c, s, 0, 2.0 * 2.0 * B * (double)np * np * kDim,                         // the similarity tiles are computed twice
                    2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0,            // descriptors once per sweep, per-row / per-column statistics, matches
                    "k_head_fused (2 sweeps)", [&] { launch_match_head_fused(hd, s); });
-      if (pruning) launch_unprune_idx(v.idx, v.n_match, c->pr_ind, B, np, c->npad, s);
+      if (pruning) launch_unprune_idx(v.idx, v.n_match, w.pr_ind, B, np, c->npad, s);
       return GN_OK;
     }
     GemmArgs gs;
     memset(&gs, 0, sizeof gs);
-    gs.A = c->md; gs.lda = kDim; gs.K1 = kDim; gs.W = c->md + (size_t)np * kDim; gs.ldw = kDim;
-    gs.Y = c->sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kDim; gs.acc_scale = 1.f;
+    gs.A = w.md; gs.lda = kDim; gs.K1 = kDim; gs.W = w.md + (size_t)np * kDim; gs.ldw = kDim;
+    gs.Y = w.sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kDim; gs.acc_scale = 1.f;
     gs.strideA = gs.strideW = 2LL * np * kDim; gs.strideY = (long long)np * np;
-    timed_gemm(c, EPI_PLAIN, gs, B, s);
+    timed_gemm(c, w, EPI_PLAIN, gs, B, s);
     launch_match_head(hd, s);
-    if (pruning) launch_unprune_idx(v.idx, v.n_match, c->pr_ind, B, np, c->npad, s);
+    if (pruning) launch_unprune_idx(v.idx, v.n_match, w.pr_ind, B, np, c->npad, s);
   }
   return GN_OK;
+}
+
+// The workspaces that exist `when` (a mask of kWs*), at the context's npad: max_batch x (elements per pair)
+int alloc_workspaces(gn_ctx* ctx, int when) {
+  int rc = GN_OK;
+  for_each_workspace(ctx->ws, ctx->npad, ctx->npad, false, [&](auto*& p, long long per_pair, int exists, const char*) {
+    if (rc == GN_OK && (exists & when)) rc = ws_alloc(ctx, &p, (size_t)ctx->max_batch * per_pair);
+  });
+  return rc;
+}
+
+// The [B][npad][npad] similarity buffer is no longer part of the matcher (fused match head): it exists only for TwistNode's
+// brute-force matcher, the unfused developer path and the phase-stamp tools, and is allocated on their first use.
+int ensure_sim(gn_ctx* ctx) { return ctx->ws.sim ? GN_OK : alloc_workspaces(ctx, kWsFirstUse); }
+
+// The view of the pairs from b0 on, for sub-batch group g (the whole context: b0 = 0, g = 0).  Kernels capture pointer values at launch, so a
+// group simply runs the ordinary path on its view.  (A null context gives an empty view: the entry points' argument checks refuse it.)
+View view_of(const gn_ctx* c, long long b0 = 0, int g = 0) {
+  View v;
+  if (!c) return v;
+  static_cast<Workspace&>(v) = c->ws;
+  v.b0 = b0; v.g = g; v.ovf = c->ovf_base + g;
+  if (b0 != 0) for_each_workspace(v, c->npad_run, c->npad, true, [&](auto*& p, long long per_pair, int, const char*) { if (p) p += b0 * per_pair; });
+  return v;
 }
 
 int alloc_workspace(gn_ctx* ctx, int max_kpts) {
   ctx->npad = ((max_kpts + 127) / 128) * 128;
   ctx->npad_run = ctx->npad;
   const size_t np = ctx->npad, T = (size_t)ctx->max_batch * 2 * np, B = ctx->max_batch;
-#define GN_ALLOC(field, count)                                     \
-  do { int rc_ = ws_alloc(ctx, &ctx->field, (count)); if (rc_ != GN_OK) return rc_; } while (0)
-  GN_ALLOC(desc, T * kInDim); GN_ALLOC(cos_t, T * kFreq); GN_ALLOC(sin_t, T * kFreq);
-  GN_ALLOC(extent, B * 4); GN_ALLOC(nvalid, B * 2);
-  GN_ALLOC(x, T * kDim); GN_ALLOC(qkv, T * 3 * kDim); GN_ALLOC(ctx, T * kDim); GN_ALLOC(msg, T * kDim);
-  GN_ALLOC(h, T * 2 * kDim); GN_ALLOC(md, T * kDim); GN_ALLOC(ls, T);
+  ctx->ws = Workspace();
   ctx->Tmax = T;
-  if (ctx->precision == GN_PREC_F16X2_BF16_ATTN) {
-    ctx->planes_mode = 1;
-    GN_ALLOC(desc_p, 2 * T * kInDim); GN_ALLOC(x_p, 2 * T * kDim); GN_ALLOC(ctx_p, 2 * T * kDim);
-    GN_ALLOC(msg_p, 2 * T * kDim); GN_ALLOC(h_p, 2 * T * 2 * kDim); GN_ALLOC(md_p, 2 * T * kDim);
-    GN_ALLOC(rot4, T * 2 * kFreq);
-  }
-  if (ctx->precision != GN_PREC_F32) { GN_ALLOC(qkb, T * 2 * kDim); GN_ALLOC(vtb, T * kDim); GN_ALLOC(attn_part, (size_t)256 * 4 * 34 * 64); GN_ALLOC(attn_tickets, 256); }
-  GN_ALLOC(rowmax, B * np); GN_ALLOC(rowlog, B * np); GN_ALLOC(colmax, B * np); GN_ALLOC(collog, B * np);
-  GN_ALLOC(max0, B * np); GN_ALLOC(m0, B * np); GN_ALLOC(m1, B * np); GN_ALLOC(max0b, B * np); GN_ALLOC(rpart_c, B * 8 * np); GN_ALLOC(uncert, B); GN_ALLOC(uncert_alt, B); GN_ALLOC(uncert_alt2, B);
-  GN_ALLOC(colbest, B * np); GN_ALLOC(col2, B * np);
-  GN_ALLOC(cpart_m, B * (np / 32) * np); GN_ALLOC(cpart_s, B * (np / 32) * np); GN_ALLOC(cpart_i, B * (np / 32) * np); GN_ALLOC(rpart_a, B * 8 * np); GN_ALLOC(rpart_b, B * 8 * np); GN_ALLOC(tickets, B * 2);
-  GN_ALLOC(e_idx, B * np * 2); GN_ALLOC(e_score, B * np); GN_ALLOC(e_mkp, B * np * 2); GN_ALLOC(e_obj, B * np * 3);
-  GN_ALLOC(vo_norm2, T); GN_ALLOC(vo_nn_idx, B * np * 2); GN_ALLOC(vo_nn_dist, B * np * 2); GN_ALLOC(vo_good, B * np);
-  GN_ALLOC(mask_ws, B * np * 16);
-  GN_ALLOC(pts_ws, B * np * 5);
-  GN_ALLOC(hyp_ws, B * 16);
-  GN_ALLOC(rmask_ws, B * np * (gn::kRansacRound + 1)); GN_ALLOC(rstate_ws, B);
-  ctx->rstate_base = ctx->rstate_ws; ctx->last_pnp_valid = false;
-  GN_ALLOC(ovf_base, 16);
-  ctx->ovf = ctx->ovf_base;
-  ctx->lists_stride = gn::kTileListBase + 2 * (np / 128) + 8 * ((np + 255) / 256);
-  GN_ALLOC(lists, B * (size_t)ctx->lists_stride);
-  GN_ALLOC(pr_ind, T); GN_ALLOC(pr_prune, T); GN_ALLOC(pr_dst, T); GN_ALLOC(pr_counts, B * 2 * kMaxLayers); GN_ALLOC(pr_nin, B * 2); GN_ALLOC(pr_z, T);
+  if (ctx->precision == GN_PREC_F16X2_BF16_ATTN) ctx->planes_mode = 1;
+  int rc = alloc_workspaces(ctx, kWsAlways | (ctx->planes_mode ? kWsF16x2 : 0) | (ctx->precision != GN_PREC_F32 ? kWsNotF32 : 0) | (ctx->s_pnp ? kWsPnpStage : 0));
+  // not per pair: the split-keys attention's partial results, TwistNode's matcher, the guard words
+  if (rc == GN_OK && ctx->precision != GN_PREC_F32) rc = ws_alloc(ctx, &ctx->attn_part, (size_t)256 * 4 * 34 * 64);
+  if (rc == GN_OK && ctx->precision != GN_PREC_F32) rc = ws_alloc(ctx, &ctx->attn_tickets, 256);
+  if (rc == GN_OK) rc = ws_alloc(ctx, &ctx->vo_norm2, T);
+  if (rc == GN_OK) rc = ws_alloc(ctx, &ctx->vo_nn_idx, B * np * 2);
+  if (rc == GN_OK) rc = ws_alloc(ctx, &ctx->vo_nn_dist, B * np * 2);
+  if (rc == GN_OK) rc = ws_alloc(ctx, &ctx->vo_good, B * np);
+  if (rc == GN_OK) rc = ws_alloc(ctx, &ctx->ovf_base, 16);
+  ctx->last_pnp_valid = false;
   ctx->prune_last_np = 0; ctx->prune_last_B = 0; ctx->prune_last_on = false;      // gn_get_prune: no matcher call yet on these workspaces
-#undef GN_ALLOC
-  return GN_OK;
+  return rc;
 }
-
-void shift_workspaces(gn_ctx* c, long long b0, int sign);
 
 // words of two device arrays that differ (16-byte granules; one atomic per wave that saw a difference)
 __global__ void k_count_diff(const uint4* a, const uint4* b, size_t n, unsigned int* cnt) {
@@ -915,13 +949,14 @@ __global__ void k_count_diff(const uint4* a, const uint4* b, size_t n, unsigned 
 // at the full padded size (the smallest bulk grid there) whatever gn_set_active_kpts has set: ffn() lays the rows out at npad_run.
 int selfcheck_fused_projection(gn_ctx* c) {
   gn_ctx* ctx = c;
+  const View w = view_of(c);             // the workspaces as allocated
   c->fused_proj_pending = false;
   c->fused_proj_status = -1;
   c->fused_proj_off = 0;
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
   if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
-      !c->qkv_fused || !c->rot4 || !c->lists || !c->msg_p || !c->h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || gn::g_ffn_shape != 0) return GN_OK;
+      !c->qkv_fused || !w.rot4 || !w.lists || !w.msg_p || !w.h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || gn::g_ffn_shape != 0) return GN_OK;
   int B = (256 * 128 + 2 * np - 1) / (2 * np);          // the smallest batch whose grid selects k_ffn128 (>= 256 tiles of 128 tokens)
   if (B > c->max_batch) return GN_OK;                   // this context never runs the bulk kernels
   const int T = B * 2 * np;
@@ -930,24 +965,24 @@ int selfcheck_fused_projection(gn_ctx* c) {
   auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (float)((st >> 40) & 0xFFFF) * (1.0f / 32768.0f) - 1.0f; };   // U(-1, 1), 16 bits
   for (int pass = 0; pass < 2; ++pass) {
     for (auto& v : h) v = 1.5f * rnd();
-    float* dst = pass == 0 ? c->x : c->ctx;
+    float* dst = pass == 0 ? w.x : w.ctx;
     GN_HIP(hipMemcpy(dst, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    launch_split_hm16(dst, pass == 0 ? c->x_p : c->ctx_p, T, kDim, 1.0f, 0);
+    launch_split_hm16(dst, pass == 0 ? w.x_p : w.ctx_p, T, kDim, 1.0f, 0);
   }
   {
     std::vector<float> cs((size_t)T * kFreq), sn((size_t)T * kFreq);
     for (size_t i = 0; i < cs.size(); ++i) { const float th = 3.14159265f * rnd(); cs[i] = cosf(th); sn[i] = sinf(th); }
-    GN_HIP(hipMemcpy(c->cos_t, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
-    GN_HIP(hipMemcpy(c->sin_t, sn.data(), sn.size() * sizeof(float), hipMemcpyHostToDevice));
-    launch_rot_table(c->cos_t, c->sin_t, c->rot4, T, (long long)c->Tmax, 0);
+    GN_HIP(hipMemcpy(w.cos_t, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
+    GN_HIP(hipMemcpy(w.sin_t, sn.data(), sn.size() * sizeof(float), hipMemcpyHostToDevice));
+    launch_rot_table(w.cos_t, w.sin_t, w.rot4, T, (long long)c->Tmax, 0);
     std::vector<int32_t> nv(2 * (size_t)B, np);
-    GN_HIP(hipMemcpy(c->nvalid, nv.data(), nv.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    launch_tile_lists(c->nvalid, 2 * B, np, c->lists, nullptr, 0);
+    GN_HIP(hipMemcpy(w.nvalid, nv.data(), nv.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    launch_tile_lists(w.nvalid, 2 * B, np, w.lists, nullptr, 0);
   }
   const size_t xbytes = (size_t)T * kDim * 4, qbytes = (size_t)T * 2 * kDim * 2, vbytes = (size_t)T * kDim * 2;
-  uint16_t* const keep_q = c->h_p;                                      // (k_ffn128 never writes the hidden tensor to memory: h_p is free scratch, 2 KB per token)
-  uint16_t* const keep_v = c->h_p + (size_t)T * 2 * kDim;
-  GN_HIP(hipMemcpy(c->msg_p, c->x_p, xbytes, hipMemcpyDeviceToDevice));  // the rows every run starts from (the tail updates x_p in place)
+  uint16_t* const keep_q = w.h_p;                                      // (k_ffn128 never writes the hidden tensor to memory: h_p is free scratch, 2 KB per token)
+  uint16_t* const keep_v = w.h_p + (size_t)T * 2 * kDim;
+  GN_HIP(hipMemcpy(w.msg_p, w.x_p, xbytes, hipMemcpyDeviceToDevice));  // the rows every run starts from (the tail updates x_p in place)
   unsigned int* cnt = c->ovf_base + 12;                                 // (words 9..15 of the guard block are unused)
   GN_HIP(hipMemset(cnt, 0, sizeof(unsigned int)));
   bool applicable = true;
@@ -965,27 +1000,27 @@ int selfcheck_fused_projection(gn_ctx* c) {
         const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
         const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
         c->use_lists = walk ? 2 : 3;
-        GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
-        GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
+        GN_HIP(hipMemcpyAsync(w.x_p, w.msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemsetAsync(w.qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(w.vtb, 0, vbytes, 0));
         c->qkv_in_tail = 1;
-        if (!ffn(c, tail, T, 0, false, next, cross != 0, np, 1)) { applicable = false; break; }
-        GN_HIP(hipMemcpyAsync(keep_q, c->qkb, qbytes, hipMemcpyDeviceToDevice, 0));
-        GN_HIP(hipMemcpyAsync(keep_v, c->vtb, vbytes, hipMemcpyDeviceToDevice, 0));
-        GN_HIP(hipMemcpyAsync(c->x_p, c->msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
-        GN_HIP(hipMemsetAsync(c->qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(c->vtb, 0, vbytes, 0));
+        if (!ffn(c, w, tail, T, 0, false, next, cross != 0, np, 1)) { applicable = false; break; }
+        GN_HIP(hipMemcpyAsync(keep_q, w.qkb, qbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemcpyAsync(keep_v, w.vtb, vbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemcpyAsync(w.x_p, w.msg_p, xbytes, hipMemcpyDeviceToDevice, 0));
+        GN_HIP(hipMemsetAsync(w.qkb, 0, qbytes, 0)); GN_HIP(hipMemsetAsync(w.vtb, 0, vbytes, 0));
         c->qkv_in_tail = 0;
-        ffn(c, tail, T, 0, false, next, cross != 0, np, 1);
-        if (!qkv_projection(c, *next, cross != 0, T, np, 1, 0)) { applicable = false; break; }
-        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_q), reinterpret_cast<const uint4*>(c->qkb), (cross ? qbytes / 2 : qbytes) / 16, cnt);
-        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_v), reinterpret_cast<const uint4*>(c->vtb), vbytes / 16, cnt);
+        ffn(c, w, tail, T, 0, false, next, cross != 0, np, 1);
+        if (!qkv_projection(c, w, *next, cross != 0, T, np, 1, 0)) { applicable = false; break; }
+        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_q), reinterpret_cast<const uint4*>(w.qkb), (cross ? qbytes / 2 : qbytes) / 16, cnt);
+        hipLaunchKernelGGL(k_count_diff, dim3(1024), dim3(256), 0, 0, reinterpret_cast<const uint4*>(keep_v), reinterpret_cast<const uint4*>(w.vtb), vbytes / 16, cnt);
       }
   }
   unsigned int diffs = 0;
   GN_HIP(hipStreamSynchronize(0));
   GN_HIP(hipMemcpy(&diffs, cnt, sizeof diffs, hipMemcpyDeviceToHost));
   // leave the workspaces as a fresh context has them
-  GN_HIP(hipMemset(c->x_p, 0, xbytes)); GN_HIP(hipMemset(c->ctx_p, 0, xbytes)); GN_HIP(hipMemset(c->msg_p, 0, xbytes)); GN_HIP(hipMemset(c->h_p, 0, qbytes + vbytes));
-  GN_HIP(hipMemset(c->qkb, 0, qbytes)); GN_HIP(hipMemset(c->vtb, 0, vbytes)); GN_HIP(hipMemset(c->x, 0, xbytes)); GN_HIP(hipMemset(c->ctx, 0, xbytes));
+  GN_HIP(hipMemset(w.x_p, 0, xbytes)); GN_HIP(hipMemset(w.ctx_p, 0, xbytes)); GN_HIP(hipMemset(w.msg_p, 0, xbytes)); GN_HIP(hipMemset(w.h_p, 0, qbytes + vbytes));
+  GN_HIP(hipMemset(w.qkb, 0, qbytes)); GN_HIP(hipMemset(w.vtb, 0, vbytes)); GN_HIP(hipMemset(w.x, 0, xbytes)); GN_HIP(hipMemset(w.ctx, 0, xbytes));
   GN_HIP(hipMemset(cnt, 0, sizeof(unsigned int)));
   if (!applicable) return GN_OK;
   c->fused_proj_status = diffs == 0 ? 1 : 0;
@@ -1054,7 +1089,7 @@ inline bool ladder_active(const gn_ctx* c) { return c->ladder && c->cert_eps_mid
 
 // The flagged pairs `flagged` (ascending) of call v again, through `run(call)` = matcher (+ gather + PnP), in whatever arithmetic the caller has
 // switched the context to; rflags[k] = the re-run's own certificate flag of flagged[k].  One contiguous run of flagged pairs is re-run IN PLACE
-// (pointers and per-pair workspaces moved to its first pair).  Scattered flagged pairs are GATHERED into a staging block first (device-to-device
+// (the call sliced at its first pair, on the view of the workspaces from that pair on).  Scattered flagged pairs are GATHERED into a staging block first (device-to-device
 // copies of their inputs), run as ONE batch on workspace slots 0 .. nf - 1, and their outputs scattered back: a batched f32 call costs ~0.8 ms per
 // pair where one- and two-pair calls cost 1.7 / 1.2 (round 6: mid-margin weights 1.26 k -> 1.9 k certified pairs/s).
 template <typename F> int rerun_pairs(gn_ctx* ctx, hipStream_t s, const Call& v, F& run, const std::vector<int>& flagged, std::vector<int32_t>& rflags) {
@@ -1093,21 +1128,15 @@ template <typename F> int rerun_pairs(gn_ctx* ctx, hipStream_t s, const Call& v,
   if (!contiguous)
     for (int k = 0; k < nf; ++k) GN_HIP(copy_pair(st, k, v, flagged[k], false));      // gather the inputs of flagged pair k into slot k
   {
-    const Restore keep(ctx->cert_inner, ctx->in_group, ctx->ovf);
-    ctx->cert_inner = true; ctx->in_group = true; ctx->ovf = ctx->ovf_base;
-    if (contiguous) {
-      const int b0 = flagged.front();
-      shift_workspaces(ctx, b0, +1);
-      rc = run(slice(v, b0, nf));
-      shift_workspaces(ctx, b0, -1);
-    } else {
-      rc = run(st);
-    }
+    const Restore keep(ctx->cert_inner, ctx->in_group);
+    ctx->cert_inner = true; ctx->in_group = true;
+    // (guard word 0 either way)
+    rc = contiguous ? run(view_of(ctx, flagged.front()), slice(v, flagged.front(), nf)) : run(view_of(ctx), st);
   }
   if (rc != GN_OK) return rc;
   if (!contiguous)
     for (int k = 0; k < nf; ++k) GN_HIP(copy_pair(v, flagged[k], st, k, true));       // scatter the outputs of slot k to flagged pair k
-  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->ws.uncert, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   GN_HIP(hipStreamSynchronize(s));
   rflags.resize(nf);
   for (int k = 0; k < nf; ++k) rflags[k] = ctx->uncert_host[contiguous ? flagged[k] : k];
@@ -1121,10 +1150,10 @@ template <typename F> int rerun_pairs(gn_ctx* ctx, hipStream_t s, const Call& v,
 template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& v, F&& run, const int32_t* flags_ready = nullptr, int flags_level = 0) {
   const int B = v.B;
   if (!flags_ready) {
-    GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->ws.uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (ffn_auto(ctx)) {
-      GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      GN_HIP(hipMemcpyAsync(ctx->uncert_host + 2 * ctx->max_batch, ctx->uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->ws.uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(ctx->uncert_host + 2 * ctx->max_batch, ctx->ws.uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
     GN_HIP(hipStreamSynchronize(s));
     flags_ready = ctx->uncert_host;
@@ -1171,24 +1200,25 @@ template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& 
 enum { kCalExactF32 = 0, kCalMid = -1 };
 struct CalPass { std::vector<float> best, second, colbest, col2; unsigned int trip = 0u; };
 int cal_pass(gn_ctx* ctx, const Call& w, int arith, bool cols, std::vector<int32_t>* nv, CalPass& out, hipStream_t s) {
+  const View vw = view_of(ctx);
   int rc = GN_OK;
   {
     const Restore keep(ctx->in_group, ctx->cal_cols, ctx->ffn_products);
     ctx->in_group = true;       // (no nested certification, ovf_groups_last untouched)
     ctx->cal_cols = cols;
-    if (arith == kCalExactF32) { const ExactF32 f32(ctx); rc = run_matcher(ctx, w, s); }
-    else if (arith == kCalMid) { const MidLevel mid(ctx); rc = run_matcher(ctx, w, s); }
-    else { ctx->ffn_products = arith; rc = run_matcher(ctx, w, s); }
+    if (arith == kCalExactF32) { const ExactF32 f32(ctx); rc = run_matcher(ctx, vw, w, s); }
+    else if (arith == kCalMid) { const MidLevel mid(ctx); rc = run_matcher(ctx, vw, w, s); }
+    else { ctx->ffn_products = arith; rc = run_matcher(ctx, vw, w, s); }
   }
   if (rc != GN_OK) return rc;
   const size_t n = (size_t)w.B * ctx->npad_run;
   out.best.resize(n); out.second.resize(n);
   if (cols) { out.colbest.resize(n); out.col2.resize(n); }
   auto get = [&](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-  const bool ok = hipStreamSynchronize(s) == hipSuccess && get(out.best.data(), ctx->max0, n * 4) && get(out.second.data(), ctx->max0b, n * 4) &&
-                  (!nv || get(nv->data(), ctx->nvalid, nv->size() * 4)) &&
-                  (!cols || (get(out.colbest.data(), ctx->colbest, n * 4) && get(out.col2.data(), ctx->col2, n * 4))) &&
-                  (arith == kCalExactF32 || !ctx->planes_mode || !ctx->guard || get(&out.trip, ctx->ovf, 4));
+  const bool ok = hipStreamSynchronize(s) == hipSuccess && get(out.best.data(), vw.max0, n * 4) && get(out.second.data(), vw.max0b, n * 4) &&
+                  (!nv || get(nv->data(), vw.nvalid, nv->size() * 4)) &&
+                  (!cols || (get(out.colbest.data(), vw.colbest, n * 4) && get(out.col2.data(), vw.col2, n * 4))) &&
+                  (arith == kCalExactF32 || !ctx->planes_mode || !ctx->guard || get(&out.trip, vw.ovf, 4));
   return ok ? GN_OK : GN_ERR_HIP;
 }
 
@@ -1357,21 +1387,13 @@ int gn_resize(gn_ctx* ctx, int max_kpts) {
   GN_HIP(hipDeviceSynchronize());                      // nothing may still be reading the old workspaces
   for (void* p : ctx->ws_allocs) hipFree(p);
   ctx->ws_allocs.clear();
-  ctx->sim = nullptr;                                  // allocated on first use (ensure_sim), for the new size
   for (bool& b : ctx->sub_pending) b = false;
   // A failure part-way (out of memory while growing) must not leave the context pointing at freed workspaces: every entry point goes
   // through check_fwd, which refuses a context whose npad is 0 until a later gn_resize succeeds.
   auto broken = [&](int rc) { for (void* p : ctx->ws_allocs) hipFree(p); ctx->ws_allocs.clear(); ctx->npad = 0; ctx->npad_run = 0; return rc; };
+  // (sim: allocated on first use again, for the new size; the overlapped pose stage's double buffers follow the padded size too)
   { const int rc = alloc_workspace(ctx, max_kpts); if (rc != GN_OK) return broken(rc); }
-  if (ctx->s_pnp) {                                    // the overlapped pose stage's double buffers follow the padded size too
-    const size_t B = ctx->max_batch, np = ctx->npad;
-    for (int i = 0; i < 2; ++i) {
-      for (int g = 0; g < 8; ++g) ctx->pnp_pending[i][g] = false;
-      int rc = ws_alloc(ctx, &ctx->o_mkp[i], B * np * 2); if (rc != GN_OK) return broken(rc);
-      rc = ws_alloc(ctx, &ctx->o_obj[i], B * np * 3); if (rc != GN_OK) return broken(rc);
-      rc = ws_alloc(ctx, &ctx->o_nmatch[i], B); if (rc != GN_OK) return broken(rc);
-    }
-  }
+  if (ctx->s_pnp) for (auto& slot : ctx->pnp_pending) for (bool& b : slot) b = false;
   return GN_OK;
 }
 
@@ -1450,7 +1472,7 @@ int gn_get_width_pruning(const gn_ctx* ctx, float* width_confidence, int* min_kp
 
 int gn_get_prune(gn_ctx* ctx, int B, int32_t* prune_q, int32_t* prune_r) {
   if (!ctx || !prune_q || !prune_r) return fail(ctx, GN_ERR_ARG, "gn_get_prune: null pointer");
-  if (ctx->prune_last_np <= 0 || ctx->prune_last_np > ctx->npad || ctx->prune_last_B < 1 || !ctx->nvalid) return fail(ctx, GN_ERR_ARG, "gn_get_prune: no matcher call yet on these workspaces");
+  if (ctx->prune_last_np <= 0 || ctx->prune_last_np > ctx->npad || ctx->prune_last_B < 1 || !ctx->ws.nvalid) return fail(ctx, GN_ERR_ARG, "gn_get_prune: no matcher call yet on these workspaces");
   if (B < 1 || B > ctx->prune_last_B) return fail(ctx, GN_ERR_ARG, "gn_get_prune: B exceeds the pairs of the most recent matcher call");
   GN_HIP(hipSetDevice(ctx->device));
   GN_HIP(hipDeviceSynchronize());
@@ -1459,11 +1481,11 @@ int gn_get_prune(gn_ctx* ctx, int B, int32_t* prune_q, int32_t* prune_r) {
   memset(prune_q, 0, (size_t)B * km * sizeof(int32_t)); memset(prune_r, 0, (size_t)B * km * sizeof(int32_t));
   if (ctx->prune_last_on) {
     std::vector<int32_t> host((size_t)B * 2 * np);
-    GN_HIP(hipMemcpy(host.data(), ctx->pr_prune, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GN_HIP(hipMemcpy(host.data(), ctx->ws.pr_prune, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int bs = 0; bs < 2 * B; ++bs) memcpy(out[bs & 1] + (size_t)(bs >> 1) * km, host.data() + (size_t)bs * np, np * sizeof(int32_t));
   } else {      // kornia without pruning: every keypoint took part in every layer
     std::vector<int32_t> nv((size_t)B * 2);
-    GN_HIP(hipMemcpy(nv.data(), ctx->nvalid, nv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GN_HIP(hipMemcpy(nv.data(), ctx->ws.nvalid, nv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int bs = 0; bs < 2 * B; ++bs)
       for (int i = 0; i < std::min(std::max(nv[bs], 0), (int)np); ++i) out[bs & 1][(size_t)(bs >> 1) * km + i] = ctx->prune_last_layers;
   }
@@ -1577,10 +1599,12 @@ int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int
   return rc;
 }
 
-int gn_match(gn_ctx* ctx, int B, int kpt_format,
-             const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
-             const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
-             int64_t* idx, float* score, int32_t* n_match, void* stream) {
+namespace {
+// gn_match on the view vw: the whole context, or a sub-batch group's / a re-run's share of it
+int match_impl(gn_ctx* ctx, const View& vw, int B, int kpt_format,
+               const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+               const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+               int64_t* idx, float* score, int32_t* n_match, void* stream) {
   int rc = check_fwd(ctx, B, stride_q, stride_r);
   if (rc != GN_OK) return rc;
   const int kfmt = kpt_format & 0xff;
@@ -1593,27 +1617,35 @@ int gn_match(gn_ctx* ctx, int B, int kpt_format,
   if (!ctx->in_group) ctx->ovf_groups_last = 1;
   Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
   v.idx = idx; v.score = score; v.n_match = n_match;
-  rc = run_matcher(ctx, v, s);
+  rc = run_matcher(ctx, vw, v, s);
   if (rc != GN_OK) return rc;
   if (ctx->certify >= 2 && !ctx->in_group && !ctx->cert_inner) {
     // certified mode (3 = deferred exists for gn_estimate's sub-batch-stream path only; everywhere else it is 2): read this call's per-pair flags (one stream synchronisation -- the reference's call site synchronises right after the
     // matcher anyway, pose_node.py:296-297) and run the flagged pairs again on the exact-f32 kernels; covers the fp16-range fallback too
-    rc = certify_rerun(ctx, s, v, [&](const Call& w) { return run_matcher(ctx, w, s); });
+    rc = certify_rerun(ctx, s, v, [&](const View& rw, const Call& w) { return run_matcher(ctx, rw, w, s); });
     if (rc != GN_OK) return rc;
   } else if (ctx->planes_mode && ctx->guard == 2 && ctx->certify < 2) {
     // guarded mode: observe the domain word of THIS call (one stream synchronisation -- the reference's call site synchronises
     // right after the matcher anyway, pose_node.py:296-297) and, if an activation left the fp16 range, run the call again in f32x3
-    GN_HIP(hipMemcpyAsync(ctx->ovf_host, ctx->ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(ctx->ovf_host, vw.ovf, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
     if (*ctx->ovf_host != 0u) {
       ++ctx->guard_trips;
       const F32x3 f32x3(ctx);
-      rc = run_matcher(ctx, v, s);
+      rc = run_matcher(ctx, vw, v, s);
       if (rc != GN_OK) return rc;
     }
   }
   GN_HIP(hipGetLastError());
   return GN_OK;
+}
+}  // namespace
+
+int gn_match(gn_ctx* ctx, int B, int kpt_format,
+             const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
+             const float* desc_r, const float* kpt_r, const int32_t* n_r, int stride_r,
+             int64_t* idx, float* score, int32_t* n_match, void* stream) {
+  return match_impl(ctx, view_of(ctx), B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r, idx, score, n_match, stream);
 }
 
 int gn_set_guard(gn_ctx* ctx, int mode) {
@@ -1744,7 +1776,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   int32_t* nm = nullptr;
   GN_HIP(hipMalloc((void**)&nm, (size_t)B * sizeof(int32_t)));
   Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
-  v.idx = ctx->e_idx; v.score = ctx->e_score; v.n_match = nm;
+  v.idx = ctx->ws.e_idx; v.score = ctx->ws.e_score; v.n_match = nm;
   // passes: the context's arithmetic -- on ALL THREE block-tail levels under gn_set_ffn_products(0) -- then the exact-f32 kernels
   const int setting = ctx->ffn_products;
   const int n_lv = setting == 0 ? 3 : 1;
@@ -1857,7 +1889,7 @@ int gn_get_uncertain(gn_ctx* ctx, int B, int32_t* host_flags, void* stream) {
   if (!ctx || !host_flags || B < 1 || B > ctx->max_batch) return GN_ERR_ARG;
   if (!ctx->certify) return fail(ctx, GN_ERR_ARG, "gn_get_uncertain: the certificate is off (gn_set_certify)");
   GN_HIP(hipSetDevice(ctx->device));
-  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  GN_HIP(hipMemcpyAsync(ctx->uncert_host, ctx->ws.uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
   GN_HIP(hipStreamSynchronize((hipStream_t)stream));
   memcpy(host_flags, ctx->uncert_host, (size_t)B * sizeof(int32_t));
   return GN_OK;
@@ -1884,7 +1916,7 @@ namespace {
 const double* dist_of(const gn_ctx* c) { return c && c->dist_on ? c->dist : nullptr; }
 // gn_pnp_ransac (cov, sigma_hat, cov_ok all null), gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine) and
 // gn_pnp_ransac_report (any of rep given: k_pnp_report runs last)
-int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
+int pnp_impl(gn_ctx* ctx, const View& w, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
              const double* K9, const double* dk, int iterations_count, float reproj_error_px, double confidence, int min_pts,
              double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
              const Report& rep = Report()) {
@@ -1899,16 +1931,14 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
   a.obj = obj; a.img = img; a.n_pts = n_pts; a.kstride = kstride; a.B = B;
   a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
   a.iterations = iterations_count; a.reproj = reproj_error_px; a.confidence = confidence; a.min_pts = min_pts;
-  a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = ctx->mask_ws; a.hyp = ctx->hyp_ws; a.pts_ws = ctx->pts_ws;
-  a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(ctx->sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
+  a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = w.mask_ws; a.hyp = w.hyp_ws; a.pts_ws = w.pts_ws;
+  a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
   a.sigma_px = sigma_px; a.cov = cov; a.sigma_hat = sigma_hat; a.cov_ok = cov_ok;
   a.inlier_mask = rep.inlier_mask; a.inlier_idx = rep.inlier_idx; a.reproj_err = rep.reproj_err;
   if (dk) { a.dist = 1; for (int i = 0; i < 5; ++i) a.dk[i] = dk[i]; }     // (null = off; the arguments travel by value, like fx .. cy)
-  a.rmask_ws = ctx->rmask_ws; a.rstate = ctx->rstate_ws; a.force_rounds = ctx->pnp_rounds;
-  {   // gn_ransac_last_counts: a sub-batch group's stage is the pairs [b0, b0 + B) of its call
-    const long long b0 = ctx->rstate_ws - ctx->rstate_base;
-    if (b0 == 0 || !ctx->last_pnp_valid) { ctx->last_pnp = a; ctx->last_npts = n_pts - b0; ctx->last_pnp_valid = true; }
-  }
+  a.rmask_ws = w.rmask_ws; a.rstate = w.rstate_ws; a.force_rounds = ctx->pnp_rounds;
+  // gn_ransac_last_counts: a sub-batch group's stage is the pairs [b0, b0 + B) of its call
+  if (w.b0 == 0 || !ctx->last_pnp_valid) { ctx->last_pnp = a; ctx->last_npts = n_pts - w.b0; ctx->last_pnp_valid = true; }
   StageTimer tm(ctx, (hipStream_t)stream, ST_PNP);
   launch_pnp(a, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
@@ -1919,7 +1949,7 @@ int pnp_impl(gn_ctx* ctx, int B, const float* obj, const float* img, const int32
 int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
                   const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
                   double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream) {
-  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+  return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   0.0, nullptr, nullptr, nullptr, stream);
 }
 
@@ -1928,7 +1958,7 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_pnp_ransac_cov: null covariance output");
-  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+  return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   sigma_px, cov_rt, sigma_hat, cov_ok, stream);
 }
 
@@ -1937,7 +1967,7 @@ int gn_pnp_ransac_report(gn_ctx* ctx, int B, const float* obj, const float* img,
                          double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                          double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
                          uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream) {
-  return pnp_impl(ctx, B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
+  return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
                   sigma_px, cov_rt, sigma_hat, cov_ok, stream, Report{inlier_mask, inlier_idx, reproj_err});
 }
 
@@ -1948,54 +1978,25 @@ int gn_ransac_last_counts(gn_ctx* ctx, int B, int32_t* niters_host, int32_t* eva
   GN_HIP(hipStreamSynchronize((hipStream_t)stream));
   GN_HIP(hipDeviceSynchronize());      // the stage may sit on the library's own streams (gn_set_overlap, gn_set_substreams)
   if (ctx->last_pnp.iterations <= 16 && !ctx->last_pnp.force_rounds) {
-    // a classic stage keeps no RansacState: fold what k_pnp_hyp left, for all B pairs from the unshifted workspaces
+    // a classic stage keeps no RansacState: fold what k_pnp_hyp left, for all B pairs from the workspaces as allocated
     PnpArgs a = ctx->last_pnp;
-    a.B = B; a.n_pts = ctx->last_npts; a.hyp = ctx->hyp_ws; a.rstate = ctx->rstate_base;
+    a.B = B; a.n_pts = ctx->last_npts; a.hyp = ctx->ws.hyp_ws; a.rstate = ctx->ws.rstate_ws;
     launch_pnp_counts(a, (hipStream_t)stream);
     GN_HIP(hipGetLastError());
     GN_HIP(hipStreamSynchronize((hipStream_t)stream));
   }
   std::vector<RansacState> st((size_t)B);
-  GN_HIP(hipMemcpy(st.data(), ctx->rstate_base, (size_t)B * sizeof(RansacState), hipMemcpyDeviceToHost));
+  GN_HIP(hipMemcpy(st.data(), ctx->ws.rstate_ws, (size_t)B * sizeof(RansacState), hipMemcpyDeviceToHost));
   for (int b = 0; b < B; ++b) { niters_host[b] = st[b].niters; evaluated_host[b] = st[b].evaluated; }
   return GN_OK;
 }
 
 namespace {
-// every per-pair workspace pointer of the context moved by `b0` pairs (sign = +1) and back (sign = -1): kernels capture
-// pointer values at launch, so a sub-batch group simply runs the ordinary path on its slice of the workspaces
-void shift_workspaces(gn_ctx* c, long long b0, int sign) {
-  const long long d = sign * b0, np = c->npad_run, T2 = 2 * np;
-  auto mv = [&](auto*& p, long long per_pair) { if (p) p += d * per_pair; };
-  mv(c->desc, T2 * kInDim); mv(c->cos_t, T2 * kFreq); mv(c->sin_t, T2 * kFreq); mv(c->rot4, T2 * 4); mv(c->extent, 4); mv(c->nvalid, 2);
-  mv(c->x, T2 * kDim); mv(c->qkv, T2 * 3 * kDim); mv(c->ctx, T2 * kDim); mv(c->msg, T2 * kDim); mv(c->h, T2 * 2 * kDim);
-  mv(c->md, T2 * kDim); mv(c->ls, T2); mv(c->sim, np * np);
-  mv(c->desc_p, 2 * T2 * kInDim); mv(c->x_p, 2 * T2 * kDim); mv(c->ctx_p, 2 * T2 * kDim); mv(c->msg_p, 2 * T2 * kDim);
-  mv(c->h_p, 2 * T2 * 2 * kDim); mv(c->md_p, 2 * T2 * kDim);
-  mv(c->qkb, T2 * 2 * kDim); mv(c->vtb, T2 * kDim);
-  mv(c->rowmax, np); mv(c->rowlog, np); mv(c->colmax, np); mv(c->collog, np); mv(c->max0, np); mv(c->m0, np); mv(c->m1, np);
-  mv(c->cpart_m, (np / 32) * np); mv(c->cpart_s, (np / 32) * np); mv(c->cpart_i, (np / 32) * np); mv(c->rpart_a, 8 * np); mv(c->rpart_b, 8 * np); mv(c->tickets, 2);
-  mv(c->max0b, np); mv(c->rpart_c, 8 * np); mv(c->uncert, 1); mv(c->uncert_alt, 1); mv(c->uncert_alt2, 1); mv(c->colbest, np); mv(c->col2, np);
-  // match lists and the PnP masks are strided by the context's padded maximum (gn_kmax), whatever the active size
-  const long long km = c->npad;
-  mv(c->e_idx, km * 2); mv(c->e_score, km); mv(c->e_mkp, km * 2); mv(c->e_obj, km * 3);
-  mv(c->mask_ws, km * 16); mv(c->hyp_ws, 16); mv(c->pts_ws, km * 5);
-  mv(c->rmask_ws, km * (gn::kRansacRound + 1)); mv(c->rstate_ws, 1);
-  for (int i = 0; i < 2; ++i) { mv(c->o_mkp[i], km * 2); mv(c->o_obj[i], km * 3); mv(c->o_nmatch[i], 1); }
-  mv(c->lists, c->lists_stride);
-  mv(c->pr_ind, T2); mv(c->pr_prune, T2); mv(c->pr_dst, T2); mv(c->pr_counts, 2 * kMaxLayers); mv(c->pr_nin, 2); mv(c->pr_z, T2);
-}
-
 // The PnP stream, its events and the double-buffered PnP inputs (gn_set_overlap, gn_set_substreams).
 int ensure_pnp_stage(gn_ctx* ctx) {
   if (ctx->s_pnp) return GN_OK;
   // s_pnp is what marks the stage as ready, so it is set last: a failure on the way leaves a context that tries again
-  const size_t B = ctx->max_batch, np = ctx->npad;
-  for (int i = 0; i < 2; ++i) {
-    int rc = ws_alloc(ctx, &ctx->o_mkp[i], B * np * 2); if (rc != GN_OK) return rc;
-    rc = ws_alloc(ctx, &ctx->o_obj[i], B * np * 3); if (rc != GN_OK) return rc;
-    rc = ws_alloc(ctx, &ctx->o_nmatch[i], B); if (rc != GN_OK) return rc;
-  }
+  { const int rc = alloc_workspaces(ctx, kWsPnpStage); if (rc != GN_OK) return rc; }
   auto event = [](hipEvent_t& e) { return e ? hipSuccess : hipEventCreateWithFlags(&e, hipEventDisableTiming); };
   for (int g = 0; g < 8; ++g) {
     for (int i = 0; i < 2; ++i) { GN_HIP(event(ctx->ev_gather[i][g])); GN_HIP(event(ctx->ev_pnp[i][g])); }
@@ -2026,35 +2027,37 @@ int join_internal(gn_ctx* ctx, hipStream_t s) {
   return rc != GN_OK ? rc : join_groups(ctx, s);
 }
 
-// Matcher, gather and PnP of call v -- or of sub-batch group g of a call, on the group's slice of the workspaces -- enqueued on `stream`.
+// Matcher, gather and PnP of call v on the view w -- the whole context, or sub-batch group w.g of a call on its share of the workspaces -- enqueued on `stream`.
 // slot < 0: all three on `stream`.  slot 0 / 1: the latency-bound PnP kernels (a few hundred single-wave workgroups) run on the PnP stream from
 // that slot of the double-buffered PnP inputs, and `stream` is free for the next call's matcher once the gather is enqueued; R / t / n_inliers / ok
 // are complete behind ev_pnp[slot][g] (gn_flush, or the waits gn_estimate enqueues one call later).
-int estimate_impl(gn_ctx* ctx, const Call& v, void* stream, int slot = -1, int g = 0) {
+int estimate_impl(gn_ctx* ctx, const View& w, const Call& v, void* stream, int slot = -1) {
+  const int g = w.g;
   // the match list: the caller's arrays when the call has them (gn_estimate_report), else the workspaces
-  int64_t* const m_idx = v.idx ? v.idx : ctx->e_idx;
-  float* const m_score = v.score ? v.score : ctx->e_score;
-  int rc = gn_match(ctx, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
+  int64_t* const m_idx = v.idx ? v.idx : w.e_idx;
+  float* const m_score = v.score ? v.score : w.e_score;
+  int rc = match_impl(ctx, w, v.B, v.kpt_format, v.desc_q, v.kpt_q, v.n_q, v.stride_q, v.desc_r, v.kpt_r, v.n_r, v.stride_r,
                     m_idx, m_score, v.n_match, stream);
   if (rc != GN_OK) return rc;
   if (slot < 0) {
     rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
-                          ctx->e_mkp, ctx->e_obj, stream);
+                          w.e_mkp, w.e_obj, stream);
     if (rc != GN_OK) return rc;
-    return pnp_impl(ctx, v.B, ctx->e_obj, ctx->e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
+    return pnp_impl(ctx, w, v.B, w.e_obj, w.e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
                     v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream, report_of(v));
   }
   hipStream_t s = (hipStream_t)stream;
+  float* const o_mkp = slot ? w.o_mkp1 : w.o_mkp0; float* const o_obj = slot ? w.o_obj1 : w.o_obj0; int32_t* const o_nmatch = slot ? w.o_nmatch1 : w.o_nmatch0;
   GN_HIP(hipSetDevice(ctx->device));
   GN_HIP(hipEventRecord(ctx->ev_head[g], s));
   if (ctx->pnp_recorded[slot][g]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot][g], 0));   // the PnP that last read this slot (two calls ago)
   rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
-                        ctx->o_mkp[slot], ctx->o_obj[slot], stream);
+                        o_mkp, o_obj, stream);
   if (rc != GN_OK) return rc;
-  GN_HIP(hipMemcpyAsync(ctx->o_nmatch[slot], v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  GN_HIP(hipMemcpyAsync(o_nmatch, v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
-  rc = pnp_impl(ctx, v.B, ctx->o_obj[slot], ctx->o_mkp[slot], ctx->o_nmatch[slot], ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
+  rc = pnp_impl(ctx, w, v.B, o_obj, o_mkp, o_nmatch, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
                 v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp, report_of(v));
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
@@ -2073,7 +2076,7 @@ int cert_resolve(gn_ctx* ctx, int slot, hipStream_t s) {
   ctx->npad_run = p.npad_run;
   // a re-run writes outputs of this call and works in slices of the workspaces that the groups and the PnP stream may still be using: it
   // goes behind every pending PnP (this call's above all) and every group first (calls without a flagged pair never get here)
-  return certify_rerun(ctx, s, p.call, [&](const Call& w) { const int rcj = join_internal(ctx, s); return rcj != GN_OK ? rcj : estimate_impl(ctx, w, s); }, p.flags, p.level);
+  return certify_rerun(ctx, s, p.call, [&](const View& rw, const Call& w) { const int rcj = join_internal(ctx, s); return rcj != GN_OK ? rcj : estimate_impl(ctx, rw, w, s); }, p.flags, p.level);
 }
 }  // namespace
 
@@ -2088,7 +2091,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
                   int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
   if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
-  if (ctx->fused_proj_pending && ctx->npad > 0 && gn_missing_tensors(ctx) == 0) {      // (the sub-batch groups below skip it: their workspace pointers are shifted)
+  if (ctx->fused_proj_pending && ctx->npad > 0 && gn_missing_tensors(ctx) == 0) {      // (the sub-batch groups below skip it: it works on the workspaces as allocated)
     GN_HIP(hipSetDevice(ctx->device));
     int rcs = ensure_composed(ctx);
     if (rcs == GN_OK) rcs = selfcheck_fused_projection(ctx);
@@ -2103,12 +2106,12 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.ransac_iters = ctx->ransac_iters; v.ransac_reproj = ctx->ransac_reproj; v.ransac_conf = ctx->ransac_conf;
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
-    // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the un-shifted workspaces, on the
+    // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the whole workspaces, on the
     // caller's stream: behind the groups first, and -- unless its own PnP goes to the PnP stream, which keeps the order -- behind their PnP.
     GN_HIP(hipSetDevice(ctx->device));
     const int rcj = ctx->overlap ? join_groups(ctx, (hipStream_t)stream) : join_internal(ctx, (hipStream_t)stream);
     if (rcj != GN_OK) return rcj;
-    return ctx->overlap ? estimate_impl(ctx, v, stream, (int)(ctx->calls++ & 1), 0) : estimate_impl(ctx, v, stream);
+    return estimate_impl(ctx, view_of(ctx), v, stream, ctx->overlap ? (int)(ctx->calls++ & 1) : -1);
   }
   if (ctx->npad <= 0) return fail(ctx, GN_ERR_ARG, "context has no workspaces (a gn_resize failed): call gn_resize again");
   if (B < 1 || B > ctx->max_batch) return fail(ctx, GN_ERR_ARG, "B out of range for this context");
@@ -2134,11 +2137,9 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     const int Bg = B / groups + (g < B % groups ? 1 : 0);
     hipStream_t sg = ctx->sub_serial ? ctx->sub_s[0] : ctx->sub_s[g];
     GN_HIP(hipStreamWaitEvent(sg, ctx->ev_fork, 0));
-    shift_workspaces(ctx, b0, +1);
-    ctx->in_group = true; ctx->ovf = ctx->ovf_base + g;            // this group's own guard word: cleared, raised and read on this group's stream only
-    const int rc = estimate_impl(ctx, slice(v, b0, Bg), sg, slot, g);
-    shift_workspaces(ctx, b0, -1);
-    ctx->ovf = ctx->ovf_base; ctx->in_group = false;
+    ctx->in_group = true;            // (the view carries this group's own guard word: cleared, raised and read on this group's stream only)
+    const int rc = estimate_impl(ctx, view_of(ctx, b0, g), slice(v, b0, Bg), sg, slot);
+    ctx->in_group = false;
     if (rc != GN_OK && rc_all == GN_OK) rc_all = rc;
     GN_HIP(hipEventRecord(ctx->ev_join[g], sg));
     ctx->sub_pending[g] = true;
@@ -2155,10 +2156,10 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     const int slot = ctx->cert_slot;
     gn_ctx::CertPending& p = ctx->cert_pend[slot];
     if (p.active) { const int rcr = cert_resolve(ctx, slot, s); if (rcr != GN_OK) return rcr; }     // (cannot happen in the alternating order; kept for safety)
-    GN_HIP(hipMemcpyAsync(p.flags, ctx->uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(p.flags, ctx->ws.uncert, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (ffn_auto(ctx)) {
-      GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      GN_HIP(hipMemcpyAsync(p.flags + 2 * ctx->max_batch, ctx->uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->ws.uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(p.flags + 2 * ctx->max_batch, ctx->ws.uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     } else memset(p.flags + ctx->max_batch, 0, (size_t)2 * ctx->max_batch * sizeof(int32_t));
     GN_HIP(hipEventRecord(p.ev, s));
     p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.npad_run = ctx->npad_run;
@@ -2169,7 +2170,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   if (!ctx->defer_join || ctx->certify == 2) { const int rcj = gn_flush(ctx, stream); if (rcj != GN_OK && rc_all == GN_OK) rc_all = rcj; }
   if (ctx->certify == 2 && rc_all == GN_OK) {
     // the groups are joined: one read-back of the call's per-pair flags, then matcher + gather + PnP of the flagged pairs again in exact f32
-    rc_all = certify_rerun(ctx, s, v, [&](const Call& w) { return estimate_impl(ctx, w, s); });
+    rc_all = certify_rerun(ctx, s, v, [&](const View& rw, const Call& w) { return estimate_impl(ctx, rw, w, s); });
   }
   return rc_all;
 }
@@ -2282,15 +2283,15 @@ int gn_vo_match(gn_ctx* ctx, int B, const float* desc_q, const int32_t* n_q, int
   VoArgs v;
   v.desc_q = desc_q; v.n_q = n_q; v.stride_q = stride_q; v.desc_r = desc_r; v.n_r = n_r; v.stride_r = stride_r;
   v.B = B; v.npad = np; v.ratio = ratio;
-  v.desc = ctx->desc; v.norm2 = ctx->vo_norm2; v.nvalid = ctx->nvalid; v.sim = ctx->sim;
+  v.desc = ctx->ws.desc; v.norm2 = ctx->vo_norm2; v.nvalid = ctx->ws.nvalid; v.sim = ctx->ws.sim;
   v.nn_idx = ctx->vo_nn_idx; v.nn_dist = ctx->vo_nn_dist; v.good = ctx->vo_good;
   v.idx = idx; v.dist = dist; v.n_good = n_good; v.kmax = np;
   launch_vo_pack(v, s);
   // q.r for every (query, train) pair on the exact-f32 MFMA GEMM, whatever the context's precision mode
   GemmArgs gs;
   memset(&gs, 0, sizeof gs);
-  gs.A = ctx->desc; gs.lda = kInDim; gs.K1 = kInDim; gs.W = ctx->desc + (size_t)np * kInDim; gs.ldw = kInDim;
-  gs.Y = ctx->sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kInDim; gs.acc_scale = 1.f;
+  gs.A = ctx->ws.desc; gs.lda = kInDim; gs.K1 = kInDim; gs.W = ctx->ws.desc + (size_t)np * kInDim; gs.ldw = kInDim;
+  gs.Y = ctx->ws.sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kInDim; gs.acc_scale = 1.f;
   gs.strideA = gs.strideW = 2LL * np * kInDim; gs.strideY = (long long)np * np;
   const int saved = gn::g_gemm_variant;
   gn::g_gemm_variant = 3;
@@ -2314,15 +2315,15 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
                      double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
                      int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
-  int64_t* const m_idx = idx ? idx : ctx->e_idx;
-  float* const m_score = score ? score : ctx->e_score;
+  int64_t* const m_idx = idx ? idx : ctx->ws.e_idx;
+  float* const m_score = score ? score : ctx->ws.e_score;
   int rc = gn_vo_match(ctx, B, desc_q, n_q, stride_q, desc_r, n_r, stride_r, ratio, m_idx, m_score, n_match,
                        nullptr, nullptr, stream);
   if (rc != GN_OK) return rc;
   rc = gn_gather_points(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, m_idx, n_match, nullptr, 0, 0,
-                        ctx->e_mkp, ctx->e_obj, stream);
+                        ctx->ws.e_mkp, ctx->ws.e_obj, stream);
   if (rc != GN_OK) return rc;
-  return pnp_impl(ctx, B, ctx->e_obj, ctx->e_mkp, n_match, ctx->npad, K9, dist_of(ctx), ctx->ransac_iters, ctx->ransac_reproj, ctx->ransac_conf, min_matches,
+  return pnp_impl(ctx, view_of(ctx), B, ctx->ws.e_obj, ctx->ws.e_mkp, n_match, ctx->npad, K9, dist_of(ctx), ctx->ransac_iters, ctx->ransac_reproj, ctx->ransac_conf, min_matches,
                   R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream, rep);
 }
 }  // namespace
@@ -2724,21 +2725,15 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
 int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream) {
   if (!ctx || !name || !host_out) return GN_ERR_ARG;
   hipSetDevice(ctx->device);
-  const size_t np = ctx->npad, T = (size_t)ctx->max_batch * 2 * np, B = ctx->max_batch;
+  const size_t np = ctx->npad, B = ctx->max_batch;
   struct Ent { const char* n; const void* p; size_t count; };
+  // the matcher's workspaces by their table names: the whole buffer in 4-byte words (nothing when it does not exist)
+  Ent ws_ent = {nullptr, nullptr, 0};      // (no name: matches nothing)
+  for_each_workspace(ctx->ws, (long long)np, (long long)np, false, [&](auto* p, long long per_pair, int, const char* n) {
+    if (n && strcmp(n, name) == 0) ws_ent = {n, p, p ? B * (size_t)per_pair * sizeof(*p) / 4 : 0};
+  });
   const Ent tab[] = {
-      {"desc", ctx->desc, T * kInDim}, {"cos", ctx->cos_t, T * kFreq}, {"sin", ctx->sin_t, T * kFreq},
-      {"x", ctx->x, T * kDim}, {"qkv", ctx->qkv, T * 3 * kDim}, {"ctx", ctx->ctx, T * kDim}, {"msg", ctx->msg, T * kDim},
-      {"h", ctx->h, T * 2 * kDim}, {"md", ctx->md, T * kDim}, {"ls", ctx->ls, T}, {"sim", ctx->sim, ctx->sim ? B * np * np : 0},
-      {"rowmax", ctx->rowmax, B * np}, {"rowlog", ctx->rowlog, B * np}, {"colmax", ctx->colmax, B * np},
-      {"collog", ctx->collog, B * np}, {"max0", ctx->max0, B * np}, {"max0b", ctx->max0b, B * np}, {"uncert", ctx->uncert, B}, {"m0", ctx->m0, B * np}, {"m1", ctx->m1, B * np},
-      {"prune_counts", ctx->pr_counts, B * 2 * kMaxLayers}, {"prune_ind", ctx->pr_ind, T}, {"prune_z", ctx->pr_z, T},      // (prune_z: f32 z of the last pruning layer's rows)
-      {"lists", ctx->lists, ctx->lists ? B * (size_t)ctx->lists_stride : 0},      // work lists of the last call as they stand (int32: [0] tiles, [1] attention items, ...)
-           // point pruning: [slot][layer] counts after each layer; [slot][npad_run] original indices
-      {"extent", ctx->extent, B * 4}, {"nvalid", ctx->nvalid, B * 2}, {"e_mkp", ctx->e_mkp, B * np * 2},
-      {"e_obj", ctx->e_obj, B * np * 3}, {"e_score", ctx->e_score, B * np},
-      {"hyp", ctx->hyp_ws, B * 16 * (sizeof(gn::HypResult) / 4)},
-      {"ransac_state", ctx->rstate_ws, B * (sizeof(gn::RansacState) / 4)}, {"ransac_mask", ctx->rmask_ws, B * np * (gn::kRansacRound + 1) / 4},
+      ws_ent,
       {"sp_enc", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * (ctx->sp_h / 8) * (ctx->sp_w / 8) * 128 : 0},          // SuperPoint: encoder output of the last pass, NHWC
       {"sp_scores", ctx->sp_maps[0], ctx->sp_maps[0] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},             // softmax + depth-to-space scores
       {"sp_nms", ctx->sp_maps[5], ctx->sp_maps[5] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},                // after simple_nms
@@ -2747,11 +2742,9 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       {"sp_x", ctx->sp_x, ctx->sp_x ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},                         // raw words of the two activation buffers
       {"sp_y", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},
       {"sp_z", ctx->sp_z, ctx->sp_z ? (size_t)ctx->sp_chunk * (ctx->sp_h / 8) * (ctx->sp_w / 8) * 256 : 0},          // f32: the raw descriptor map [h][w][256] after a full pass, the logits [h][w][128] after a pass stopped at layer 9 (knob 39)
-      {"sp_ts", ctx->sp_ts, ctx->sp_ts ? (size_t)8192 * 32 * 2 : 0},                                                     // phase stamps (knob 35), int64 pairs of 4-byte words
-      {"desc_p", ctx->desc_p, ctx->desc_p ? T * kInDim : 0}, {"x_p", ctx->x_p, ctx->x_p ? T * kDim : 0}, {"msg_p", ctx->msg_p, ctx->msg_p ? T * kDim : 0},   // hm16 rows, raw (4 bytes per value)
-      {"qkb", ctx->qkb, ctx->qkb ? T * kDim : 0}, {"rot4", ctx->rot4, ctx->rot4 ? T * 2 * kFreq : 0}, {"vtb", ctx->vtb, ctx->vtb ? T * kDim / 2 : 0}};
+      {"sp_ts", ctx->sp_ts, ctx->sp_ts ? (size_t)8192 * 32 * 2 : 0}};                                                     // phase stamps (knob 35), int64 pairs of 4-byte words
   for (const Ent& e : tab)
-    if (strcmp(e.n, name) == 0) {
+    if (e.n && strcmp(e.n, name) == 0) {
       size_t count = e.count;
       if ((int64_t)(count * 4) > max_bytes) count = (size_t)max_bytes / 4;
       if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GN_ERR_HIP;
@@ -2783,7 +2776,7 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
     size_t count = B * np * 2;
     if ((int64_t)(count * 8) > max_bytes) count = (size_t)max_bytes / 8;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GN_ERR_HIP;
-    if (hipMemcpy(host_out, ctx->e_idx, count * 8, hipMemcpyDeviceToHost) != hipSuccess) return GN_ERR_HIP;
+    if (hipMemcpy(host_out, ctx->ws.e_idx, count * 8, hipMemcpyDeviceToHost) != hipSuccess) return GN_ERR_HIP;
     return (int64_t)count;
   }
   return fail(ctx, GN_ERR_NAME, std::string("unknown debug tensor ") + name);
@@ -2845,12 +2838,12 @@ int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale, c
   a.nvalid = nkv; a.npad = npad; a.cross = cross; a.qscale = qscale; a.BS = BS;
   a.qb = a.kb = a.vt = nullptr; a.ldqb = a.ldkb = 0; a.outp = nullptr; a.half_fmt = ctx->attn_f16; a.ncu = ctx->ncu;
   const long long cap = (long long)ctx->max_batch * 2 * ctx->npad;
-  if (ctx->precision != GN_PREC_F32 && ctx->attn_f16 != 2 && ctx->attn_variant >= 1 && ctx->qkb && ctx->vtb && (long long)BS * npad <= cap) {
+  if (ctx->precision != GN_PREC_F32 && ctx->attn_f16 != 2 && ctx->attn_variant >= 1 && ctx->ws.qkb && ctx->ws.vtb && (long long)BS * npad <= cap) {
     // the production kernel (k_attn_bf16_v5) on the layouts the projection epilogues would have written
-    launch_pack_attn_bf16(a, ctx->qkb, ctx->vtb, (hipStream_t)stream);
-    a.qb = ctx->qkb; a.kb = ctx->qkb + kDim; a.ldqb = a.ldkb = 2 * kDim; a.vt = ctx->vtb;
+    launch_pack_attn_bf16(a, ctx->ws.qkb, ctx->ws.vtb, (hipStream_t)stream);
+    a.qb = ctx->ws.qkb; a.kb = ctx->ws.qkb + kDim; a.ldqb = a.ldkb = 2 * kDim; a.vt = ctx->ws.vtb;
     gn::g_attn_variant = ctx->attn_variant;
-    gn::g_attn_stamps = (ctx->attn_variant == 73 && ctx->sim) ? reinterpret_cast<long long*>(ctx->sim) : nullptr;
+    gn::g_attn_stamps = (ctx->attn_variant == 73 && ctx->ws.sim) ? reinterpret_cast<long long*>(ctx->ws.sim) : nullptr;
     attn_split(ctx, a);
     launch_attention_bf16_v2(a, (hipStream_t)stream);
   } else {
@@ -2892,7 +2885,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 2) ctx->dbg_planes = value;
   else if (which == 3) ctx->no_planes = value;
   else if (which == 4) ctx->stop_after = value;
-  else if (which == 5) ctx->planes_mode = (value && ctx->x_p) ? 1 : 0;
+  else if (which == 5) ctx->planes_mode = (value && ctx->ws.x_p) ? 1 : 0;
   else if (which == 6) ctx->dbg_reuse = value;
   else if (which == 7) ctx->dbg_out = value;
   else if (which == 10) ctx->ffn_fused = value;
@@ -2964,7 +2957,7 @@ int gn_debug_lds_dma_probe(gn_ctx* ctx, const float* pattern, unsigned int* out,
 int gn_debug_mfma_probe(gn_ctx* ctx, int blocks, int iters, void* stream) {
   if (!ctx || blocks < 1 || iters == 0) return GN_ERR_ARG;
   GN_HIP(hipSetDevice(ctx->device));
-  launch_mfma_probe(ctx->ls, blocks, iters, (hipStream_t)stream);
+  launch_mfma_probe(ctx->ws.ls, blocks, iters, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
   return GN_OK;
 }

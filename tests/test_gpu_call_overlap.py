@@ -9,7 +9,7 @@ a bit of any output:
     later, when the contract says they are final, and after the flush for the last one -- are bitwise what the same engine returns for the same
     batches on one stream under set_certify("rerun").  Margin-built weights (nothing flagged) and the mid-margin family of test_gpu_round6.py (some
     pairs flagged and re-run in exact f32: a re-run that raced the pending PnP of its call would leave that PnP's pose in the outputs);
-  * a call of ONE pair takes the single-stream path on the caller's stream, in the un-shifted workspaces.  Right behind a deferred grouped call,
+  * a call of ONE pair takes the single-stream path on the caller's stream, in the whole workspaces.  Right behind a deferred grouped call,
     without a flush (PoseEngine.estimate_bucketed's remainder bucket), it must order itself behind that call's groups and PnP: both calls bitwise
     equal to their synchronous results, three times over;
   * k_prep's own hm16 descriptor rows and rot4 table equal, bit for bit, what k_split_hm16 and k_rot_table make of its f32 outputs (developer knob 48:

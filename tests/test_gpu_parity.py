@@ -626,8 +626,8 @@ def test_overlapped_pose_stage_gives_identical_results(state_dict_np, dev):
 
 @pytest.mark.gpu
 def test_substreams_give_identical_results(state_dict_np, dev):
-    """gn_set_substreams: the pairs of a call run as out-of-phase groups on internal streams over shifted workspace
-    slices -- every output must equal the single-stream result, also for uneven group sizes."""
+    """gn_set_substreams: the pairs of a call run as out-of-phase groups on internal streams over views of the
+    workspaces -- every output must equal the single-stream result, also for uneven group sizes."""
     from gisnav_amd.engine import PoseEngine
     eng = PoseEngine(0, max_batch=5, max_kpts=256, precision="f16x2_bf16_attn", state_dict=state_dict_np)
     inp = eng.stage_inputs([make_pair(80 + i, n_q=256 - 7 * i, n_r=256 - 3 * i) for i in range(5)])
