@@ -725,7 +725,11 @@ class PoseEngine:
         batch of messages spread widely, and one gn_estimate call pads every pair to the batch maximum (attention cost grows with the
         SQUARE of the padded length).  The pairs are sorted by max(n_q, n_r) (host-side counts: no device read), run as groups of
         `bucket_pairs` consecutive pairs each padded to ITS maximum (gn_set_active_kpts), and the results are returned in the caller's
-        order.  Results do not depend on the padding (tests).  They DO depend, at rounding level, on the number of pairs per call: calls of one or
+        order.  Padding slots are never read, and within one kernel family results are the same bits whatever the padding; calls of one or two
+        pairs choose their family by pair count alone, so they never depend on it.  A call of more pairs chooses by its number of 128-token tiles
+        and workgroups (k_qkv from 128 tiles, k_ffn128 from 256, k_attn_pw at multiples of 256 slots): there the padded size can change the family,
+        and with it the result at rounding level -- within the mode's fp64 budgets, not the same bits (tests/test_gpu_fp64_padded_sizes.py,
+        DESIGN 11.7).  Results depend in the same way on the number of pairs per call: calls of one or
         two pairs (and sub-stream groups of that size) run the small-grid kernel family, whose summation order differs from the bulk kernels' -- a
         remainder bucket of one or two pairs therefore gives the same matches and poses up to rounding, not the same bits, as one padded call
         (tests/test_gpu_round6.py).  With the certificate on (set_certify) the correspondence indices are the exact arithmetic's either

@@ -151,7 +151,7 @@ class PoseNode:
             self._dem_dev = (dem_key, self._dem_buf)
         inputs = dict(desc_q=None, kpt_q=self._dev_in[4:4 + n * 133].view(1, n, 133), n_q=self._dev_in[:1].view(torch.int32),
                       desc_r=None, kpt_r=rec_r_t, n_r=n_r_t, dem=self._dem_dev[1], kpt_format=_lib.GN_KPT_RECORD)
-        eng.set_active_kpts(max(n, self._cached_n_r, 1))    # pad to what this pair needs, not to max_kpts (results do not depend on it)
+        eng.set_active_kpts(max(n, self._cached_n_r, 1))    # pad to what this pair needs, not to max_kpts (one pair: the kernel family follows the pair count, so the result's bits do not depend on it)
         try:
             if self._certify and self._cal_left > 0 and n >= 2 and self._cached_n_r >= 2:
                 try:
