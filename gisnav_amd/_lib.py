@@ -57,6 +57,8 @@ SIGNATURES = {
     "gn_get_ransac": (C.c_int, [VP, C.POINTER(C.c_int), c_f32p, c_f64p]),
     "gn_ransac_last_counts": (C.c_int, [VP, C.c_int, c_i32p, c_i32p, VP]),
     "gn_undistort_points": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, c_f64p, C.c_int, VP, VP]),
+    "gn_set_pair_cameras": (C.c_int, [VP, VP, C.c_int, C.c_int]),      # cams: DEVICE [n][GN_PAIR_CAMERA_DOUBLES] f64
+    "gn_get_pair_cameras": (C.c_int, [VP, C.POINTER(VP), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gn_set_overlap": (C.c_int, [VP, C.c_int]),
     "gn_flush": (C.c_int, [VP, VP]),
     "gn_set_substreams": (C.c_int, [VP, C.c_int]),
@@ -145,6 +147,7 @@ GN_PREC_F16X2_F16X2_ATTN = 5
 GN_FEATURE_SIFT = 0
 GN_FEATURE_SUPERPOINT = 1
 GN_RANSAC_MAX_ITERATIONS = 4096
+GN_PAIR_CAMERA_DOUBLES = 9   # fx, fy, cx, cy, k1, k2, p1, p2, k3
 GN_KPT_LAF = 0
 GN_KPT_XYSA = 1
 GN_KPT_RECORD = 2   # raw 532-byte KEYPOINT_DTYPE wire records (133 floats per keypoint)

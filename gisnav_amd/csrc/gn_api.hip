@@ -49,6 +49,9 @@ struct Call {
   const double* K9 = nullptr; int min_matches = 0;
   int dist = 0; double dk[5] = {0, 0, 0, 0, 0};   // lens distortion as the context held it when the call was issued (gn_set_distortion), by value
   int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac, captured the same way
+  // per-pair cameras (gn_set_pair_cameras) as the context held them when the call was issued: DEVICE [B][GN_PAIR_CAMERA_DOUBLES], a per-pair input
+  // like n_q (null = off: K9 / dist / dk above); cam_model picks the PnP instantiation for the whole call
+  const double* cams = nullptr; int cam_model = 0;
   int kw = 0, in_dim = 0; size_t km = 0;   // floats per keypoint, per descriptor; match-list stride (gn_kmax)
   Call() = default;
   Call(int feature, int npad, int B_, int kpt_format_, const float* desc_q_, const float* kpt_q_, const int32_t* n_q_, int stride_q_,
@@ -64,6 +67,7 @@ template <typename F, typename... C> void pair_arrays(const Call& h, F&& f, C&..
   f((size_t)h.stride_q * h.in_dim * 4, false, c.desc_q...); f((size_t)h.stride_r * h.in_dim * 4, false, c.desc_r...);
   f((size_t)h.stride_q * h.kw * 4, false, c.kpt_q...); f((size_t)h.stride_r * h.kw * 4, false, c.kpt_r...);
   f((size_t)4, false, c.n_q...); f((size_t)4, false, c.n_r...); f((size_t)h.H * h.W, false, c.dem...);
+  f((size_t)GN_PAIR_CAMERA_DOUBLES * 8, false, c.cams...);
   f((size_t)72, true, c.R...); f((size_t)24, true, c.t...); f((size_t)4, true, c.n_match...); f((size_t)4, true, c.n_inliers...); f((size_t)1, true, c.ok...);
   f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...);
   f((size_t)288, true, c.cov...); f((size_t)8, true, c.sigma_hat...); f((size_t)1, true, c.cov_ok...);
@@ -138,7 +142,9 @@ inline long long lists_stride_of(long long km) { return gn::kTileListBase + 2 * 
   X(float, sim, np * np, kWsFirstUse, "sim")                                                                                     \
   /* PnP inputs of the overlapped pose stage, double-buffered by call parity */                                                  \
   X(float, o_mkp0, km * 2, kWsPnpStage, nullptr) X(float, o_obj0, km * 3, kWsPnpStage, nullptr) X(int32_t, o_nmatch0, 1, kWsPnpStage, nullptr) \
-  X(float, o_mkp1, km * 2, kWsPnpStage, nullptr) X(float, o_obj1, km * 3, kWsPnpStage, nullptr) X(int32_t, o_nmatch1, 1, kWsPnpStage, nullptr)
+  X(float, o_mkp1, km * 2, kWsPnpStage, nullptr) X(float, o_obj1, km * 3, kWsPnpStage, nullptr) X(int32_t, o_nmatch1, 1, kWsPnpStage, nullptr) \
+  /* the call's rows of the per-pair camera table beside them (written and read only while gn_set_pair_cameras is on) */         \
+  X(double, o_cams0, GN_PAIR_CAMERA_DOUBLES, kWsPnpStage, nullptr) X(double, o_cams1, GN_PAIR_CAMERA_DOUBLES, kWsPnpStage, nullptr)
 
 struct Workspace {
 #define X(type, field, per_pair, when, name) type* field = nullptr;
@@ -219,6 +225,8 @@ struct gn_ctx {
   int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac: what gn_estimate / gn_vo_estimate pass to the PnP stage
   gn::PnpArgs last_pnp; bool last_pnp_valid = false; const int32_t* last_npts = nullptr;   // the most recent PnP stage (gn_ransac_last_counts)
   int dist_on = 0; double dist[5] = {0, 0, 0, 0, 0};      // gn_set_distortion: plumb-bob (k1, k2, p1, p2, k3) of the PnP stage; off = the pinhole kernels
+  // gn_set_pair_cameras: the caller's DEVICE table [pair_cams_n][GN_PAIR_CAMERA_DOUBLES] (null = off) and the model (0 pinhole, 1 plumb-bob) its calls run
+  const double* pair_cams = nullptr; int pair_cams_n = 0, pair_cams_model = 0;
   float size_q[2] = {0.f, 0.f}, size_r[2] = {0.f, 0.f};   // gn_set_image_size: (w, h) per side for the keypoint normalisation, 0 = keypoint extent
   int npad_run = 0;        // padded keypoint count the matcher runs at (<= npad, gn_set_active_kpts); buffers are laid out for it per call
   int n_layers = kMaxLayers;
@@ -1298,6 +1306,23 @@ int gn_get_distortion(const gn_ctx* ctx, double* d5_host) {
   return ctx->dist_on;
 }
 
+int gn_set_pair_cameras(gn_ctx* ctx, const double* cams, int n, int model) {
+  if (!ctx) return GN_ERR_ARG;
+  if (n < 0 || n > ctx->max_batch) return fail(ctx, GN_ERR_ARG, "gn_set_pair_cameras: n must be in 0..max_batch of this context");
+  if (model != 0 && model != 1) return fail(ctx, GN_ERR_ARG, "gn_set_pair_cameras: model must be 0 (pinhole) or 1 (plumb-bob)");
+  if (!cams || n == 0) { ctx->pair_cams = nullptr; ctx->pair_cams_n = 0; ctx->pair_cams_model = 0; return GN_OK; }
+  ctx->pair_cams = cams; ctx->pair_cams_n = n; ctx->pair_cams_model = model;
+  return GN_OK;
+}
+
+int gn_get_pair_cameras(const gn_ctx* ctx, const double** cams, int* n, int* model) {
+  if (!ctx) return GN_ERR_ARG;
+  if (cams) *cams = ctx->pair_cams;
+  if (n) *n = ctx->pair_cams_n;
+  if (model) *model = ctx->pair_cams_model;
+  return ctx->pair_cams ? 1 : 0;
+}
+
 int gn_set_ransac(gn_ctx* ctx, int iterations_count, float reproj_error_px, double confidence) {
   if (!ctx) return GN_ERR_ARG;
   if (iterations_count < 1 || iterations_count > GN_RANSAC_MAX_ITERATIONS)
@@ -1318,13 +1343,20 @@ int gn_get_ransac(const gn_ctx* ctx, int* iterations_count, float* reproj_error_
 
 int gn_undistort_points(gn_ctx* ctx, int B, const float* img, const int32_t* n_pts, int kstride, const double* K9, int to_pixels,
                         float* out, void* stream) {
-  if (!ctx || !img || !n_pts || !K9 || !out || B < 1 || kstride < 1) return fail(ctx, GN_ERR_ARG, "bad gn_undistort_points argument");
+  if (!ctx || !img || !n_pts || (!K9 && !ctx->pair_cams) || !out || B < 1 || kstride < 1) return fail(ctx, GN_ERR_ARG, "bad gn_undistort_points argument");
+  if (ctx->pair_cams && B > ctx->pair_cams_n) return fail(ctx, GN_ERR_ARG, "gn_undistort_points: B exceeds the rows of the table (gn_set_pair_cameras)");
   GN_HIP(hipSetDevice(ctx->device));
   UndistortArgs a;
   a.img = img; a.n_pts = n_pts; a.kstride = kstride; a.B = B;
-  a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
-  a.dist = ctx->dist_on;
-  for (int i = 0; i < 5; ++i) a.dk[i] = ctx->dist[i];
+  if (ctx->pair_cams) {      // row b for pair b; K9 and the gn_set_distortion state are not read
+    a.fx = a.fy = a.cx = a.cy = 0.0;
+    a.cams = ctx->pair_cams; a.dist = ctx->pair_cams_model;
+    for (int i = 0; i < 5; ++i) a.dk[i] = 0.0;
+  } else {
+    a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
+    a.dist = ctx->dist_on;
+    for (int i = 0; i < 5; ++i) a.dk[i] = ctx->dist[i];
+  }
   a.to_pixels = to_pixels ? 1 : 0; a.out = out;
   launch_undistort(a, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
@@ -1914,13 +1946,23 @@ int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int
 namespace {
 // the context's coefficients (gn_set_distortion), null when off
 const double* dist_of(const gn_ctx* c) { return c && c->dist_on ? c->dist : nullptr; }
+// the per-pair table a PnP stage runs with (gn_set_pair_cameras): rows = null when off
+struct PairCams { const double* rows = nullptr; int model = 0; };
+extern "C++" {
+PairCams pair_cams_of(const gn_ctx* c) { return c && c->pair_cams ? PairCams{c->pair_cams, c->pair_cams_model} : PairCams(); }
+PairCams pair_cams_of(const Call& v) { return {v.cams, v.cam_model}; }
+}
+// a call of B pairs needs B rows
+int pair_cams_fit(gn_ctx* ctx, int B) {
+  return ctx && ctx->pair_cams && B > ctx->pair_cams_n ? fail(ctx, GN_ERR_ARG, "B exceeds the rows of the table (gn_set_pair_cameras)") : GN_OK;
+}
 // gn_pnp_ransac (cov, sigma_hat, cov_ok all null), gn_pnp_ransac_cov (all three given: k_pnp_cov runs behind k_pnp_refine) and
 // gn_pnp_ransac_report (any of rep given: k_pnp_report runs last)
 int pnp_impl(gn_ctx* ctx, const View& w, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
              const double* K9, const double* dk, int iterations_count, float reproj_error_px, double confidence, int min_pts,
              double* R, double* t, int32_t* n_inliers, uint8_t* ok, double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
-             const Report& rep = Report()) {
-  if (!ctx || !obj || !img || !n_pts || !K9 || !R || !t || !n_inliers || !ok || B < 1 || B > ctx->max_batch)
+             const Report& rep = Report(), const PairCams& pc = PairCams()) {
+  if (!ctx || !obj || !img || !n_pts || (!K9 && !pc.rows) || !R || !t || !n_inliers || !ok || B < 1 || B > ctx->max_batch)
     return fail(ctx, GN_ERR_ARG, "bad gn_pnp_ransac argument");
   if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
   if (kstride < 1 || kstride > ctx->npad) return fail(ctx, GN_ERR_ARG, "kstride exceeds max_kpts of this context");
@@ -1929,7 +1971,8 @@ int pnp_impl(gn_ctx* ctx, const View& w, int B, const float* obj, const float* i
   GN_HIP(hipSetDevice(ctx->device));
   PnpArgs a;
   a.obj = obj; a.img = img; a.n_pts = n_pts; a.kstride = kstride; a.B = B;
-  a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5];
+  if (pc.rows) { a.fx = a.fy = a.cx = a.cy = 0.0; a.cams = pc.rows; a.dist = pc.model; dk = nullptr; }      // row b for pair b: K9 and dk are not read
+  else { a.fx = K9[0]; a.fy = K9[4]; a.cx = K9[2]; a.cy = K9[5]; }
   a.iterations = iterations_count; a.reproj = reproj_error_px; a.confidence = confidence; a.min_pts = min_pts;
   a.R = R; a.t = t; a.n_inliers = n_inliers; a.ok = ok; a.mask_ws = w.mask_ws; a.hyp = w.hyp_ws; a.pts_ws = w.pts_ws;
   a.dbg_ts = ctx->pnp_stamps ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 15: phase stamps land in the (idle) sim buffer
@@ -1949,8 +1992,9 @@ int pnp_impl(gn_ctx* ctx, const View& w, int B, const float* obj, const float* i
 int gn_pnp_ransac(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
                   const double* K9, int iterations_count, float reproj_error_px, double confidence, int min_pts,
                   double* R, double* t, int32_t* n_inliers, uint8_t* ok, void* stream) {
+  if (const int rcf = pair_cams_fit(ctx, B)) return rcf;
   return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
-                  0.0, nullptr, nullptr, nullptr, stream);
+                  0.0, nullptr, nullptr, nullptr, stream, Report(), pair_cams_of(ctx));
 }
 
 int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
@@ -1958,8 +2002,9 @@ int gn_pnp_ransac_cov(gn_ctx* ctx, int B, const float* obj, const float* img, co
                       double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                       double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok, void* stream) {
   if (!cov_rt || !sigma_hat || !cov_ok) return fail(ctx, GN_ERR_ARG, "gn_pnp_ransac_cov: null covariance output");
+  if (const int rcf = pair_cams_fit(ctx, B)) return rcf;
   return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
-                  sigma_px, cov_rt, sigma_hat, cov_ok, stream);
+                  sigma_px, cov_rt, sigma_hat, cov_ok, stream, Report(), pair_cams_of(ctx));
 }
 
 int gn_pnp_ransac_report(gn_ctx* ctx, int B, const float* obj, const float* img, const int32_t* n_pts, int kstride,
@@ -1967,8 +2012,9 @@ int gn_pnp_ransac_report(gn_ctx* ctx, int B, const float* obj, const float* img,
                          double* R, double* t, int32_t* n_inliers, uint8_t* ok,
                          double sigma_px, double* cov_rt, double* sigma_hat, uint8_t* cov_ok,
                          uint8_t* inlier_mask, int32_t* inlier_idx, float* reproj_err, void* stream) {
+  if (const int rcf = pair_cams_fit(ctx, B)) return rcf;
   return pnp_impl(ctx, view_of(ctx), B, obj, img, n_pts, kstride, K9, dist_of(ctx), iterations_count, reproj_error_px, confidence, min_pts, R, t, n_inliers, ok,
-                  sigma_px, cov_rt, sigma_hat, cov_ok, stream, Report{inlier_mask, inlier_idx, reproj_err});
+                  sigma_px, cov_rt, sigma_hat, cov_ok, stream, Report{inlier_mask, inlier_idx, reproj_err}, pair_cams_of(ctx));
 }
 
 int gn_ransac_last_counts(gn_ctx* ctx, int B, int32_t* niters_host, int32_t* evaluated_host, void* stream) {
@@ -2044,7 +2090,7 @@ int estimate_impl(gn_ctx* ctx, const View& w, const Call& v, void* stream, int s
                           w.e_mkp, w.e_obj, stream);
     if (rc != GN_OK) return rc;
     return pnp_impl(ctx, w, v.B, w.e_obj, w.e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
-                    v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream, report_of(v));
+                    v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream, report_of(v), pair_cams_of(v));
   }
   hipStream_t s = (hipStream_t)stream;
   float* const o_mkp = slot ? w.o_mkp1 : w.o_mkp0; float* const o_obj = slot ? w.o_obj1 : w.o_obj0; int32_t* const o_nmatch = slot ? w.o_nmatch1 : w.o_nmatch0;
@@ -2055,10 +2101,18 @@ int estimate_impl(gn_ctx* ctx, const View& w, const Call& v, void* stream, int s
                         o_mkp, o_obj, stream);
   if (rc != GN_OK) return rc;
   GN_HIP(hipMemcpyAsync(o_nmatch, v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  // the call's camera rows travel with its match counts: the PnP stream reads the slot's copy, so the caller's table is read in the order of
+  // `stream` like every other input (no table: neither the copy nor the line exists for this call)
+  PairCams pc = pair_cams_of(v);
+  if (pc.rows) {
+    double* const o_cams = slot ? w.o_cams1 : w.o_cams0;
+    GN_HIP(hipMemcpyAsync(o_cams, pc.rows, (size_t)v.B * GN_PAIR_CAMERA_DOUBLES * sizeof(double), hipMemcpyDeviceToDevice, s));
+    pc.rows = o_cams;
+  }
   GN_HIP(hipEventRecord(ctx->ev_gather[slot][g], s));
   GN_HIP(hipStreamWaitEvent(ctx->s_pnp, ctx->ev_gather[slot][g], 0));
   rc = pnp_impl(ctx, w, v.B, o_obj, o_mkp, o_nmatch, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
-                v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp, report_of(v));
+                v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, ctx->s_pnp, report_of(v), pc);
   if (rc != GN_OK) return rc;
   GN_HIP(hipEventRecord(ctx->ev_pnp[slot][g], ctx->s_pnp));
   ctx->pnp_pending[slot][g] = ctx->pnp_recorded[slot][g] = true;
@@ -2091,6 +2145,8 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
                   int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
   if ((cov || sigma_hat || cov_ok) && !(cov && sigma_hat && cov_ok)) return fail(ctx, GN_ERR_ARG, "cov_rt, sigma_hat and cov_ok go together");
+  if (const int rcf = pair_cams_fit(ctx, B)) return rcf;
+  if (ctx->pair_cams) K9 = nullptr;      // the table rules: the caller's matrix is neither read nor saved
   if (ctx->fused_proj_pending && ctx->npad > 0 && gn_missing_tensors(ctx) == 0) {      // (the sub-batch groups below skip it: it works on the workspaces as allocated)
     GN_HIP(hipSetDevice(ctx->device));
     int rcs = ensure_composed(ctx);
@@ -2103,6 +2159,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.sigma_px = sigma_px; v.cov = cov; v.sigma_hat = sigma_hat; v.cov_ok = cov_ok;
   v.idx = idx; v.score = score; v.inlier_mask = rep.inlier_mask; v.inlier_idx = rep.inlier_idx; v.reproj_err = rep.reproj_err;
   v.dist = ctx->dist_on; memcpy(v.dk, ctx->dist, sizeof v.dk);      // captured now: a deferred re-run of this call (cert_pend) keeps them
+  v.cams = ctx->pair_cams; v.cam_model = ctx->pair_cams_model;      // (the pointer: the caller keeps the table alive as it keeps n_q)
   v.ransac_iters = ctx->ransac_iters; v.ransac_reproj = ctx->ransac_reproj; v.ransac_conf = ctx->ransac_conf;
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
@@ -2163,7 +2220,8 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     } else memset(p.flags + ctx->max_batch, 0, (size_t)2 * ctx->max_batch * sizeof(int32_t));
     GN_HIP(hipEventRecord(p.ev, s));
     p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.npad_run = ctx->npad_run;
-    p.call = v; memcpy(p.K9, K9, sizeof p.K9); p.call.K9 = p.K9;
+    p.call = v;
+    if (K9) { memcpy(p.K9, K9, sizeof p.K9); p.call.K9 = p.K9; }
     ctx->cert_slot ^= 1;
     return cert_resolve(ctx, slot ^ 1, s);
   }
@@ -2315,6 +2373,7 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
                      double sigma_px, double* cov, double* sigma_hat, uint8_t* cov_ok, void* stream,
                      int64_t* idx = nullptr, float* score = nullptr, const Report& rep = Report()) {
   if (!ctx) return fail(nullptr, GN_ERR_ARG, "null context");
+  if (const int rcf = pair_cams_fit(ctx, B)) return rcf;
   int64_t* const m_idx = idx ? idx : ctx->ws.e_idx;
   float* const m_score = score ? score : ctx->ws.e_score;
   int rc = gn_vo_match(ctx, B, desc_q, n_q, stride_q, desc_r, n_r, stride_r, ratio, m_idx, m_score, n_match,
@@ -2324,7 +2383,7 @@ int vo_estimate_call(gn_ctx* ctx, int B, int kpt_format,
                         ctx->ws.e_mkp, ctx->ws.e_obj, stream);
   if (rc != GN_OK) return rc;
   return pnp_impl(ctx, view_of(ctx), B, ctx->ws.e_obj, ctx->ws.e_mkp, n_match, ctx->npad, K9, dist_of(ctx), ctx->ransac_iters, ctx->ransac_reproj, ctx->ransac_conf, min_matches,
-                  R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream, rep);
+                  R, t, n_inliers, ok, sigma_px, cov, sigma_hat, cov_ok, stream, rep, pair_cams_of(ctx));
 }
 }  // namespace
 

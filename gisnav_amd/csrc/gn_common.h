@@ -369,7 +369,11 @@ struct PnpArgs {
   uint8_t* inlier_mask = nullptr;   // [B][kstride]
   int32_t* inlier_idx = nullptr;    // [B][kstride]
   float* reproj_err = nullptr;      // [B][kstride]
+  // per-pair cameras (gn_set_pair_cameras): null = the by-value fx .. cy / dk above for every pair, as ever.  Else [B][kPairCamDoubles]
+  // (fx, fy, cx, cy, k1, k2, p1, p2, k3): pair b is solved with row b, `dist` picks the instantiation for the whole call, fx .. dk are not read
+  const double* cams = nullptr;
 };
+constexpr int kPairCamDoubles = 9;      // GN_PAIR_CAMERA_DOUBLES
 void launch_pnp(const PnpArgs& a, hipStream_t s);
 // niters / evaluated of a classic (<= 16) stage into rstate[b], from the results k_pnp_hyp left in a.hyp (gn_ransac_last_counts)
 void launch_pnp_counts(const PnpArgs& a, hipStream_t s);
@@ -378,6 +382,7 @@ struct UndistortArgs {       // gn_undistort_points
   double fx, fy, cx, cy;
   int dist; double dk[5];
   int to_pixels; float* out;
+  const double* cams = nullptr;      // as PnpArgs::cams: row (point / kstride) instead of fx .. dk
 };
 void launch_undistort(const UndistortArgs& a, hipStream_t s);
 void launch_epnp_debug(const double* pws, const double* us, double* out, int n, hipStream_t s);

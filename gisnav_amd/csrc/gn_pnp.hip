@@ -922,9 +922,20 @@ __device__ bool epnp5(Shared& sh, int lane, double Rb[3][3], double tb[3], doubl
 // function below that touches an image point is a template on DIST: the `false` instantiations are the code this file had without distortion.
 template <bool DIST> struct CamT { double fx, fy, cx, cy; };
 template <> struct CamT<true> { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
-template <bool DIST> __device__ __forceinline__ CamT<DIST> make_cam(const PnpArgs& a) {
-  if constexpr (DIST) return {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
-  else return {a.fx, a.fy, a.cx, a.cy};
+// TAB = false: the call's one camera, from the kernel arguments (scalar registers).  TAB = true: row `pair` of the per-pair table
+// (gn_set_pair_cameras).  Every caller's `pair` is uniform over its wave (one pair per workgroup or per wave) and nothing writes the table while
+// a stage runs, so the row is read through the constant address space: scalar loads, and the camera stays in scalar registers as the kernel
+// arguments do -- no vector register is spent on it.  The TAB = false instantiations are the code this file had without the table.
+typedef const double __attribute__((address_space(4))) * CamRowPtr;
+template <bool DIST, bool TAB = false> __device__ __forceinline__ CamT<DIST> make_cam(const PnpArgs& a, int pair) {
+  if constexpr (TAB) {
+    const CamRowPtr r = (CamRowPtr)(a.cams + (size_t)pair * kPairCamDoubles);
+    if constexpr (DIST) return {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8]};
+    else return {r[0], r[1], r[2], r[3]};
+  } else {
+    if constexpr (DIST) return {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
+    else return {a.fx, a.fy, a.cx, a.cy};
+  }
 }
 
 // cvProjectPoints2's distortion of a normalised point: xd = x c + 2 p1 x y + p2 (r2 + 2 x^2), yd = y c + p1 (r2 + 2 y^2) + 2 p2 x y with
@@ -1552,7 +1563,7 @@ __device__ __forceinline__ void hyp_eval(const PnpArgs& a, Shared& sh, int lane,
 // one wave per pair replays the sequential `good > max(maxGood, 4)` / RANSACUpdateNumIters logic over
 // the results in hypothesis order (hypotheses past the adapted iteration count are ignored, exactly as
 // the sequential loop would never have computed them) and refines the winner.
-template <bool DIST>
+template <bool DIST, bool TAB = false>
 __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
   __shared__ Shared shs[kHypPack];
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1565,7 +1576,7 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_hyp(PnpArgs a, int nh) {
   const float* img = a.img + (size_t)b * a.kstride * 2;
   uint8_t* mask_w = a.mask_ws + ((size_t)b * kMaxHyp + wave) * a.kstride;
   HypResult* hyp = a.hyp + (size_t)b * kMaxHyp;
-  const CamT<DIST> cam = make_cam<DIST>(a);
+  const CamT<DIST> cam = make_cam<DIST, TAB>(a, b);
   if (n < a.min_pts || n < 5) return;
   {
     unsigned long long rng = 0xFFFFFFFFFFFFFFFFull;
@@ -1628,7 +1639,7 @@ __device__ inline int ransac_fold(const HypResult* res, int first, int cnt, int 
   return win;
 }
 
-template <bool DIST>
+template <bool DIST, bool TAB = false>
 __global__ __launch_bounds__(64 * kHypPack) void k_pnp_round(PnpArgs a, int round, int nh) {
   __shared__ Shared shs[kHypPack];
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1641,7 +1652,7 @@ __global__ __launch_bounds__(64 * kHypPack) void k_pnp_round(PnpArgs a, int roun
   const float* obj = a.obj + (size_t)b * a.kstride * 3;
   const float* img = a.img + (size_t)b * a.kstride * 2;
   uint8_t* mask_w = a.rmask_ws + ((size_t)b * (kRansacRound + 1) + j) * a.kstride;
-  const CamT<DIST> cam = make_cam<DIST>(a);
+  const CamT<DIST> cam = make_cam<DIST, TAB>(a, b);
   const int* sub = st->subs[j];
   hyp_eval<DIST>(a, shs[slot], lane, [&](int l) __attribute__((always_inline)) { return sub[l]; }, obj, img, n, cam, mask_w, st->round + j, nullptr);
 }
@@ -1846,7 +1857,7 @@ __device__ __noinline__ bool p3p_gao(const float* obj, const float* img, const C
 
 constexpr int kLdsPts = 2048;   // inlier correspondences k_pnp_refine keeps in LDS (20 bytes each)
 // ROUND: the winner (R, t, inlier count, mask) comes from the pair's RansacState instead of the replay over hyp_ws
-template <bool DIST, bool ROUND = false>
+template <bool DIST, bool ROUND = false, bool TAB = false>
 __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   __shared__ Shared sh;
   __shared__ float cpts[5 * kLdsPts];
@@ -1856,7 +1867,7 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
   const HypResult* hyp = ROUND ? &a.rstate[b].win : a.hyp + (size_t)b * kMaxHyp;
   double* Rout = a.R + (size_t)b * 9;
   double* tout = a.t + (size_t)b * 3;
-  const CamT<DIST> cam = make_cam<DIST>(a);
+  const CamT<DIST> cam = make_cam<DIST, TAB>(a, b);
   long long ts[8];
   auto stamp = [&](int k) __attribute__((always_inline)) { if (a.dbg_ts) ts[k] = (long long)__builtin_amdgcn_s_memtime(); };
   stamp(0);
@@ -2019,7 +2030,7 @@ __global__ __launch_bounds__(64) void k_pnp_refine(PnpArgs a) {
 // (22 DPP reductions and a few hundred dependent f64 operations behind one pass over the points), and dealt out one wave to a workgroup they
 // would each hold a compute unit against a matcher workgroup of a concurrent stream.
 constexpr int kCovPack = 8;
-template <bool DIST, bool ROUND = false>
+template <bool DIST, bool ROUND = false, bool TAB = false>
 __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * kCovPack + slot;
@@ -2047,7 +2058,7 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
   if (good) {
     const float* obj = a.obj + (size_t)b * a.kstride * 3;
     const float* img = a.img + (size_t)b * a.kstride * 2;
-    const CamT<DIST> cam = make_cam<DIST>(a);
+    const CamT<DIST> cam = make_cam<DIST, TAB>(a, b);
     double Rm[3][3], p[6], R[3][3], dR[3][9];
 #pragma unroll
     for (int i = 0; i < 3; ++i) { p[3 + i] = a.t[(size_t)b * 3 + i];
@@ -2134,7 +2145,7 @@ __global__ __launch_bounds__(64 * kCovPack) void k_pnp_cov(PnpArgs a) {
 // base carried from chunk to chunk.  The index tail [count, kstride) is filled with -1 afterwards: disjoint from what the loop wrote, so nothing
 // has to be waited for.  Every pointer may be null on its own.  No LDS, no barrier; kReportPack waves to a workgroup for the reason given at k_pnp_cov.
 constexpr int kReportPack = 8;
-template <bool DIST, bool ROUND = false>
+template <bool DIST, bool ROUND = false, bool TAB = false>
 __global__ __launch_bounds__(64 * kReportPack) void k_pnp_report(PnpArgs a) {
   const int lane = threadIdx.x & 63, slot = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * kReportPack + slot;
@@ -2160,7 +2171,7 @@ __global__ __launch_bounds__(64 * kReportPack) void k_pnp_report(PnpArgs a) {
   uint8_t* const omask = a.inlier_mask ? a.inlier_mask + (size_t)b * ks : nullptr;
   int32_t* const oidx = a.inlier_idx ? a.inlier_idx + (size_t)b * ks : nullptr;
   float* const oerr = a.reproj_err ? a.reproj_err + (size_t)b * ks : nullptr;
-  const CamT<DIST> cam = make_cam<DIST>(a);
+  const CamT<DIST> cam = make_cam<DIST, TAB>(a, b);
   double R[3][3], p[6] = {0, 0, 0, 0, 0, 0}, dR[3][9];
 #pragma unroll
   for (int i = 0; i < 3; ++i) { p[3 + i] = a.t[(size_t)b * 3 + i];
@@ -2200,14 +2211,20 @@ __global__ __launch_bounds__(256) void k_undistort_points(UndistortArgs a) {
   if (i >= a.n_pts[b]) return;
   const float u = a.img[2 * idx], v = a.img[2 * idx + 1];
   double x, y;
+  // the call's camera, or row b of the per-pair table: a workgroup may straddle two pairs, so the row is loaded per thread
+  double c[kPairCamDoubles] = {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
+  if (a.cams) {
+#pragma unroll
+    for (int k = 0; k < kPairCamDoubles; ++k) c[k] = a.cams[(size_t)b * kPairCamDoubles + k];
+  }
   if (a.dist) {
-    const CamT<true> cam = {a.fx, a.fy, a.cx, a.cy, a.dk[0], a.dk[1], a.dk[2], a.dk[3], a.dk[4]};
+    const CamT<true> cam = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]};
     normalise_pt<true>(cam, u, v, x, y);
   } else {
-    const CamT<false> cam = {a.fx, a.fy, a.cx, a.cy};
+    const CamT<false> cam = {c[0], c[1], c[2], c[3]};
     normalise_pt<false>(cam, u, v, x, y);
   }
-  if (a.to_pixels) { x = x * a.fx + a.cx; y = y * a.fy + a.cy; }
+  if (a.to_pixels) { x = x * c[0] + c[2]; y = y * c[1] + c[3]; }
   a.out[2 * idx] = (float)x; a.out[2 * idx + 1] = (float)y;
 }
 }  // namespace
@@ -2243,40 +2260,41 @@ void launch_epnp_debug(const double* pws, const double* us, double* out, int n, 
 
 namespace {
 inline bool wants_report(const PnpArgs& a) { return a.inlier_mask || a.inlier_idx || a.reproj_err; }
-template <bool DIST>
+template <bool DIST, bool TAB>
 void launch_pnp_rounds(PnpArgs a, hipStream_t s) {
   a.dbg_ts = nullptr;      // the phase stamps are laid out for the classic launches
   const dim3 gs((a.B + kSelPack - 1) / kSelPack), gc((a.B + kCovPack - 1) / kCovPack);
   hipLaunchKernelGGL(k_pnp_select, gs, dim3(64 * kSelPack), 0, s, a, -1);
   for (int r = 0; r * kRansacRound < a.iterations; ++r) {
     const int left = a.iterations - r * kRansacRound, nh = left < kRansacRound ? left : kRansacRound;
-    hipLaunchKernelGGL(k_pnp_round<DIST>, dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, r, nh);
+    hipLaunchKernelGGL((k_pnp_round<DIST, TAB>), dim3((nh * a.B + kHypPack - 1) / kHypPack), dim3(64 * kHypPack), 0, s, a, r, nh);
     hipLaunchKernelGGL(k_pnp_select, gs, dim3(64 * kSelPack), 0, s, a, r);
   }
-  hipLaunchKernelGGL((k_pnp_refine<DIST, true>), dim3(a.B), dim3(64), 0, s, a);
-  if (a.cov) hipLaunchKernelGGL((k_pnp_cov<DIST, true>), gc, dim3(64 * kCovPack), 0, s, a);
-  if (wants_report(a)) hipLaunchKernelGGL((k_pnp_report<DIST, true>), dim3((a.B + kReportPack - 1) / kReportPack), dim3(64 * kReportPack), 0, s, a);
+  hipLaunchKernelGGL((k_pnp_refine<DIST, true, TAB>), dim3(a.B), dim3(64), 0, s, a);
+  if (a.cov) hipLaunchKernelGGL((k_pnp_cov<DIST, true, TAB>), gc, dim3(64 * kCovPack), 0, s, a);
+  if (wants_report(a)) hipLaunchKernelGGL((k_pnp_report<DIST, true, TAB>), dim3((a.B + kReportPack - 1) / kReportPack), dim3(64 * kReportPack), 0, s, a);
 }
-}  // namespace
-
-void launch_pnp(const PnpArgs& a, hipStream_t s) {
+// DIST: gn_set_distortion, or model 1 of a per-pair table -- the plumb-bob instantiations; otherwise the pinhole code, untouched.
+// TAB: the per-pair table (make_cam); without it the instantiations every call had before the table existed.
+template <bool DIST, bool TAB>
+void launch_pnp_t(const PnpArgs& a, hipStream_t s) {
   if (a.iterations > kMaxHyp || a.force_rounds) {   // gn_api refuses counts outside 1..GN_RANSAC_MAX_ITERATIONS
-    if (a.dist) launch_pnp_rounds<true>(a, s); else launch_pnp_rounds<false>(a, s);
+    launch_pnp_rounds<DIST, TAB>(a, s);
     return;
   }
   const int nh = a.iterations < 1 ? 1 : (a.iterations > kMaxHyp ? kMaxHyp : a.iterations);
   const dim3 gh((nh * a.B + kHypPack - 1) / kHypPack), gc((a.B + kCovPack - 1) / kCovPack), gr((a.B + kReportPack - 1) / kReportPack);
-  if (a.dist) {      // gn_set_distortion: the plumb-bob instantiations; otherwise the pinhole code, untouched
-    hipLaunchKernelGGL(k_pnp_hyp<true>, gh, dim3(64 * kHypPack), 0, s, a, nh);
-    hipLaunchKernelGGL(k_pnp_refine<true>, dim3(a.B), dim3(64), 0, s, a);
-    if (a.cov) hipLaunchKernelGGL(k_pnp_cov<true>, gc, dim3(64 * kCovPack), 0, s, a);
-    if (wants_report(a)) hipLaunchKernelGGL(k_pnp_report<true>, gr, dim3(64 * kReportPack), 0, s, a);
-    return;
-  }
-  hipLaunchKernelGGL(k_pnp_hyp<false>, gh, dim3(64 * kHypPack), 0, s, a, nh);
-  hipLaunchKernelGGL(k_pnp_refine<false>, dim3(a.B), dim3(64), 0, s, a);
-  if (a.cov) hipLaunchKernelGGL(k_pnp_cov<false>, gc, dim3(64 * kCovPack), 0, s, a);
-  if (wants_report(a)) hipLaunchKernelGGL(k_pnp_report<false>, gr, dim3(64 * kReportPack), 0, s, a);
+  hipLaunchKernelGGL((k_pnp_hyp<DIST, TAB>), gh, dim3(64 * kHypPack), 0, s, a, nh);
+  hipLaunchKernelGGL((k_pnp_refine<DIST, false, TAB>), dim3(a.B), dim3(64), 0, s, a);
+  if (a.cov) hipLaunchKernelGGL((k_pnp_cov<DIST, false, TAB>), gc, dim3(64 * kCovPack), 0, s, a);
+  if (wants_report(a)) hipLaunchKernelGGL((k_pnp_report<DIST, false, TAB>), gr, dim3(64 * kReportPack), 0, s, a);
+}
+}  // namespace
+
+void launch_pnp(const PnpArgs& a, hipStream_t s) {
+  if (a.cams) { if (a.dist) launch_pnp_t<true, true>(a, s); else launch_pnp_t<false, true>(a, s); }
+  else if (a.dist) launch_pnp_t<true, false>(a, s);
+  else launch_pnp_t<false, false>(a, s);
 }
 
 void launch_pnp_counts(const PnpArgs& a, hipStream_t s) {

@@ -9,6 +9,7 @@ core/_shared.py:109-116.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import struct
 from typing import Dict, Optional, Tuple
@@ -48,6 +49,48 @@ def check_width_pruning(width_confidence, min_kpts=None) -> None:
             raise TypeError(f"pruning min_kpts must be an integer or None, got {type(min_kpts).__name__}")
         if int(min_kpts) < 0:
             raise ValueError(f"pruning min_kpts must be >= 0 (None = the default 1536), got {int(min_kpts)}")
+
+
+def check_pair_cameras(K, d=None) -> np.ndarray:
+    """The rows of a per-pair camera table from B intrinsic matrices K (B, 3, 3) and B plumb-bob coefficient sets d (B, 4 | 5) or None:
+    (B, GN_PAIR_CAMERA_DOUBLES) f64 = fx, fy, cx, cy, k1, k2, p1, p2, k3.  ValueError for a wrong shape, non-finite values, a last row other than
+    (0, 0, 1) or a non-zero skew K[b, 0, 1] -- on the host, before any GPU call (the library cannot validate device memory)."""
+    K = np.asarray(K, np.float64)
+    if K.ndim != 3 or K.shape[1:] != (3, 3) or K.shape[0] < 1:
+        raise ValueError(f"pair_cameras: K must be (B, 3, 3), got {K.shape}")
+    B = K.shape[0]
+    rows = np.zeros((B, _lib.GN_PAIR_CAMERA_DOUBLES), np.float64)
+    if d is not None:
+        d = np.asarray(d, np.float64)
+        if d.ndim != 2 or d.shape[0] != B or d.shape[1] not in (4, 5):
+            raise ValueError(f"pair_cameras: d must be ({B}, 4) or ({B}, 5) plumb-bob coefficients, got {d.shape}")
+        rows[:, 4:4 + d.shape[1]] = d
+    if not np.isfinite(K).all() or not np.isfinite(rows).all():
+        raise ValueError("pair_cameras: non-finite value")
+    if (K[:, 2] != np.array([0.0, 0.0, 1.0])).any():
+        raise ValueError("pair_cameras: the last row of every K must be (0, 0, 1)")
+    if (K[:, 0, 1] != 0.0).any():
+        raise ValueError("pair_cameras: a skew K[b, 0, 1] is not supported by the PnP stage")
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    return rows
+
+
+def check_camera_table(cameras, camera_model, B: int) -> None:
+    """A `cameras` argument as the calls take it: a (B, GN_PAIR_CAMERA_DOUBLES) f64 contiguous tensor (PoseEngine.pair_cameras makes one) with
+    one row per pair of the call, camera_model 0 or 1.  ValueError otherwise, before any GPU call."""
+    if not isinstance(cameras, torch.Tensor) or cameras.dtype != torch.float64 or cameras.dim() != 2 or cameras.shape[1] != _lib.GN_PAIR_CAMERA_DOUBLES:
+        raise ValueError(f"cameras must be a (B, {_lib.GN_PAIR_CAMERA_DOUBLES}) float64 tensor (PoseEngine.pair_cameras)")
+    if cameras.shape[0] != B:
+        raise ValueError(f"cameras has {cameras.shape[0]} rows for a call of {B} pairs")
+    if not cameras.is_contiguous():
+        raise ValueError("cameras must be contiguous")
+    if isinstance(camera_model, bool) or camera_model not in (0, 1):
+        raise ValueError(f"camera_model must be 0 (pinhole) or 1 (plumb-bob), got {camera_model!r}")
+
+
+def _k9_ptr(K):
+    """K9_host of the C calls: None (NULL) when the call runs with a per-pair table and no matrix was given."""
+    return None if K is None else np.ascontiguousarray(np.asarray(K, np.float64).reshape(9)).ctypes.data_as(_lib.c_f64p)
 
 
 _PRECISIONS = {"f32": _lib.GN_PREC_F32, "bf16_attn": _lib.GN_PREC_BF16_ATTN, "f32x3_bf16_attn": _lib.GN_PREC_F32X3_BF16_ATTN,
@@ -404,6 +447,28 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_get_distortion")
         return d if rc == 1 else None
 
+    def pair_cameras(self, K, d=None) -> Tuple[torch.Tensor, int]:
+        """A per-pair camera table for estimate / vo_estimate / pnp_ransac / undistort_points (`cameras=`, `camera_model=`; gn_set_pair_cameras):
+        K (B, 3, 3), d None or (B, 4 | 5) plumb-bob coefficients -> (cams (B, 9) f64 on the device, model); model = 1 iff d is given.  Checked on
+        the host first (check_pair_cameras), uploaded through the pinned staging, and the caller's own tensor (a later table does not alias it)."""
+        rows = check_pair_cameras(K, d)
+        return self.to_device("pair_cameras", rows, torch.float64).clone(), (0 if d is None else 1)
+
+    @contextlib.contextmanager
+    def _camera_table(self, cameras, camera_model, B: int, K):
+        """The table in charge for the C call inside (host-side state only: set before, off after).  None: nothing is touched."""
+        if cameras is None:
+            if K is None:
+                raise ValueError("K is required without a cameras table")
+            yield
+            return
+        check_camera_table(cameras, camera_model, B)
+        _lib.check(self.ctx, self.lib.gn_set_pair_cameras(self.ctx, _ptr(cameras), int(B), int(camera_model)), "gn_set_pair_cameras")
+        try:
+            yield
+        finally:
+            self.lib.gn_set_pair_cameras(self.ctx, None, 0, 0)
+
     def set_ransac(self, iterations: int = RANSAC_ITERATIONS, reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE) -> None:
         """cv2.solvePnPRansac's iterationsCount / reprojectionError / confidence for the PnP stage inside estimate / vo_estimate and the
         certificate's re-runs (gn_set_ransac): 1 .. 4096 hypotheses.  Sticky, captured per call; the default is the reference's (10, 8.0, 0.99).
@@ -425,17 +490,18 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_ransac_last_counts")
         return niters, evaluated
 
-    def undistort_points(self, img, n_pts, K: np.ndarray, to_pixels: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def undistort_points(self, img, n_pts, K: Optional[np.ndarray] = None, to_pixels: bool = False, out: Optional[torch.Tensor] = None,
+                         cameras: Optional[torch.Tensor] = None, camera_model: int = 0) -> torch.Tensor:
         """cv2.undistortPoints with this engine's coefficients (gn_undistort_points).  img [B,S,2] f32 pixels, n_pts [B] i32 (device) ->
         [B,S,2] f32: normalised coordinates, or pixels again with to_pixels (cv2's P = K).  Slots past n_pts keep what `out` held (zeros
-        when it is allocated here)."""
+        when it is allocated here).  cameras / camera_model (pair_cameras): row b for point list b instead of K and the engine's coefficients."""
         B, S = img.shape[0], img.shape[1]
-        if out is None:
-            out = torch.zeros((B, S, 2), dtype=torch.float32, device=self.device)
-        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
-        rc = self.lib.gn_undistort_points(self.ctx, B, _ptr(img), _ptr(n_pts), S, K9.ctypes.data_as(_lib.c_f64p), int(bool(to_pixels)),
-                                          _ptr(out), self._stream())
-        _lib.check(self.ctx, rc, "gn_undistort_points")
+        with self._camera_table(cameras, camera_model, B, K):
+            if out is None:
+                out = torch.zeros((B, S, 2), dtype=torch.float32, device=self.device)
+            rc = self.lib.gn_undistort_points(self.ctx, B, _ptr(img), _ptr(n_pts), S, _k9_ptr(K), int(bool(to_pixels)),
+                                              _ptr(out), self._stream())
+            _lib.check(self.ctx, rc, "gn_undistort_points")
         return out
 
     def set_num_layers(self, n: int) -> None:
@@ -536,23 +602,30 @@ class PoseEngine:
 
     def pnp_ransac(self, obj, img, n_pts, K: np.ndarray, iterations: int = RANSAC_ITERATIONS,
                    reproj_px: float = RANSAC_REPROJ_PX, confidence: float = RANSAC_CONFIDENCE, min_pts: int = 5,
-                   covariance: bool = False, sigma_px: float = 0.0, report: bool = False, report_out: Optional[dict] = None):
+                   covariance: bool = False, sigma_px: float = 0.0, report: bool = False, report_out: Optional[dict] = None,
+                   cameras: Optional[torch.Tensor] = None, camera_model: int = 0):
         """gn_pnp_ransac.  obj [B,S,3] f32, img [B,S,2] f32, n_pts [B] i32 (device).  Returns (R, t, n_inliers, ok); with covariance=True
         (gn_pnp_ransac_cov) also cov [B,6,6] f64 of (rvec, tvec), sigma [B] f64 (a-posteriori pixel sigma) and cov_ok [B] u8.  sigma_px > 0
         states the pixel noise; 0 scales the covariance with the residuals' own sigma.  report=True (gn_pnp_ransac_report) appends
         inlier_mask [B,S] u8, inlier_idx [B,S] i32 (cv2's `inliers`: the first n_inliers entries, then -1) and reproj_err [B,S] f32 (pixels at
-        the returned pose, -1 past n_pts and where ok = 0); report_out: a dict of those three to write into instead of fresh tensors."""
+        the returned pose, -1 past n_pts and where ok = 0); report_out: a dict of those three to write into instead of fresh tensors.
+        cameras / camera_model (pair_cameras): pair b is solved with row b instead of K (which may then be None) and the engine's coefficients."""
+        B = obj.shape[0]
+        with self._camera_table(cameras, camera_model, B, K):
+            return self._pnp_ransac(obj, img, n_pts, K, iterations, reproj_px, confidence, min_pts, covariance, sigma_px, report, report_out)
+
+    def _pnp_ransac(self, obj, img, n_pts, K, iterations, reproj_px, confidence, min_pts, covariance, sigma_px, report, report_out):
         B = obj.shape[0]
         if report:
             R = torch.empty((B, 3, 3), dtype=torch.float64, device=self.device)
             t = torch.empty((B, 3, 1), dtype=torch.float64, device=self.device)
             n_inl = torch.empty((B,), dtype=torch.int32, device=self.device)
             ok = torch.empty((B,), dtype=torch.uint8, device=self.device)
-            K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+            K9 = _k9_ptr(K)
             c = self._alloc_cov(B) if covariance else {}
             r = report_out if report_out is not None else self._alloc_report(B, obj.shape[1])
             rc = self.lib.gn_pnp_ransac_report(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
-                                               K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                                               K9, iterations, reproj_px, confidence, min_pts,
                                                _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), float(sigma_px), _ptr(c.get("cov")), _ptr(c.get("sigma")), _ptr(c.get("cov_ok")),
                                                _ptr(r.get("inlier_mask")), _ptr(r.get("inlier_idx")), _ptr(r.get("reproj_err")), self._stream())
             _lib.check(self.ctx, rc, "gn_pnp_ransac_report")
@@ -562,17 +635,17 @@ class PoseEngine:
         t = torch.empty((B, 3, 1), dtype=torch.float64, device=self.device)
         n_inl = torch.empty((B,), dtype=torch.int32, device=self.device)
         ok = torch.empty((B,), dtype=torch.uint8, device=self.device)
-        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        K9 = _k9_ptr(K)
         if covariance:
             c = self._alloc_cov(B)
             rc = self.lib.gn_pnp_ransac_cov(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
-                                            K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                                            K9, iterations, reproj_px, confidence, min_pts,
                                             _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), float(sigma_px), _ptr(c["cov"]), _ptr(c["sigma"]), _ptr(c["cov_ok"]),
                                             self._stream())
             _lib.check(self.ctx, rc, "gn_pnp_ransac_cov")
             return R, t, n_inl, ok, c["cov"], c["sigma"], c["cov_ok"]
         rc = self.lib.gn_pnp_ransac(self.ctx, B, _ptr(obj), _ptr(img), _ptr(n_pts), obj.shape[1],
-                                    K9.ctypes.data_as(_lib.c_f64p), iterations, reproj_px, confidence, min_pts,
+                                    K9, iterations, reproj_px, confidence, min_pts,
                                     _ptr(R), _ptr(t), _ptr(n_inl), _ptr(ok), self._stream())
         _lib.check(self.ctx, rc, "gn_pnp_ransac")
         return R, t, n_inl, ok
@@ -691,7 +764,14 @@ class PoseEngine:
         """gn_estimate on staged inputs: PoseNode._pose lines 246-308 for the whole batch.  covariance=True (gn_estimate_cov): `out` also
         carries cov [B,6,6], sigma [B], cov_ok [B] (alloc_outputs(B, covariance=True)), complete when R / t / ok are.  report=True
         (gn_estimate_report): `out` also carries the match list idx [B,kmax,2], score [B,kmax] and inlier_mask / inlier_idx / reproj_err
-        [B,kmax] of its rows (alloc_outputs(B, report=True)), complete when R / t / ok are."""
+        [B,kmax] of its rows (alloc_outputs(B, report=True)), complete when R / t / ok are.
+        inputs["cameras"] / inputs["camera_model"] (pair_cameras): pair b's PnP runs with row b instead of K (which may then be None) and
+        the engine's coefficients; the table is an input like the others (keep it alive as long as them)."""
+        B = inputs["kpt_q"].shape[0]
+        with self._camera_table(inputs.get("cameras"), inputs.get("camera_model", 0), B, K):
+            return self._estimate(inputs, K, min_matches, out, covariance, sigma_px, report)
+
+    def _estimate(self, inputs, K, min_matches, out, covariance, sigma_px, report):
         B = inputs["kpt_q"].shape[0]
         if out is None:
             out = self.alloc_outputs(B, covariance, report)
@@ -702,12 +782,12 @@ class PoseEngine:
             self._last_out_ptr = out["R"].data_ptr()
         dem = inputs.get("dem")
         H, W = (dem.shape[1], dem.shape[2]) if dem is not None else (0, 0)
-        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        K9 = _k9_ptr(K)
         # (GN_KPT_RECORD inputs carry the descriptors inside the keypoint records: desc_q / desc_r are None)
         args = (self.ctx, B, inputs["kpt_format"],
                 _ptr(inputs.get("desc_q")), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["kpt_q"].shape[1],
                 _ptr(inputs.get("desc_r")), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["kpt_r"].shape[1],
-                _ptr(dem), H, W, K9.ctypes.data_as(_lib.c_f64p), min_matches,
+                _ptr(dem), H, W, K9, min_matches,
                 _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
         if report:
             cov3 = (_ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"])) if covariance else (None, None, None)
@@ -766,12 +846,12 @@ class PoseEngine:
                      "groups": (B + bucket_pairs - 1) // bucket_pairs}
 
     def estimate_images(self, frames, tiles, K: np.ndarray, dem=None, sift=None, min_matches: int = MIN_MATCHES, out: Optional[dict] = None,
-                        report: bool = False):
+                        report: bool = False, cameras: Optional[torch.Tensor] = None, camera_model: int = 0):
         """Frames -> pose from pixels for B pairs, everything in HBM: one batched SIFT pass over the B camera frames and the
         B map tiles (`gn_sift_detect_and_compute_batch`), the matcher padded to what the batch needs (`gn_set_active_kpts`),
         then `gn_estimate`.  frames / tiles: (B, H, W) uint8 (numpy or device tensors, one size); dem: (B, H, W) uint8 or
         None (flat).  report=True: as estimate; `kpt_q` / `kpt_r` [B,S,4] of the extraction are then added to the outputs, so that idx can be
-        resolved to pixel coordinates.  Returns (estimate outputs, n_keypoints [2B] int32 on the host: frames first)."""
+        resolved to pixel coordinates.  cameras / camera_model (pair_cameras): one camera per frame, as estimate.  Returns (estimate outputs, n_keypoints [2B] int32 on the host: frames first)."""
         from .sift import SIFT
         if sift is None:
             if getattr(self, "_sift", None) is None:
@@ -793,6 +873,8 @@ class PoseEngine:
         if dem is None:
             dem = torch.zeros((B, int(f.shape[1]), int(f.shape[2])), dtype=torch.uint8, device=self.device)
         inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], dem=to_dev(dem), kpt_format=_lib.GN_KPT_XYSA)
+        if cameras is not None:
+            inputs.update(cameras=cameras, camera_model=camera_model)
         self.set_active_kpts(max(int(n.max()), 1))
         try:
             res = self.estimate(inputs, K, min_matches, out=out, report=report)
@@ -821,15 +903,20 @@ class PoseEngine:
     def vo_estimate(self, inputs: dict, K: np.ndarray, ratio: float = 0.7, min_matches: int = 30, out: Optional[dict] = None,
                     covariance: bool = False, sigma_px: float = 0.0, report: bool = False):
         """gn_vo_estimate on staged inputs: TwistNode._pose lines 227-289 for the whole batch (covariance=True: gn_vo_estimate_cov, report=True:
-        gn_vo_estimate_report, both as estimate; `score` is then the matches' distance)."""
+        gn_vo_estimate_report, both as estimate; `score` is then the matches' distance).  inputs["cameras"] / inputs["camera_model"]: as estimate."""
+        B = inputs["desc_q"].shape[0]
+        with self._camera_table(inputs.get("cameras"), inputs.get("camera_model", 0), B, K):
+            return self._vo_estimate(inputs, K, ratio, min_matches, out, covariance, sigma_px, report)
+
+    def _vo_estimate(self, inputs, K, ratio, min_matches, out, covariance, sigma_px, report):
         B = inputs["desc_q"].shape[0]
         if out is None:
             out = self.alloc_outputs(B, covariance, report)
-        K9 = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        K9 = _k9_ptr(K)
         args = (self.ctx, B, inputs["kpt_format"],
                 _ptr(inputs["desc_q"]), _ptr(inputs["kpt_q"]), _ptr(inputs["n_q"]), inputs["desc_q"].shape[1],
                 _ptr(inputs["desc_r"]), _ptr(inputs["kpt_r"]), _ptr(inputs["n_r"]), inputs["desc_r"].shape[1],
-                K9.ctypes.data_as(_lib.c_f64p), float(ratio), min_matches,
+                K9, float(ratio), min_matches,
                 _ptr(out["R"]), _ptr(out["t"]), _ptr(out["n_match"]), _ptr(out["n_inliers"]), _ptr(out["ok"]))
         if report:
             cov3 = (_ptr(out["cov"]), _ptr(out["sigma"]), _ptr(out["cov_ok"])) if covariance else (None, None, None)

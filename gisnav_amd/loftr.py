@@ -305,7 +305,8 @@ def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_m
     gn_gather_points, ONE gn_pnp_ransac over the B pairs and ONE read-back.  Returns a list of B entries, each what `loftr_pose` returns for that
     pair (None below `min_matches` / without a model).  The engine must have been created with max_batch >= B; it is grown to the matcher's
     per-pair cap when that exceeds its keypoint capacity.  dist, ransac_iterations, return_inliers: as for `loftr_pose` (the inlier indices
-    ride in the one read-back)."""
+    ride in the one read-back).  K (B, 3, 3) with dist None or (B, 4 | 5): one camera per pair (PoseEngine.pair_cameras; with dist every pair
+    runs the plumb-bob kernels, a row of zeros being a pinhole camera run through them); K (3, 3) / dist (4 | 5,): one camera for all."""
     stack = lambda x: x if isinstance(x, torch.Tensor) else torch.stack([torch.as_tensor(v) for v in x])  # noqa: E731
     frames01, tiles01 = stack(frames01), stack(tiles01)
     B, H, W = matcher._batch_shape(frames01, tiles01)
@@ -329,8 +330,17 @@ def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_m
         d = dems.to(dev) if isinstance(dems, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.stack([np.asarray(v) for v in dems]), np.uint8), device=dev)
         d = d.to(torch.uint8).contiguous()
     mkp, obj = engine.gather_points(g(k0), g(k1), idx, cnt, d, _lib.GN_KPT_XYSA)
-    res = _pnp_with_dist(engine, dist, obj, mkp, cnt, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance,
-                         **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
+    K = np.asarray(K, np.float64)
+    if K.ndim == 3:
+        # one camera per pair: the one PnP call runs with a per-pair table (K (B, 3, 3), dist None or (B, 4 | 5)); checked on the host first
+        if K.shape[0] != B:
+            raise ValueError(f"K has {K.shape[0]} matrices for {B} pairs")
+        cams, model = engine.pair_cameras(K, dist)
+        res = engine.pnp_ransac(obj, mkp, cnt, None, min_pts=min_matches, covariance=return_covariance, cameras=cams, camera_model=model,
+                                **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
+    else:
+        res = _pnp_with_dist(engine, dist, obj, mkp, cnt, K.reshape(3, 3), min_pts=min_matches, covariance=return_covariance,
+                             **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
     back = [res[0], res[1], res[3], cnt] + ([res[4], res[6]] if return_covariance else []) + ([res[2], res[-2]] if return_inliers else [])
     host = engine.to_host(*back)
     R, t, ok, cn = host[:4]

@@ -11,10 +11,13 @@ inliers (`gn_pnp_ransac_cov`, DESIGN.md "Pose covariance"), or None in its place
 engine's own `set_ransac` state is neither read nor changed.
 `return_inliers=True` appends cv2.solvePnPRansac's fourth return value: `inliers`, an (n_inliers, 1) int32 array of ascending indices into
 `mkp_qry` / `mkp_ref` (`gn_pnp_ransac_report`); `return_residuals=True` after it the per-point pixel residual (n,) f32 at the returned pose.
+
+`compute_pose_batch(camera_infos, mkp_qry_list, mkp_ref_list, elevations)` is the same seam for B messages that each carry their own
+`CameraInfo`: one `gn_pnp_ransac` call with a per-pair camera table (`gn_set_pair_cameras`), one result per message.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -80,3 +83,71 @@ def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevatio
     if return_residuals:
         out += (res[-1],)
     return out
+
+
+_batch_engine: Optional[PoseEngine] = None
+
+
+def _engine_batch(B: int, max_pts: int) -> PoseEngine:
+    global _batch_engine
+    if _batch_engine is None or _batch_engine.kmax < max_pts or _batch_engine.max_batch < B:
+        _batch_engine = PoseEngine(0, max_batch=max(B, 32), max_kpts=max(max_pts, 1024))
+    return _batch_engine
+
+
+def _object_points(mkp_ref, elevation) -> np.ndarray:
+    """compute_pose's lift: reference keypoint + the DEM cell under it (z = 0 without a raster), f32 [n][3]"""
+    obj = np.zeros((len(mkp_ref), 3), np.float32)
+    obj[:, :2] = mkp_ref
+    if elevation is not None:
+        cell = np.floor(np.asarray(mkp_ref)).astype(np.intp)
+        obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
+    return obj
+
+
+def compute_pose_batch(camera_infos: Sequence, mkp_qry_list: Sequence[np.ndarray], mkp_ref_list: Sequence[np.ndarray],
+                       elevations: Sequence[Optional[np.ndarray]], *, use_distortion: bool = False, ransac_iterations: Optional[int] = None,
+                       return_inliers: bool = False, engine: Optional[PoseEngine] = None) -> List[Optional[Tuple[np.ndarray, ...]]]:
+    """compute_pose for B messages with their own CameraInfo each, as ONE PnP call: message b is solved with camera_infos[b].k (and, with
+    use_distortion, camera_infos[b].d) through a per-pair camera table.  Returns a list with, per message, what compute_pose returns: (R, t),
+    with return_inliers (R, t, inliers), or None (fewer than 4 points, or no model).
+    use_distortion=True reads every camera_info.d through distortion_of (an unsupported model raises, before any GPU call) and runs the
+    plumb-bob kernels for the whole batch whenever any message has a non-zero coefficient: a message without coefficients is then a pinhole
+    camera run through them -- the same pose as compute_pose's up to rounding (1e-8 relative), the same bits for the messages that have some."""
+    B = len(camera_infos)
+    if not (len(mkp_qry_list) == len(mkp_ref_list) == len(elevations) == B):
+        raise ValueError("compute_pose_batch: camera_infos, mkp_qry_list, mkp_ref_list and elevations must have one entry per message")
+    iterations = RANSAC_ITERATIONS if ransac_iterations is None else check_ransac_iterations(ransac_iterations)
+    dists = None
+    if use_distortion:
+        dists = np.zeros((B, 5), np.float64)
+        for b, ci in enumerate(camera_infos):
+            d = distortion_of(ci)
+            if d.size not in (0, 4, 5):
+                raise ValueError(f"message {b}: {d.size} distortion coefficients (plumb-bob has 4 or 5)")
+            dists[b, :d.size] = d
+        if not dists.any():
+            dists = None      # no message is distorted: the pinhole kernels, as compute_pose runs them
+    results: List[Optional[Tuple[np.ndarray, ...]]] = [None] * B
+    live = [b for b in range(B) if len(mkp_qry_list[b]) >= 4]      # (compute_pose: fewer than 4 points = no pose)
+    if not live:
+        return results
+    n = np.array([len(mkp_qry_list[b]) for b in live], np.int32)
+    S = int(n.max())
+    eng = engine or _engine_batch(len(live), S)
+    obj = np.zeros((len(live), S, 3), np.float32)
+    img = np.zeros((len(live), S, 2), np.float32)
+    for k, b in enumerate(live):
+        obj[k, :n[k]] = _object_points(mkp_ref_list[b], elevations[b])
+        img[k, :n[k]] = np.asarray(mkp_qry_list[b], np.float32)
+    K = np.stack([np.asarray(camera_infos[b].k, np.float64).reshape(3, 3) for b in live])
+    cams, model = eng.pair_cameras(K, None if dists is None else dists[live])
+    res = eng.pnp_ransac(eng.to_device("cpb_obj", obj), eng.to_device("cpb_img", img), eng.to_device("cpb_n", n, torch.int32), None, iterations,
+                         min_pts=4, report=return_inliers, cameras=cams, camera_model=model)
+    R, t, n_inl, ok = eng.to_host(*res[:4])
+    idx = eng.to_host(res[-2])[0] if return_inliers else None
+    for k, b in enumerate(live):
+        if not ok[k]:
+            continue
+        results[b] = (R[k], t[k]) + ((idx[k, :int(n_inl[k])].reshape(-1, 1).astype(np.int32),) if return_inliers else ())
+    return results

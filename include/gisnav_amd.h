@@ -401,6 +401,28 @@ int gn_get_distortion(const gn_ctx* ctx, double* d5_host);
 int gn_undistort_points(gn_ctx* ctx, int B, const float* img, const int32_t* n_pts, int kstride,
                         const double* K9_host, int to_pixels, float* out, void* stream);
 
+/* Per-pair cameras: one camera per pair of a batch instead of one K9_host (and one gn_set_distortion state) per call -- frames of several
+ * vehicles, each with its own CameraInfo, in one call.
+ * cams: DEVICE [n][GN_PAIR_CAMERA_DOUBLES] f64, row b = the camera of pair b of every later call.
+ * model 0: the pinhole instantiations (coefficient columns ignored); 1: the plumb-bob instantiations for every pair
+ * (a row of zero coefficients is a pinhole camera run through them).  cams = NULL or n = 0 switches the table off.
+ * Sticky host-side state like gn_set_distortion, off by default; n < 0, n > max_batch or a model outside {0, 1} returns GN_ERR_ARG
+ * (gn_last_error names this setter) and leaves the state as it was.  Off, every output is bit for bit what it was and nothing more is
+ * launched, copied or read.
+ * While a table is set it rules every gn_pnp_ransac(_cov|_report), gn_estimate(_cov|_report), gn_vo_estimate(_cov|_report) and
+ * gn_undistort_points call: a call with B > n returns GN_ERR_ARG; K9_host may be NULL and is ignored; the gn_set_distortion state is ignored
+ * for those calls (it stays stored and applies again once the table is off).  Every mode works: gn_set_overlap, gn_set_substreams (a group
+ * reads its own rows), gn_set_deferred_join, the certificate's re-runs (a re-run pair takes its row with it), more than 16 RANSAC
+ * iterations, point pruning, gn_set_active_kpts.
+ * Lifetime: the table is an input of the call, like n_q: read in stream order (the overlapped PnP stage reads a copy made in stream order),
+ * the pointer and the model captured when the call is issued; the caller keeps it alive and unchanged as long as the call's other inputs --
+ * until gn_flush under gn_set_deferred_join or the deferred certificate.  The rows are not validated (they are device memory): fx, fy > 0
+ * and finite values are the caller's to ensure (PoseEngine.pair_cameras checks them on the host). */
+#define GN_PAIR_CAMERA_DOUBLES 9      /* fx, fy, cx, cy, k1, k2, p1, p2, k3 */
+int gn_set_pair_cameras(gn_ctx* ctx, const double* cams, int n, int model);
+/* The table in effect: each pointer may be NULL; returns 1 when on, 0 when off (then *cams = NULL, *n = 0, *model = 0). */
+int gn_get_pair_cameras(const gn_ctx* ctx, const double** cams, int* n, int* model);
+
 /* PoseNode._pose lines 246-308 for B pairs: match -> gather -> MIN_MATCHES gate -> PnP. */
 int gn_estimate(gn_ctx* ctx, int B, int kpt_format,
                 const float* desc_q, const float* kpt_q, const int32_t* n_q, int stride_q,
