@@ -314,7 +314,7 @@ struct gn_ctx {
                   uint16_t* wfh = nullptr; float acc_scale = 1.f; };   // wfh: fp16 pairs in fragment order (contexts of the f16x2 mode)
   SpConv sp[12];
   std::vector<void*> sp_allocs; int sp_h = 0, sp_w = 0, sp_chunk = 0, sp_cap = 0, sp_max = 0;
-  float *sp_x = nullptr, *sp_y = nullptr, *sp_z = nullptr, *sp_maps[6] = {};
+  float *sp_x = nullptr, *sp_y = nullptr, *sp_z = nullptr, *sp_maps[3] = {};      // full-resolution maps: scores, simple_nms output, score sink of callers without a score pointer
   int *sp_cand = nullptr, *sp_counts = nullptr, *sp_index = nullptr;
   // visual-odometry matcher workspace (gn_vo_match)
   float* vo_norm2 = nullptr; int32_t* vo_nn_idx = nullptr; float* vo_nn_dist = nullptr; uint8_t* vo_good = nullptr;
@@ -2700,7 +2700,7 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     ctx->sp_y = (float*)alloc(full * 64 * sizeof(float));
     ctx->sp_z = (float*)alloc((size_t)chunk * h * w * 256 * sizeof(float));
     bool ok = ctx->sp_x && ctx->sp_y && ctx->sp_z;
-    for (int k = 0; k < 6; ++k) { ctx->sp_maps[k] = (float*)alloc(full * sizeof(float)); ok = ok && ctx->sp_maps[k]; }
+    for (int k = 0; k < 3; ++k) { ctx->sp_maps[k] = (float*)alloc(full * sizeof(float)); ok = ok && ctx->sp_maps[k]; }
     ctx->sp_cand = (int*)alloc((size_t)chunk * cap * 2 * sizeof(int));      // (raster index, score bits) pairs
     ctx->sp_counts = (int*)alloc((size_t)chunk * 4 * sizeof(int));
     ctx->sp_index = (int*)alloc((size_t)chunk * 2048 * sizeof(int));
@@ -2719,11 +2719,9 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     const bool hm = split && ctx->sp[i].wfh != nullptr;
     const bool half_io = hm && ctx->sp_split == 2;
     // split mode (round 5): every activation between the layers travels as hm16 records (k_sp_conv_s); the two head outputs stay f32
-    // GN_SP_FP16 with k_sp_conv_h16 (knob 24 = 2): fp16 activations all the way to the two head outputs (the single-product staging rounds the same
-    // values to fp16 anyway); with the older kernels only layers 1 .. 6 read and layers 1 .. 5 write fp16
-    const bool h_all = gn::g_sp_conv_h == 2;
-    const int in_fmt = hm16_io ? 2 : (half_io && i >= 1 && (h_all || i <= 6) ? 1 : 0);
-    const int out_fmt = hm16_io ? (i == 9 || i == 11 ? 0 : 2) : (half_io && i >= 1 && (h_all ? (i != 9 && i != 11) : i <= 5) ? 1 : 0);
+    // GN_SP_FP16 (k_sp_conv_h16): fp16 activations all the way to the two head outputs (the single-product staging rounds the same values to fp16 anyway)
+    const int in_fmt = hm16_io ? 2 : (half_io && i >= 1 ? 1 : 0);
+    const int out_fmt = hm16_io ? (i == 9 || i == 11 ? 0 : 2) : (half_io && i >= 1 && i != 9 && i != 11 ? 1 : 0);
     sp_conv(in, n, hh, ww, ctx->sp[i].cin, ctx->sp[i].wf, ctx->sp[i].b, out, ctx->sp[i].cout_pad, ctx->sp[i].taps, relu, s,
             hm ? ctx->sp[i].wfh : nullptr, ctx->sp[i].acc_scale, ctx->ovf_base + 8, pool, ctx->sp_split == 2, in_fmt, out_fmt,
             (ctx->sp_ts_layer == i && ctx->sp_ts != nullptr) ? ctx->sp_ts : nullptr);
@@ -2737,7 +2735,7 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     hm16_io = split && ctx->sp_split == 1 && gn::g_sp_conv_s != 0 && (size_t)H * W * 256 < 0x7fffffffull;
     for (int i = 1; i < 12; ++i) hm16_io = hm16_io && ctx->sp[i].wfh != nullptr;
     ctx->sp_enc_hm16 = hm16_io;
-    ctx->sp_enc_fp16 = !hm16_io && split && ctx->sp_split == 2 && gn::g_sp_conv_h == 2 && ctx->sp[7].wfh != nullptr;
+    ctx->sp_enc_fp16 = !hm16_io && split && ctx->sp_split == 2 && ctx->sp[7].wfh != nullptr;
     // round 6: in the split-fp16 mode the first convolution is evaluated inside the second one's halo staging (k_sp_conv_s16<., ., true>): its
     // full-resolution 64-channel map -- 0.53 GB of records per 1080p frame -- is neither written nor read; same bits (knob 46 = 0: two launches)
     const bool fuse1 = hm16_io && gn::g_sp_fuse1 && gn::g_sp_conv_s == 2 && ctx->sp[1].cin == 64 && ctx->sp[1].cout_pad == 64 && ctx->sp[1].taps == 9 && ctx->sp_stop != 1 &&
@@ -2760,9 +2758,9 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     const bool tail_det = ctx->sp_stop <= 0 || ctx->sp_stop >= 9, tail_desc = ctx->sp_stop <= 0 || ctx->sp_stop >= 11;
     if (tail_det) {
     sp_scores(Z, ctx->sp[9].cout_pad, ctx->sp_maps[0], n, h, w, s);
-    sp_nms(ctx->sp_maps[0], n, H, W, 4, ctx->sp_maps[1], ctx->sp_maps[2], ctx->sp_maps[3], ctx->sp_maps[4], ctx->sp_maps[5], s);
-    sp_select(ctx->sp_maps[5], n, H, W, 0.005f, 4, ctx->sp_cand, ctx->sp_counts, ctx->sp_cap, max_kpts,
-              kpt_xysa + (size_t)b0 * max_kpts * 4, score ? score + (size_t)b0 * max_kpts : ctx->sp_maps[1], ctx->sp_index, max_kpts, s);
+    sp_nms(ctx->sp_maps[0], n, H, W, ctx->sp_maps[1], s);
+    sp_select(ctx->sp_maps[1], n, H, W, 0.005f, 4, ctx->sp_cand, ctx->sp_counts, ctx->sp_cap, max_kpts,
+              kpt_xysa + (size_t)b0 * max_kpts * 4, score ? score + (size_t)b0 * max_kpts : ctx->sp_maps[2], ctx->sp_index, max_kpts, s);
     }
     conv(10, Y, X, n, h, w, 1);            conv(11, X, Z, n, h, w, 0);                          // descriptor head: Z = raw descriptor map [h][w][256]
     if (tail_desc) sp_describe(Z, n, h, w, kpt_xysa + (size_t)b0 * max_kpts * 4, ctx->sp_counts, max_kpts, max_kpts, desc + (size_t)b0 * max_kpts * 256, s);
@@ -2795,7 +2793,7 @@ int64_t gn_debug_read(gn_ctx* ctx, const char* name, void* host_out, int64_t max
       ws_ent,
       {"sp_enc", ctx->sp_y, ctx->sp_y ? (size_t)ctx->sp_chunk * (ctx->sp_h / 8) * (ctx->sp_w / 8) * 128 : 0},          // SuperPoint: encoder output of the last pass, NHWC
       {"sp_scores", ctx->sp_maps[0], ctx->sp_maps[0] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},             // softmax + depth-to-space scores
-      {"sp_nms", ctx->sp_maps[5], ctx->sp_maps[5] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},                // after simple_nms
+      {"sp_nms", ctx->sp_maps[1], ctx->sp_maps[1] ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w : 0},                // after simple_nms
       {"sp_counts", ctx->sp_counts, ctx->sp_counts ? (size_t)ctx->sp_chunk * 4 : 0},                                    // per image: candidates, keypoints, candidates seen by the select
       {"sp_cand", ctx->sp_cand, ctx->sp_cand ? (size_t)ctx->sp_chunk * ctx->sp_cap * 2 : 0},                            // (raster index, score bits) pairs, [image][cap]
       {"sp_x", ctx->sp_x, ctx->sp_x ? (size_t)ctx->sp_chunk * ctx->sp_h * ctx->sp_w * 64 : 0},                         // raw words of the two activation buffers
@@ -2928,6 +2926,8 @@ static bool retired_variant(int which, int value) {
                    value == 71 || value == 72 || value >= 1000;
     case 8: return value != 0 && value != 1;
     case 12: return value != 0 && value != 8 && value != 136;
+    case 24: case 36: return true;            // SuperPoint's older single-product kernels and the 16-launch simple_nms
+    case 34: return value != 0 && value != 2; // ... and its 3 x 3 k_sp_conv_s (1): the round-2 kernels (0) and the shipped form (2) live on
     case 42: return (value & 0xff) != 0;      // LoFTR's forms of rounds 3-4; bits 8.. (lf_conv's cost model) live on
     default: return false;
   }
@@ -2960,9 +2960,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 19) ctx->qkv_fused = value;
   else if (which == 20) ctx->qkv_stamps = value;
   else if (which == 21) ctx->sp_split = value;
-  else if (which == 24) gn::g_sp_conv_h = value;
   else if (which == 34) gn::g_sp_conv_s = value;
-  else if (which == 36) gn::g_sp_nms_fused = value;
   else if (which == 40) gn::g_sp_select_stream = value;
   else if (which == 41) gn::g_gemm_m64 = value;
   else if (which == 42) gn::g_lf_conv_knob = value;

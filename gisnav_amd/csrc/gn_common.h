@@ -156,7 +156,6 @@ bool ffn_selects_128(const FfnArgs& a);   // true when launch_ffn_fused(a) dispa
 void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s);   // gn_ffn128.hip: 128 tokens per workgroup (a.cp set, a.T % 128 == 0); stamps: developer knob 12
 extern int g_ffn_stamps;
 extern int g_ffn_shape;
-extern int g_sp_conv_h;
 void build_weight_fragments(const float* w, int N, int K, float scale, int permute_k, uint16_t* out);   // host arrays; out: 2 * N * K halfs
 
 // ---- attention input projections of the f16x2 mode (gn_qkv.hip): hm16 rows in, bf16 q | k rows and bf16 V^T panels out -------
@@ -443,7 +442,7 @@ void sp_conv1(const float* in, const float* w, const float* bias, float* out, in
 void sp_conv_fused1(const float* gray, const float* w1, const float* b1, int B, int H, int W, const float* bias, float* out, int Cout_pad, hipStream_t s,
                     const uint16_t* wfh, float acc_scale, unsigned int* ovf);   // layers 0 + 1 in one launch (split-fp16 mode, hm16 records out, 2 x 2 max-pool fused)
 extern int g_sp_fuse1;   // out_half: 0 f32, 1 fp16, 2 hm16 records (guarded by ovf)
-extern int g_sp_conv_s, g_sp_nms_fused, g_sp_select_stream;
+extern int g_sp_conv_s, g_sp_select_stream;
 void sp_weight_fragments_hm16(const float* w, int Cout, int Cin, int taps, int Cout_pad, float scale, uint16_t* out);   // host arrays; out: 2 * Cout_pad * taps * Cin halfs
 void sp_conv(const float* in, int B, int H, int W, int Cin, const float* wf, const float* bias, float* out, int Cout_pad, int taps, int relu, hipStream_t s,
              const uint16_t* wfh = nullptr, float acc_scale = 1.f, unsigned int* ovf = nullptr, int pool = 0,
@@ -451,7 +450,7 @@ void sp_conv(const float* in, int B, int H, int W, int Cin, const float* wf, con
                                                                                  // in_half / out_half: 1 = fp16 NHWC activations, 2 = hm16 records (k_sp_conv_s)   // wfh != nullptr: split-fp16 arithmetic; pool: fused 2 x 2 max-pool, out is [H/2][W/2]
 void sp_pool(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);
 void sp_scores(const float* logits, int cp, float* scores, int B, int h, int w, hipStream_t s);
-void sp_nms(const float* scores, int B, int H, int W, int r, float* pooled, float* tmp, float* mask, float* supp, float* aux, hipStream_t s);
+void sp_nms(const float* scores, int B, int H, int W, float* out, hipStream_t s);   // simple_nms(scores, 4)
 void sp_select(const float* nms, int B, int H, int W, float thr, int border, int* cand, int* counts, int cap, int k,
                float* kpt_xysa, float* score, int* kp_index, long long out_stride, hipStream_t s);
 void sp_describe(const float* dmap, int B, int h, int w, const float* kpt_xysa, const int* counts, long long out_stride, int max_k, float* desc, hipStream_t s);

@@ -7,15 +7,13 @@
 //                     matrix instruction v_mfma_f32_32x32x2_f32 (bitwise an fmaf chain): weights are the A operand, fetched
 //                     from L2 straight into registers in MFMA fragment order (re-laid-out once at load time, like gn_ffn.hip);
 //                     output pixels are the B operand, read from an LDS halo tile of 18 x 34 pixels x 32 input channels
-//   k_sp_conv_s       (round 5) the split-fp16 convolution on hm16 activation RECORDS: halo tile and weight fragments by LDS-DMA, unrolled taps,
-//                     scalar VALU-lean epilogue through an LDS slab; bitwise k_sp_conv<., 1, ...>'s results.  Runs the 1 x 1 head layers
-//   k_sp_conv_s16     (round 5) the same with 16-channel slices and four workgroups per CU: the 3 x 3 layers of the split mode (matrix pipe busy 0.72-0.81)
+//   k_sp_conv_s       (round 5) the split-fp16 1 x 1 convolution on hm16 activation RECORDS: tile and weight fragments by LDS-DMA, scalar VALU-lean
+//                     epilogue through an LDS slab; bitwise k_sp_conv<1, 1, ...>'s results.  Runs the 1 x 1 head layers
+//   k_sp_conv_s16     (round 5) the 3 x 3 layers of the split mode: 16-channel slices, unrolled taps, four workgroups per CU (matrix pipe busy 0.72-0.81)
 //   k_sp_conv_h16     (round 5) k_sp_conv_s16's form for GN_SP_FP16 (fp16 activations, one product per block)
-//   k_sp_nms_fused    (round 5) simple_nms in one kernel (the five 9 x 9 pools of a 64 x 32 tile in LDS); k_sp_maxrow/col + k_sp_nms_step stay as knob 36 = 0
+//   k_sp_nms_fused    (round 5) simple_nms in one kernel (the five 9 x 9 pools of a 64 x 32 tile in LDS, restated exactly: -inf padding)
 //   k_sp_pool         2x2 max-pool
 //   k_sp_scores       65-way softmax per 8x8 cell, dustbin dropped, depth-to-space -> full-resolution score map
-//   k_sp_maxrow/col   separable (2 r + 1)^2 max-pool passes of simple_nms (restated exactly: -inf padding)
-//   k_sp_nms_step     the mask algebra of simple_nms between the pools
 //   k_sp_candidates   threshold 0.005 + border 4 -> candidate list (atomic append)
 //   k_sp_select       top-k by score: 4 x 8-bit radix select of the k-th largest score, compaction, rank sort (score descending,
 //                     raster index ascending on ties) -- one workgroup per image
@@ -37,7 +35,7 @@ constexpr int TW = 32;                   // output tile of k_sp_conv: (4 RPW) ro
 constexpr int CH = 32;                   // input channels staged per pass (128 B per pixel in LDS)
 
 template <int OUT_FMT>   // 0: f32 NHWC; 1: the 64-channel map leaves as fp16 (GN_SP_FP16); 2: as hm16 records (16 high terms, 16 residual terms per 16 channels:
-                         // what k_sp_conv_s stages without touching it; the thread's 16 channels are one record group, 64 contiguous bytes)
+                         // what k_sp_conv_s16 stages without touching it; the thread's 16 channels are one record group, 64 contiguous bytes)
 __global__ __launch_bounds__(256) void k_sp_conv1(const float* in, const float* w /*[64][9]*/, const float* bias, float* out, int H, int W, unsigned int* ovf) {
   // the 576 weights + 64 biases sit in LDS: a lane's channel group differs from its neighbours', so reading them from memory was
   // 144 vector loads per thread (the layer ran at 1.5 TB/s of output instead of the HBM rate).  Round 5: a thread owns FOUR horizontally
@@ -142,7 +140,7 @@ struct ConvArgs {
   int relu;
   const uint16_t* wfh; float acc_scale;      // HM variant: weights as fp16 pairs in fragment order (sp_weight_fragments_hm16), scaled by 1 / acc_scale
   unsigned int* ovf;                         // HM variant: raised when an input activation does not fit fp16 (the caller re-runs the exact path)
-  long long* dbg_ts;                         // developer: s_memtime stamps of k_sp_conv_s's phases, [workgroup][32] (tools/sp_phases.py), or nullptr
+  long long* dbg_ts;                         // developer: s_memtime stamps of k_sp_conv_s's phases, [workgroup][32] (knob 35), or nullptr
   int in_half, out_half;                     // GN_SP_FP16 only: the layer reads / writes its NHWC activations as fp16 (half the HBM traffic of the full-resolution layers)
   // k_sp_conv_s16<., ., true> (round 6): the network's FIRST convolution (1 -> 64, 3 x 3 + ReLU) is evaluated while the halo tile is staged, from the
   // gray image itself -- `in` is then unused, Cin = 64
@@ -394,219 +392,29 @@ __global__ __launch_bounds__(256) void k_sp_conv(ConvArgs a) {
   if (HM == 2 && a.out_half) ovf_commit(a.ovf, amax);
 }
 
-// GN_SP_FP16, 3 x 3 layers: the single-product arithmetic of k_sp_conv<9, 2, ...> with a tiling made for it.  With one MFMA per
-// fragment pair that kernel reads 1 KB of LDS per MFMA and the LDS port sets its pace; here a wave owns FOUR pixel rows, the taps are
-// walked column by column (dx), the three weight fragments of a kernel column stay in registers and a pixel fragment (tile row r,
-// column ql + dx) is read ONCE for the up to three taps (dy = r - j) that use it: 12 LDS reads per 24 MFMAs.  The halo tile holds high
-// terms only (64 bytes per pixel: chunk 2 s + hh of pixel (ly, lx) at position (2 s + hh) ^ ((lx >> 2) & 3), conflict-free for the lane
-// groups of ds_read_b128), 18 x 34 pixels = 38 KB, + 24 KB of weight hand-over: two workgroups per CU.
-constexpr int RPW4 = 4, TH4 = 4 * RPW4, LH4 = TH4 + 2, LW4 = TW + 2;
-template <bool POOL>
-__global__ __launch_bounds__(256, 2) void k_sp_conv_h(ConvArgs a) {   // two workgroups per CU: at most 256 registers
-  __shared__ __attribute__((aligned(16))) unsigned char tb[LH4 * LW4 * 64];
-  __shared__ __attribute__((aligned(16))) unsigned char wbuf[2 * 12288];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hh = lane >> 5, ql = lane & 31;
-  const int ogroups = a.Cout / 64;
-  const int img = blockIdx.z / ogroups, og = blockIdx.z % ogroups;
-  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH4;
-  const uint4* wfh = reinterpret_cast<const uint4*>(a.wfh) + lane;
-  auto fsw = [](int lx) { return (lx >> 2) & 3; };
-
-  f32x16 acc[2][RPW4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < RPW4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float amax = 0.f;
-
-  for (int c0 = 0; c0 < a.Cin; c0 += CH) {
-    __syncthreads();     // the previous slice is done with the tile
-    // stage the halo tile of this 32-channel slice: thread -> (pixel, 16-byte chunk of 8 channels); zero outside the image
-    constexpr int NQ = (LH4 * LW4 * 4 + 255) / 256, SB = 10;
-    if (a.in_half) {
-      const uint16_t* inh = reinterpret_cast<const uint16_t*>(a.in) + (long long)img * a.H * a.W * a.Cin;
-#pragma unroll
-      for (int q0 = 0; q0 < NQ; q0 += SB) {
-        uint4 v[SB];
-#pragma unroll
-        for (int e = 0; e < SB; ++e) {
-          const int q = (q0 + e) * 256 + tid;
-          const int pix = q >> 2, c8 = q & 3;
-          const int ly = pix / LW4, lx = pix - ly * LW4;
-          const int gy = y0 + ly - 1, gx = x0 + lx - 1;
-          v[e] = make_uint4(0u, 0u, 0u, 0u);
-          if (q0 + e < NQ && q < LH4 * LW4 * 4 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
-            v[e] = *reinterpret_cast<const uint4*>(inh + ((long long)gy * a.W + gx) * a.Cin + c0 + c8 * 8);
-        }
-#pragma unroll
-        for (int e = 0; e < SB; ++e) {
-          const int q = (q0 + e) * 256 + tid;
-          if (q0 + e >= NQ || q >= LH4 * LW4 * 4) continue;
-          const int pix = q >> 2, c8 = q & 3;
-          const int lx = pix % LW4;
-          *reinterpret_cast<uint4*>(tb + pix * 64 + ((c8 ^ fsw(lx)) * 16)) = v[e];
-        }
-      }
-    } else {
-      const float* in = a.in + (long long)img * a.H * a.W * a.Cin;
-      constexpr int SBF = 5;
-#pragma unroll
-      for (int q0 = 0; q0 < NQ; q0 += SBF) {
-        f32x4 v[SBF][2];
-#pragma unroll
-        for (int e = 0; e < SBF; ++e) {
-          const int q = (q0 + e) * 256 + tid;
-          const int pix = q >> 2, c8 = q & 3;
-          const int ly = pix / LW4, lx = pix - ly * LW4;
-          const int gy = y0 + ly - 1, gx = x0 + lx - 1;
-          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-          v[e][0] = z; v[e][1] = z;
-          if (q0 + e < NQ && q < LH4 * LW4 * 4 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
-            const float* p = in + ((long long)gy * a.W + gx) * a.Cin + c0 + c8 * 8;
-            v[e][0] = *reinterpret_cast<const f32x4*>(p); v[e][1] = *reinterpret_cast<const f32x4*>(p + 4);
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < SBF; ++e) {
-          const int q = (q0 + e) * 256 + tid;
-          if (q0 + e >= NQ || q >= LH4 * LW4 * 4) continue;
-          const int pix = q >> 2, c8 = q & 3;
-          const int lx = pix % LW4;
-          ovf_track(amax, v[e][0].x, v[e][0].y); ovf_track(amax, v[e][0].z, v[e][0].w);
-          ovf_track(amax, v[e][1].x, v[e][1].y); ovf_track(amax, v[e][1].z, v[e][1].w);
-          const h16x4 lo = __builtin_convertvector(v[e][0], h16x4), hi = __builtin_convertvector(v[e][1], h16x4);
-          *reinterpret_cast<h16x4*>(tb + pix * 64 + ((c8 ^ fsw(lx)) * 16)) = lo;
-          *reinterpret_cast<h16x4*>(tb + pix * 64 + ((c8 ^ fsw(lx)) * 16) + 8) = hi;
-        }
-      }
-    }
-    __syncthreads();
-    // weight fragments (high terms) of the three taps of kernel column dx: block tid >> 6 = i * 2 + k-step of tap dy * 3 + dx
-    auto wsrc = [&](int dy, int dx) __attribute__((always_inline)) {
-      const int b = tid >> 6, i = b >> 1, ks = b & 1;
-      return wfh[(size_t)((((2 * og + i) * 9 + (dy * 3 + dx)) * (a.Cin / 16) + (c0 / 16 + ks)) * 2) * 64];
-    };
-    uint4 wn[3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) wn[dy] = wsrc(dy, 0);
-#pragma unroll 1
-    for (int dx = 0; dx < 3; ++dx) {
-      unsigned char* const wb = wbuf + (dx & 1) * 12288;
-#pragma unroll
-      for (int dy = 0; dy < 3; ++dy) *reinterpret_cast<uint4*>(wb + dy * 4096 + (tid >> 6) * 1024 + lane * 16) = wn[dy];
-      if (dx + 1 < 3) {
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) wn[dy] = wsrc(dy, dx + 1);
-      }
-      __syncthreads();     // (the buffer written two columns ago is no longer read: one barrier in between)
-      const int lx = ql + dx;
-#pragma unroll
-      for (int s = 0; s < CH / 16; ++s) {
-        h16x8 fa[3][2];
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-          for (int i = 0; i < 2; ++i) fa[dy][i] = *reinterpret_cast<const h16x8*>(wb + dy * 4096 + (i * 2 + s) * 1024 + lane * 16);
-#pragma unroll
-        for (int r = 0; r < RPW4 + 2; ++r) {
-          const h16x8 fb = *reinterpret_cast<const h16x8*>(tb + ((RPW4 * wave + r) * LW4 + lx) * 64 + (((2 * s + hh) ^ fsw(lx)) * 16));
-#pragma unroll
-          for (int dy = 0; dy < 3; ++dy) {
-            const int j = r - dy;
-            if (j >= 0 && j < RPW4) {
-#pragma unroll
-              for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[dy][i], fb, acc[i][j], 0, 0, 0);
-            }
-          }
-        }
-      }
-    }
-  }
-  // epilogue: lane = pixel (row RPW4 wave + j, column ql); registers 4 g + c = output channels 32 i + 8 g + 4 hh + c
-  const int gx = x0 + ql;
-  const float ascale = a.acc_scale;
-  if (POOL) {
-#pragma unroll
-    for (int jp = 0; jp < RPW4 / 2; ++jp) {
-      const int gy = y0 + RPW4 * wave + 2 * jp;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int c = 64 * og + 32 * i + 8 * g + 4 * hh;
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + c);
-          f32x4 m;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float v0 = acc[i][2 * jp][4 * g + e] * ascale + b4[e], v1 = acc[i][2 * jp + 1][4 * g + e] * ascale + b4[e];
-            if (a.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-            float mv = fmaxf(v0, v1);
-            mv = fmaxf(mv, __shfl_xor(mv, 1));
-            m[e] = mv;
-          }
-          const bool wr = !(ql & 1) && gy + 1 < a.H && gx + 1 < a.W;
-          const long long o = (long long)img * (a.H / 2) * (a.W / 2) * a.Cout + ((long long)(gy >> 1) * (a.W / 2) + (gx >> 1)) * a.Cout + c;
-          if (a.out_half) {
-            ovf_track(amax, m.x, m.y); ovf_track(amax, m.z, m.w);
-            if (wr) *reinterpret_cast<h16x4*>(reinterpret_cast<uint16_t*>(a.out) + o) = __builtin_convertvector(m, h16x4);
-          } else if (wr) {
-            *reinterpret_cast<f32x4*>(a.out + o) = m;
-          }
-        }
-    }
-    ovf_commit(a.ovf, amax);
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < RPW4; ++j) {
-    const int gy = y0 + RPW4 * wave + j;
-    if (gy >= a.H || gx >= a.W) continue;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = 64 * og + 32 * i + 8 * g + 4 * hh;
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(a.bias + c);
-        f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-        v = v * ascale + b4;
-        if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        const long long o = (long long)img * a.H * a.W * a.Cout + ((long long)gy * a.W + gx) * a.Cout + c;
-        if (a.out_half) {
-          ovf_track(amax, v.x, v.y); ovf_track(amax, v.z, v.w);
-          *reinterpret_cast<h16x4*>(reinterpret_cast<uint16_t*>(a.out) + o) = __builtin_convertvector(v, h16x4);
-        } else {
-          *reinterpret_cast<f32x4*>(a.out + o) = v;
-        }
-      }
-  }
-  ovf_commit(a.ovf, amax);
-}
-
 // Split-fp16 convolution on hm16 activations (round 5).  What the counters said about k_sp_conv<., 1, ...> (tools/sp_pmc.sh): matrix pipe busy
-// 0.47-0.50 on every layer, 4.5 VALU instructions per MFMA -- the split of the f32 halo tile into fp16 terms while it is staged (~35
+// 0.47-0.50 on every layer, 4.5 VALU instructions per MFMA -- the split of the f32 tile into fp16 terms while it is staged (~35
 // instructions per 16-byte chunk, once per channel slice, per output-channel group and per halo overlap) and the fragment addresses of a
 // run-time tap (dy, dx), none of it in the shadow of an MFMA (a wave's VALU work overlaps the matrix pipe only inside its own instruction
 // stream).  Here the activations TRAVEL as hm16 records -- per pixel and 16 channels: 16 high terms, 16 residual terms (64 B; the same 4 bytes
 // per value as f32, and exactly the terms the staging pass computed: h = fp16(v), m = fp16(v - h)) -- written once by the producer's
 // epilogue, so that
-//  * the halo tile of a 32-channel slice is the pixel records' bytes as they are: staged by LDS-DMA (`buffer_load_dwordx4 ... lds`: 1 KB = 8
+//  * the tile of a 32-channel slice is the pixel records' bytes as they are: staged by LDS-DMA (`buffer_load_dwordx4 ... lds`: 1 KB = 8
 //    pixels per instruction and wave, no register round trip, no VALU; the chunk swizzle is applied on the global side, pixels outside the
 //    image are out-of-range offsets of the buffer descriptor and arrive as zeros: tools/probes/buf_lds.hip);
-//  * the weight fragments of a tap (8 KB) are handed over the same way, one tap ahead;
-//  * the nine taps are unrolled: every fragment read is `one of 12 base registers + immediate`;
+//  * the weight fragments of a slice (8 KB) are handed over the same way;
+//  * every fragment read is `base register + immediate`;
 //  * the fp16-range guard moves to the producer (the values it checked are the producer's outputs).
-// Arithmetic: identical to k_sp_conv<., 1, ...> product for product (same terms, same order of the three products and of the k-steps), so the
-// results are bitwise the same.  Tiles, accumulator layout and the fused 2 x 2 max-pool are k_sp_conv's.
+// k_sp_conv_s is the 1 x 1 form (the two head outputs and whatever 1 x 1 layer sits between record maps): a 12 x 32 pixel tile, no halo.  Arithmetic:
+// identical to k_sp_conv<1, 1, ...> product for product (same terms, same order of the three products and of the k-steps), so the results are
+// bitwise the same.  Tile and accumulator layout are k_sp_conv's.  The 3 x 3 layers run k_sp_conv_s16 below.
 //
-// What the phase stamps of the first version said (tools/sp_phases.py; two workgroups per CU): with the co-resident workgroup in its MFMA
+// What the phase stamps of the first version said (developer knob 35; two workgroups per CU): with the co-resident workgroup in its MFMA
 // stream, a VALU instruction of this one issues about once per 16-20 cycles (the dense MFMA stream of the other wave holds the SIMD's VALU
 // port), so the ~420 VALU instructions of the per-lane staging offsets cost 6.8 k cycles and the ~900 of the epilogue 26 k, of a workgroup's
-// 72 k -- against 21 k cycles of MFMAs.  Hence the VALU diet: a staging instruction covers 8 pixels of ONE halo row (row validity and row
-// offset are scalar: SALU; five per-lane offset registers per tile; the two-pixel tail of a 34-pixel row is an EXEC-masked instruction), the
-// epilogue is 16 instructions per four values (packed fma, max3 for the range guard, v_fma_mix for the residual term), the rows leave as
+// 72 k -- against 21 k cycles of MFMAs.  Hence the VALU diet: a staging instruction covers 8 pixels of ONE tile row (row validity and row
+// offset are scalar: SALU; one per-lane offset register per 8-pixel segment), the
+// epilogue is 16 instructions per four values (scalar fma, max3 for the range guard, v_fma_mix for the residual term), the rows leave as
 // whole 256-byte record segments through a per-wave LDS slab and buffer stores whose descriptor ends at the image border.
 typedef __attribute__((address_space(3))) void* sp_lptr_t;
 // Two wait states behind a 16-byte buffer store with an SGPR soffset, before anything may rewrite its data registers (hipcc's hazard recogniser
@@ -619,15 +427,13 @@ __device__ __forceinline__ float sp_scale_bias(float a, float s, float b) { floa
 __device__ __forceinline__ void sp_store_guard() { asm volatile("s_nop 1" ::: "memory"); }
 __device__ __forceinline__ float sp_resid_lo(unsigned int h, float y) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(y)); return r; }
 __device__ __forceinline__ float sp_resid_hi(unsigned int h, float y) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(y)); return r; }
-template <int TAPS, int RPW, bool POOL, bool OUTHM>   // OUTHM: the output leaves as hm16 records (else f32: the two head outputs)
+template <bool OUTHM>   // OUTHM: the output leaves as hm16 records (else f32: the two head outputs)
 __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
-  constexpr int TH = 4 * RPW;
-  constexpr int HALO = TAPS == 9 ? 1 : 0;
-  constexpr int LW = TW + 2 * HALO, LH = TH + 2 * HALO;
-  constexpr int NSEG = (LW + 7) / 8;                // staging instructions per halo row (8 pixels = 1 KB each)
-  constexpr int TAIL = LW - 8 * (NSEG - 1);         // pixels of the last one
-  constexpr int NROW = (LH + 3) / 4;                // halo rows per wave (row q * 4 + wave)
-  constexpr int TILE_B = ((LH * LW * 128 + 1023) / 1024) * 1024;
+  constexpr int RPW = 3, TH = 4 * RPW;              // three rows per wave: the staged tile is the 12 x 32 output tile (1 x 1: no halo)
+  constexpr int NSEG = TW / 8;                      // staging instructions per tile row (8 pixels = 1 KB each)
+  constexpr int TILE_B = TH * TW * 128;
+  // (the second 8 KB weight buffer is the one the retired 3 x 3 form double-buffered its taps through; it stays allocated so that the kernel's
+  // LDS footprint, like its code, is what shipped before that form went)
   __shared__ __attribute__((aligned(1024))) unsigned char smem[TILE_B + 2 * 8192];
   unsigned char* const tb = smem;
   unsigned char* const wbuf = smem + TILE_B;
@@ -640,10 +446,10 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
   unsigned char* const ibase = const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.in)) + (size_t)img * a.H * a.W * rec;
   const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(ibase, 0, (unsigned int)((size_t)a.H * a.W * rec), 0x00020000);
   const __amdgpu_buffer_rsrc_t irs0 = __builtin_amdgcn_make_buffer_rsrc(ibase, 0, 0, 0x00020000);      // rows outside the image: every lane out of range = zeros
-  // weights: block (((tile * TAPS + tap) * (Cin / 16) + kstep) * 2 + term) of 1 KB; this workgroup's tiles are 2 og, 2 og + 1
+  // weights: block ((tile * (Cin / 16) + kstep) * 2 + term) of 1 KB; this workgroup's tiles are 2 og, 2 og + 1
   const unsigned int ksteps = (unsigned int)a.Cin / 16u;
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wfh) + (size_t)(2 * og) * TAPS * ksteps * 1024, 0, 2u * TAPS * ksteps * 2048u, 0x00020000);
+      const_cast<uint16_t*>(a.wfh) + (size_t)(2 * og) * ksteps * 1024, 0, 2u * ksteps * 2048u, 0x00020000);
   const unsigned int lds_tile = (unsigned int)(size_t)(sp_lptr_t)tb, lds_w = (unsigned int)(size_t)(sp_lptr_t)wbuf;
   const unsigned int lane16 = (unsigned int)lane * 16u;
   const int wg_lin = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -657,59 +463,52 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) b4[i][g] = *reinterpret_cast<const f32x4*>(a.bias + 64 * og + 32 * i + 8 * g + 4 * hh);
 
-  // staging: instruction (row r, segment sg) covers halo pixels lx = 8 sg .. 8 sg + 7 of row r: lane -> (pixel lane >> 3, position lane & 7);
+  // staging: instruction (row r, segment sg) covers tile pixels lx = 8 sg .. 8 sg + 7 of row r: lane -> (pixel lane >> 3, position lane & 7);
   // the piece that belongs at position pos of pixel lx is pos ^ psw(lx).  Per-lane part of the offset (column + piece), one register per segment;
   // the row part (and the channel slice) is the instruction's scalar offset
   unsigned int lanepart[NSEG];
 #pragma unroll
   for (int sg = 0; sg < NSEG; ++sg) {
-    const int lx = 8 * sg + (lane >> 3), gx = x0 + lx - HALO;
+    const int lx = 8 * sg + (lane >> 3), gx = x0 + lx;
     lanepart[sg] = (gx >= 0 && gx < a.W) ? (unsigned int)gx * rec + (unsigned int)(((lane & 7) ^ psw(lx)) * 16) : 0x80000000u;
   }
-  // the wave's two 1 KB weight blocks of a tap: block 4 e + wave = (i * 2 + s) * 2 + pl  ->  source block ((i * TAPS + tap) * ksteps + c0 / 16 + s) * 2 + pl
-  auto weights_dma = [&](int tap, int c0, int buf) __attribute__((always_inline)) {
+  // the wave's two 1 KB weight blocks of a slice: block 4 e + wave = (i * 2 + s) * 2 + pl  ->  source block (i * ksteps + c0 / 16 + s) * 2 + pl
+  auto weights_dma = [&](int c0) __attribute__((always_inline)) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int blk = 4 * e + wave, i = blk >> 2, ks = (blk >> 1) & 1, pl = blk & 1;
-      const unsigned int src = ((((unsigned int)i * TAPS + tap) * ksteps + (unsigned int)(c0 / 16 + ks)) * 2u + pl) * 1024u;
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(lane16), "s"(wrs), "s"(lds_w + (unsigned int)(buf * 8192 + blk * 1024)), "s"(src) : "memory");
+      const unsigned int src = (((unsigned int)i * ksteps + (unsigned int)(c0 / 16 + ks)) * 2u + pl) * 1024u;
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(lane16), "s"(wrs), "s"(lds_w + (unsigned int)(blk * 1024)), "s"(src) : "memory");
     }
   };
   auto dma_wait = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
 
   auto stage_issue = [&](int c0) __attribute__((always_inline)) {
 #pragma unroll
-    for (int q = 0; q < NROW; ++q) {
+    for (int q = 0; q < RPW; ++q) {      // tile rows of this wave: q * 4 + wave
       const int r = q * 4 + wave;
-      if (r < LH) {
-        const int gy = y0 + r - HALO;
+      // (r < TH and the two `>= 0` tests hold for every wave of a launch; the compiler cannot know it -- `wave` is a readfirstlane, x0 and y0 are
+      // products of block indices -- so they are instructions of the kernel that ships, and they stay with it)
+      if (r < TH) {
+        const int gy = y0 + r;
         const bool rv = gy >= 0 && gy < a.H;
         const __amdgpu_buffer_rsrc_t rs = rv ? irs : irs0;
         const unsigned int soff = rv ? (unsigned int)(gy * a.W) * rec + (unsigned int)(c0 * 4) : 0u;
-        const unsigned int dst = lds_tile + (unsigned int)(r * LW * 128);
+        const unsigned int dst = lds_tile + (unsigned int)(r * TW * 128);
 #pragma unroll
-        for (int sg = 0; sg < NSEG; ++sg) {
-          if (sg + 1 < NSEG || TAIL == 8)
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(lanepart[sg]), "s"(rs), "s"(dst + (unsigned int)(sg * 1024)), "s"(soff) : "memory");
-          else     // the row's last TAIL pixels: the other lanes must not write (their slots are the next row's first pixels)
-            asm volatile("s_mov_b32 m0, %2\n\ts_mov_b64 exec, %4\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds\n\ts_mov_b64 exec, -1" ::"v"(lanepart[sg]), "s"(rs), "s"(dst + (unsigned int)(sg * 1024)), "s"(soff), "n"((1ull << (8 * TAIL)) - 1ull) : "memory");
-        }
+        for (int sg = 0; sg < NSEG; ++sg)
+          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(lanepart[sg]), "s"(rs), "s"(dst + (unsigned int)(sg * 1024)), "s"(soff) : "memory");
       }
     }
-    weights_dma(0, c0, 0);
+    weights_dma(c0);
   };
   stage_issue(0);
   stamp(1);
   // (behind the first requests, in the shadow of their latency)
-  // fragment addresses: pixel (RPW wave + j + dy, ql + dx), piece 4 s + 2 pl + hh -> base[dx][2 s + pl] + (j + dy) * LW * 128
-  unsigned int fbase[TAPS == 9 ? 3 : 1][4];
+  // fragment addresses: pixel (RPW wave + j, ql), piece 4 s + 2 pl + hh -> fbase[2 s + pl] + j * TW * 128
+  unsigned int fbase[4];
 #pragma unroll
-  for (int dx = 0; dx < (TAPS == 9 ? 3 : 1); ++dx)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int lx = ql + dx;
-      fbase[dx][c] = (unsigned int)((RPW * wave * LW + lx) * 128 + (((2 * c + hh) ^ psw(lx)) * 16));
-    }
+  for (int c = 0; c < 4; ++c) fbase[c] = (unsigned int)((RPW * wave * TW + ql) * 128 + (((2 * c + hh) ^ psw(ql)) * 16));
 
   f32x16 acc[2][RPW];
 #pragma unroll
@@ -722,7 +521,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   for (int c0 = 0; c0 < a.Cin; c0 += CH) {
     if (c0 > 0) {
-      __syncthreads();      // every wave is done with the previous slice's tile and weight buffers
+      __syncthreads();      // every wave is done with the previous slice's tile and weight buffer
       stage_issue(c0);
       stamp(12);
     }
@@ -730,33 +529,26 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
     __syncthreads();
     stamp(c0 == 0 ? 2 : 13);
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-      const int dy = TAPS == 9 ? tap / 3 : 0, dx = TAPS == 9 ? tap % 3 : 0;
-      if (tap + 1 < TAPS) weights_dma(tap + 1, c0, (tap + 1) & 1);      // (that buffer's last readers passed the barrier in front of this tap)
-      const unsigned char* const wb = wbuf + (tap & 1) * 8192;
+    for (int s = 0; s < CH / 16; ++s) {
+      h16x8 fa[2][2], fb[RPW][2];
 #pragma unroll
-      for (int s = 0; s < CH / 16; ++s) {
-        h16x8 fa[2][2], fb[RPW][2];
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) fa[i][pl] = *reinterpret_cast<const h16x8*>(wbuf + ((i * 2 + s) * 2 + pl) * 1024 + lane16);
+#pragma unroll
+      for (int j = 0; j < RPW; ++j)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) fb[j][pl] = *reinterpret_cast<const h16x8*>(tb + fbase[2 * s + pl] + j * TW * 128);
+      // products: W_m X_h, W_h X_m, W_h X_h (small terms first) -- the order of k_sp_conv
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int pl = 0; pl < 2; ++pl) fa[i][pl] = *reinterpret_cast<const h16x8*>(wb + ((i * 2 + s) * 2 + pl) * 1024 + lane16);
-#pragma unroll
-        for (int j = 0; j < RPW; ++j)
-#pragma unroll
-          for (int pl = 0; pl < 2; ++pl) fb[j][pl] = *reinterpret_cast<const h16x8*>(tb + fbase[dx][2 * s + pl] + (j + dy) * LW * 128);
-        // products: W_m X_h, W_h X_m, W_h X_h (small terms first) -- the order of k_sp_conv
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < RPW; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][p == 0 ? 1 : 0], fb[j][p == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
-      }
-      if (tap + 1 < TAPS) { dma_wait(); __syncthreads(); }
-      stamp((c0 == 0 ? 3 : 14) + tap);       // slices beyond the second overwrite the second's stamps
+          for (int j = 0; j < RPW; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][p == 0 ? 1 : 0], fb[j][p == 1 ? 1 : 0], acc[i][j], 0, 0, 0);
     }
+    stamp(c0 == 0 ? 3 : 14);       // slices beyond the second overwrite the second's stamps
   }
   stamp(24);
 
@@ -770,9 +562,9 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
   const float relu_lo = a.relu ? 0.f : -INFINITY;     // ReLU as one v_max_f32 per value, whatever the flag
   constexpr int PSTR = 256 + 16;                      // slab bytes per pixel (the pad spreads the lanes' pieces over the banks)
   constexpr int SLAB = 32 * PSTR;
-  static_assert(4 * SLAB <= TILE_B, "the slabs alias the halo tile");
+  static_assert(4 * SLAB <= TILE_B, "the slabs alias the tile");
   unsigned char* const slab = smem + wave * SLAB;
-  __syncthreads();                                    // every wave is done with the tile and the weight buffers
+  __syncthreads();                                    // every wave is done with the tile and the weight buffer
   stamp(26);
   auto put4 = [&](int p, int i, int g, f32x2v v0, f32x2v v1) __attribute__((always_inline)) {      // v0, v1: scaled + biased (+ ReLU'd) values of channels c .. c + 3
     const int cl = 32 * i + 8 * g + 4 * hh;
@@ -792,42 +584,6 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
   unsigned char* const obase = reinterpret_cast<unsigned char*>(a.out) + (size_t)og * 256;
   const unsigned int rd = (unsigned int)((lane >> 4) * PSTR + (lane & 15) * 16);                     // read-back address inside the slab
   const unsigned int so = (unsigned int)(lane >> 4) * (unsigned int)orec + (unsigned int)(lane & 15) * 16u;   // ... and inside the output row
-  if (POOL) {
-    static_assert(!POOL || RPW == 2, "the fused pool pairs the two rows of a wave");
-    const int gy = y0 + RPW * wave;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x2v m[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const f32x2v bk = {b4[i][g][2 * k], b4[i][g][2 * k + 1]};
-          // (ascale is a power of two: the fused multiply-add rounds like the multiplication followed by the addition)
-          const f32x2v v0 = {sp_scale_bias(acc[i][0][4 * g + 2 * k], ascale, bk[0]), sp_scale_bias(acc[i][0][4 * g + 2 * k + 1], ascale, bk[1])};
-          const f32x2v v1 = {sp_scale_bias(acc[i][RPW - 1][4 * g + 2 * k], ascale, bk[0]), sp_scale_bias(acc[i][RPW - 1][4 * g + 2 * k + 1], ascale, bk[1])};
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            float mv = fmaxf(fmaxf(v0[e], v1[e]), relu_lo);      // max(relu(a), relu(b)) = relu(max(a, b))
-            mv = fmaxf(mv, __shfl_xor(mv, 1));
-            m[k][e] = mv;
-          }
-        }
-        if (!(ql & 1)) put4(ql >> 1, i, g, m[0], m[1]);
-      }
-    if (out_hm) ovf_commit(a.ovf, amax);
-    const size_t prow = ((size_t)img * (a.H / 2) + (gy >> 1)) * (a.W / 2) + (x0 >> 1);
-    const int npix = gy + 1 < a.H ? min(16, (a.W - x0) / 2) : 0;
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(obase + prow * orec, 0, npix > 0 ? (unsigned int)((npix - 1) * orec + 256) : 0u, 0x00020000);
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const u32x4_sp v = *reinterpret_cast<const u32x4_sp*>(slab + rd + it * 4 * PSTR);
-      __builtin_amdgcn_raw_buffer_store_b128(v, ors, so, (unsigned int)(it * 4) * (unsigned int)orec, 0);
-      sp_store_guard();
-    }
-    stamp(25);
-    return;
-  }
 #pragma unroll
   for (int j = 0; j < RPW; ++j) {
     const int gy = y0 + RPW * wave + j;
@@ -863,8 +619,9 @@ __global__ __launch_bounds__(256, 2) void k_sp_conv_s(ConvArgs a) {
 // 35 KB per workgroup, accumulators for two rows per wave -> up to four workgroups (16 waves) per CU, so that a staging workgroup leaves others on
 // the matrix pipe (with two per CU the full-resolution layer ran at HBM time PLUS MFMA time).  The weight fragments run two taps ahead through
 // three 4 KB buffers, across the slice boundaries (they do not depend on the tile), and are waited for with a counted vmcnt.  LDS pixel layout:
-// 64 bytes = pieces 2 pl + hh at position piece ^ ((lx >> 2) & 3) (k_sp_conv_h's).  Same products, but the k order is (slice of 16, tap) instead
-// of (slice of 32, tap, k-step): results equal k_sp_conv_s's to f32 rounding, not bitwise.
+// 64 bytes per halo pixel (ly, lx) = four 16-byte pieces, piece 2 pl + hh (term pl, channel half hh) at position piece ^ ((lx >> 2) & 3): conflict-free
+// for the lane groups of ds_read_b128.  Same products as k_sp_conv<9, 1, ...>, but the k order is (slice of 16, tap) instead of (slice of 32, tap,
+// k-step): results equal that kernel's to f32 rounding, not bitwise.
 // FUSE1 (round 6): this is the network's SECOND convolution and the first one (1 -> 64 channels, 3 x 3, ReLU) is not a launch of its own
 // any more: its 64-channel full-resolution map -- 0.53 GB of hm16 records per 1080p frame, written by k_sp_conv1 and read straight back here -- never
 // exists.  A slice's halo tile (10 x 34 pixels x 16 channels) is COMPUTED into LDS from a 12 x 36 patch of the gray image: per pixel and channel the fma
@@ -1146,11 +903,10 @@ __global__ __launch_bounds__(256, 3) void k_sp_conv_s16(ConvArgs a) {
 }
 
 // GN_SP_FP16 (one fp16 product per block, fp16 NHWC activations: the arithmetic BASELINE configs[4] names) in k_sp_conv_s16's form, for the 3 x 3 layers
-// whose input already is fp16 (layers 1 .. 6: 85 % of the extractor's flops): a 32-channel slice of an fp16 pixel is the same 64 bytes as a
-// 16-channel slice of an hm16 record, so the halo tile, the LDS-DMA staging, the three-buffer weight pipeline (high-term blocks only: k-steps s = 0, 1
-// of the slice where k_sp_conv_s16 has the two terms) and the slab epilogue are that kernel's; per tap 8 MFMAs on 8 fragment reads.  Replaces
-// k_sp_conv_h there (fragment reuse across the taps of a kernel column, but staging through registers and run-time tap addressing: 0.12 of the
-// single-product issue ceiling).  A tolerance mode like k_sp_conv_h (another k order: f32 rounding).
+// (their input is fp16: every layer behind the first): a 32-channel slice of an fp16 pixel is the same 64 bytes as a
+// 16-channel slice of an hm16 record, so the halo tile (piece 2 s + hh = k-step s, channel half hh, at position piece ^ ((lx >> 2) & 3)), the LDS-DMA
+// staging, the three-buffer weight pipeline (high-term blocks only: k-steps s = 0, 1 of the slice where k_sp_conv_s16 has the two terms) and the slab
+// epilogue are that kernel's; per tap 8 MFMAs on 8 fragment reads.  A tolerance mode: every layer rounds its activations to fp16.
 template <bool POOL, bool OUTH>   // OUTH: fp16 NHWC output (else f32)
 __global__ __launch_bounds__(256, 3) void k_sp_conv_h16(ConvArgs a) {
   constexpr int RPW = 2, TH = 8, LW = TW + 2, LH = TH + 2, TAPS = 9;
@@ -1399,45 +1155,13 @@ __global__ __launch_bounds__(256) void k_sp_scores(const float* logits, int cp, 
   scores[(b * h * 8 + cy * 8 + (lane >> 3)) * (long long)(w * 8) + cx * 8 + (lane & 7)] = e / sum;
 }
 
-// F.max_pool2d(kernel 2 r + 1, stride 1, padding r) split into a row pass and a column pass (-inf padding = ignore)
-__global__ __launch_bounds__(256) void k_sp_maxrow(const float* in, float* out, int H, int W, int r, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int x = (int)(idx % W);
-  const float* row = in + (idx - x);
-  float m = -INFINITY;
-  for (int d = -r; d <= r; ++d) { const int xx = x + d; if (xx >= 0 && xx < W) m = fmaxf(m, row[xx]); }
-  out[idx] = m;
-}
-__global__ __launch_bounds__(256) void k_sp_maxcol(const float* in, float* out, int H, int W, int r, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int x = (int)(idx % W);
-  const long long p = idx / W;
-  const int y = (int)(p % H);
-  const float* col = in + (idx - (long long)y * W);
-  float m = -INFINITY;
-  for (int d = -r; d <= r; ++d) { const int yy = y + d; if (yy >= 0 && yy < H) m = fmaxf(m, col[(long long)yy * W]); }
-  out[idx] = m;
-  (void)x;
-}
-// simple_nms mask algebra.  mode 0: mask = (scores == pooled);  mode 1: supp = pooled(mask) > 0, tmp = supp ? 0 : scores (written to `aux`);
-// mode 2: mask |= (aux == pooled(aux)) & !supp  (supp recomputed as aux == 0 && ... is not exact, so it is kept in `supp`)
-__global__ __launch_bounds__(256) void k_sp_nms_step(int mode, const float* scores, const float* pooled, float* mask, float* supp, float* aux, long long total) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  if (mode == 0) mask[i] = scores[i] == pooled[i] ? 1.f : 0.f;
-  else if (mode == 1) { const float sp = pooled[i] > 0.f ? 1.f : 0.f; supp[i] = sp; aux[i] = sp != 0.f ? 0.f : scores[i]; }
-  else if (mode == 2) { if (aux[i] == pooled[i] && supp[i] == 0.f) mask[i] = 1.f; }
-  else { /* mode 3: final scores = mask ? scores : 0, in place into aux */ aux[i] = mask[i] != 0.f ? scores[i] : 0.f; }
-}
-
-// simple_nms(scores, 4) in ONE kernel (round 5; the 16 launches above moved 50 full-resolution maps through HBM per call: 0.69 ms per four 1080p
-// frames).  The five 9 x 9 max-pools of the algorithm reach 4 + 2 x 8 = 20 pixels: a workgroup computes a 64 x 32 output tile from the
+// simple_nms(scores, 4) in ONE kernel: mask = (scores == pool(scores)); twice { supp = pool(mask) > 0; aux = supp ? 0 : scores;
+// mask |= (aux == pool(aux)) & !supp }; out = mask ? scores : 0, where pool = F.max_pool2d(kernel 9, stride 1, padding 4).  (As separate
+// full-resolution launches it moved 50 maps through HBM per call: 0.69 ms per four 1080p frames.)  The five 9 x 9 max-pools of the algorithm reach 4 + 2 x 8 = 20 pixels: a workgroup computes a 64 x 32 output tile from the
 // 104 x 72 region around it, every intermediate in LDS; values within 4 k pixels of the region's edge are wrong after k pools and are never
 // read by the tile.  A pool is a row pass and a column pass; one work item = 8 consecutive outputs of a row (column) from 16 inputs held in
 // registers (window maxima by doubling: 45 maximum operations per 8 outputs).  Pixels outside the image are -inf (F.max_pool2d's padding),
-// carry no mask and never become maxima.  Comparisons, selections and their order are those of k_sp_nms_step: identical output.
+// carry no mask and never become maxima.  Comparisons and selections are the oracle's, on the same f32 values: the output equals simple_nms bitwise.
 constexpr int NMS_TX = 64, NMS_TY = 32, NMS_HL = 20, NMS_RW = NMS_TX + 2 * NMS_HL, NMS_RH = NMS_TY + 2 * NMS_HL;
 constexpr int NMS_LP = 8, NMS_PITCH = NMS_RW + 2 * NMS_LP;      // 8 pad columns of -inf on either side (16-byte aligned row segments)
 __device__ __forceinline__ void nms_window9(const float (&v)[16], float (&o)[8]) {
@@ -1804,9 +1528,8 @@ void sp_weight_fragments_hm16(const float* w, int Cout, int Cin, int taps, int C
           }
 }
 
-int g_sp_conv_h = 2;   // developer knob 24: 2 = GN_SP_FP16 3 x 3 layers with fp16 input through k_sp_conv_h16 (round 5), 1 = all through k_sp_conv_h, 0 = through k_sp_conv<9, 2, ...> (the first single-product kernel)
-int g_sp_conv_s = 2;   // developer knob 34: 0 = the split-fp16 mode on f32 activations through k_sp_conv<., 1, ...> (the round-2 kernel); 1 = hm16 activations, k_sp_conv_s
-                       // for every layer (bitwise the round-2 results); 2 = k_sp_conv_s16 for the 3 x 3 layers (5 % faster, another k order: f32 rounding)
+int g_sp_conv_s = 2;   // developer knob 34: 0 = the split-fp16 mode on f32 activations through k_sp_conv<., 1, ...> (the round-2 kernel, also the path of frames
+                       // beyond 8 Mpixel); 2 = hm16 activations: k_sp_conv_s16 for the 3 x 3 layers (another k order: f32 rounding), k_sp_conv_s for the 1 x 1 layers
 void sp_conv1(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, hipStream_t s, int out_half, unsigned int* ovf) {
   const long long n = (long long)H * W;      // threads: (quad of pixels, 16-channel group) = H * W / 4 * 4
   const dim3 grid((unsigned)((n + 255) / 256), 1, B);
@@ -1823,42 +1546,31 @@ void sp_conv(const float* in, int B, int H, int W, int Cin, const float* wf, con
   const bool hm = wfh != nullptr;
   const bool single = hm && single_product;
   if (hm && !single && in_half == 2) {   // split fp16 on hm16 activations
-    if (taps == 9 && g_sp_conv_s == 2) {   // 16-channel slices, 8 x 32 tiles
+    if (taps == 9) {   // 16-channel slices, 8 x 32 tiles
       const dim3 g8((W + TW - 1) / TW, (H + 7) / 8, B * (Cout_pad / 64));
       if (pool) hipLaunchKernelGGL((k_sp_conv_s16<true, true>), g8, dim3(256), 0, s, a);
       else if (out_half == 2) hipLaunchKernelGGL((k_sp_conv_s16<false, true>), g8, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((k_sp_conv_s16<false, false>), g8, dim3(256), 0, s, a);
       return;
     }
-    if (pool) hipLaunchKernelGGL((k_sp_conv_s<9, 2, true, true>), grid, dim3(256), 0, s, a);      // (the pooled layers are inner layers)
-    else if (taps == 9 && out_half == 2) hipLaunchKernelGGL((k_sp_conv_s<9, 3, false, true>), grid, dim3(256), 0, s, a);
-    else if (taps == 9) hipLaunchKernelGGL((k_sp_conv_s<9, 3, false, false>), grid, dim3(256), 0, s, a);
-    else if (out_half == 2) hipLaunchKernelGGL((k_sp_conv_s<1, 3, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_sp_conv_s<1, 3, false, false>), grid, dim3(256), 0, s, a);
+    if (out_half == 2) hipLaunchKernelGGL((k_sp_conv_s<true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_sp_conv_s<false>), grid, dim3(256), 0, s, a);
     return;
   }
-  if (single && taps == 9 && g_sp_conv_h == 2 && in_half == 1) {   // fp16 activations in: k_sp_conv_s16's form
+  if (single && taps == 9) {   // GN_SP_FP16: every 3 x 3 layer behind the first reads fp16 activations (in_half == 1): k_sp_conv_s16's form
     const dim3 g8((W + TW - 1) / TW, (H + 7) / 8, B * (Cout_pad / 64));
     if (pool) hipLaunchKernelGGL((k_sp_conv_h16<true, true>), g8, dim3(256), 0, s, a);     // (the pooled layers write fp16)
     else if (out_half == 1) hipLaunchKernelGGL((k_sp_conv_h16<false, true>), g8, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_sp_conv_h16<false, false>), g8, dim3(256), 0, s, a);
     return;
   }
-  if (single && taps == 9 && g_sp_conv_h) {
-    const dim3 grid4((W + TW - 1) / TW, (H + TH4 - 1) / TH4, B * (Cout_pad / 64));
-    if (pool) hipLaunchKernelGGL((k_sp_conv_h<true>), grid4, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_sp_conv_h<false>), grid4, dim3(256), 0, s, a);
+  if (single) {   // the 1 x 1 head layers of GN_SP_FP16
+    hipLaunchKernelGGL((k_sp_conv<1, 2, 3, false>), grid, dim3(256), 0, s, a);
     return;
   }
   if (pool) {   // 3 x 3 layers only (the SuperPoint blocks that end in a max-pool)
-    if (single) hipLaunchKernelGGL((k_sp_conv<9, 2, 2, true>), grid, dim3(256), 0, s, a);
-    else if (hm) hipLaunchKernelGGL((k_sp_conv<9, 1, 2, true>), grid, dim3(256), 0, s, a);
+    if (hm) hipLaunchKernelGGL((k_sp_conv<9, 1, 2, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_sp_conv<9, 0, 2, true>), grid, dim3(256), 0, s, a);
-    return;
-  }
-  if (single) {
-    if (taps == 9) hipLaunchKernelGGL((k_sp_conv<9, 2, 3, false>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_sp_conv<1, 2, 3, false>), grid, dim3(256), 0, s, a);
     return;
   }
   if (hm) {
@@ -1886,30 +1598,11 @@ void sp_scores(const float* logits, int cp, float* scores, int B, int h, int w, 
   const long long cells = (long long)B * h * w;
   hipLaunchKernelGGL(k_sp_scores, dim3((unsigned)((cells + 3) / 4)), dim3(256), 0, s, logits, cp, scores, h, w, cells);
 }
-// simple_nms(scores, r) -> `aux` (the suppressed score map); scratch: pooled, tmp, mask, supp (each B*H*W floats)
-int g_sp_select_stream = 0;   // developer knob 40: 1 = k_sp_select reads the candidate list from memory in every pass (the path of frames with more than 40 960 candidates)
-int g_sp_nms_fused = 1;   // developer knob 36: 0 = simple_nms as 16 full-resolution launches (the round-1 form)
-void sp_nms(const float* scores, int B, int H, int W, int r, float* pooled, float* tmp, float* mask, float* supp, float* aux, hipStream_t s) {
-  if (g_sp_nms_fused && r == 4) {
-    hipLaunchKernelGGL(k_sp_nms_fused, dim3((W + NMS_TX - 1) / NMS_TX, (H + NMS_TY - 1) / NMS_TY, B), dim3(1024), 0, s, scores, aux, H, W);
-    return;
-  }
-  const long long total = (long long)B * H * W;
-  const dim3 g((unsigned)((total + 255) / 256)), blk(256);
-  auto pool = [&](const float* src) {
-    hipLaunchKernelGGL(k_sp_maxrow, g, blk, 0, s, src, tmp, H, W, r, total);
-    hipLaunchKernelGGL(k_sp_maxcol, g, blk, 0, s, tmp, pooled, H, W, r, total);
-  };
-  pool(scores);
-  hipLaunchKernelGGL(k_sp_nms_step, g, blk, 0, s, 0, scores, pooled, mask, supp, aux, total);
-  for (int it = 0; it < 2; ++it) {
-    pool(mask);
-    hipLaunchKernelGGL(k_sp_nms_step, g, blk, 0, s, 1, scores, pooled, mask, supp, aux, total);
-    pool(aux);
-    hipLaunchKernelGGL(k_sp_nms_step, g, blk, 0, s, 2, scores, pooled, mask, supp, aux, total);
-  }
-  hipLaunchKernelGGL(k_sp_nms_step, g, blk, 0, s, 3, scores, pooled, mask, supp, aux, total);
+// simple_nms(scores, 4) -> `out` (the suppressed score map)
+void sp_nms(const float* scores, int B, int H, int W, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_sp_nms_fused, dim3((W + NMS_TX - 1) / NMS_TX, (H + NMS_TY - 1) / NMS_TY, B), dim3(1024), 0, s, scores, out, H, W);
 }
+int g_sp_select_stream = 0;   // developer knob 40: 1 = k_sp_select reads the candidate list from memory in every pass (the path of frames with more than 40 960 candidates)
 void sp_select(const float* nms, int B, int H, int W, float thr, int border, int* cand, int* counts, int cap, int k,
                float* kpt_xy, float* score, int* kp_index, long long out_stride, hipStream_t s) {
   hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(int), s);

@@ -721,7 +721,8 @@ int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);
  * 5 k_attn16_v5 always, 56 the exact running maximum in every key tile (the path a workgroup of the default kernel falls back to), 60 the
  * optimistic fp16 form, 70 / 73 k_attn_pw whenever it applies (73 with phase stamps), 80 / 81 k_attn_ks always (eight / four waves).  Knob 8: 0 / 1
  * (the 256 x 256 GEMM k_gemm_p2w off / automatic).  Retired timing ablations and rejected experiments (knob 0 = 51-57, 61-67; knob 1 = 41-46,
- * 48, 51-55, 57, 58, 71, 72, >= 1000; knob 8 >= 2; knob 12 other than 0 / 8 / 136; knob 18; knob 42 with any of bits 0-7) return GN_ERR_ARG.  A bench line run with any knob set records it in `debug_variant`.
+ * 48, 51-55, 57, 58, 71, 72, >= 1000; knob 8 >= 2; knob 12 other than 0 / 8 / 136; knob 18; knob 24 and knob 36 with any value, knob 34 other than 0 / 2: SuperPoint's superseded
+ * convolution and simple_nms forms; knob 42 with any of bits 0-7) return GN_ERR_ARG.  A bench line run with any knob set records it in `debug_variant`.
  * Process-wide knobs of late round 5 (every context; the shipped value is 0 unless noted): 41 largest 128 x 128 grid the exact-f32 GEMM leaves to 64-row
  * tiles (320; 0 = never), 42 bits 8 and up: the overhead term of the rows-per-wave cost model of LoFTR's convolutions x 100 (0 = the shipped 0.25; bits
  * 0-7 selected LoFTR's forms of rounds 3-4 and are retired), 43 exact-f32 attention of one or two pairs (bits 0-1: 0 = k_attn_f32_ks, 1 = k_attn_f32 always, 2 = k_attn_f32_ks

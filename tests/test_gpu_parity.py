@@ -337,12 +337,18 @@ def test_c_abi_rejects_bad_arguments(eng256, dev):
 def test_retired_developer_knob_values_are_refused(eng256_h2, state_dict_t, dev):
     """Knob values of retired timing ablations and rejected experiments return an error instead of timing the default kernel under
     their label; the context still matches the oracle afterwards."""
-    for which, value in ((1, 41), (1, 48), (1, 1000), (0, 51), (8, 2), (12, 1), (18, 1), (42, 1), (42, 2), (42, 4), (42, 8), (42, 16), (42, 15)):
+    for which, value in ((1, 41), (1, 48), (1, 1000), (0, 51), (8, 2), (12, 1), (18, 1), (42, 1), (42, 2), (42, 4), (42, 8), (42, 16), (42, 15),
+                         (24, 0), (24, 1), (24, 2), (36, 0), (36, 1), (34, 1)):      # SuperPoint's superseded convolution and simple_nms forms
         assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, which, value) != 0, (which, value)
     try:     # knob 42 keeps its bits 8 and up: the overhead term of the cost model of LoFTR's convolutions
         assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 42, 50 << 8) == 0
     finally:
         eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 42, 0)
+    try:     # knob 34 keeps the round-2 kernels on f32 activations (0, also the path of frames beyond 8 Mpixel) and the shipped form (2)
+        assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 34, 0) == 0
+        assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 34, 2) == 0
+    finally:
+        eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 34, 2)
     p = make_pair(63, n_q=129, n_r=128)
     inp = eng256_h2.stage_inputs([p])
     idx, score, n_match = eng256_h2.match(inp["desc_q"], inp["kpt_q"], inp["n_q"], inp["desc_r"], inp["kpt_r"], inp["n_r"])

@@ -1,4 +1,5 @@
-"""Developer tool: phase stamps (s_memtime) of k_sp_conv_s (knob 34 = 1: the 32-channel-slice form carries the stamps) for SuperPoint layers, 4 x 1080p per call.   python tools/sp_phases.py [layers...]"""
+"""Developer tool of round 5: phase stamps (s_memtime) of the 3 x 3 k_sp_conv_s (knob 34 = 1: the 32-channel-slice form carried the stamps) for SuperPoint layers, 4 x 1080p per call.
+That form is retired and knob 34 = 1 is refused: kept for the record of how docs/DESIGN_HISTORY.md 12.4 measured its phases.   python tools/archive/sp_phases.py [layers...]"""
 import sys
 import numpy as np, torch
 sys.path.insert(0, "/root/repo")
