@@ -53,6 +53,10 @@ SIGNATURES = {
                                      c_f64p, C.c_int, VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gn_set_distortion": (C.c_int, [VP, c_f64p, C.c_int]),
     "gn_get_distortion": (C.c_int, [VP, c_f64p]),
+    "gn_gather_points_scored": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
+    "gn_set_dem_format": (C.c_int, [VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double]),
+    "gn_get_dem_format": (C.c_int, [VP, C.POINTER(C.c_int), c_f64p, c_f64p, C.POINTER(C.c_int), c_f64p]),
+    "gn_dem_last_dropped": (C.c_int, [VP, C.c_int, c_i32p, VP]),
     "gn_set_ransac": (C.c_int, [VP, C.c_int, C.c_float, C.c_double]),
     "gn_get_ransac": (C.c_int, [VP, C.POINTER(C.c_int), c_f32p, c_f64p]),
     "gn_ransac_last_counts": (C.c_int, [VP, C.c_int, c_i32p, c_i32p, VP]),
@@ -90,6 +94,7 @@ SIGNATURES = {
     "gn_vo_estimate_report": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, c_f64p, C.c_double, C.c_int,
                                         VP, VP, VP, VP, VP, C.c_double, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "gn_rotate_crop_center": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, c_f64p, VP]),
+    "gn_stereo_reference_dem": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, VP, c_f64p, VP]),
     "gn_stereo_reference": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, VP, VP, c_f64p, VP]),
     "gn_proj_to_affine": (C.c_int, [C.c_char_p, c_f64p]),
     "gn_wgs84_to_ecef": (C.c_int, [C.c_double, C.c_double, C.c_double, c_f64p]),
@@ -147,6 +152,7 @@ GN_PREC_F16X2_F16X2_ATTN = 5
 GN_FEATURE_SIFT = 0
 GN_FEATURE_SUPERPOINT = 1
 GN_RANSAC_MAX_ITERATIONS = 4096
+GN_DEM_U8, GN_DEM_U16, GN_DEM_I16, GN_DEM_F32 = 0, 1, 2, 3      # element types of an elevation raster (gn_set_dem_format)
 GN_PAIR_CAMERA_DOUBLES = 9   # fx, fy, cx, cy, k1, k2, p1, p2, k3
 GN_KPT_LAF = 0
 GN_KPT_XYSA = 1

@@ -42,7 +42,10 @@ enum Stage { ST_PREP = 0, ST_PROJ, ST_ATTN, ST_FFN, ST_HEAD, ST_GATHER, ST_PNP, 
 struct Call {
   int B = 0, kpt_format = 0, stride_q = 0, stride_r = 0;
   const float *desc_q = nullptr, *kpt_q = nullptr, *desc_r = nullptr, *kpt_r = nullptr; const int32_t *n_q = nullptr, *n_r = nullptr;
-  const uint8_t* dem = nullptr; int H = 0, W = 0;
+  const uint8_t* dem = nullptr; int H = 0, W = 0;      // dem: [B][H][W] elements of demf.type
+  // gn_set_dem_format as the context held it when the call was issued, by value; dropped: the call's rows of the dem_dropped workspace while the
+  // format states a void value (null otherwise) -- a per-pair output like n_match, so slices, staged re-runs and their scatter carry it
+  gn::DemFormat demf; int32_t* dropped = nullptr;
   double *R = nullptr, *t = nullptr; int32_t *n_match = nullptr, *n_inliers = nullptr; uint8_t* ok = nullptr; int64_t* idx = nullptr; float* score = nullptr;
   double *cov = nullptr, *sigma_hat = nullptr; uint8_t* cov_ok = nullptr; double sigma_px = 0.0;   // pose covariance (gn_estimate_cov): null = not asked for
   uint8_t* inlier_mask = nullptr; int32_t* inlier_idx = nullptr; float* reproj_err = nullptr;   // report of the pose stage (gn_estimate_report): each null = not asked for
@@ -66,10 +69,10 @@ struct Call {
 template <typename F, typename... C> void pair_arrays(const Call& h, F&& f, C&... c) {
   f((size_t)h.stride_q * h.in_dim * 4, false, c.desc_q...); f((size_t)h.stride_r * h.in_dim * 4, false, c.desc_r...);
   f((size_t)h.stride_q * h.kw * 4, false, c.kpt_q...); f((size_t)h.stride_r * h.kw * 4, false, c.kpt_r...);
-  f((size_t)4, false, c.n_q...); f((size_t)4, false, c.n_r...); f((size_t)h.H * h.W, false, c.dem...);
+  f((size_t)4, false, c.n_q...); f((size_t)4, false, c.n_r...); f((size_t)h.H * h.W * gn::dem_elem_bytes(h.demf.type), false, c.dem...);
   f((size_t)GN_PAIR_CAMERA_DOUBLES * 8, false, c.cams...);
   f((size_t)72, true, c.R...); f((size_t)24, true, c.t...); f((size_t)4, true, c.n_match...); f((size_t)4, true, c.n_inliers...); f((size_t)1, true, c.ok...);
-  f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...);
+  f(h.km * 16, true, c.idx...); f(h.km * 4, true, c.score...); f((size_t)4, true, c.dropped...);
   f((size_t)288, true, c.cov...); f((size_t)8, true, c.sigma_hat...); f((size_t)1, true, c.cov_ok...);
   f(h.km, true, c.inlier_mask...); f(h.km * 4, true, c.inlier_idx...); f(h.km * 4, true, c.reproj_err...);
 }
@@ -131,6 +134,8 @@ inline long long lists_stride_of(long long km) { return gn::kTileListBase + 2 * 
   X(int64_t, e_idx, km * 2, kWsAlways, nullptr) X(float, e_score, km, kWsAlways, "e_score") X(float, e_mkp, km * 2, kWsAlways, "e_mkp") \
   X(float, e_obj, km * 3, kWsAlways, "e_obj") X(uint8_t, mask_ws, km * 16, kWsAlways, nullptr) X(float, pts_ws, km * 5, kWsAlways, nullptr) \
   X(gn::HypResult, hyp_ws, 16, kWsAlways, "hyp")                                                                                 \
+  /* matches the gather removed as void (gn_set_dem_format with a void value; written and read only then): gn_dem_last_dropped */ \
+  X(int32_t, dem_dropped, 1, kWsAlways, "dem_dropped")                                                                           \
   /* round path of the PnP stage: [kRansacRound + 1][km] masks whatever iterations_count, one state */                           \
   X(uint8_t, rmask_ws, km * (gn::kRansacRound + 1), kWsAlways, "ransac_mask") X(gn::RansacState, rstate_ws, 1, kWsAlways, "ransac_state") \
   X(int, lists, lists_stride_of(km), kWsAlways, "lists") /* work lists of the call as they stand ([0] tiles, [1] attention items, ...) */ \
@@ -223,6 +228,7 @@ struct gn_ctx {
   int precision_api = 0;   // the gn_precision value gn_create was called with
   int feature = 0;         // GN_FEATURE_SIFT / GN_FEATURE_SUPERPOINT (gn_create_ex)
   int ransac_iters = 10; float ransac_reproj = 8.0f; double ransac_conf = 0.99;   // gn_set_ransac: what gn_estimate / gn_vo_estimate pass to the PnP stage
+  gn::DemFormat demf;      // gn_set_dem_format: element type, scale, offset and void value of every `dem` argument (default: uint8, 1, 0, none)
   gn::PnpArgs last_pnp; bool last_pnp_valid = false; const int32_t* last_npts = nullptr;   // the most recent PnP stage (gn_ransac_last_counts)
   int dist_on = 0; double dist[5] = {0, 0, 0, 0, 0};      // gn_set_distortion: plumb-bob (k1, k2, p1, p2, k3) of the PnP stage; off = the pinhole kernels
   // gn_set_pair_cameras: the caller's DEVICE table [pair_cams_n][GN_PAIR_CAMERA_DOUBLES] (null = off) and the model (0 pinhole, 1 plumb-bob) its calls run
@@ -1927,19 +1933,79 @@ int gn_get_uncertain(gn_ctx* ctx, int B, int32_t* host_flags, void* stream) {
   return GN_OK;
 }
 
-int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
-                     const int64_t* idx, const int32_t* n_match, const uint8_t* dem, int H, int W,
-                     float* mkp_q, float* obj, void* stream) {
+namespace {
+// The gather stage under the DEM format `f` (the context's for gn_gather_points, the call's for gn_estimate*).  The default format, and a call
+// without a DEM, launch k_gather as always; otherwise gn_dem.hip's typed lift, and with a void value its one-workgroup-per-pair compaction,
+// which rewrites idx / score / n_match in place and counts into `dropped`.
+int gather_impl(gn_ctx* ctx, const DemFormat& f, int32_t* dropped, int B, int kpt_format, const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
+                int64_t* idx, float* score, int32_t* n_match, const uint8_t* dem, int H, int W, float* mkp_q, float* obj, void* stream) {
   if (!ctx || !kpt_q || !kpt_r || !idx || !n_match || !mkp_q || !obj || B < 1 || B > ctx->max_batch)
     return fail(ctx, GN_ERR_ARG, "bad gn_gather_points argument");
   if (dem && (H < 1 || W < 1)) return fail(ctx, GN_ERR_ARG, "bad DEM shape");
   GN_HIP(hipSetDevice(ctx->device));
-  GatherArgs g;
+  DemGatherArgs d;
+  GatherArgs& g = d.g;
   g.kpt_q = kpt_q; g.stride_q = stride_q; g.kpt_r = kpt_r; g.stride_r = stride_r; g.kpt_format = kpt_format & 0xff;
   g.idx = idx; g.n_match = n_match; g.kmax = ctx->npad; g.B = B; g.dem = dem; g.H = H; g.W = W; g.mkp_q = mkp_q; g.obj = obj;
   StageTimer tm(ctx, (hipStream_t)stream, ST_GATHER);
-  launch_gather(g, (hipStream_t)stream);
+  if (!dem || dem_format_is_default(f)) launch_gather(g, (hipStream_t)stream);
+  else {
+    d.f = f; d.idx = idx; d.score = score; d.n_match = n_match; d.dropped = dropped;
+    launch_gather_dem(d, (hipStream_t)stream);
+  }
   GN_HIP(hipGetLastError());
+  return GN_OK;
+}
+}  // namespace
+
+int gn_gather_points_scored(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
+                            int64_t* idx, float* score, int32_t* n_match, const uint8_t* dem, int H, int W,
+                            float* mkp_q, float* obj, void* stream) {
+  return gather_impl(ctx, ctx ? ctx->demf : DemFormat(), ctx ? ctx->ws.dem_dropped : nullptr, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r,
+                     idx, score, n_match, dem, H, W, mkp_q, obj, stream);
+}
+
+int gn_gather_points(gn_ctx* ctx, int B, int kpt_format, const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
+                     const int64_t* idx, const int32_t* n_match, const uint8_t* dem, int H, int W,
+                     float* mkp_q, float* obj, void* stream) {
+  // (the match list is written only while the context's DEM format states a void value: include/gisnav_amd.h)
+  return gn_gather_points_scored(ctx, B, kpt_format, kpt_q, stride_q, kpt_r, stride_r, const_cast<int64_t*>(idx), nullptr, const_cast<int32_t*>(n_match),
+                                 dem, H, W, mkp_q, obj, stream);
+}
+
+int gn_set_dem_format(gn_ctx* ctx, int type, double scale, double offset, int has_nodata, double nodata) {
+  if (!ctx) return fail(nullptr, GN_ERR_ARG, "gn_set_dem_format: null context");
+  if (type != GN_DEM_U8 && type != GN_DEM_U16 && type != GN_DEM_I16 && type != GN_DEM_F32)
+    return fail(ctx, GN_ERR_ARG, "gn_set_dem_format: type must be GN_DEM_U8, GN_DEM_U16, GN_DEM_I16 or GN_DEM_F32");
+  if (!std::isfinite(scale) || scale == 0.0) return fail(ctx, GN_ERR_ARG, "gn_set_dem_format: scale must be finite and not zero");
+  if (!std::isfinite(offset)) return fail(ctx, GN_ERR_ARG, "gn_set_dem_format: offset must be finite");
+  if (has_nodata && type != GN_DEM_F32) {
+    const double lo = type == GN_DEM_I16 ? -32768.0 : 0.0, hi = type == GN_DEM_U8 ? 255.0 : type == GN_DEM_U16 ? 65535.0 : 32767.0;
+    if (!(nodata >= lo && nodata <= hi) || nodata != std::floor(nodata))
+      return fail(ctx, GN_ERR_ARG, "gn_set_dem_format: nodata is not representable in the element type (an integer within its range)");
+  }
+  ctx->demf.type = type; ctx->demf.scale = scale; ctx->demf.offset = offset;
+  ctx->demf.has_nodata = has_nodata ? 1 : 0; ctx->demf.nodata = has_nodata ? nodata : 0.0;
+  return GN_OK;
+}
+
+int gn_get_dem_format(const gn_ctx* ctx, int* type, double* scale, double* offset, int* has_nodata, double* nodata) {
+  if (!ctx) return GN_ERR_ARG;
+  if (type) *type = ctx->demf.type;
+  if (scale) *scale = ctx->demf.scale;
+  if (offset) *offset = ctx->demf.offset;
+  if (has_nodata) *has_nodata = ctx->demf.has_nodata;
+  if (nodata) *nodata = ctx->demf.nodata;
+  return GN_OK;
+}
+
+int gn_dem_last_dropped(gn_ctx* ctx, int B, int32_t* dropped_host, void* stream) {
+  if (!ctx || B < 1 || B > ctx->max_batch || !dropped_host) return fail(ctx, GN_ERR_ARG, "bad gn_dem_last_dropped argument");
+  if (!ctx->ws.dem_dropped) return fail(ctx, GN_ERR_ARG, "gn_dem_last_dropped: context has no workspaces (a gn_resize failed)");
+  GN_HIP(hipSetDevice(ctx->device));
+  GN_HIP(hipStreamSynchronize((hipStream_t)stream));
+  GN_HIP(hipDeviceSynchronize());      // the gather may sit on the library's own streams (gn_set_substreams)
+  GN_HIP(hipMemcpy(dropped_host, ctx->ws.dem_dropped, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
   return GN_OK;
 }
 
@@ -2086,8 +2152,8 @@ int estimate_impl(gn_ctx* ctx, const View& w, const Call& v, void* stream, int s
                     m_idx, m_score, v.n_match, stream);
   if (rc != GN_OK) return rc;
   if (slot < 0) {
-    rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
-                          w.e_mkp, w.e_obj, stream);
+    rc = gather_impl(ctx, v.demf, v.dropped, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, m_score, v.n_match, v.dem, v.H, v.W,
+                     w.e_mkp, w.e_obj, stream);
     if (rc != GN_OK) return rc;
     return pnp_impl(ctx, w, v.B, w.e_obj, w.e_mkp, v.n_match, ctx->npad, v.K9, v.dist ? v.dk : nullptr, v.ransac_iters, v.ransac_reproj, v.ransac_conf, v.min_matches,
                     v.R, v.t, v.n_inliers, v.ok, v.sigma_px, v.cov, v.sigma_hat, v.cov_ok, stream, report_of(v), pair_cams_of(v));
@@ -2097,8 +2163,8 @@ int estimate_impl(gn_ctx* ctx, const View& w, const Call& v, void* stream, int s
   GN_HIP(hipSetDevice(ctx->device));
   GN_HIP(hipEventRecord(ctx->ev_head[g], s));
   if (ctx->pnp_recorded[slot][g]) GN_HIP(hipStreamWaitEvent(s, ctx->ev_pnp[slot][g], 0));   // the PnP that last read this slot (two calls ago)
-  rc = gn_gather_points(ctx, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, v.n_match, v.dem, v.H, v.W,
-                        o_mkp, o_obj, stream);
+  rc = gather_impl(ctx, v.demf, v.dropped, v.B, v.kpt_format, v.kpt_q, v.stride_q, v.kpt_r, v.stride_r, m_idx, m_score, v.n_match, v.dem, v.H, v.W,
+                   o_mkp, o_obj, stream);
   if (rc != GN_OK) return rc;
   GN_HIP(hipMemcpyAsync(o_nmatch, v.n_match, (size_t)v.B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   // the call's camera rows travel with its match counts: the PnP stream reads the slot's copy, so the caller's table is read in the order of
@@ -2161,6 +2227,7 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
   v.dist = ctx->dist_on; memcpy(v.dk, ctx->dist, sizeof v.dk);      // captured now: a deferred re-run of this call (cert_pend) keeps them
   v.cams = ctx->pair_cams; v.cam_model = ctx->pair_cams_model;      // (the pointer: the caller keeps the table alive as it keeps n_q)
   v.ransac_iters = ctx->ransac_iters; v.ransac_reproj = ctx->ransac_reproj; v.ransac_conf = ctx->ransac_conf;
+  v.demf = ctx->demf; v.dropped = dem && v.demf.has_nodata ? ctx->ws.dem_dropped : nullptr;
   const int groups = std::min(ctx->n_sub, B);
   if (groups <= 1) {
     // An earlier grouped call may be unjoined (deferred join, deferred certificate) and this call works in the whole workspaces, on the
@@ -2472,6 +2539,28 @@ int gn_stereo_reference(gn_ctx* ctx, const uint8_t* bgr, const uint8_t* dem, int
   a.src0 = bgr; a.src1 = dem; a.H = H; a.W = W; a.crop_h = crop_h; a.crop_w = crop_w; a.out0 = out_ref; a.out1 = out_dem;
   rotate_crop_matrices(H, W, angle_degrees, crop_h, crop_w, a.M, &a.dx, &a.dy, back9_host);
   launch_rotate_crop(a, true, (hipStream_t)stream);
+  GN_HIP(hipGetLastError());
+  return GN_OK;
+}
+
+int gn_stereo_reference_dem(gn_ctx* ctx, const uint8_t* bgr, const void* dem, int dem_type, int has_nodata, double nodata, int H, int W,
+                            double angle_degrees, int crop_h, int crop_w, uint8_t* out_ref, void* out_dem, double* back9_host, void* stream) {
+  if (!ctx || !bgr || !dem || !out_ref || !out_dem || H < 1 || W < 1 || crop_h < 1 || crop_w < 1 || crop_h > H || crop_w > W)
+    return fail(ctx, GN_ERR_ARG, "bad gn_stereo_reference_dem argument");
+  if (dem_type != GN_DEM_U8 && dem_type != GN_DEM_U16 && dem_type != GN_DEM_I16 && dem_type != GN_DEM_F32)
+    return fail(ctx, GN_ERR_ARG, "gn_stereo_reference_dem: dem_type must be GN_DEM_U8, GN_DEM_U16, GN_DEM_I16 or GN_DEM_F32");
+  if (has_nodata && dem_type != GN_DEM_F32) {
+    const double lo = dem_type == GN_DEM_I16 ? -32768.0 : 0.0, hi = dem_type == GN_DEM_U8 ? 255.0 : dem_type == GN_DEM_U16 ? 65535.0 : 32767.0;
+    if (!(nodata >= lo && nodata <= hi) || nodata != std::floor(nodata))
+      return fail(ctx, GN_ERR_ARG, "gn_stereo_reference_dem: nodata is not representable in the element type");
+  }
+  GN_HIP(hipSetDevice(ctx->device));
+  DemWarpArgs d;
+  WarpArgs& a = d.w;
+  a.src0 = bgr; a.src1 = nullptr; a.H = H; a.W = W; a.crop_h = crop_h; a.crop_w = crop_w; a.out0 = out_ref; a.out1 = nullptr;
+  d.dem = dem; d.out_dem = out_dem; d.dem_type = dem_type; d.has_nodata = has_nodata ? 1 : 0; d.nodata = has_nodata ? nodata : 0.0;
+  rotate_crop_matrices(H, W, angle_degrees, crop_h, crop_w, a.M, &a.dx, &a.dy, back9_host);
+  launch_rotate_crop_dem(d, (hipStream_t)stream);
   GN_HIP(hipGetLastError());
   return GN_OK;
 }

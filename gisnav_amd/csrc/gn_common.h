@@ -325,6 +325,19 @@ struct GatherArgs {
 };
 void launch_gather(const GatherArgs& a, hipStream_t s);
 
+// Elevation rasters beyond 8 bits (gn_set_dem_format; gn_dem.hip): the element type of GatherArgs::dem, the affine map raw cell -> z and the void value.
+// The default (GN_DEM_U8, 1, 0, no voids) never reaches gn_dem.hip: it is launch_gather above.
+struct DemFormat { int type = 0; double scale = 1.0, offset = 0.0; int has_nodata = 0; double nodata = 0.0; };
+inline bool dem_format_is_default(const DemFormat& f) { return f.type == 0 && f.scale == 1.0 && f.offset == 0.0 && !f.has_nodata; }
+inline size_t dem_elem_bytes(int type) { return type == 0 ? 1 : type == 3 ? 4 : 2; }
+struct DemGatherArgs {
+  GatherArgs g;            // g.dem: elements of f.type; the pair offset is in elements
+  DemFormat f;
+  // voids (f.has_nodata): the match list is compacted in place -- idx, score (null = the call has none), n_match -- and dropped[b] counts the rows removed
+  int64_t* idx = nullptr; float* score = nullptr; int32_t* n_match = nullptr; int32_t* dropped = nullptr;
+};
+void launch_gather_dem(const DemGatherArgs& a, hipStream_t s);
+
 struct HypResult { double R[9]; double t[3]; int good; int valid; };   // one RANSAC hypothesis
 
 // Round path of the PnP stage (iterations_count > 16; DESIGN.md "RANSAC beyond 16 hypotheses"): hypotheses run kRansacRound at a time and
@@ -411,6 +424,9 @@ struct WarpArgs {
   uint8_t* out0; uint8_t* out1;               // out1 != nullptr: two planes [crop_h][crop_w]; else interleaved [crop_h][crop_w][2]
 };
 void launch_rotate_crop(const WarpArgs& a, bool fused_gray, hipStream_t s);
+// gn_stereo_reference_dem: w.src0 = BGR, w.out0 = gray, as the fused form above; the DEM plane has elements of dem_type (w.src1 / w.out1 unused)
+struct DemWarpArgs { WarpArgs w; const void* dem = nullptr; void* out_dem = nullptr; int dem_type = 0, has_nodata = 0; double nodata = 0.0; };
+void launch_rotate_crop_dem(const DemWarpArgs& a, hipStream_t s);
 
 // ---- SIFT (cv2.SIFT_create().detectAndCompute) -------------------------------------------------------------
 constexpr int kSiftMaxOctaves = 12;

@@ -88,6 +88,40 @@ def check_camera_table(cameras, camera_model, B: int) -> None:
         raise ValueError(f"camera_model must be 0 (pinhole) or 1 (plumb-bob), got {camera_model!r}")
 
 
+# element types of an elevation raster (gn_set_dem_format): numpy dtype name -> (GN_DEM_* constant, lowest, highest representable value)
+_DEM_TYPES = {"uint8": (_lib.GN_DEM_U8, 0, 255), "uint16": (_lib.GN_DEM_U16, 0, 65535), "int16": (_lib.GN_DEM_I16, -32768, 32767),
+              "float32": (_lib.GN_DEM_F32, None, None)}
+
+
+def dem_dtype_name(dtype) -> str:
+    """'uint8' / 'uint16' / 'int16' / 'float32' for a torch or numpy dtype of an elevation raster; ValueError for any other."""
+    name = str(dtype).replace("torch.", "") if isinstance(dtype, torch.dtype) else np.dtype(dtype).name
+    if name not in _DEM_TYPES:
+        raise ValueError(f"an elevation raster must be uint8, uint16, int16 or float32, got {name}")
+    return name
+
+
+def check_dem_format(dtype, scale=1.0, offset=0.0, nodata=None) -> Tuple[int, float, float, int, float]:
+    """The library's argument rules for gn_set_dem_format, before any GPU call: (type, scale, offset, has_nodata, nodata) for a raster of
+    `dtype`.  ValueError for another dtype, a scale that is zero or not finite, an offset that is not finite, or -- for the integer types -- a
+    nodata that is not an integer within the type's range.  nodata None = no void value; NaN (float32 only) = the non-finite cells alone."""
+    typ, lo, hi = _DEM_TYPES[dem_dtype_name(dtype)]
+    for name, v in (("dem_scale", scale), ("dem_offset", offset)) + ((("dem_nodata", nodata),) if nodata is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name} must be a number, got {type(v).__name__}")
+    scale, offset = float(scale), float(offset)
+    if not np.isfinite(scale) or scale == 0.0:
+        raise ValueError(f"dem_scale must be finite and not zero, got {scale}")
+    if not np.isfinite(offset):
+        raise ValueError(f"dem_offset must be finite, got {offset}")
+    if nodata is None:
+        return typ, scale, offset, 0, 0.0
+    nodata = float(nodata)
+    if lo is not None and not (lo <= nodata <= hi and nodata == np.floor(nodata)):
+        raise ValueError(f"dem_nodata {nodata} is not representable in {dem_dtype_name(dtype)} (an integer in {lo}..{hi})")
+    return typ, scale, offset, 1, nodata
+
+
 def _k9_ptr(K):
     """K9_host of the C calls: None (NULL) when the call runs with a per-pair table and no matrix was given."""
     return None if K is None else np.ascontiguousarray(np.asarray(K, np.float64).reshape(9)).ctypes.data_as(_lib.c_f64p)
@@ -105,7 +139,7 @@ def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
 def _dev_tensor(t, dtype, device) -> torch.Tensor:
     if isinstance(t, np.ndarray):
         t = torch.from_numpy(np.ascontiguousarray(t))
-    t = t.to(device=device, dtype=dtype, non_blocking=True)
+    t = t.to(device=device, dtype=dtype, non_blocking=True) if dtype is not None else t.to(device=device, non_blocking=True)
     return t.contiguous()
 
 
@@ -144,7 +178,7 @@ class RecordStager:
     """
 
     def __init__(self, engine: "PoseEngine", max_batch: int, max_kpts: int, dem_hw: Tuple[int, int], depth: int = 3, copy_threads: int = 4,
-                 numa: Optional[str] = "auto"):
+                 numa: Optional[str] = "auto", dem_dtype=torch.uint8):
         import os
         from concurrent.futures import ThreadPoolExecutor
         # one rank per GPU: the copy threads of a rank stay on the cores of its GPU's NUMA node (host staging is ~6 ms of memcpy
@@ -168,19 +202,20 @@ class RecordStager:
         # (~6 GB/s) would be slower than the GPU's step; numpy releases the GIL inside the copies
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(copy_threads)), initializer=_pin) if copy_threads > 1 else None
         dev, (H, W) = engine.device, dem_hw
+        self.dem_dtype = getattr(torch, dem_dtype_name(dem_dtype))      # the rasters' element type (set_dem_format): the pinned and device buffers hold it
         self.copy_stream = torch.cuda.Stream(device=dev)
         mk = lambda shape, dt, **kw: torch.empty(shape, dtype=dt, **kw)  # noqa: E731
         self.slots = []
         for _ in range(self.depth):
             host = dict(rec_q=mk((self.B, self.K, 133), torch.float32, pin_memory=True), rec_r=mk((self.B, self.K, 133), torch.float32, pin_memory=True),
-                        dem=mk((self.B, H, W), torch.uint8, pin_memory=True), n=mk((2, self.B), torch.int32, pin_memory=True))
+                        dem=mk((self.B, H, W), self.dem_dtype, pin_memory=True), n=mk((2, self.B), torch.int32, pin_memory=True))
             devb = {k: torch.empty_like(v, device=dev) for k, v in host.items()}
             self.slots.append(dict(host=host, host_np={k: v.numpy() for k, v in host.items()}, dev=devb,
                                    uploaded=torch.cuda.Event(), consumed=torch.cuda.Event(), used=False))
         self._next = 0
 
     def stage(self, msgs) -> dict:
-        """msgs: up to max_batch tuples (query_sift bytes, reference-keypoint bytes, dem (H, W) uint8).  Returns the inputs dict of
+        """msgs: up to max_batch tuples (query_sift bytes, reference-keypoint bytes, dem (H, W) of the stager's dem_dtype).  Returns the inputs dict of
         `PoseEngine.estimate`; call wait() on the compute stream before using it and release() after the last kernel that reads it."""
         slot = self.slots[self._next]
         h = slot["host_np"]
@@ -194,6 +229,8 @@ class RecordStager:
                 raise _lib.GnError(f"pair {b}: {max(len(q), len(r)) // 532} keypoints exceed the stager's max_kpts {self.K}")
             if tuple(np.shape(dem)) != tuple(h["dem"].shape[1:]):
                 raise _lib.GnError(f"pair {b}: DEM raster {tuple(np.shape(dem))}, the stager was built for {tuple(h['dem'].shape[1:])}")
+            if np.asarray(dem).dtype != h["dem"].dtype:
+                raise _lib.GnError(f"pair {b}: DEM raster of {np.asarray(dem).dtype}, the stager was built for {h['dem'].dtype} (dem_dtype)")
 
         self._next = (self._next + 1) % self.depth
         if slot["used"]:
@@ -482,6 +519,44 @@ class PoseEngine:
         _lib.check(self.ctx, self.lib.gn_get_ransac(self.ctx, C.byref(it), C.byref(px), C.byref(conf)), "gn_get_ransac")
         return int(it.value), float(px.value), float(conf.value)
 
+    # set_dem_format: (scale, offset, nodata) for the calls to come -- the element type is each call's dem.dtype -- and what the context
+    # holds right now (gn_set_dem_format's default until a call needs another)
+    _dem_fmt = (1.0, 0.0, None)
+    _dem_applied = (_lib.GN_DEM_U8, 1.0, 0.0, 0, 0.0)
+
+    def set_dem_format(self, scale: float = 1.0, offset: float = 0.0, nodata=None) -> None:
+        """Elevation rasters beyond 8 bits (gn_set_dem_format): z = (float)(raw * scale + offset) for the `dem` of estimate / estimate_bucketed /
+        estimate_images / gather_points, and `nodata` = the raw value of a void cell (None: no voids; NaN: the non-finite cells of a float32
+        raster alone).  A match on a void cell is removed before PnP and the outputs describe the shorter list.  The element type is taken from
+        the dtype of each call's `dem` tensor (uint8 / uint16 / int16 / float32; ValueError otherwise, and for a nodata the type cannot hold).
+        Sticky, captured per call; the default (1, 0, None) with a uint8 raster computes bit for bit what it always did."""
+        check_dem_format(np.float32, scale, offset, None if nodata is None else float("nan"))      # (nodata against the type: per call)
+        if nodata is not None and (isinstance(nodata, bool) or not isinstance(nodata, (int, float, np.integer, np.floating))):
+            raise TypeError(f"dem_nodata must be a number or None, got {type(nodata).__name__}")
+        self._dem_fmt = (float(scale), float(offset), None if nodata is None else float(nodata))
+
+    def dem_format(self) -> Tuple[float, float, Optional[float]]:
+        """(scale, offset, nodata) in effect (set_dem_format)."""
+        return self._dem_fmt
+
+    def _apply_dem_format(self, dem) -> None:
+        """The context's DEM format for a call with raster `dem` (None: nothing to lift)."""
+        if dem is None:
+            return
+        fmt = check_dem_format(dem.dtype, *self._dem_fmt)
+        same = fmt[:4] == self._dem_applied[:4] and (fmt[4] == self._dem_applied[4] or (fmt[4] != fmt[4] and self._dem_applied[4] != self._dem_applied[4]))
+        if not same:
+            _lib.check(self.ctx, self.lib.gn_set_dem_format(self.ctx, *fmt), "gn_set_dem_format")
+            self._dem_applied = fmt
+
+    def dem_last_dropped(self, B: int) -> np.ndarray:
+        """Matches removed as void from pairs 0 .. B-1 of the most recent call that ran with a void value (gn_dem_last_dropped); [B] int32.
+        Synchronises the device."""
+        dropped = np.zeros(int(B), np.int32)
+        rc = self.lib.gn_dem_last_dropped(self.ctx, int(B), dropped.ctypes.data_as(_lib.c_i32p), self._stream())
+        _lib.check(self.ctx, rc, "gn_dem_last_dropped")
+        return dropped
+
     def ransac_last_counts(self, B: int) -> Tuple[np.ndarray, np.ndarray]:
         """Per pair of the most recent PnP stage: (final adapted iteration count, hypotheses actually evaluated), int32 [B] each
         (gn_ransac_last_counts).  Synchronises the device."""
@@ -546,7 +621,7 @@ class PoseEngine:
         dr = np.zeros((B, nr, D), np.float32); kr = np.zeros((B, nr, 4), np.float32)
         n_q = np.zeros(B, np.int32); n_r = np.zeros(B, np.int32)
         h, w = pairs[0].dem.shape
-        dem = np.zeros((B, h, w), np.uint8)
+        dem = np.zeros((B, h, w), np.dtype(dem_dtype_name(pairs[0].dem.dtype)))
         for b, p in enumerate(pairs):
             a, c = len(p.kp_q), len(p.kp_r)
             n_q[b], n_r[b] = a, c
@@ -557,7 +632,7 @@ class PoseEngine:
         f = lambda a, dt: _dev_tensor(a, dt, self.device)  # noqa: E731
         return dict(desc_q=f(dq, torch.float32), kpt_q=f(kq, torch.float32), n_q=f(n_q, torch.int32),
                     desc_r=f(dr, torch.float32), kpt_r=f(kr, torch.float32), n_r=f(n_r, torch.int32),
-                    dem=f(dem, torch.uint8), kpt_format=kpt_format)
+                    dem=f(dem, None), kpt_format=kpt_format)
 
     # ------------------------------------------------------------------ hot path
     def match(self, desc_q, kpt_q, n_q, desc_r, kpt_r, n_r, kpt_format: int = _lib.GN_KPT_XYSA,
@@ -577,14 +652,22 @@ class PoseEngine:
         _lib.check(self.ctx, rc, "gn_match")
         return idx, score, n_match
 
-    def gather_points(self, kpt_q, kpt_r, idx, n_match, dem, kpt_format: int = _lib.GN_KPT_XYSA):
+    def gather_points(self, kpt_q, kpt_r, idx, n_match, dem, kpt_format: int = _lib.GN_KPT_XYSA, score=None):
+        """gn_gather_points: (mkp_q [B,kmax,2], obj [B,kmax,3]) of the match list idx / n_match, the reference side lifted with `dem` under
+        set_dem_format.  With a void value set, idx, n_match and `score` (optional [B,kmax] f32: gn_gather_points_scored) are compacted in
+        place to the matches on valid cells."""
         B = kpt_q.shape[0]
+        self._apply_dem_format(dem)
         mkp_q = torch.zeros((B, self.kmax, 2), dtype=torch.float32, device=self.device)
         obj = torch.zeros((B, self.kmax, 3), dtype=torch.float32, device=self.device)
         H, W = (dem.shape[1], dem.shape[2]) if dem is not None else (0, 0)
-        rc = self.lib.gn_gather_points(self.ctx, B, kpt_format, _ptr(kpt_q), kpt_q.shape[1], _ptr(kpt_r), kpt_r.shape[1],
-                                       _ptr(idx), _ptr(n_match), _ptr(dem), H, W, _ptr(mkp_q), _ptr(obj), self._stream())
-        _lib.check(self.ctx, rc, "gn_gather_points")
+        if score is not None:
+            rc = self.lib.gn_gather_points_scored(self.ctx, B, kpt_format, _ptr(kpt_q), kpt_q.shape[1], _ptr(kpt_r), kpt_r.shape[1],
+                                                  _ptr(idx), _ptr(score), _ptr(n_match), _ptr(dem), H, W, _ptr(mkp_q), _ptr(obj), self._stream())
+        else:
+            rc = self.lib.gn_gather_points(self.ctx, B, kpt_format, _ptr(kpt_q), kpt_q.shape[1], _ptr(kpt_r), kpt_r.shape[1],
+                                           _ptr(idx), _ptr(n_match), _ptr(dem), H, W, _ptr(mkp_q), _ptr(obj), self._stream())
+        _lib.check(self.ctx, rc, "gn_gather_points_scored" if score is not None else "gn_gather_points")
         return mkp_q, obj
 
     def _alloc_cov(self, B: int) -> dict:
@@ -781,6 +864,7 @@ class PoseEngine:
                                    "alternate two output dicts, or flush() between the calls")
             self._last_out_ptr = out["R"].data_ptr()
         dem = inputs.get("dem")
+        self._apply_dem_format(dem)
         H, W = (dem.shape[1], dem.shape[2]) if dem is not None else (0, 0)
         K9 = _k9_ptr(K)
         # (GN_KPT_RECORD inputs carry the descriptors inside the keypoint records: desc_q / desc_r are None)
@@ -823,7 +907,9 @@ class PoseEngine:
         need = np.maximum(np.maximum(n_q_host, n_r_host), 1)
         order = np.argsort(-need, kind="stable")
         perm = torch.as_tensor(order, device=self.device)
-        srt = {k: (v.index_select(0, perm) if isinstance(v, torch.Tensor) else v) for k, v in inputs.items()}
+        # (a uint16 raster is permuted through its int16 view: the same bytes, and an index kernel every torch build has)
+        pick = lambda v: v.view(torch.int16).index_select(0, perm).view(torch.uint16) if v.dtype == torch.uint16 else v.index_select(0, perm)  # noqa: E731
+        srt = {k: (pick(v) if isinstance(v, torch.Tensor) else v) for k, v in inputs.items()}
         tmp = self.alloc_outputs(B, report=report)
         pad_tokens = 0
         try:
@@ -849,8 +935,8 @@ class PoseEngine:
                         report: bool = False, cameras: Optional[torch.Tensor] = None, camera_model: int = 0):
         """Frames -> pose from pixels for B pairs, everything in HBM: one batched SIFT pass over the B camera frames and the
         B map tiles (`gn_sift_detect_and_compute_batch`), the matcher padded to what the batch needs (`gn_set_active_kpts`),
-        then `gn_estimate`.  frames / tiles: (B, H, W) uint8 (numpy or device tensors, one size); dem: (B, H, W) uint8 or
-        None (flat).  report=True: as estimate; `kpt_q` / `kpt_r` [B,S,4] of the extraction are then added to the outputs, so that idx can be
+        then `gn_estimate`.  frames / tiles: (B, H, W) uint8 (numpy or device tensors, one size); dem: (B, H, W) uint8, uint16, int16 or
+        float32 (set_dem_format), or None (flat).  report=True: as estimate; `kpt_q` / `kpt_r` [B,S,4] of the extraction are then added to the outputs, so that idx can be
         resolved to pixel coordinates.  cameras / camera_model (pair_cameras): one camera per frame, as estimate.  Returns (estimate outputs, n_keypoints [2B] int32 on the host: frames first)."""
         from .sift import SIFT
         if sift is None:
@@ -872,7 +958,7 @@ class PoseEngine:
         nd = torch.as_tensor(n, device=self.device)
         if dem is None:
             dem = torch.zeros((B, int(f.shape[1]), int(f.shape[2])), dtype=torch.uint8, device=self.device)
-        inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], dem=to_dev(dem), kpt_format=_lib.GN_KPT_XYSA)
+        inputs = dict(desc_q=desc[:B], kpt_q=kpt[:B], n_q=nd[:B], desc_r=desc[B:], kpt_r=kpt[B:], n_r=nd[B:], dem=dem if isinstance(dem, torch.Tensor) else _dev_tensor(np.asarray(dem), None, self.device), kpt_format=_lib.GN_KPT_XYSA)
         if cameras is not None:
             inputs.update(cameras=cameras, camera_model=camera_model)
         self.set_active_kpts(max(int(n.max()), 1))

@@ -5,6 +5,8 @@ from the result -- the call signature and output dictionary mirrored here.  Mars
 dual-softmax coarse matching and the fine level run in libgisnav_amd.so (`gn_loftr_*`, csrc/gn_loftr.hip)."""
 from __future__ import annotations
 
+import contextlib
+
 import ctypes as C
 from typing import Dict, Optional
 
@@ -234,12 +236,38 @@ class LoFTR:
         return buf[: int(n)]
 
 
+@contextlib.contextmanager
+def _dem_format(engine, dem_scale, dem_offset, dem_nodata):
+    """PoseEngine.set_dem_format for one call (nothing is touched while all three are the defaults)."""
+    if (dem_scale, dem_offset, dem_nodata) == (1.0, 0.0, None):
+        yield
+        return
+    before = engine.dem_format()
+    engine.set_dem_format(dem_scale, dem_offset, dem_nodata)
+    try:
+        yield
+    finally:
+        engine.set_dem_format(*before)
+
+
+def _dem_tensor(dem, dev) -> torch.Tensor:
+    """An elevation raster (or a stack of them) on the device in its own element type: uint8, uint16, int16 or float32 (ValueError otherwise)."""
+    from .engine import dem_dtype_name
+    if not isinstance(dem, torch.Tensor):
+        dem = torch.from_numpy(np.ascontiguousarray(dem))
+    dem_dtype_name(dem.dtype)
+    return dem.to(dev).contiguous()
+
+
 def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Tensor, dem, K, min_matches: int = 15, conf_threshold: float = 0.0,
-               return_covariance: bool = False, dist=None, ransac_iterations=None, return_inliers: bool = False):
+               return_covariance: bool = False, dist=None, ransac_iterations=None, return_inliers: bool = False,
+               dem_scale: float = 1.0, dem_offset: float = 0.0, dem_nodata=None):
     """Camera frame <-> map tile pose with the detector-free matcher in front of the SAME solver as the SIFT / LightGlue path: LoFTR matches
     (`keypoints0` in the frame, `keypoints1` in the tile) -> DEM lift of the tile points (`_shared.py:95-102`) -> solvePnPRansac + Rodrigues
     (`gn_gather_points`, `gn_pnp_ransac`; seam B2).  Everything stays on the device.  frame01 / tile01: (H, W) float in [0, 1];
-    dem: (H, W) uint8 or None.  Returns (R (3,3), t (3,1), n_matches) or None below `min_matches` / when RANSAC finds no model;
+    dem: (H, W) uint8, uint16, int16 or float32 (the raster keeps its dtype), or None; dem_scale / dem_offset / dem_nodata: z = raw * dem_scale +
+    dem_offset, and matches on a cell equal to dem_nodata are dropped before PnP (PoseEngine.set_dem_format, for this call) -- n_matches and
+    the inlier indices then describe the shorter list.  Returns (R (3,3), t (3,1), n_matches) or None below `min_matches` / when RANSAC finds no model;
     with return_covariance also the 6x6 covariance of (rvec, tvec) from the inliers (None when it is not defined) as a fourth entry.
     dist: distCoeffs of the frame's camera for the solver (PoseEngine.set_distortion for this call; None = the engine's state).
     ransac_iterations: cv2.solvePnPRansac's iterationsCount for this call, 1 .. 4096 (None = the reference's 10).
@@ -260,8 +288,11 @@ def loftr_pose(matcher: "LoFTR", engine, frame01: torch.Tensor, tile01: torch.Te
     idx_full = torch.zeros((1, engine.kmax, 2), dtype=torch.int64, device=dev)
     idx_full[0, :n] = idx[0]
     nm = torch.tensor([n], dtype=torch.int32, device=dev)
-    d = None if dem is None else torch.as_tensor(np.ascontiguousarray(dem, np.uint8), device=dev)[None]
-    mkp, obj = engine.gather_points(pad(k0), pad(k1), idx_full, nm, d, _lib.GN_KPT_XYSA)
+    d = None if dem is None else _dem_tensor(dem, dev)[None]
+    with _dem_format(engine, dem_scale, dem_offset, dem_nodata):
+        mkp, obj = engine.gather_points(pad(k0), pad(k1), idx_full, nm, d, _lib.GN_KPT_XYSA)
+    if dem_nodata is not None and d is not None:
+        n = int(nm.cpu()[0])      # the matches left on valid cells
     res = _pnp_with_dist(engine, dist, obj, mkp, nm, np.asarray(K, np.float64).reshape(3, 3), min_pts=min_matches, covariance=return_covariance,
                          **_iterations_kw(ransac_iterations), **_report_kw(return_inliers))
     R, t, ok = res[0], res[1], res[3]
@@ -299,9 +330,9 @@ def _pnp_with_dist(engine, dist, *args, **kwargs):
 
 
 def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_matches: int = 15, conf_threshold: float = 0.0, return_covariance: bool = False,
-                     dist=None, ransac_iterations=None, return_inliers: bool = False):
-    """`loftr_pose` for B pairs at once: frames01 / tiles01 (B, H, W) (or sequences of B (H, W) images), dems (B, H, W) uint8 (or a sequence of
-    B) or None.  ONE batched match (the counts stay on the device), the confidence filter as a stable per-pair compaction on the device, ONE
+                     dist=None, ransac_iterations=None, return_inliers: bool = False, dem_scale: float = 1.0, dem_offset: float = 0.0, dem_nodata=None):
+    """`loftr_pose` for B pairs at once: frames01 / tiles01 (B, H, W) (or sequences of B (H, W) images), dems (B, H, W) uint8, uint16, int16 or
+    float32 (or a sequence of B) or None; dem_scale / dem_offset / dem_nodata as for `loftr_pose`.  ONE batched match (the counts stay on the device), the confidence filter as a stable per-pair compaction on the device, ONE
     gn_gather_points, ONE gn_pnp_ransac over the B pairs and ONE read-back.  Returns a list of B entries, each what `loftr_pose` returns for that
     pair (None below `min_matches` / without a model).  The engine must have been created with max_batch >= B; it is grown to the matcher's
     per-pair cap when that exceeds its keypoint capacity.  dist, ransac_iterations, return_inliers: as for `loftr_pose` (the inlier indices
@@ -327,9 +358,9 @@ def loftr_pose_batch(matcher: "LoFTR", engine, frames01, tiles01, dems, K, min_m
     idx = torch.where(torch.arange(engine.kmax, device=dev)[None, :, None] < cnt[:, None, None], idx, torch.zeros_like(idx)).contiguous()
     d = None
     if dems is not None:
-        d = dems.to(dev) if isinstance(dems, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.stack([np.asarray(v) for v in dems]), np.uint8), device=dev)
-        d = d.to(torch.uint8).contiguous()
-    mkp, obj = engine.gather_points(g(k0), g(k1), idx, cnt, d, _lib.GN_KPT_XYSA)
+        d = _dem_tensor(dems if isinstance(dems, torch.Tensor) else np.stack([np.asarray(v) for v in dems]), dev)
+    with _dem_format(engine, dem_scale, dem_offset, dem_nodata):
+        mkp, obj = engine.gather_points(g(k0), g(k1), idx, cnt, d, _lib.GN_KPT_XYSA)
     K = np.asarray(K, np.float64)
     if K.ndim == 3:
         # one camera per pair: the one PnP call runs with a per-pair table (K (B, 3, 3), dist None or (B, 4 | 5)); checked on the host first

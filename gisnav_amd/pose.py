@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .engine import PoseEngine, RANSAC_ITERATIONS, check_ransac_iterations
+from .engine import PoseEngine, RANSAC_ITERATIONS, check_dem_format, check_ransac_iterations
 
 _default_engine: Optional[PoseEngine] = None
 
@@ -53,24 +53,53 @@ def distortion_of(camera_info) -> np.ndarray:
     return np.zeros(0, np.float64) if d is None else np.asarray(d, np.float64).reshape(-1)
 
 
+def lift_points(mkp_qry, mkp_ref, elevation, dem_scale: float = 1.0, dem_offset: float = 0.0, dem_nodata=None):
+    """The host-side twin of gn_gather_points' lift under a DEM format (PoseEngine.set_dem_format): object points (n', 3) f32 = reference
+    keypoint + z = (float)(raw * dem_scale + dem_offset) of the cell under it (product and sum in f64, rounded once each; z = 0 without a
+    raster), and the query points (n', 2) f32 of the same rows.  With dem_nodata, rows whose cell is void (raw == dem_nodata; non-finite for a
+    float raster) are dropped, order kept: n' <= n.  The raster keeps its dtype (uint8 / uint16 / int16 / float32); the argument rules are
+    check_dem_format's."""
+    obj = np.zeros((len(mkp_ref), 3), np.float32)
+    obj[:, :2] = mkp_ref
+    img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
+    if elevation is None:
+        return obj, img
+    elevation = np.asarray(elevation)
+    cell = np.floor(np.asarray(mkp_ref)).astype(np.intp)
+    raw = elevation[cell[:, 1], cell[:, 0]]
+    if dem_scale == 1.0 and dem_offset == 0.0 and dem_nodata is None:      # nothing set: the raster as it always was read, whatever its dtype
+        obj[:, 2] = raw
+        return obj, img
+    _, scale, offset, has_nodata, nodata = check_dem_format(elevation.dtype, dem_scale, dem_offset, dem_nodata)
+    if scale == 1.0 and offset == 0.0:
+        obj[:, 2] = raw
+    else:
+        obj[:, 2] = (raw.astype(np.float64) * scale + offset).astype(np.float32)
+    if has_nodata:
+        void = raw.astype(np.float64) == nodata
+        if raw.dtype.kind == "f":
+            void |= ~np.isfinite(raw)
+        obj, img = np.ascontiguousarray(obj[~void]), np.ascontiguousarray(img[~void])
+    return obj, img
+
+
 def compute_pose(camera_info, mkp_qry: np.ndarray, mkp_ref: np.ndarray, elevation: Optional[np.ndarray],
                  engine: Optional[PoseEngine] = None, return_covariance: bool = False, sigma_px: float = 0.0,
                  use_distortion: bool = False, ransac_iterations: Optional[int] = None, return_inliers: bool = False,
-                 return_residuals: bool = False) -> Optional[Tuple[np.ndarray, ...]]:
+                 return_residuals: bool = False, dem_scale: float = 1.0, dem_offset: float = 0.0,
+                 dem_nodata=None) -> Optional[Tuple[np.ndarray, ...]]:
     iterations = RANSAC_ITERATIONS if ransac_iterations is None else check_ransac_iterations(ransac_iterations)
     dist = distortion_of(camera_info) if use_distortion else None      # (checked before anything else: an unsupported model raises)
-    n = len(mkp_qry)
+    # the lift: reference keypoint + the DEM cell under it under (dem_scale, dem_offset); rows on a void cell (dem_nodata) are dropped here,
+    # so everything below -- the 4-point rule, PnP, return_inliers' indices -- sees the shortened list
+    if len(mkp_qry) < 4:
+        return None
+    obj, img = lift_points(mkp_qry, mkp_ref, elevation, dem_scale, dem_offset, dem_nodata)
+    n = len(img)
     if n < 4:                     # cv2.solvePnPRansac asserts npoints >= 4 (the reference would raise); the shim reports "no pose"
         return None
     eng = engine or _engine(n)
-    # object points = reference keypoint + the DEM cell under it (z = 0 without a raster: TwistNode), marshalled straight into the f32 [n][3]
-    # array gn_pnp_ransac reads -- the host-side twin of gn_gather_points' lift (reference: _shared.py:95-102)
-    obj = np.zeros((n, 3), np.float32)
-    obj[:, :2] = mkp_ref
-    if elevation is not None:
-        cell = np.floor(np.asarray(mkp_ref)).astype(np.intp)
-        obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
-    img = np.ascontiguousarray(mkp_qry, dtype=np.float32)
+    # (obj / img: the f32 arrays gn_pnp_ransac reads; reference: _shared.py:95-102)
     k_matrix = np.asarray(camera_info.k, dtype=np.float64).reshape((3, 3))
     report = return_inliers or return_residuals
     res = eng.pnp_ransac_host(obj, img, k_matrix, iterations, min_pts=4,   # n == 4: OpenCV's P3P branch
@@ -95,19 +124,10 @@ def _engine_batch(B: int, max_pts: int) -> PoseEngine:
     return _batch_engine
 
 
-def _object_points(mkp_ref, elevation) -> np.ndarray:
-    """compute_pose's lift: reference keypoint + the DEM cell under it (z = 0 without a raster), f32 [n][3]"""
-    obj = np.zeros((len(mkp_ref), 3), np.float32)
-    obj[:, :2] = mkp_ref
-    if elevation is not None:
-        cell = np.floor(np.asarray(mkp_ref)).astype(np.intp)
-        obj[:, 2] = np.asarray(elevation)[cell[:, 1], cell[:, 0]]
-    return obj
-
-
 def compute_pose_batch(camera_infos: Sequence, mkp_qry_list: Sequence[np.ndarray], mkp_ref_list: Sequence[np.ndarray],
                        elevations: Sequence[Optional[np.ndarray]], *, use_distortion: bool = False, ransac_iterations: Optional[int] = None,
-                       return_inliers: bool = False, engine: Optional[PoseEngine] = None) -> List[Optional[Tuple[np.ndarray, ...]]]:
+                       return_inliers: bool = False, engine: Optional[PoseEngine] = None, dem_scale: float = 1.0, dem_offset: float = 0.0,
+                       dem_nodata=None) -> List[Optional[Tuple[np.ndarray, ...]]]:
     """compute_pose for B messages with their own CameraInfo each, as ONE PnP call: message b is solved with camera_infos[b].k (and, with
     use_distortion, camera_infos[b].d) through a per-pair camera table.  Returns a list with, per message, what compute_pose returns: (R, t),
     with return_inliers (R, t, inliers), or None (fewer than 4 points, or no model).
@@ -129,17 +149,19 @@ def compute_pose_batch(camera_infos: Sequence, mkp_qry_list: Sequence[np.ndarray
         if not dists.any():
             dists = None      # no message is distorted: the pinhole kernels, as compute_pose runs them
     results: List[Optional[Tuple[np.ndarray, ...]]] = [None] * B
-    live = [b for b in range(B) if len(mkp_qry_list[b]) >= 4]      # (compute_pose: fewer than 4 points = no pose)
+    # compute_pose's lift per message (dem_scale / dem_offset / dem_nodata: one format for the batch); rows on void cells are dropped here
+    lifted = [lift_points(mkp_qry_list[b], mkp_ref_list[b], elevations[b], dem_scale, dem_offset, dem_nodata) if len(mkp_qry_list[b]) >= 4 else None
+              for b in range(B)]
+    live = [b for b in range(B) if lifted[b] is not None and len(lifted[b][1]) >= 4]      # (compute_pose: fewer than 4 points = no pose)
     if not live:
         return results
-    n = np.array([len(mkp_qry_list[b]) for b in live], np.int32)
+    n = np.array([len(lifted[b][1]) for b in live], np.int32)
     S = int(n.max())
     eng = engine or _engine_batch(len(live), S)
     obj = np.zeros((len(live), S, 3), np.float32)
     img = np.zeros((len(live), S, 2), np.float32)
     for k, b in enumerate(live):
-        obj[k, :n[k]] = _object_points(mkp_ref_list[b], elevations[b])
-        img[k, :n[k]] = np.asarray(mkp_qry_list[b], np.float32)
+        obj[k, :n[k]], img[k, :n[k]] = lifted[b]
     K = np.stack([np.asarray(camera_infos[b].k, np.float64).reshape(3, 3) for b in live])
     cams, model = eng.pair_cameras(K, None if dists is None else dists[live])
     res = eng.pnp_ransac(eng.to_device("cpb_obj", obj), eng.to_device("cpb_img", img), eng.to_device("cpb_n", n, torch.int32), None, iterations,

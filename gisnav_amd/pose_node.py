@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import MIN_MATCHES, RANSAC_ITERATIONS, PoseEngine, check_ransac_iterations, check_width_pruning
+from .engine import MIN_MATCHES, RANSAC_ITERATIONS, PoseEngine, check_dem_format, check_ransac_iterations, check_width_pruning, dem_dtype_name
 from .wire import CameraInfo, OrthoStereoImage, pack_keypoints
 
 
@@ -30,7 +30,8 @@ class PoseNode:
     def __init__(self, state_dict, extractor: Optional[Callable] = None, device: int = 0, max_kpts: int = 4096, precision: str = "f32",
                  certify: bool = True, certify_calibration_calls: int = 8, *, certify_ladder: bool = False, covariance: bool = False,
                  sigma_px: float = 0.0, use_distortion: bool = False, ransac_iterations: int = RANSAC_ITERATIONS, report: bool = False,
-                 width_confidence: float = -1.0, pruning_min_kpts: Optional[int] = None, sift_params: Optional[dict] = None):
+                 width_confidence: float = -1.0, pruning_min_kpts: Optional[int] = None, sift_params: Optional[dict] = None,
+                 dem_scale: float = 1.0, dem_offset: float = 0.0, dem_nodata=None):
         from .matcher import _check_ladder
         from .sift import SIFT, check_sift_params
         # sift_params: cv2.SIFT_create's keywords (nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma) for the tile extractor this
@@ -43,6 +44,7 @@ class PoseNode:
         except TypeError as e:
             raise ValueError(f"sift_params: {e}") from None
         ransac_iterations = check_ransac_iterations(ransac_iterations)      # (refused before any device work)
+        check_dem_format("float32", dem_scale, dem_offset, None)            # (likewise; dem_nodata is checked against each raster's element type)
         # width_confidence > 0: LightGlue's point pruning (gn_set_width_pruning; the reference asks for 0.99 at pose_node.py:88-107 behind a
         # comparison that is never true).  Not under the margin certificate: certify=False for the fast precision modes.
         check_width_pruning(width_confidence, pruning_min_kpts)
@@ -93,6 +95,10 @@ class PoseNode:
         # serves a stale raster to a caller that reuses a stamp.  cache_dem = True keys the device copy on the REFERENCE image's stamp instead --
         # the stamp the reference itself trusts for the tile's features (pose_node.py:226-241): dem and reference are cut from the same raster.
         self.cache_dem = False
+        # dem_scale / dem_offset / dem_nodata: the message's elevation raster may be uint8, uint16, int16 or float32 (ImageMsg.data keeps its
+        # dtype); z = raw * dem_scale + dem_offset, matches on a cell equal to dem_nodata are dropped before PnP (PoseEngine.set_dem_format)
+        if (dem_scale, dem_offset, dem_nodata) != (1.0, 0.0, None):
+            self._engine.set_dem_format(dem_scale, dem_offset, dem_nodata)
         self._dem_dev = None
         self._dem_pin = None
         self._io_kmax = -1
@@ -140,12 +146,13 @@ class PoseNode:
         self._pin_np[4:4 + n * 133] = np.frombuffer(msg.query_sift, dtype=np.float32, count=n * 133)
         self._pin_np[:1].view(np.int32)[0] = n
         self._dev_in[:4 + n * 133].copy_(self._pin[:4 + n * 133], non_blocking=True)
-        dem_key = (stamp, dem.shape[0], dem.shape[1])
+        dem_key = (stamp, dem.shape[0], dem.shape[1], dem.dtype.name)
         if self._dem_dev is None or self._dem_dev[0] != dem_key or not self.cache_dem:
             # through a pinned staging raster and one asynchronous copy (a pageable .to(dev) stalls the stream for ~90 us)
-            if self._dem_pin is None or self._dem_pin.shape[1:] != dem.shape[:2]:
-                self._dem_pin = torch.empty((1, dem.shape[0], dem.shape[1]), dtype=torch.uint8, pin_memory=True)
-                self._dem_buf = torch.empty((1, dem.shape[0], dem.shape[1]), dtype=torch.uint8, device=dev)
+            dem_dt = getattr(torch, dem_dtype_name(dem.dtype))      # the pinned and device rasters hold the message's element type
+            if self._dem_pin is None or self._dem_pin.shape[1:] != dem.shape[:2] or self._dem_pin.dtype != dem_dt:
+                self._dem_pin = torch.empty((1, dem.shape[0], dem.shape[1]), dtype=dem_dt, pin_memory=True)
+                self._dem_buf = torch.empty((1, dem.shape[0], dem.shape[1]), dtype=dem_dt, device=dev)
             self._dem_pin.numpy()[0] = dem.reshape(dem.shape[0], dem.shape[1])
             self._dem_buf.copy_(self._dem_pin, non_blocking=True)
             self._dem_dev = (dem_key, self._dem_buf)

@@ -47,6 +47,32 @@ def image_to_mono8(img: Any) -> np.ndarray:
     return buf[: h * step].reshape(h, step)[:, :w]
 
 
+# sensor_msgs/Image encodings of an elevation raster -> numpy element type (GN_DEM_U8 / U16 / I16 / F32)
+DEM_ENCODINGS = {"mono8": "u1", "8UC1": "u1", "mono16": "u2", "16UC1": "u2", "16SC1": "i2", "32FC1": "f4"}
+
+
+def image_to_dem(img: Any) -> np.ndarray:
+    """sensor_msgs/Image holding an elevation raster -> (height, width) array of its element type: mono8 / 8UC1 uint8, mono16 / 16UC1 uint16,
+    16SC1 int16, 32FC1 float32, in native byte order.  Honours `step` (bytes per row, which may exceed width x element size) and `is_bigendian`.
+    Any other encoding is refused by name."""
+    enc = getattr(img, "encoding", "mono8")
+    if enc not in DEM_ENCODINGS:
+        raise ValueError(f"expected an elevation raster of encoding {', '.join(DEM_ENCODINGS)}, got encoding {enc!r}")
+    dt = np.dtype(DEM_ENCODINGS[enc]).newbyteorder(">" if getattr(img, "is_bigendian", 0) else "<")
+    h, w = int(img.height), int(img.width)
+    step = int(getattr(img, "step", w * dt.itemsize)) or w * dt.itemsize
+    if step < w * dt.itemsize:
+        raise ValueError(f"image step {step} is shorter than a row of {w} {enc} elements")
+    buf = np.frombuffer(bytes(img.data) if not isinstance(img.data, (bytes, bytearray, memoryview, np.ndarray)) else img.data, dtype=np.uint8)
+    if buf.size < h * step:
+        raise ValueError("image data shorter than height x step")
+    rows = buf[: h * step].reshape(h, step)[:, : w * dt.itemsize]
+    if dt.itemsize == 1:
+        return rows
+    out = np.ascontiguousarray(rows).view(dt).reshape(h, w)
+    return out if dt.isnative else out.astype(dt.newbyteorder("="))
+
+
 def ortho_stereo_image_from_ros(msg: Any) -> OrthoStereoImage:
     """gisnav_msgs/OrthoStereoImage -> the wire dataclass `PoseNode.estimate` takes.  `query_sift.data` is passed on as bytes: the 532-byte
     KEYPOINT_DTYPE records go to the device as they are."""
@@ -57,7 +83,7 @@ def ortho_stereo_image_from_ros(msg: Any) -> OrthoStereoImage:
         q_stamp = _stamp(msg.query_sift.header)
     return OrthoStereoImage(query_sift=raw,
                             reference=ImageMsg(image_to_mono8(msg.reference), _stamp(msg.reference.header)),
-                            dem=ImageMsg(image_to_mono8(msg.dem), _stamp(msg.dem.header)),
+                            dem=ImageMsg(image_to_dem(msg.dem), _stamp(msg.dem.header)),      # (the raster keeps its element type)
                             crs=str(msg.crs.data), query_stamp=q_stamp)
 
 
@@ -110,11 +136,12 @@ def make_node_class():
         """`~/pose_earth` from `/camera/camera_info` + StereoNode's pose image, computed by gisnav_amd (one message = one GPU call, ~1 ms)."""
 
         def __init__(self, state_dict, *args, device: int = 0, precision: str = "f16x2_f16_attn", use_distortion: bool = False,
-                     ransac_iterations: int = 10, report: bool = False, **kwargs):
+                     ransac_iterations: int = 10, report: bool = False, dem_scale: float = 1.0, dem_offset: float = 0.0, dem_nodata=None, **kwargs):
             super().__init__(*args, **kwargs)
             # report=True: `last_report` holds the matches, cv2-style inliers and residuals of the most recent message (PoseNode.last_report)
             self._impl = PoseNode(state_dict, device=device, precision=precision, covariance=True, use_distortion=use_distortion,
-                                  ransac_iterations=ransac_iterations, report=report)
+                                  ransac_iterations=ransac_iterations, report=report,
+                                  dem_scale=dem_scale, dem_offset=dem_offset, dem_nodata=dem_nodata)
             self._camera_info: Optional[CameraInfo] = None
             qos = QoSPresetProfiles.SENSOR_DATA.value
             self._pub = self.create_publisher(PoseWithCovarianceStamped, ROS_TOPIC_POSE_EARTH, qos)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import PoseEngine, _ptr
+from .engine import PoseEngine, _ptr, check_dem_format, dem_dtype_name
 
 
 def rotate_and_crop_center(engine: PoseEngine, image, angle_degrees: float, shape: Tuple[int, int]):
@@ -30,18 +30,28 @@ def rotate_and_crop_center(engine: PoseEngine, image, angle_degrees: float, shap
     return out, back.reshape(3, 3)
 
 
-def stereo_reference(engine: PoseEngine, orthoimage_bgr, dem, map_rotation: float, crop_shape: Tuple[int, int]):
-    """stereo_node.py:229-262 in one device pass: (reference (h, w) u8, dem (h, w) u8, 3x3 f64 matrix)."""
+def stereo_reference(engine: PoseEngine, orthoimage_bgr, dem, map_rotation: float, crop_shape: Tuple[int, int], nodata=None):
+    """stereo_node.py:229-262 in one device pass: (reference (h, w) u8, dem (h, w) of the DEM's dtype, 3x3 f64 matrix).  dem: uint8, uint16,
+    int16 or float32 (numpy array or device tensor); nodata: the raw value of a void cell (None: none) -- an output cell is void when a tap of
+    non-zero weight is void or outside the source.  A uint8 DEM without nodata takes gn_stereo_reference, every other gn_stereo_reference_dem."""
+    dem_dtype = getattr(torch, dem_dtype_name(dem.dtype))
+    typ, _, _, has_nodata, nodata = check_dem_format(dem.dtype, 1.0, 0.0, nodata)      # (ValueError before any device work)
     dev = engine.device
     b = engine.to_device("stereo_bgr", orthoimage_bgr, torch.uint8)
-    d = engine.to_device("stereo_dem", dem, torch.uint8)
+    d = engine.to_device("stereo_dem", dem, dem_dtype)
     assert b.dtype == torch.uint8 and b.dim() == 3 and b.shape[2] == 3 and d.shape == b.shape[:2]
     H, W = int(b.shape[0]), int(b.shape[1])
     ref = torch.empty(crop_shape, dtype=torch.uint8, device=dev)
-    dm = torch.empty(crop_shape, dtype=torch.uint8, device=dev)
+    dm = torch.empty(crop_shape, dtype=dem_dtype, device=dev)
     back = np.zeros(9, np.float64)
-    rc = engine.lib.gn_stereo_reference(engine.ctx, _ptr(b.contiguous()), _ptr(d.contiguous()), H, W, float(map_rotation),
-                                        int(crop_shape[0]), int(crop_shape[1]), _ptr(ref), _ptr(dm),
-                                        back.ctypes.data_as(_lib.c_f64p), engine._stream())
-    _lib.check(engine.ctx, rc, "gn_stereo_reference")
+    if typ == _lib.GN_DEM_U8 and not has_nodata:
+        rc = engine.lib.gn_stereo_reference(engine.ctx, _ptr(b.contiguous()), _ptr(d.contiguous()), H, W, float(map_rotation),
+                                            int(crop_shape[0]), int(crop_shape[1]), _ptr(ref), _ptr(dm),
+                                            back.ctypes.data_as(_lib.c_f64p), engine._stream())
+        _lib.check(engine.ctx, rc, "gn_stereo_reference")
+    else:
+        rc = engine.lib.gn_stereo_reference_dem(engine.ctx, _ptr(b.contiguous()), _ptr(d.contiguous()), typ, has_nodata, nodata, H, W,
+                                                float(map_rotation), int(crop_shape[0]), int(crop_shape[1]), _ptr(ref), _ptr(dm),
+                                                back.ctypes.data_as(_lib.c_f64p), engine._stream())
+        _lib.check(engine.ctx, rc, "gn_stereo_reference_dem")
     return ref, dm, back.reshape(3, 3)

@@ -50,7 +50,8 @@ class Stamp:
 
 @dataclass
 class ImageMsg:
-    """The subset of sensor_msgs/Image PoseNode touches (mono8 rasters)."""
+    """The subset of sensor_msgs/Image PoseNode touches: a mono8 raster, or -- for the elevation raster -- uint8 / uint16 / int16 / float32
+    (`data.dtype` is the element type: ros2_node.image_to_dem)."""
     data: np.ndarray
     stamp: Stamp = field(default_factory=Stamp)
 

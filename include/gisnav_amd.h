@@ -309,12 +309,43 @@ int gn_kmax(const gn_ctx* ctx);
 
 /* Gather matched points and lift the reference side to 3-D with the DEM.
  *   mkp_q [B][kmax][2] f32, obj [B][kmax][3] f32 = (x_r, y_r, dem[floor(y_r)][floor(x_r)])
- *   dem   [B][H][W] u8 or NULL (z = 0). */
+ *   dem   [B][H][W] u8 or NULL (z = 0).  `const uint8_t* dem` here and in gn_estimate* points at elements of the context's DEM type
+ *         (gn_set_dem_format below; uint8 by default), densely packed.  While that format states a void value, a match on a void cell is
+ *         removed: idx and n_match are then rewritten in place (the shorter list), whatever their const qualifier says. */
 int gn_gather_points(gn_ctx* ctx, int B, int kpt_format,
                      const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
                      const int64_t* idx, const int32_t* n_match,
                      const uint8_t* dem, int H, int W,
                      float* mkp_q, float* obj, void* stream);
+/* gn_gather_points for a match list that carries scores: score [B][kmax] f32 (may be NULL) is compacted beside idx when voids are removed.
+ * Without a void value in the format it is gn_gather_points and idx / score / n_match are only read. */
+int gn_gather_points_scored(gn_ctx* ctx, int B, int kpt_format,
+                            const float* kpt_q, int stride_q, const float* kpt_r, int stride_r,
+                            int64_t* idx, float* score, int32_t* n_match,
+                            const uint8_t* dem, int H, int W,
+                            float* mkp_q, float* obj, void* stream);
+
+/* Elevation rasters beyond 8 bits (DESIGN.md "Elevation rasters: element types, scale, offset, voids"; the reference's own TODOs:
+ * pose_node.py:220 "Support 16-bit elevation", gis_node.py:691).  The element type of every `dem` argument of gn_gather_points and
+ * gn_estimate*, an affine map from the raw cell to z, and a void value.  Rasters stay [B][H][W], densely packed in elements of the type.
+ *   lift    the cell is chosen as always (floorf, clamped to the raster); z = (float)(raw * scale + offset), the product and the sum taken in
+ *           f64 and rounded once each, then rounded to f32.  With scale = 1, offset = 0 this is (float)raw.
+ *   voids   with has_nodata, a cell whose raw value equals nodata is void; for GN_DEM_F32 every non-finite cell is void too (nodata = NaN:
+ *           those alone).  A match whose reference keypoint lands on a void cell is removed from the call's match list before PnP and the
+ *           list is compacted stably: n_match, idx, score, mkp_q and obj all describe the shorter list (the caller's arrays in
+ *           gn_estimate_report, the workspaces otherwise), so min_matches, PnP, the covariance and the report need no mask.  A pair whose
+ *           matches are all void reports n_match = 0, ok = 0.  gn_match never sees a DEM and is unchanged.
+ * Sticky host-side state like gn_set_ransac, captured by value when a call is issued.  The default (GN_DEM_U8, 1, 0, no voids) launches the
+ * uint8 gather it always did: same bits, no launch more, no buffer more.  GN_ERR_ARG, with gn_last_error naming this function and the state
+ * left alone: unknown type; scale zero or not finite; offset not finite; nodata not representable in an integer type (non-integral or out
+ * of its range; ignored when has_nodata = 0). */
+enum { GN_DEM_U8 = 0, GN_DEM_U16 = 1, GN_DEM_I16 = 2, GN_DEM_F32 = 3 };
+int gn_set_dem_format(gn_ctx* ctx, int type, double scale, double offset, int has_nodata, double nodata);
+/* The values in effect (each pointer may be NULL). */
+int gn_get_dem_format(const gn_ctx* ctx, int* type, double* scale, double* offset, int* has_nodata, double* nodata);
+/* Matches removed as void from pairs 0 .. B-1 of the most recent call that ran with a void value (gn_estimate*, gn_gather_points*);
+ * zeros before the first.  dropped_host: HOST [B] int32.  Synchronises the device (the call may sit on the library's own streams). */
+int gn_dem_last_dropped(gn_ctx* ctx, int B, int32_t* dropped_host, void* stream);
 
 /* Batched solvePnPRansac + Rodrigues.
  *   obj [B][kstride][3] f32, img [B][kstride][2] f32, n_pts [B] int32, K9: HOST 3x3 row-major f64.
@@ -530,6 +561,16 @@ int gn_rotate_crop_center(gn_ctx* ctx, const uint8_t* stack, int H, int W, doubl
  * bgr [H][W][3] u8, dem [H][W] u8 (device) -> out_ref, out_dem [crop_h][crop_w] u8 (device). */
 int gn_stereo_reference(gn_ctx* ctx, const uint8_t* bgr, const uint8_t* dem, int H, int W, double angle_degrees,
                         int crop_h, int crop_w, uint8_t* out_ref, uint8_t* out_dem, double* back9_host, void* stream);
+/* gn_stereo_reference for a DEM of any element type (GN_DEM_*): dem [H][W] and out_dem [crop_h][crop_w] hold elements of dem_type.  The type
+ * and the void value are arguments, not context state (StereoNode and PoseNode are different processes).  out_ref is byte for byte
+ * gn_stereo_reference's, as if the two rasters were warped separately.  A GN_DEM_U8 DEM keeps the fixed-point arithmetic.  The other types
+ * use the float bilinear form this build defines: source cell and 1/32 fractions fx, fy as for the gray channel; f32 weights
+ * (32-fx)(32-fy)/1024, fx(32-fy)/1024, (32-fx)fy/1024, fx fy/1024; v = ((t0 w0 + t1 w1) + t2 w2) + t3 w3, every product and sum rounded
+ * to f32; taps outside the source, and taps of zero weight, read 0; integer outputs are rint (half to even) saturated to the type.
+ * With has_nodata an output cell stores nodata when any tap of non-zero weight is void (equal to nodata; non-finite for GN_DEM_F32) or
+ * outside the source: angle 0 is an exact crop and voids do not dilate.  nodata must be representable in an integer type (GN_ERR_ARG). */
+int gn_stereo_reference_dem(gn_ctx* ctx, const uint8_t* bgr, const void* dem, int dem_type, int has_nodata, double nodata, int H, int W,
+                            double angle_degrees, int crop_h, int crop_w, uint8_t* out_ref, void* out_dem, double* back9_host, void* stream);
 
 /* ---- post-pose georeferencing (host-side scalar code, no context) ---- */
 /* _transformations.py:298-323 proj_to_affine: "+proj=affine +xoff=.. +s11=.. ..." -> 3x4 row-major [s11 s12 s13 xoff; ...]. */
