@@ -77,6 +77,10 @@ SIGNATURES = {
     "gn_get_ffn_level1": (C.c_int, [VP, c_f32p, c_i64p]),
     "gn_set_ffn_level_eps1": (C.c_int, [VP, C.c_float]),
     "gn_debug_ffn_level_sim": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, C.c_int, VP, VP]),
+    "gn_set_qkv_products": (C.c_int, [VP, C.c_int]),
+    "gn_get_qkv_level": (C.c_int, [VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_f32p, c_i64p]),
+    "gn_set_qkv_level_eps": (C.c_int, [VP, C.c_float]),
+    "gn_debug_ffn_level_sim_rung": (C.c_int, [C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "gn_fused_projection_status": (C.c_int, [VP]),
     "gn_device_numa_node": (C.c_int, [C.c_int]),
     "gn_get_certify_stats": (C.c_int, [VP, c_i64p]),

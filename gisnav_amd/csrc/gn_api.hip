@@ -125,6 +125,7 @@ inline long long lists_stride_of(long long km) { return gn::kTileListBase + 2 * 
   X(float, collog, np, kWsAlways, "collog") X(float, max0, np, kWsAlways, "max0") X(int32_t, m0, np, kWsAlways, "m0")            \
   X(int32_t, m1, np, kWsAlways, "m1") X(float, max0b, np, kWsAlways, "max0b") X(float, rpart_c, 8 * np, kWsAlways, nullptr)      \
   X(int32_t, uncert, 1, kWsAlways, "uncert") X(int32_t, uncert_alt, 1, kWsAlways, nullptr) X(int32_t, uncert_alt2, 1, kWsAlways, nullptr) \
+  X(int32_t, uncert_alt3, 1, kWsAlways, nullptr)                                                                                 \
   X(float, colbest, np, kWsAlways, nullptr) X(float, col2, np, kWsAlways, nullptr)                                               \
   /* fused head: column partials [np / 32][np], row partials [8][np], two arrival counters (zero between calls) */               \
   X(float, cpart_m, (np / 32) * np, kWsAlways, nullptr) X(float, cpart_s, (np / 32) * np, kWsAlways, nullptr)                    \
@@ -206,13 +207,13 @@ struct gn_ctx {
   int cert_eps_src = 0;        // where cert_eps comes from: 0 the built-in default, 1 stated (gn_set_certify), 2 measured (gn_calibrate_certify),
                                // 3 measured on weights since replaced (gn_load_tensor; cert_eps is then +inf: every pair goes to exact f32)
   float cert_eps_f32 = 1.0e-4f;   // the same for the exact-f32 kernels (GPU f32 against the torch-CPU f32 oracle: summation order only)
-  int32_t* uncert_host = nullptr;   // pinned [3 * max_batch] (flags | the two other levels' flags)
+  int32_t* uncert_host = nullptr;   // pinned [4 * max_batch] (flags | the three other arithmetics' flags)
   bool cert_inner = false;     // a certificate re-run is being enqueued (no nested certification)
   void* cert_stage = nullptr; size_t cert_stage_bytes = 0;      // staging block of the gathered re-run (certify_rerun), grown on demand
   // mode 3 (deferred): gn_estimate leaves the flags of call n in a pinned slot behind an event and resolves them -- reads them, re-runs the flagged
   // pairs from the SAVED arguments -- after call n + 1 has been enqueued (or in gn_flush), so the host never waits for an idle GPU
   struct CertPending {
-    bool active = false; hipEvent_t ev = nullptr; int32_t* flags = nullptr;   // flags: pinned [3 * max_batch] (own level | the two alternates, as uncert_host)
+    bool active = false; hipEvent_t ev = nullptr; int32_t* flags = nullptr;   // flags: pinned [4 * max_batch] (own level | the three alternates, as uncert_host)
     int npad_run = 0, level = 0;
     Call call; double K9[9] = {0};      // call.K9 points at K9, the saved copy of the caller's matrix
   } cert_pend[2];
@@ -296,7 +297,15 @@ struct gn_ctx {
   int auto_ok1 = 0;        // consecutive level-2 windows that passed level 1's test
   int ffn_products = 3;    // gn_set_ffn_products: fp16 partial products of the block tail's two GEMMs on bulk grids (k_ffn128, composed form): 3 = f32-accurate split,
                            // 2 = the activations' fp16 high term only (meant to run under the margin certificate)
-  int qkv_products = 2;    // knob 27: fp16 partial products of the attention input projections (2 or 3), per context
+  int qkv_products = 2;    // knob 27: fp16 partial products of the attention input projections (2 or 3; 1 = gn_set_qkv_products(1)), per context
+  // The rung below level 1 (gn_set_qkv_products): the attention input projections on ONE product as well (W_h X_h: k_qkv<., true, 1>, k_ffn128<., ., ., 3 / 4, 1>)
+  // wherever the tail runs on level 1 and the bulk kernels are selected.  qkv_set: 2 = never (two products, as before), 1 = always there, 0 = automatic: part
+  // of the automatic ladder (gn_set_ffn_products(0)) -- cert_eps_proj1 is the eps of that arithmetic (level 1 + one-product projections, >= cert_eps_one;
+  // < 0 = not calibrated), the head evaluates it as a fourth eps on every automatic call (uncert_alt3), and after one window on level 1 in which it flags at
+  // most 1 pair in 64 more than three products would the context steps onto the rung (auto_rung); one failing window there goes back to level 1, or further
+  // when level 1 fails too.  gn_set_ffn_products(1) alone never selects it.  `level` stays 1 on the rung.
+  int qkv_set = 0, auto_rung = 0, qkv_force = 0;      // qkv_force: +1 / -1 = the rung on / off whatever the setting (calibration and self-check passes), 0 = the setting decides
+  float cert_eps_proj1 = -1.f; long long auto_proj1 = 0, auto_calls_proj1 = 0;
   unsigned long long* tile_feedback = nullptr;   // pinned host [8]: (all tiles << 32 | valid tiles) written by k_tile_lists of sub-batch group g's last call
   int n_sub = 1; hipStream_t sub_s[8] = {}; hipEvent_t ev_fork = nullptr; hipEvent_t ev_join[8] = {}; bool sub_pending[8] = {};
   // overlapped pose stage (gn_set_overlap): PnP of call n runs on an internal stream beside the matcher of call n+1
@@ -565,8 +574,12 @@ bool qkv_projection_applies(const gn_ctx* c, const View& w, const Block& blk, in
 bool skinny_applies(const gn_ctx* c, int T, int np) {
   return (c->skinny & 3) && c->planes_mode && c->x_planes_only && T % 32 == 0 && np > 0 && ((c->skinny & 3) == 2 || T / np <= 4);
 }
+inline bool proj_one(const gn_ctx* c);                 // (below, with the block tail's levels)
+inline bool tail_is_bulk(const gn_ctx* c, int T);
 bool qkv_projection(gn_ctx* c, const View& w, const Block& blk, bool cross, int T, int np, int vt_perm, hipStream_t s) {
-  const bool skinny = skinny_applies(c, T, np) && !(c->skinny & 4) && c->qkv_fused && blk.proj_in.wf && w.x_p && w.qkb && w.vtb && w.rot4 && np % 32 == 0 && vt_perm == 1 && !c->qkv_stamps;
+  // one product: beside the bulk one-product tail only, and by the bulk kernel whatever the number of pairs (the small-grid kernel keeps two products)
+  const bool one = c->qkv_products != 3 && proj_one(c) && tail_is_bulk(c, T) && qkv_projection_applies(c, w, blk, T, np, vt_perm);
+  const bool skinny = !one && skinny_applies(c, T, np) && !(c->skinny & 4) && c->qkv_fused && blk.proj_in.wf && w.x_p && w.qkb && w.vtb && w.rot4 && np % 32 == 0 && vt_perm == 1 && !c->qkv_stamps;
   if (!skinny && !qkv_projection_applies(c, w, blk, T, np, vt_perm)) return false;
   QkvArgs q;
   q.xp = w.x_p; q.wf = blk.proj_in.wf; q.acc_scale = blk.proj_in.acc_scale; q.bias = blk.proj_in.b;
@@ -574,7 +587,7 @@ bool qkv_projection(gn_ctx* c, const View& w, const Block& blk, bool cross, int 
   q.qscale = 0.125f; q.scale = 0.35355339059327373f; q.vt_perm = vt_perm; q.T = T;
   q.half_fmt = c->attn_f16; q.ovf = (c->attn_f16 && c->guard) ? w.ovf : nullptr;
   q.tiles = (c->use_lists && w.lists && !c->qkv_stamps) ? w.lists : nullptr;
-  q.products = c->qkv_products == 3 ? 3 : 2; q.ncu = c->ncu;
+  q.products = c->qkv_products == 3 ? 3 : one ? 1 : 2; q.ncu = c->ncu;
   q.dbg_ts = (c->qkv_stamps && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 20
   const double N = cross ? 2.0 * kDim : 3.0 * kDim;
   timed_launch(c, s, 0, 2.0 * T * N * kDim, 4.0 * T * kDim + 2.0 * T * N + 4.0 * N * kDim + (cross ? 0.0 : 2.0 * 4.0 * T * kFreq),   // x in (hm16), bf16 out, weights once, rotary tables
@@ -652,10 +665,24 @@ bool tail_should_walk(const gn_ctx* c, int g) {
 inline bool ffn_auto(const gn_ctx* c) { return c->ffn_products == 0 && c->cert_eps_lvl[0] >= 0.f && c->cert_eps_lvl[1] >= 0.f && c->certify >= 2; }
 inline int ffn_level(const gn_ctx* c) { return c->attn_f16 == 2 ? 3 : c->ffn_products == 0 ? (ffn_auto(c) ? c->auto_level : 3) : c->ffn_products; }
 inline float ffn_level_eps(const gn_ctx* c, int lvl) { return lvl == 1 ? c->cert_eps_one : c->cert_eps_lvl[lvl - 2]; }
-inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? ffn_level_eps(c, c->auto_level) : c->cert_eps; }
+// the rung below level 1: true when a call's attention input projections run on one product (on bulk grids, beside the one-product tail)
+inline bool proj_one(const gn_ctx* c) {
+  if (c->attn_f16 != 1 || c->qkv_products == 3 || ffn_level(c) != 1) return false;
+  if (c->qkv_force != 0) return c->qkv_force > 0;
+  return c->qkv_set == 1 || (c->qkv_set == 0 && ffn_auto(c) && c->auto_rung != 0 && c->cert_eps_proj1 >= 0.f);
+}
+// the arithmetic an automatic call runs on, as one number: its level, or kRung on the rung (ffn_level_update, deferred calls)
+enum { kRung = 4 };
+inline int ffn_auto_state(const gn_ctx* c) { return (c->auto_level == 1 && proj_one(c)) ? (int)kRung : c->auto_level; }
+inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? (ffn_auto_state(c) == kRung ? c->cert_eps_proj1 : ffn_level_eps(c, c->auto_level)) : c->cert_eps; }
+// the bulk block tail (composed k_ffn128) is what a call of T token rows runs: the grids on which the one-product projections exist
+inline bool tail_is_bulk(const gn_ctx* c, int T) {
+  return c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && c->ffn_fold && c->ffn_compose && T % 128 == 0 &&
+         (gn::g_ffn_shape == 128 || (gn::g_ffn_shape == 0 && T / 128 >= 256));
+}
 // the two levels whose certificates a call on level lvl evaluates beside its own (HeadArgs::uncert_alt, uncert_alt2): the other of {2, 3} and 1; on level 1: 2 and 3
 inline int ffn_alt_level(int lvl, int k) { return lvl == 1 ? 2 + k : (k == 0 ? 5 - lvl : 1); }
-inline void ffn_window_reset(gn_ctx* c, int level) { c->auto_level = level; c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = 0; c->auto_ok1 = 0; }
+inline void ffn_window_reset(gn_ctx* c, int level) { c->auto_level = level; c->auto_rung = 0; c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = c->auto_proj1 = 0; c->auto_ok1 = 0; }
 
 // x += ffn3(gelu(ln(ffn0([x | msg]))))
 // next / next_cross: the block whose attention input projection follows this tail (nullptr: none) -- when the tail runs as the composed k_ffn128 and that
@@ -690,6 +717,7 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
                           c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, w, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
       f.qkv = next_cross ? 2 : 1;
+      if (f.products == 1 && proj_one(c)) f.qkv += 2;      // 3 / 4: the projection on one product as well (what qkv_projection launches on this grid)
       f.q_wf = next->proj_in.wf; f.q_acc_scale = next->proj_in.acc_scale; f.q_bias = next->proj_in.b;
       f.q_rot4 = w.rot4; f.q_rot_stride = (long long)c->Tmax; f.q_qkb = w.qkb; f.q_vt = w.vtb;
       f.q_qscale = 0.125f; f.q_scale = 0.35355339059327373f;
@@ -873,6 +901,8 @@ int run_matcher(gn_ctx* c, const View& w, const Call& v, hipStream_t s) {
     if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) {
       hd.uncert_alt = w.uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
       hd.uncert_alt2 = w.uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
+      // the fourth arithmetic: the rung's eps -- or, on the rung (whose own eps is cert_eps), level 1's
+      hd.uncert_alt3 = w.uncert_alt3; hd.cert_eps_alt3 = ffn_auto_state(c) == kRung ? c->cert_eps_one : (c->qkv_set == 0 ? c->cert_eps_proj1 : -1.f);
     }
     hd.idx = v.idx; hd.score = v.score; hd.n_match = v.n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
     hd.md = c->planes_mode ? (const void*)w.md_p : (const void*)w.md; hd.md_f32 = c->planes_mode ? 0 : 1;
@@ -959,7 +989,8 @@ __global__ void k_count_diff(const uint4* a, const uint4* b, size_t n, unsigned 
 // k_qkv launches on ITS weights before it is used: the first forward call after a weight (re)load runs, on pseudo-random token rows in the context's own
 // workspaces, the block tail with the projection fused (self and cross form, one-tile and walking form) and tail + k_qkv separately, and compares the
 // q | k rows and V^T panels bit for bit.  Any difference switches the fusion off for this context (gn_fused_projection_status).  ~60 ms, once.
-// Every block-tail level the context can select is proved: three products, two when gn_set_ffn_products is 2 or 0 (automatic), one when it is 1 or 0.  The check runs
+// Every block-tail level the context can select is proved: three products, two when gn_set_ffn_products is 2 or 0 (automatic), one when it is 1 or 0, and the
+// one-product projection forms (k_ffn128<., ., ., 3 / 4, 1> against k_qkv<., true, 1>) when gn_set_qkv_products lets the context select them.  The check runs
 // at the full padded size (the smallest bulk grid there) whatever gn_set_active_kpts has set: ffn() lays the rows out at npad_run.
 int selfcheck_fused_projection(gn_ctx* c) {
   gn_ctx* ctx = c;
@@ -970,7 +1001,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
   if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
-      !c->qkv_fused || !w.rot4 || !w.lists || !w.msg_p || !w.h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || gn::g_ffn_shape != 0) return GN_OK;
+      !c->qkv_fused || !w.rot4 || !w.lists || !w.msg_p || !w.h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || (gn::g_ffn_shape != 0 && gn::g_ffn_shape != 128)) return GN_OK;      // (shape 128 = k_ffn128 forced: the grid below selects it either way)
   int B = (256 * 128 + 2 * np - 1) / (2 * np);          // the smallest batch whose grid selects k_ffn128 (>= 256 tiles of 128 tokens)
   if (B > c->max_batch) return GN_OK;                   // this context never runs the bulk kernels
   const int T = B * 2 * np;
@@ -1001,16 +1032,19 @@ int selfcheck_fused_projection(gn_ctx* c) {
   GN_HIP(hipMemset(cnt, 0, sizeof(unsigned int)));
   bool applicable = true;
   {
-    const Restore keep(c->use_lists, c->qkv_in_tail, c->guard, c->ktiming, c->launch_count, c->stop_after, c->npad_run, c->ffn_products);
+    const Restore keep(c->use_lists, c->qkv_in_tail, c->guard, c->ktiming, c->launch_count, c->stop_after, c->npad_run, c->ffn_products, c->qkv_force);
     const int prod0 = c->ffn_products;
     c->ktiming = false; c->stop_after = 0; c->guard = 0; c->npad_run = np;
     const int nblk = c->n_layers > 1 ? 1 : 0;
-    const int lvs[3] = {3, prod0 == 1 ? 1 : 2, 1};
+    int lvs[4] = {3, prod0 == 1 ? 1 : 2, 1, 1};
     const int n_lv = prod0 == 0 ? 3 : (prod0 == 2 || prod0 == 1) ? 2 : 1;     // levels: 3, then 2 and / or 1 when the context can select them
-    for (int lv = 0; lv < n_lv && applicable; ++lv)
+    // ... and the rung below level 1 (k_ffn128<., ., ., 3 / 4, 1> against k_qkv<., true, 1>) whenever the context can select it: pass n_lv
+    const bool rung = c->attn_f16 == 1 && (c->qkv_set == 1 ? (prod0 == 0 || prod0 == 1) : (c->qkv_set == 0 && prod0 == 0));
+    lvs[n_lv] = 1;
+    for (int lv = 0; lv < n_lv + (rung ? 1 : 0) && applicable; ++lv)
     for (int cross = 0; cross < 2 && applicable; ++cross)
       for (int walk = 0; walk < 2 && applicable; ++walk) {
-        c->ffn_products = lvs[lv];
+        c->ffn_products = lvs[lv]; c->qkv_force = lv == n_lv ? 1 : -1;
         const Block& tail = cross ? c->self_blk[0] : c->cross_blk[0];     // (any tail will do; the projection is the OTHER kind's)
         const Block* next = cross ? &c->cross_blk[0] : &c->self_blk[nblk];
         c->use_lists = walk ? 2 : 3;
@@ -1061,19 +1095,36 @@ int ffn_level_next(int level, int* ok1_run, long long pairs, long long n1, long 
   return next;
 }
 
-// one certified call's flags (those of the level it ran on, and the two other levels' from the same scores) into the window
-void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt, const int32_t* alt2, int lvl) {      // lvl: the level the call ran on (a deferred call's: saved with it)
-  if (!ffn_auto(c) || c->precision == GN_PREC_F32 || lvl < 1 || lvl > 3) return;
-  ++(lvl == 1 ? c->auto_calls_one : c->auto_calls_lvl[lvl - 2]);
-  int n[4] = {0, 0, 0, 0};
-  const int la = ffn_alt_level(lvl, 0), lb = ffn_alt_level(lvl, 1);
-  for (int b = 0; b < B; ++b) { n[lvl] += flags[b] == 1; n[la] += alt[b] == 1; n[lb] += alt2[b] == 1; }
-  c->auto_pairs += B; c->auto_one += n[1]; c->auto_wide += n[2]; c->auto_narrow += n[3];
+// The same rule with the rung below level 1 (one-product attention input projections, gn_set_qkv_products): *rung says whether a context on level 1 stands
+// on it; n0: pairs of the window the rung's certificate flags; have0: the rung has an eps.  Level 1 steps onto the rung after ONE window, evaluated on level
+// 1, in which the rung would have flagged at most 1 pair in 64 more than three products; on the rung one window that fails that test goes back to level 1 --
+// and further, by the rule above, when level 1 fails its own test too.  Everything else, and every answer when have0 is false, is ffn_level_next's.
+int ffn_level_next_rung(int level, int* rung, int* ok1_run, long long pairs, long long n0, long long n1, long long n2, long long n3, bool have1, bool have0) {
+  const bool ok0 = have0 && have1 && (n0 - n3) * 64 <= pairs;
+  if (level == 1 && *rung && ok0) return 1;
+  const bool was_rung = level == 1 && *rung;
+  const int next = ffn_level_next(level, ok1_run, pairs, n1, n2, n3, have1);
+  *rung = (level == 1 && !was_rung && next == 1 && ok0) ? 1 : 0;
+  return next;
+}
+
+// one certified call's flags (those of the arithmetic it ran on, and the three others' from the same scores) into the window
+void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt, const int32_t* alt2, const int32_t* alt3, int lvl) {      // lvl: the level the call ran on, kRung = level 1 on the rung (a deferred call's: saved with it)
+  if (!ffn_auto(c) || c->precision == GN_PREC_F32 || lvl < 1 || lvl > kRung) return;
+  const int tail = lvl == kRung ? 1 : lvl;
+  ++(tail == 1 ? c->auto_calls_one : c->auto_calls_lvl[tail - 2]);
+  if (lvl == kRung) ++c->auto_calls_proj1;
+  int n[5] = {0, 0, 0, 0, 0};
+  const int la = ffn_alt_level(tail, 0), lb = ffn_alt_level(tail, 1), lc = lvl == kRung ? 1 : (int)kRung;
+  for (int b = 0; b < B; ++b) { n[lvl] += flags[b] == 1; n[la] += alt[b] == 1; n[lb] += alt2[b] == 1; n[lc] += alt3 != nullptr && alt3[b] == 1; }
+  c->auto_pairs += B; c->auto_one += n[1]; c->auto_wide += n[2]; c->auto_narrow += n[3]; c->auto_proj1 += n[kRung];
   if (c->auto_pairs < 64) return;
-  const int next = ffn_level_next(c->auto_level, &c->auto_ok1, c->auto_pairs, c->auto_one, c->auto_wide, c->auto_narrow, c->cert_eps_one >= 0.f);
-  if (next != c->auto_level) ++c->auto_switches;
+  const int rung0 = c->auto_rung;
+  const int next = ffn_level_next_rung(c->auto_level, &c->auto_rung, &c->auto_ok1, c->auto_pairs, c->auto_proj1, c->auto_one, c->auto_wide, c->auto_narrow, c->cert_eps_one >= 0.f,
+                                       c->qkv_set == 0 && c->cert_eps_proj1 >= 0.f && c->attn_f16 == 1 && c->qkv_products != 3);
+  if (next != c->auto_level || c->auto_rung != rung0) ++c->auto_switches;
   c->auto_level = next;
-  c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = 0;
+  c->auto_pairs = c->auto_wide = c->auto_narrow = c->auto_one = c->auto_proj1 = 0;
 }
 
 // The arithmetics a call is run again in, each for the duration of a scope (counters and statistics are never part of one):
@@ -1168,11 +1219,13 @@ template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& 
     if (ffn_auto(ctx)) {
       GN_HIP(hipMemcpyAsync(ctx->uncert_host + ctx->max_batch, ctx->ws.uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
       GN_HIP(hipMemcpyAsync(ctx->uncert_host + 2 * ctx->max_batch, ctx->ws.uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      GN_HIP(hipMemcpyAsync(ctx->uncert_host + 3 * ctx->max_batch, ctx->ws.uncert_alt3, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
     GN_HIP(hipStreamSynchronize(s));
     flags_ready = ctx->uncert_host;
   }
-  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_ready + 2 * ctx->max_batch, flags_level ? flags_level : ctx->auto_level);     // (both callers lay the other levels' flags max_batch and 2 max_batch entries behind)
+  ffn_level_update(ctx, B, flags_ready, flags_ready + ctx->max_batch, flags_ready + 2 * ctx->max_batch, flags_ready + 3 * ctx->max_batch,
+                   flags_level ? flags_level : ffn_auto_state(ctx));     // (both callers lay the other arithmetics' flags max_batch, 2 and 3 max_batch entries behind)
   ++ctx->cert_calls; ctx->cert_pairs += B;
   std::vector<int> flagged, margin;
   for (int b = 0; b < B; ++b) {
@@ -1209,20 +1262,23 @@ template <typename F> int certify_rerun(gn_ctx* ctx, hipStream_t s, const Call& 
 }
 
 // gn_calibrate_certify: one pass of the sample w (the whole sample, its first pair, or its first pair with the reference side cut) in arithmetic
-// `arith` -- 1 / 2 / 3 = the context's own on that block-tail level, kCalExactF32, kCalMid = the ladder's middle level -- and the host copies of every row's
+// `arith` -- 1 / 2 / 3 = the context's own on that block-tail level, kCalProj1 = level 1 with one-product attention input projections (the rung),
+// kCalExactF32, kCalMid = the ladder's middle level -- and the host copies of every row's
 // best score and runner-up, of every column's when `cols`, of the per-slot counts when `nv`, and the guard word's trip bit (not read in exact f32)
-enum { kCalExactF32 = 0, kCalMid = -1 };
+enum { kCalExactF32 = 0, kCalMid = -1, kCalProj1 = 4 };
 struct CalPass { std::vector<float> best, second, colbest, col2; unsigned int trip = 0u; };
 int cal_pass(gn_ctx* ctx, const Call& w, int arith, bool cols, std::vector<int32_t>* nv, CalPass& out, hipStream_t s) {
   const View vw = view_of(ctx);
   int rc = GN_OK;
   {
-    const Restore keep(ctx->in_group, ctx->cal_cols, ctx->ffn_products);
+    const Restore keep(ctx->in_group, ctx->cal_cols, ctx->ffn_products, ctx->qkv_force);
+    // (under the automatic setting the levels 1 / 2 / 3 are measured with two-product projections and the rung separately; a fixed setting measures what it runs)
+    ctx->qkv_force = arith == kCalProj1 ? 1 : (ctx->ffn_products == 0 ? -1 : 0);
     ctx->in_group = true;       // (no nested certification, ovf_groups_last untouched)
     ctx->cal_cols = cols;
     if (arith == kCalExactF32) { const ExactF32 f32(ctx); rc = run_matcher(ctx, vw, w, s); }
     else if (arith == kCalMid) { const MidLevel mid(ctx); rc = run_matcher(ctx, vw, w, s); }
-    else { ctx->ffn_products = arith; rc = run_matcher(ctx, vw, w, s); }
+    else { ctx->ffn_products = arith == kCalProj1 ? 1 : arith; rc = run_matcher(ctx, vw, w, s); }
   }
   if (rc != GN_OK) return rc;
   const size_t n = (size_t)w.B * ctx->npad_run;
@@ -1394,10 +1450,10 @@ int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int fea
   if (hipHostMalloc((void**)&ctx->ovf_host, (16 + 4096 + 16) * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
   memset(ctx->ovf_host, 0, (16 + 4096 + 16) * sizeof(unsigned int));
   ctx->tile_feedback = reinterpret_cast<unsigned long long*>(ctx->ovf_host + 16 + 4096);   // [8] x 8 bytes behind the counters (8-byte aligned)
-  if (hipHostMalloc((void**)&ctx->uncert_host, (size_t)3 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
-  memset(ctx->uncert_host, 0, (size_t)3 * max_batch * sizeof(int32_t));
+  if (hipHostMalloc((void**)&ctx->uncert_host, (size_t)4 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
+  memset(ctx->uncert_host, 0, (size_t)4 * max_batch * sizeof(int32_t));
   for (auto& pd : ctx->cert_pend) {
-    if (hipHostMalloc((void**)&pd.flags, (size_t)3 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+    if (hipHostMalloc((void**)&pd.flags, (size_t)4 * max_batch * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "certificate slots: allocation failed"); }
   }
   ctx->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -1628,7 +1684,7 @@ int gn_load_tensor(gn_ctx* ctx, const char* name_c, const float* host, const int
   if (rc == GN_OK) {
     ctx->loaded[name] = true; ctx->fused_proj_pending = true;
     // a calibration belongs to the weights it was measured on: the automatic block-tail level goes back to "not calibrated" (three products, cert_eps)
-    ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = ctx->cert_eps_one = -1.f; ffn_window_reset(ctx, 3);
+    ctx->cert_eps_lvl[0] = ctx->cert_eps_lvl[1] = ctx->cert_eps_one = ctx->cert_eps_proj1 = -1.f; ffn_window_reset(ctx, 3);
     ctx->cert_eps_mid = -1.f;   // (the ladder sends flagged pairs straight to exact f32 until the next calibration)
     // and so does the single eps when it was measured (a stated one is the caller's to keep): every pair is flagged -- exact f32 -- until
     // gn_calibrate_certify runs again or gn_set_certify states an eps
@@ -1748,6 +1804,32 @@ int gn_set_ffn_level_eps(gn_ctx* ctx, float eps2, float eps3, int level) {
 int gn_set_ffn_level_eps1(gn_ctx* ctx, float eps1) {
   if (!ctx || !(eps1 >= 0.f)) return GN_ERR_ARG;
   ctx->cert_eps_one = std::max(eps1, std::max(ctx->cert_eps_lvl[0], ctx->cert_eps_lvl[1]));      // eps_one >= eps_two >= eps_three, as gn_calibrate_certify stores them
+  if (ctx->cert_eps_proj1 >= 0.f) ctx->cert_eps_proj1 = std::max(ctx->cert_eps_proj1, ctx->cert_eps_one);
+  return GN_OK;
+}
+
+int gn_set_qkv_products(gn_ctx* ctx, int products) {
+  if (!ctx || products < 0 || products > 2) return GN_ERR_ARG;
+  if (products != ctx->qkv_set) {
+    ffn_window_reset(ctx, 3);
+    ctx->fused_proj_pending = true;        // the one-product projection forms are proved whenever the new setting can select them
+  }
+  ctx->qkv_set = products;
+  return GN_OK;
+}
+
+int gn_set_qkv_level_eps(gn_ctx* ctx, float eps_proj1) {
+  if (!ctx || !(eps_proj1 >= 0.f)) return GN_ERR_ARG;
+  ctx->cert_eps_proj1 = std::max(eps_proj1, std::max(ctx->cert_eps_one, std::max(ctx->cert_eps_lvl[0], ctx->cert_eps_lvl[1])));
+  return GN_OK;
+}
+
+int gn_get_qkv_level(gn_ctx* ctx, int32_t* setting, int32_t* on_rung, float* eps_proj1, int64_t* calls_proj1) {
+  if (!ctx) return GN_ERR_ARG;
+  if (setting) *setting = ctx->qkv_set;
+  if (on_rung) *on_rung = proj_one(ctx) ? 1 : 0;
+  if (eps_proj1) *eps_proj1 = ctx->cert_eps_proj1;
+  if (calls_proj1) *calls_proj1 = ctx->auto_calls_proj1;
   return GN_OK;
 }
 
@@ -1769,9 +1851,26 @@ int gn_debug_ffn_level_sim(int n_calls, int B, const int32_t* f1, const int32_t*
     const int lvl = c->auto_level;
     if (levels_out) levels_out[i] = lvl;
     const size_t o = (size_t)i * B;
-    ffn_level_update(c.get(), B, f[lvl] + o, f[ffn_alt_level(lvl, 0)] + o, f[ffn_alt_level(lvl, 1)] + o, lvl);
+    ffn_level_update(c.get(), B, f[lvl] + o, f[ffn_alt_level(lvl, 0)] + o, f[ffn_alt_level(lvl, 1)] + o, nullptr, lvl);      // (no rung eps: the rule of the three levels)
   }
   if (out4) { out4[0] = c->auto_level; out4[1] = c->auto_switches; out4[2] = c->auto_calls_lvl[0]; out4[3] = c->auto_calls_one; }
+  return GN_OK;
+}
+
+int gn_debug_ffn_level_sim_rung(int n_calls, int B, const int32_t* f0, const int32_t* f1, const int32_t* f2, const int32_t* f3, int have1, int have0, int32_t* levels_out, int32_t* rung_out, int64_t* out5) {
+  if (n_calls < 0 || B < 1 || !f0 || !f1 || !f2 || !f3) return GN_ERR_ARG;
+  std::unique_ptr<gn_ctx> c(new gn_ctx);
+  c->ffn_products = 0; c->certify = 2; c->precision = GN_PREC_F16X2_BF16_ATTN; c->attn_f16 = 1;
+  c->cert_eps_lvl[0] = 2.f; c->cert_eps_lvl[1] = 1.f; c->cert_eps_one = have1 ? 3.f : -1.f; c->cert_eps_proj1 = have0 ? 4.f : -1.f;
+  const int32_t* f[5] = {nullptr, f1, f2, f3, f0};
+  for (int i = 0; i < n_calls; ++i) {
+    const int st = ffn_auto_state(c.get()), tail = st == kRung ? 1 : st;
+    if (levels_out) levels_out[i] = tail;
+    if (rung_out) rung_out[i] = st == kRung ? 1 : 0;
+    const size_t o = (size_t)i * B;
+    ffn_level_update(c.get(), B, f[st] + o, f[ffn_alt_level(tail, 0)] + o, f[ffn_alt_level(tail, 1)] + o, f[st == kRung ? 1 : (int)kRung] + o, st);
+  }
+  if (out5) { out5[0] = c->auto_level; out5[1] = c->auto_switches; out5[2] = c->auto_calls_lvl[0]; out5[3] = c->auto_calls_one; out5[4] = ffn_auto_state(c.get()) == kRung ? 1 : 0; }
   return GN_OK;
 }
 
@@ -1815,12 +1914,14 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   GN_HIP(hipMalloc((void**)&nm, (size_t)B * sizeof(int32_t)));
   Call v(ctx->feature, ctx->npad, B, kpt_format, desc_q, kpt_q, n_q, stride_q, desc_r, kpt_r, n_r, stride_r);
   v.idx = ctx->ws.e_idx; v.score = ctx->ws.e_score; v.n_match = nm;
-  // passes: the context's arithmetic -- on ALL THREE block-tail levels under gn_set_ffn_products(0) -- then the exact-f32 kernels
+  // passes: the context's arithmetic -- on ALL THREE block-tail levels under gn_set_ffn_products(0), and on the rung below level 1 (one-product attention
+  // input projections) unless gn_set_qkv_products(2) rules it out -- then the exact-f32 kernels
   const int setting = ctx->ffn_products;
-  const int n_lv = setting == 0 ? 3 : 1;
-  const int lv[3] = {setting == 0 ? 1 : setting, 2, 3};
+  const bool rung = setting == 0 && ctx->qkv_set == 0 && ctx->attn_f16 == 1 && ctx->qkv_products != 3;
+  const int n_lv = setting == 0 ? (rung ? 4 : 3) : 1;
+  const int lv[4] = {setting == 0 ? 1 : setting, 2, 3, kCalProj1};
   const float L = ctx->threshold > 0.f ? logf(ctx->threshold) : -INFINITY;
-  CalPass whole[4];
+  CalPass whole[5];
   std::vector<int32_t> nv(2 * (size_t)B);
   unsigned int tripped = 0u;
   const bool lad = ctx->ladder && ctx->planes_mode && ctx->attn_f16 != 2;   // (gn_set_certify_ladder refuses every other context)
@@ -1841,7 +1942,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   // the sample's first pair alone, and with its reference side cut to 128 and to 2 keypoints: the one-pair grid of bucket remainders, and the
   // few-keypoint sides of a ragged stream, where the fp16 attention's rounding averages over few keys (measured against fp64 on a ragged bulk
   // batch: 1.7x the eps of a 16 x 1024 sample alone, tests/test_gpu_fp64_parity.py).  Each level's eps is taken over these passes too.
-  double var_mx[3] = {0.0, 0.0, 0.0};
+  double var_mx[4] = {0.0, 0.0, 0.0, 0.0};
   int32_t* nr1 = nullptr;
   if (rc == GN_OK && !tripped && nv[0] >= 2 && nv[1] >= 2 && hipMalloc((void**)&nr1, sizeof(int32_t)) != hipSuccess) rc = GN_ERR_HIP;
   Call v1 = slice(v, 0, 1);
@@ -1849,7 +1950,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   for (int var = 0; nr1 && rc == GN_OK && var < 3; ++var) {
     const int32_t nr_cut = var == 0 ? nv[1] : std::min(nv[1], var == 1 ? 128 : 2);
     if (hipMemcpy(nr1, &nr_cut, sizeof nr_cut, hipMemcpyHostToDevice) != hipSuccess) { rc = GN_ERR_HIP; break; }
-    CalPass p[4];
+    CalPass p[5];
     unsigned int trip = 0u;
     for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
       rc = cal_pass(ctx, v1, pass == n_lv ? kCalExactF32 : lv[pass], false, nullptr, p[pass], s);
@@ -1863,7 +1964,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
   if (tripped) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample left the fp16 range of this precision mode (nothing to calibrate: such calls are re-run as a whole)");
   // largest difference between the two arithmetics over every valid row's best score and runner-up (max_diff)
-  float eps_of[3] = {0.f, 0.f, 0.f}, mx_of[3] = {0.f, 0.f, 0.f};
+  float eps_of[4] = {0.f, 0.f, 0.f, 0.f}, mx_of[4] = {0.f, 0.f, 0.f, 0.f};
   for (int k = 0; k < n_lv; ++k) {
     long long rows = 0;
     double mx = max_diff(whole[k], whole[n_lv], nv, B, np, false, L, &rows);
@@ -1876,6 +1977,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
   if (setting == 0) {
     // the wider level's bound is never stated tighter than the narrower one's (a sample can happen to show the opposite)
     ctx->cert_eps_lvl[1] = eps_of[2]; ctx->cert_eps_lvl[0] = std::max(eps_of[1], eps_of[2]); ctx->cert_eps_one = std::max(eps_of[0], ctx->cert_eps_lvl[0]);
+    ctx->cert_eps_proj1 = rung ? std::max(eps_of[3], ctx->cert_eps_one) : -1.f;      // eps_proj1 >= eps_one >= eps_two >= eps_three
     ffn_window_reset(ctx, 3);
   }
   if (lad && mid_mx >= 0.0) {
@@ -1883,7 +1985,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     ctx->cert_eps_mid = std::max(floor_eps, safety * (float)mid_mx);
     ctx->cert_mid_measured = (float)mid_mx;
   }
-  const int rep = n_lv - 1;       // reported: the three-product level's values under the automatic setting (gn_get_ffn_level returns both eps)
+  const int rep = setting == 0 ? 2 : 0;       // reported: the three-product level's values under the automatic setting (gn_get_ffn_level returns both eps)
   ctx->cert_eps = eps_of[rep]; ctx->cert_eps_src = 2;
   if (measured_host) *measured_host = mx_of[rep];
   if (eps_host) *eps_host = eps_of[rep];
@@ -1919,7 +2021,7 @@ int gn_reset_certify_stats(gn_ctx* ctx) {
   if (!ctx) return GN_ERR_ARG;
   ctx->cert_calls = ctx->cert_pairs = ctx->cert_flag_margin = ctx->cert_flag_range = ctx->cert_rerun = ctx->cert_f32_marginal = 0;
   ctx->mid_rerun = ctx->mid_certified = ctx->mid_passed = 0;
-  ctx->auto_calls_lvl[0] = ctx->auto_calls_lvl[1] = ctx->auto_calls_one = ctx->auto_switches = 0;
+  ctx->auto_calls_lvl[0] = ctx->auto_calls_lvl[1] = ctx->auto_calls_one = ctx->auto_calls_proj1 = ctx->auto_switches = 0;
   return GN_OK;
 }
 
@@ -2284,9 +2386,10 @@ int estimate_call(gn_ctx* ctx, int B, int kpt_format,
     if (ffn_auto(ctx)) {
       GN_HIP(hipMemcpyAsync(p.flags + ctx->max_batch, ctx->ws.uncert_alt, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
       GN_HIP(hipMemcpyAsync(p.flags + 2 * ctx->max_batch, ctx->ws.uncert_alt2, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    } else memset(p.flags + ctx->max_batch, 0, (size_t)2 * ctx->max_batch * sizeof(int32_t));
+      GN_HIP(hipMemcpyAsync(p.flags + 3 * ctx->max_batch, ctx->ws.uncert_alt3, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    } else memset(p.flags + ctx->max_batch, 0, (size_t)3 * ctx->max_batch * sizeof(int32_t));
     GN_HIP(hipEventRecord(p.ev, s));
-    p.active = true; p.level = ffn_auto(ctx) ? ctx->auto_level : -1; p.npad_run = ctx->npad_run;
+    p.active = true; p.level = ffn_auto(ctx) ? ffn_auto_state(ctx) : -1; p.npad_run = ctx->npad_run;
     p.call = v;
     if (K9) { memcpy(p.K9, K9, sizeof p.K9); p.call.K9 = p.K9; }
     ctx->cert_slot ^= 1;
@@ -3066,7 +3169,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 23) ctx->attn_split = value;
   else if (which == 25) ctx->dbg_trip_group = value;
   else if (which == 26) ctx->sub_serial = value;
-  else if (which == 27) ctx->qkv_products = value == 3 ? 3 : 2;
+  else if (which == 27) { ctx->qkv_products = value == 3 ? 3 : 2; if (value == 1) ctx->qkv_set = 1; ctx->fused_proj_pending = true; }      // (1: as gn_set_qkv_products(1))
   else if (which == 28) ctx->ffn_compose = value;
   else if (which == 31) ctx->use_lists = value;
   else if (which == 32) ctx->qkv_in_tail = value ? 1 : 0;

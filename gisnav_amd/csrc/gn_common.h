@@ -309,6 +309,8 @@ struct HeadArgs {
   float cert_eps_alt = -1.f;       // scores (gn_set_ffn_products(0): the context weighs the two levels' re-run fractions against each other); 0 / 1
   int32_t* uncert_alt2 = nullptr;  // [B] out (optional): and for a third eps, cert_eps_alt2 (the automatic block-tail level weighs three levels: own + two alternates)
   float cert_eps_alt2 = -1.f;
+  int32_t* uncert_alt3 = nullptr;  // [B] out (optional): and for a fourth, cert_eps_alt3 (the rung below level 1: one-product attention input projections)
+  float cert_eps_alt3 = -1.f;
   float* colbest = nullptr;        // [B][npad] out (optional, fused head): best score and runner-up of every column (gn_calibrate_certify's middle
   float* col2 = nullptr;           // level measures its eps over row AND column decisions)
   const int32_t* n_in = nullptr;   // [B*2] the call's INPUT counts while point pruning is on (gn_prune.hip), nullptr = nvalid: kornia's _no_match looks at the

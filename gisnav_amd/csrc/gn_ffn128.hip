@@ -69,7 +69,8 @@ constexpr float kErf2Clamp = 5.75f;
 // 1 = the weights' fp16 high term only as well (W_h X_h: plane 0 of every fragment pair, p == 2 of the product loops): one MFMA per k-step instead of two and
 // half the weight bytes in GEMM 1 and GEMM 2 -- a second rounding of the GEMM inputs, independent of the activations' and of the same relative size.  The bias
 // through the accumulators, the LayerNorm statistics, the degree-4 erf, the fp16 publish, the epilogue, the range guard and the padding-tile exit are level 2's;
-// the fused next-block projection (QKV) stays on two products, expression for expression.  Under the certificate and composed form only, as 2.
+// the fused next-block projection stays on two products, expression for expression, with QKV == 1 / 2, and runs on one (W_h X_h, k_qkv<., true, 1>) with
+// QKV == 3 / 4 (gn_set_qkv_products).  Under the certificate and composed form only, as 2.
 template <int ABL, bool COMP, bool LOOP = false, int QKV = 0, int PROD = 3>   // LOOP: the workgroup walks the work list (one workgroup per CU); ABL: 0, or 8 = s_memtime stamps per phase into a.dbg_ts, + 128 = per k-tile stamps too (results stay valid)
 __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
   static_assert(PROD == 3 || ((PROD == 2 || PROD == 1) && COMP), "two partial products / one: composed form only");
@@ -833,11 +834,16 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     // order, the same epilogue expressions -> the same bits.  Token operand = the fp16 HIGH terms the row-wise epilogue just produced (xh[]), written
     // into the k-tile layout the other GEMMs of this kernel read; weights register-fed through a ring; wave w owns feature tiles 8 pass + 2 w + {0, 1}
     // of every pass (64 features x 128 tokens = 128 accumulator registers), i.e. one head of q, of k and of v.
-    constexpr bool CROSS = QKV == 2;
+    // QKV == 3 / 4 (PROD == 1 only): the projection of QKV == 1 / 2 on ONE product, W_h X_h -- k_qkv<CROSS, true, 1>: plane 0 of every fragment pair alone, one
+    // MFMA per k-step and accumulator (4 per pair-step instead of 8), half the weight bytes, twice the k-steps in flight in the same registers
+    static_assert(QKV < 3 || PROD == 1, "the one-product projection exists beside the one-product tail only");
+    constexpr bool CROSS = QKV == 2 || QKV == 4;
+    constexpr bool Q1 = QKV >= 3;
+    constexpr int QPL = Q1 ? 1 : 2;                   // weight terms the projection reads
     constexpr int NPASS = CROSS ? 2 : 3;
     constexpr int NQK = CROSS ? kDim : 2 * kDim;      // q | k (or qk) features = the pitch of the fp16 rows
     constexpr int ROT = 8 * KT;                       // [16 feature groups][128 tokens] f32x4 rotary entries behind the token tile (32 KB)
-    constexpr int RQ = 4;                             // weight k-steps in flight (4 KB per wave each)
+    constexpr int RQ = Q1 ? 8 : 4;                    // weight k-steps in flight (4 KB per wave each; one product: 2 KB)
     const int slot = bm / a.npad, i0 = bm - slot * a.npad;
     f32x4 rq[CROSS ? 1 : 8];
     if constexpr (!CROSS) {      // the tile's rotary entries: thread -> entries tid + 256 k of [fg][token] (consecutive threads = consecutive tokens)
@@ -865,7 +871,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
     }
     window(0);
     window(1);
-    f16x8 qa[RQ][2][2];
+    f16x8 qa[RQ][2][QPL];
     f16x8 qb[3][2];          // token fragments of one pair of token tiles (j = 2 jp, 2 jp + 1), high terms only
     auto read_q = [&](int gp) __attribute__((always_inline)) {      // pair-step gp = 2 ks + jp
       const int ks = gp >> 1, jp = gp & 1;
@@ -887,7 +893,7 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
-          for (int pl = 0; pl < 2; ++pl) load_q(q, q, i2, pl);
+          for (int pl = 0; pl < QPL; ++pl) load_q(q, q, i2, pl);
       f32x4 bias4[2][4];
       if (!vpass) {
 #pragma unroll
@@ -918,11 +924,17 @@ __global__ __launch_bounds__(256) void k_ffn128(FfnArgs a_in) {
             for (int jl = 0; jl < 2; ++jl)
 #pragma unroll
               for (int i2 = 0; i2 < 2; ++i2) {
-                const int j = 2 * jp + jl, m = 8 * jp + 4 * p + 2 * jl + i2;
-                const f16x8 w = qa[ks % RQ][i2][p == 0 ? 1 : 0], x = qb[gp % 3][jl];
+                if (Q1 && p == 0) continue;                   // (W_m X_h: not in the one-product form)
+                // MFMA number inside the k-step: 16 on two products, 8 on one -- one weight load per four MFMAs either way (a k-step consumes four
+                // fragments on two products, two on one), in the gap behind the second MFMA of each group of four
+                const int j = 2 * jp + jl, m = Q1 ? 4 * jp + 2 * jl + i2 : 8 * jp + 4 * p + 2 * jl + i2;
+                const f16x8 w = qa[ks % RQ][i2][(p == 0 && QPL == 2) ? 1 : 0], x = qb[gp % 3][jl];
                 qacc[i2][j] = vpass ? __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, qacc[i2][j], 0, 0, 0)     // rows = tokens, columns = features
                                     : __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, qacc[i2][j], 0, 0, 0);    // rows = features, columns = tokens
-                if (m % 4 == 1 && ks >= 1 && ks + RQ - 1 < 16) load_q((ks - 1) % RQ, ks + RQ - 1, (m / 4) >> 1, (m / 4) & 1);
+                if (m % 4 == 1 && ks >= 1 && ks + RQ - 1 < 16) {
+                  if (Q1) load_q((ks - 1) % RQ, ks + RQ - 1, m / 4, 0);
+                  else load_q((ks - 1) % RQ, ks + RQ - 1, (m / 4) >> 1, (m / 4) & 1);
+                }
                 GN_PIN();
               }
         }
@@ -1029,7 +1041,9 @@ void launch_ffn128_level1(const FfnArgs& b, dim3 grid, bool walk, int stamps, in
 #define GN_F1(Q) do { if (stamps == 8) hipLaunchKernelGGL((k_ffn128<8, true, false, 0, 1>), grid, block, 0, s, b); \
                       else if (walk) hipLaunchKernelGGL((k_ffn128<0, true, true, Q, 1>), grid, block, 0, s, b); \
                       else hipLaunchKernelGGL((k_ffn128<0, true, false, Q, 1>), grid, block, 0, s, b); } while (0)
-  if (qv == 1) { GN_F1(1); g_last_kernel = walk ? "k_ffn128<0, true, true, 1, 1>" : "k_ffn128<0, true, false, 1, 1>"; }
+  if (qv == 3) { GN_F1(3); g_last_kernel = walk ? "k_ffn128<0, true, true, 3, 1>" : "k_ffn128<0, true, false, 3, 1>"; }
+  else if (qv == 4) { GN_F1(4); g_last_kernel = walk ? "k_ffn128<0, true, true, 4, 1>" : "k_ffn128<0, true, false, 4, 1>"; }
+  else if (qv == 1) { GN_F1(1); g_last_kernel = walk ? "k_ffn128<0, true, true, 1, 1>" : "k_ffn128<0, true, false, 1, 1>"; }
   else if (qv == 2) { GN_F1(2); g_last_kernel = walk ? "k_ffn128<0, true, true, 2, 1>" : "k_ffn128<0, true, false, 2, 1>"; }
   else { GN_F1(0); g_last_kernel = walk ? "k_ffn128<0, true, true, 0, 1>" : "k_ffn128<0, true, false, 0, 1>"; }
 #undef GN_F1

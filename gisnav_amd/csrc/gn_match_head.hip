@@ -154,12 +154,13 @@ __global__ __launch_bounds__(256) void k_compact(HeadArgs a) {
   // (point pruning: the rule looks at the call's input counts; a pruned side needs one row to run)
   const bool nomatch = (a.n_in ? a.n_in[2 * b] : n0) < 2 || (a.n_in ? a.n_in[2 * b + 1] : n1) < 2 || n0 < 1 || n1 < 1;
   if (nomatch || (a.ovf != nullptr && *a.ovf != 0u)) {  // kornia LightGlueMatcher._no_match; or the f16x2 domain guard tripped (gn_common.h)
-    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = nomatch ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; }
+    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = nomatch ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; if (a.uncert_alt3) a.uncert_alt3[b] = 0; }
     return;
   }
   if (tid == 0 && a.uncert) a.uncert[b] = 1;
   if (tid == 0 && a.uncert_alt) a.uncert_alt[b] = 1;
   if (tid == 0 && a.uncert_alt2) a.uncert_alt2[b] = 1;
+  if (tid == 0 && a.uncert_alt3) a.uncert_alt3[b] = 1;
   for (int i0 = 0; i0 < n0; i0 += 256) {
     const int i = i0 + tid;
     bool valid = false; int j = 0; float sc = 0.f;
@@ -544,7 +545,8 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   const bool cert2 = cert && a.uncert_alt != nullptr && a.cert_eps_alt >= 0.f;      // the same three tests for a second eps (HeadArgs::uncert_alt)
   const float Lth = a.threshold > 0.f ? logf(a.threshold) : -INFINITY;
   const bool cert3 = cert && a.uncert_alt2 != nullptr && a.cert_eps_alt2 >= 0.f;    // and for a third (HeadArgs::uncert_alt2)
-  int unc = 0, unc2 = 0, unc3 = 0;
+  const bool cert4 = cert && a.uncert_alt3 != nullptr && a.cert_eps_alt3 >= 0.f;    // and for a fourth (HeadArgs::uncert_alt3: the one-product projections' rung)
+  int unc = 0, unc2 = 0, unc3 = 0, unc4 = 0;
   for (int j = tid; j < n1; j += 512) {
     float m = -INFINITY, sm = 0.f; int bi = 0x7fffffff; float m2 = -INFINITY;
     for (int p0 = 0; p0 < nparts; p0 += 16) {     // partials in increasing row order: a strict comparison keeps the lowest row on ties
@@ -573,6 +575,7 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
       if (cert && m >= Lth - a.cert_eps && !(m - m2 > 2.f * a.cert_eps)) unc = 1;     // (b)
       if (cert2 && m >= Lth - a.cert_eps_alt && !(m - m2 > 2.f * a.cert_eps_alt)) unc2 = 1;
       if (cert3 && m >= Lth - a.cert_eps_alt2 && !(m - m2 > 2.f * a.cert_eps_alt2)) unc3 = 1;
+      if (cert4 && m >= Lth - a.cert_eps_alt3 && !(m - m2 > 2.f * a.cert_eps_alt3)) unc4 = 1;
     }
   }
   stamp(5);
@@ -585,7 +588,7 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
   if (tid == 0) *base_s = 0;
   __syncthreads();
   if (nomatch || (a.ovf != nullptr && *a.ovf != 0u)) {
-    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = nomatch ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; }   // 2: an activation left the fp16 range -- nothing of this call can be certified
+    if (tid == 0) { a.n_match[b] = 0; if (a.uncert) a.uncert[b] = nomatch ? 0 : 2; if (a.uncert_alt) a.uncert_alt[b] = 0; if (a.uncert_alt2) a.uncert_alt2[b] = 0; if (a.uncert_alt3) a.uncert_alt3[b] = 0; }   // 2: an activation left the fp16 range -- nothing of this call can be certified
     return;
   }
   for (int ib = 0; ib < n0; ib += 512) {
@@ -602,6 +605,7 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
         if (fabsf(best - Lth) <= a.cert_eps) unc = 1;                                    // (c)
         if (cert2 && ((best >= Lth - a.cert_eps_alt && !(best - second > 2.f * a.cert_eps_alt)) || fabsf(best - Lth) <= a.cert_eps_alt)) unc2 = 1;
         if (cert3 && ((best >= Lth - a.cert_eps_alt2 && !(best - second > 2.f * a.cert_eps_alt2)) || fabsf(best - Lth) <= a.cert_eps_alt2)) unc3 = 1;
+        if (cert4 && ((best >= Lth - a.cert_eps_alt3 && !(best - second > 2.f * a.cert_eps_alt3)) || fabsf(best - Lth) <= a.cert_eps_alt3)) unc4 = 1;
       }
     }
     const unsigned long long bal = __ballot(valid);
@@ -630,6 +634,10 @@ __global__ __launch_bounds__(512) void k_head_fused(HeadArgs a) {
     if (a.uncert_alt2) {
       const int any3 = __syncthreads_or(unc3);
       if (tid == 0) a.uncert_alt2[b] = (cert3 && any3) ? 1 : 0;
+    }
+    if (a.uncert_alt3) {
+      const int any4 = __syncthreads_or(unc4);
+      if (tid == 0) a.uncert_alt3[b] = (cert4 && any4) ? 1 : 0;
     }
   }
   stamp(6);

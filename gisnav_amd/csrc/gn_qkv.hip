@@ -39,6 +39,9 @@ constexpr int NJ = TM / 32;             // token tiles of 32
 //                 of the V^T layout (keys permuted inside 16-groups as k_attn_bf16_v5 reads them) = one 16-byte store.
 // F16: the outputs are fp16 instead of bf16 (GN_PREC_F16X2_F16_ATTN, the reference's CUDA arithmetic); a value outside fp16's range raises a.ovf
 // NP = 2 (developer knob 27, an accuracy experiment): the x_m . w_h product is dropped -- the outputs are rounded to 16 bits anyway
+// NP = 1 (gn_set_qkv_products, under the margin certificate beside the one-product block tail): W_h X_h alone -- only plane 0 of every fragment pair is
+// fetched (same buffer, same layout), one MFMA per k-step and token tile, twice the k-steps in flight in the registers the pairs took; k order, epilogue
+// expressions and range guard are NP = 2's
 template <bool CROSS, bool F16 = false, int NP = 3>
 __global__ __launch_bounds__(512) void k_qkv(QkvArgs a) {
   constexpr int NQK = CROSS ? kDim : 2 * kDim;      // q | k (or qk) features
@@ -87,8 +90,9 @@ __global__ __launch_bounds__(512) void k_qkv(QkvArgs a) {
   };
   // weight fragments: block ((tile * 16 + kstep) * 2 + term) of 1 KB, lane l -> bytes [16 l, 16 l + 16); a ring of k-steps
   const uint4* const wf = reinterpret_cast<const uint4*>(a.wf) + lane;
-  constexpr int RA = CROSS ? 8 : 6;     // k-steps in flight (2 KB per wave each); the rotary pass needs the registers
-  f16x8 fa[RA][2];
+  constexpr int NPL = NP == 1 ? 1 : 2;               // weight terms read: W_h alone (plane 0 of every fragment pair), or W_h and W_m
+  constexpr int RA = (CROSS ? 8 : 6) * (2 / NPL);    // k-steps in flight (2 KB per wave each, 1 KB on one product); the rotary pass needs the registers
+  f16x8 fa[RA][NPL];
   const float ascale = a.acc_scale;
   const int slot = bm / a.npad, i0 = bm - slot * a.npad;
   __syncthreads();
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(512) void k_qkv(QkvArgs a) {
     const int tile = 8 * pass + wave;            // feature tile of this wave in this pass
     auto load_a = [&](int slot_, int ks) __attribute__((always_inline)) {
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) fa[slot_][pl] = __builtin_bit_cast(f16x8, wf[(size_t)((tile * 16 + ks) * 2 + pl) * 64]);
+      for (int pl = 0; pl < NPL; ++pl) fa[slot_][pl] = __builtin_bit_cast(f16x8, wf[(size_t)((tile * 16 + ks) * 2 + pl) * 64]);
     };
 #pragma unroll
     for (int q = 0; q < RA; ++q) load_a(q, q);
@@ -128,7 +132,8 @@ __global__ __launch_bounds__(512) void k_qkv(QkvArgs a) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           if (NP == 2 && p == 1) continue;
-          const f16x8 w = fa[rs][p == 0 ? 1 : 0], x = fb[cb][j][p == 1 ? 1 : 0];
+          if (NP == 1 && p != 2) continue;
+          const f16x8 w = fa[rs][(p == 0 && NPL == 2) ? 1 : 0], x = fb[cb][j][p == 1 ? 1 : 0];
           acc[j] = vpass ? __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, acc[j], 0, 0, 0)     // rows = tokens, columns = features
                          : __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, acc[j], 0, 0, 0);    // rows = features, columns = tokens
         }
@@ -254,6 +259,11 @@ int device_cu_count() {
 void launch_qkv(const QkvArgs& a, bool cross, hipStream_t s) {
   const int ncu = a.ncu > 0 ? a.ncu : device_cu_count();
   const dim3 grid(a.tiles != nullptr ? std::min(a.T / TM, ncu) : a.T / TM), block(512);
+  if (a.products == 1) {      // one product: fp16 outputs only (it runs beside the one-product block tail, under the certificate)
+    if (cross) { hipLaunchKernelGGL((k_qkv<true, true, 1>), grid, block, 0, s, a); g_last_kernel = "k_qkv<true, true, 1>"; }
+    else { hipLaunchKernelGGL((k_qkv<false, true, 1>), grid, block, 0, s, a); g_last_kernel = "k_qkv<false, true, 1>"; }
+    return;
+  }
   const int sel = (a.half_fmt ? 4 : 0) | (cross ? 2 : 0) | (a.products == 2 ? 1 : 0);
   switch (sel) {
     case 7: hipLaunchKernelGGL((k_qkv<true, true, 2>), grid, block, 0, s, a); g_last_kernel = "k_qkv<true, true, 2>"; break;

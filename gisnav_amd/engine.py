@@ -341,12 +341,24 @@ class PoseEngine:
 
     def set_ffn_products(self, products) -> None:
         """gn_set_ffn_products: 3 (default, f32-accurate), 2 (activations' fp16 high term only; run it under set_certify), 1 (weights' high term only as
-        well: W_h X_h), or "auto" (0): the level follows the certificate -- calibrate_certify then measures eps for all three levels, and under
+        well: W_h X_h), or "auto" (0): the level follows the certificate -- calibrate_certify then measures eps for all three levels (and for the rung below level 1, set_qkv_products), and under
         set_certify("rerun" / "deferred") the context runs on two products only while that flags (at most 1 pair in 64) no more pairs than three products
         would, and on one after two consecutive such windows for level 1.  Indices do not depend on the level."""
         p = 0 if products in ("auto", 0) else int(products)
         self._ffn_auto = p == 0
         _lib.check(self.ctx, self.lib.gn_set_ffn_products(self.ctx, p), "gn_set_ffn_products")
+
+    def set_qkv_products(self, products) -> None:
+        """gn_set_qkv_products: partial products of the attention input projections on bulk grids.  2: two (W_m X_h + W_h X_h), as before; 1: one (W_h X_h)
+        wherever the block tail runs on level 1 and the bulk kernels are selected; "auto" (0, the default): a rung of the automatic ladder
+        (set_ffn_products("auto")) below level 1 -- calibrate_certify measures its eps as a fourth arithmetic and a context on level 1 steps onto it after one
+        clean window of 64 pairs.  set_ffn_products(1) alone never selects it."""
+        p = 0 if products in ("auto", 0) else int(products)
+        _lib.check(self.ctx, self.lib.gn_set_qkv_products(self.ctx, p), "gn_set_qkv_products")
+
+    def set_qkv_level_eps(self, eps_projection: float) -> None:
+        """gn_set_qkv_level_eps: the rung's eps as an earlier calibrate_certify measured it (after set_ffn_level_eps)."""
+        _lib.check(self.ctx, self.lib.gn_set_qkv_level_eps(self.ctx, float(eps_projection)), "gn_set_qkv_level_eps")
 
     def set_ffn_level_eps(self, eps_two: float, eps_three: float, level: int = 3, eps_one: Optional[float] = None) -> None:
         """gn_set_ffn_level_eps (and gn_set_ffn_level_eps1): the levels' eps as an earlier calibrate_certify (same weights, same batch size) measured them, and
@@ -361,9 +373,15 @@ class PoseEngine:
         _lib.check(self.ctx, self.lib.gn_get_ffn_level(self.ctx, C.byref(lvl), C.byref(e2), C.byref(e3), buf), "gn_get_ffn_level")
         e1, c1 = C.c_float(0.0), C.c_int64(0)
         _lib.check(self.ctx, self.lib.gn_get_ffn_level1(self.ctx, C.byref(e1), C.byref(c1)), "gn_get_ffn_level1")
+        qs, qr, e0, c0 = C.c_int32(0), C.c_int32(0), C.c_float(0.0), C.c_int64(0)
+        _lib.check(self.ctx, self.lib.gn_get_qkv_level(self.ctx, C.byref(qs), C.byref(qr), C.byref(e0), C.byref(c0)), "gn_get_qkv_level")
+        # (the rung below level 1 -- one-product attention input projections -- keeps level == 1: "projection_one_product" says whether the next call runs on it;
+        # calls_one_product counts the rung's calls too)
         return {"level": int(lvl.value), "eps_two_products": float(e2.value), "eps_three_products": float(e3.value), "eps_one_product": float(e1.value),
                 "calls_two_products": int(buf[0]), "calls_three_products": int(buf[1]), "calls_one_product": int(c1.value),
-                "switches": int(buf[2]), "automatic": bool(buf[3])}
+                "switches": int(buf[2]), "automatic": bool(buf[3]),
+                "eps_one_product_projection": float(e0.value), "calls_projection_one_product": int(c0.value), "projection_one_product": bool(qr.value),
+                "qkv_products_setting": int(qs.value)}
 
     def calibrate_certify(self, inputs: dict, safety: float = 4.0, floor_eps: float = 1.0e-5) -> Dict[str, float]:
         """gn_calibrate_certify on staged inputs (the dict of stage_inputs / RecordStager.stage): measures max |P_mode - P_f32| over the deciding
@@ -382,6 +400,7 @@ class PoseEngine:
         if getattr(self, "_ffn_auto", False):      # set_ffn_products("auto"): all three levels were measured; measured / eps are the three-product level's
             d["eps_two_products"], d["eps_three_products"] = lv["eps_two_products"], lv["eps_three_products"]
             d["eps_one_product"] = lv["eps_one_product"]
+            d["eps_one_product_projection"] = lv["eps_one_product_projection"]      # (< 0: not measured -- set_qkv_products(2), or another precision mode)
         return d
 
     def set_certify_ladder(self, enable: bool, eps_mid: Optional[float] = None) -> None:

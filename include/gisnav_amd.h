@@ -191,6 +191,27 @@ int gn_set_ffn_level_eps1(gn_ctx* ctx, float eps1);
  * [n_calls][B] flags (0 / 1) the one-, two- and three-product certificates would raise on each call's scores; have1: level 1 has an eps.  levels_out
  * [n_calls] (may be NULL): the level each call ran on; out4 (may be NULL) = {level after the last call, switches, calls on two products, calls on one}. */
 int gn_debug_ffn_level_sim(int n_calls, int B, const int32_t* f1, const int32_t* f2, const int32_t* f3, int have1, int32_t* levels_out, int64_t* out4);
+/* Partial products of the attention input projections on bulk grids (k_qkv, and the projection fused behind the block tail):
+ * 2 = two (W_m X_h + W_h X_h), as before.
+ * 1 = ONE (W_h X_h: half the matrix-pipe work and weight bytes of the projection; its outputs are rounded to fp16 in any case) wherever the block tail runs on
+ *     level 1 and the bulk kernels are selected -- GN_PREC_F16X2_F16_ATTN only; small grids, the three-product levels and every other mode keep two.
+ * 0 (default) = automatic: a rung of the automatic ladder (gn_set_ffn_products(0)) below level 1.  gn_calibrate_certify then measures a fourth arithmetic,
+ *     level 1 + one-product projections (stored so that eps_proj1 >= eps_one), every automatic call evaluates that eps too, and a context on level 1 steps onto
+ *     the rung after ONE window of >= 64 certified pairs on level 1 in which the rung would have flagged at most 1 pair in 64 more than three products; on the
+ *     rung one window that fails that test goes back to level 1 (further when level 1 fails its own test).  192 clean pairs still end on level 1 after two
+ *     switches; the rung is first possible after 256.  gn_set_ffn_products(1) alone never selects it.
+ * The level reported by gn_get_ffn_level stays 1 on the rung; gn_get_qkv_level says whether the next call's projections run on one product (on_rung), the
+ * rung's eps (< 0: not calibrated -- never selected automatically) and the certified calls that ran on it.  gn_set_qkv_level_eps states that eps instead of
+ * measuring it (after gn_set_ffn_level_eps1 / gn_set_ffn_level_eps; stored as max(eps_proj1, eps_one)).  The fused forms are proved against the separate
+ * launches like every other (gn_fused_projection_status).  Any pointer may be NULL. */
+int gn_set_qkv_products(gn_ctx* ctx, int products);
+int gn_get_qkv_level(gn_ctx* ctx, int32_t* setting, int32_t* on_rung, float* eps_proj1, int64_t* calls_proj1);
+int gn_set_qkv_level_eps(gn_ctx* ctx, float eps_proj1);
+/* gn_debug_ffn_level_sim with the rung: f0 = the flags the rung's certificate would raise, have0: the rung has an eps.  rung_out [n_calls] (may be NULL): 1 where
+ * the call ran on the rung (levels_out is then 1); out5 (may be NULL) = {level after, switches, calls on two products, calls on one (rung included), on the rung after}.
+ * With have0 == 0 every answer is gn_debug_ffn_level_sim's. */
+int gn_debug_ffn_level_sim_rung(int n_calls, int B, const int32_t* f0, const int32_t* f1, const int32_t* f2, const int32_t* f3, int have1, int have0,
+                                int32_t* levels_out, int32_t* rung_out, int64_t* out5);
 /* On bulk grids the block-tail kernel also computes the next block's attention input projection (one launch and one pass over the residual rows
  * less).  Every context proves that fused form against the separate launches on its own weights before using it: at the first forward call after
  * a weight (re)load or a change of gn_set_ffn_products both forms run on pseudo-random rows, at the full padded size whatever gn_set_active_kpts
