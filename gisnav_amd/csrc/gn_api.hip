@@ -1960,6 +1960,39 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     for (int k = 0; k < n_lv; ++k) var_mx[k] = std::max(var_mx[k], max_diff(p[k], p[n_lv], nv, 1, np, false, L));
   }
   if (nr1) hipFree(nr1);
+  // the whole sample once more with every descriptor cut to its three largest bins: the error of the 16-bit arithmetic follows the statistics of the
+  // descriptors, not only the weights -- a sample of dense descriptors understated it for sparse ones (few strong bins: a larger input to every block;
+  // measured against fp64, d / eps 1.15 on three-bin descriptors, tests/test_gpu_ood_inputs.py).  Every level's eps, and eps_mid, is taken over this
+  // pass too.  (RootSIFT descriptors given as such -- GN_DESC_ROOTSIFT -- and 256-d features are used as they come: nothing normalises a cut row.)
+  double cut_mx[4] = {0.0, 0.0, 0.0, 0.0}, cut_mid = -1.0;
+  if (rc == GN_OK && !tripped && ctx->feature == GN_FEATURE_SIFT && !(kpt_format & GN_DESC_ROOTSIFT)) {
+    const bool rec = (kpt_format & 0xff) == GN_KPT_RECORD;       // (the descriptor is the tail of the keypoint's own record)
+    const int row_floats = rec ? gn::kRecordFloats : kInDim, off = rec ? 5 : 0;
+    const float* src[2] = {rec ? kpt_q : desc_q, rec ? kpt_r : desc_r};
+    const size_t rows[2] = {(size_t)B * stride_q, (size_t)B * stride_r};
+    float* cut[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2 && rc == GN_OK; ++k) {
+      const size_t bytes = rows[k] * row_floats * sizeof(float);
+      if (hipMalloc((void**)&cut[k], bytes) != hipSuccess || hipMemcpyAsync(cut[k], src[k], bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) { rc = GN_ERR_HIP; break; }
+      gn::launch_desc_top3(cut[k], (long long)rows[k], row_floats, off, s);
+    }
+    Call vc = v;
+    (rec ? vc.kpt_q : vc.desc_q) = cut[0]; (rec ? vc.kpt_r : vc.desc_r) = cut[1];
+    CalPass p[5];
+    unsigned int trip = 0u;
+    for (int pass = 0; pass <= n_lv && rc == GN_OK; ++pass) {
+      rc = cal_pass(ctx, vc, pass == n_lv ? kCalExactF32 : lv[pass], pass == n_lv && lad, nullptr, p[pass], s);
+      trip |= p[pass].trip;
+    }
+    for (int k = 0; k < n_lv && rc == GN_OK && !trip; ++k) cut_mx[k] = max_diff(p[k], p[n_lv], nv, B, np, false, L);
+    if (lad && rc == GN_OK && !trip) {
+      CalPass mid;
+      rc = cal_pass(ctx, vc, kCalMid, true, nullptr, mid, s);
+      if (rc == GN_OK && !mid.trip) cut_mid = max_diff(mid, p[n_lv], nv, B, np, true, L);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && rc == GN_OK) rc = GN_ERR_HIP;
+    for (int k = 0; k < 2; ++k) if (cut[k]) hipFree(cut[k]);
+  }
   hipFree(nm);
   if (rc != GN_OK) return rc == GN_ERR_HIP ? fail(ctx, rc, "gn_calibrate_certify: a HIP call failed") : rc;
   if (tripped) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample left the fp16 range of this precision mode (nothing to calibrate: such calls are re-run as a whole)");
@@ -1971,7 +2004,8 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     if (!std::isfinite(mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the sample");
     if (rows == 0) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: the sample holds no pair with at least two keypoints per side (nothing to measure)");
     if (!std::isfinite(var_mx[k])) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the one-pair passes");
-    mx = std::max(mx, var_mx[k]);
+    if (!std::isfinite(cut_mx[k])) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the cut-descriptor passes");
+    mx = std::max(mx, std::max(var_mx[k], cut_mx[k]));
     mx_of[k] = (float)mx; eps_of[k] = std::max(floor_eps, safety * (float)mx);
   }
   if (setting == 0) {
@@ -1981,6 +2015,7 @@ int gn_calibrate_certify(gn_ctx* ctx, int B, int kpt_format,
     ffn_window_reset(ctx, 3);
   }
   if (lad && mid_mx >= 0.0) {
+    mid_mx = std::max(mid_mx, cut_mid);
     if (!std::isfinite(mid_mx)) return fail(ctx, GN_ERR_ARG, "gn_calibrate_certify: non-finite scores in the middle level's pass");
     ctx->cert_eps_mid = std::max(floor_eps, safety * (float)mid_mx);
     ctx->cert_mid_measured = (float)mid_mx;

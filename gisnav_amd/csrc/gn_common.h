@@ -279,6 +279,8 @@ struct PrepArgs {
   unsigned int* ovf_clear; unsigned int ovf_init;   // f16x2 domain guard word of the call: k_extent stores ovf_init into it (nullptr: left alone)
 };
 void launch_prep(const PrepArgs& a, hipStream_t s);
+// in place: every 128-bin descriptor of `rows` rows of `row_floats` floats (descriptor `off` floats in) cut to its three largest bins
+void launch_desc_top3(float* d, long long rows, int row_floats, int off, hipStream_t s);
 void launch_ln_gelu(float* h, const float* gamma, const float* beta, int rows, hipStream_t s,
                     uint16_t* hp = nullptr, unsigned int* ovf = nullptr);   // hp: write hm16 rows [rows][512] instead of h
 void launch_matchability(const float* x, const float* w, const float* b, float* ls, int rows, hipStream_t s);

@@ -174,6 +174,27 @@ __global__ __launch_bounds__(256) void k_prep_sp(PrepArgs a) {
   }
 }
 
+// gn_calibrate_certify's derived sample: every 128-bin descriptor cut, in place, to its three largest bins (ties: the lowest bins).  One wave per
+// row of `row_floats` floats whose descriptor starts `off` floats in (a plain descriptor row: 128, 0; a GN_KPT_RECORD record: kRecordFloats, 5)
+__global__ __launch_bounds__(256) void k_desc_top3(float* d, long long rows, int row_floats, int off) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;      // (wave-uniform)
+  float* p = d + row * row_floats + off;
+  const float a0 = fabsf(p[lane]), a1 = fabsf(p[lane + 64]);
+  bool k0 = false, k1 = false;
+  for (int r = 0; r < 3; ++r) {
+    const float m = wave_max(fmaxf(k0 ? -1.f : a0, k1 ? -1.f : a1));
+    int cand = (!k0 && a0 == m) ? lane : (!k1 && a1 == m) ? lane + 64 : kInDim;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
+    k0 = k0 || cand == lane;
+    k1 = k1 || cand == lane + 64;
+  }
+  if (!k0) p[lane] = 0.f;
+  if (!k1) p[lane + 64] = 0.f;
+}
+
 // one wave per 512-wide row, in place
 __global__ __launch_bounds__(256) void k_ln_gelu(float* h, const float* gamma, const float* beta, int rows, uint16_t* hp, unsigned int* ovf) {
   const int lane = threadIdx.x & 63;
@@ -315,6 +336,9 @@ void launch_prep(const PrepArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_extent, dim3(a.B * 2), dim3(256), 0, s, a);
   if (a.feature == 1) hipLaunchKernelGGL(k_prep_sp, dim3(a.npad / 4, a.B * 2), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_prep, dim3(a.npad / 4, a.B * 2), dim3(256), 0, s, a);
+}
+void launch_desc_top3(float* d, long long rows, int row_floats, int off, hipStream_t s) {
+  if (rows > 0) hipLaunchKernelGGL(k_desc_top3, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, d, rows, row_floats, off);
 }
 void launch_ln_gelu(float* h, const float* gamma, const float* beta, int rows, hipStream_t s, uint16_t* hp, unsigned int* ovf) {
   hipLaunchKernelGGL(k_ln_gelu, dim3((rows + 3) / 4), dim3(256), 0, s, h, gamma, beta, rows, hp, ovf);

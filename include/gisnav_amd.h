@@ -244,7 +244,9 @@ int gn_get_certify_ladder_stats(gn_ctx* ctx, int64_t* out4);
  * context's arithmetic and on the exact-f32 kernels -- and eps = max(floor_eps, safety * max |P_mode - P_f32|) over the best score and the
  * runner-up of every valid row that comes within 1 of log(filter_threshold) in either arithmetic (all rows when the threshold is 0, or when no row
  * of the sample comes that close) -- over the batch, and over three one-pair passes on its first pair: as it is, and with its reference side
- * cut to 128 and to 2 keypoints (the one-pair grid of bucket remainders; few-keypoint sides, where the fp16 attention's error is larger).
+ * cut to 128 and to 2 keypoints (the one-pair grid of bucket remainders; few-keypoint sides, where the fp16 attention's error is larger), and
+ * over the batch once more with every 128-d descriptor cut to its three largest bins (the error follows the descriptors' statistics: a sample of
+ * dense descriptors understates it for sparse ones; not for GN_DESC_ROOTSIFT input or 256-d features, which are used as they come).
  * Synchronises; sets the context's eps and returns the measured maximum and eps through the two host pointers (either may be NULL).  Call
  * it once after loading a checkpoint, on representative pairs, IN A BATCH OF THE SIZE THE REAL CALLS HAVE (the kernel family -- and with it the arithmetic
  * whose error is being measured -- follows the grid size); safety >= 1 is the stated safety factor (the Python mirror uses 4). */
