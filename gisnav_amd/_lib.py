@@ -125,6 +125,7 @@ SIGNATURES = {
     "gn_loftr_match_batch": (C.c_int, [VP, C.c_int, VP, VP, VP, VP, VP, VP, VP, C.POINTER(C.c_int32), VP]),
     "gn_loftr_cap": (C.c_int, [VP]),
     "gn_loftr_debug_read": (C.c_int64, [VP, C.c_char_p, VP, C.c_int64, VP]),
+    "gn_loftr_debug_set_variant": (C.c_int, [VP, C.c_int, C.c_int]),
     "gn_loftr_set_certify": (C.c_int, [VP, C.c_int, C.c_float]),
     "gn_loftr_calibrate_certify": (C.c_int, [VP, C.c_int, VP, VP, C.c_float, C.c_float, C.POINTER(C.c_float), VP]),
     "gn_loftr_get_uncertain": (C.c_int, [VP, C.c_int, C.POINTER(C.c_int32)]),

@@ -255,7 +255,8 @@ struct gn_ctx {
   float* attn_part = nullptr; unsigned int* attn_tickets = nullptr;   // split-keys attention of small batches: <= 256 partial results, their tickets
   int attn_split = 1;      // developer knob 23: largest number of key ranges the attention of a small batch is split into (default 1 = never: the
                            // split changes the rounding of the probabilities, and results would then depend on batch size / padding / sub-streams)
-  int attn_variant = 4;    // developer knob 1: 0 = k_attn_bf16 (f32 inputs, in-kernel conversion), otherwise the k_attn_bf16_v5 family (4 = automatic choice)
+  gn::LaunchKnobs knobs;   // the kernel selectors of this context's launches (gn_debug_set_variant); gn_create sets knobs.gemm_variant from the precision:
+                           // 3 f32 MFMA (LDS-DMA), 5 f32x3 (GN_PREC_F32X3_BF16_ATTN), 6 f16x2
   int stop_after = 0;      // developer knob: return from run_matcher after this many GEMM/attention launches
   int launch_count = 0;
   int no_planes = 0;       // developer knob: ignore the pre-split weight planes (f32x3 splits B on the fly)
@@ -266,7 +267,6 @@ struct gn_ctx {
   int dbg_vt_skip = 0;     // timing probe: projection epilogues skip the V^T panel stores (wrong results)
   int dbg_reuse = 0;       // gn_debug_gemm: keep the operand planes of the previous call (micro-benchmarks time the GEMM alone)
   uint16_t* dbg_ap = nullptr; size_t dbg_ap_n = 0;   // gn_debug_gemm, variant 7: A planes for k_gemm_p2
-  int gemm_variant = -1;   // -1: library default (f32 MFMA, LDS-DMA); 5: f32x3 (GN_PREC_F32X3_BF16_ATTN)
   // sub-batch streams (gn_set_substreams): the pairs of one call are split into groups that run the whole path on
   // internal streams, out of phase with each other (fork / join events around them on the caller's stream)
   int defer_join = 0, sub_last_B = 0, sub_last_np = 0;   // gn_set_deferred_join; shape of the last unjoined sub-stream call
@@ -447,7 +447,6 @@ template <typename F> bool timed_launch(gn_ctx* c, hipStream_t s, int kclass, do
 }
 
 void timed_gemm(gn_ctx* c, const View& w, int epi, const GemmArgs& g_in, int batch, hipStream_t s) {
-  if (c->gemm_variant >= 0) gn::g_gemm_variant = c->gemm_variant;
   GemmArgs g = g_in;
   if (c->no_planes) g.Wp = nullptr;
   bool p2 = false;
@@ -479,7 +478,7 @@ void timed_gemm(gn_ctx* c, const View& w, int epi, const GemmArgs& g_in, int bat
   else if (epi != EPI_LN_GELU) by += (g.Y ? 4.0 * mn : 0.0) + (g.Yp ? 4.0 * mn : 0.0);
   if (epi == EPI_RESIDUAL) by += 4.0 * mn;
   if (epi == EPI_ROTARY || epi == EPI_ROTARY_BF16) by += 2.0 * 4.0 * (double)g.M * kFreq;
-  timed_launch(c, s, 0, 2.0 * g.M * (double)g.N * g.K * batch, by, nullptr, [&] { if (p2) launch_gemm_p2(epi, g, batch, s); else launch_gemm_f32(epi, g, batch, s); });
+  timed_launch(c, s, 0, 2.0 * g.M * (double)g.N * g.K * batch, by, nullptr, [&] { if (p2) launch_gemm_p2(epi, g, batch, s, c->knobs); else launch_gemm_f32(epi, g, batch, s, c->knobs); });
 }
 
 void gemm(gn_ctx* c, const View& w, int epi, GemmArgs& g, hipStream_t s) {
@@ -551,7 +550,7 @@ static void attn_split(gn_ctx* c, AttnArgs& a) {
 
 void attention(gn_ctx* c, const AttnArgs& a, hipStream_t s) {
   if (c->precision != GN_PREC_F32 && c->attn_f16 == 2) launch_attention_f16x2(a, s);
-  else if (c->precision != GN_PREC_F32) launch_attention_bf16(a, s); else launch_attention_f32(a, s);
+  else if (c->precision != GN_PREC_F32) launch_attention_bf16(a, s); else launch_attention_f32(a, s, c->knobs);
 }
 
 // one attention launch of the matcher schedule, optionally bracketed by HIP events (kernel class 1);
@@ -559,7 +558,7 @@ void attention(gn_ctx* c, const AttnArgs& a, hipStream_t s) {
 void timed_attention(gn_ctx* c, const AttnArgs& a, bool bf16v2, hipStream_t s) {
   timed_launch(c, s, 1, 4.0 * a.BS * kHeads * (double)a.npad * a.npad * kHeadDim,
                (double)a.BS * a.npad * kDim * (a.qb ? 2.0 + 2.0 + 2.0 : 12.0) + (double)a.BS * a.npad * kDim * 4.0,   // q, k, v in; context rows out
-               nullptr, [&] { if (bf16v2) launch_attention_bf16_v2(a, s); else attention(c, a, s); });
+               nullptr, [&] { if (bf16v2) launch_attention_bf16_v2(a, s, c->knobs); else attention(c, a, s); });
 }
 
 // q | k | v (or qk | v) projection of one block straight into the attention kernel's bf16 layouts; false when the shape / mode
@@ -650,7 +649,7 @@ int ensure_composed(gn_ctx* ctx) {
 // true when the block-tail kernel also computes msg = out_proj(ctx): the schedule then skips the out_proj GEMM launch
 bool tail_folds_out_proj(const gn_ctx* c, const Block& blk, int T) {
   return c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && c->ffn_fold && blk.ffn0.wf && blk.ffn0.wf2 && blk.ffn3.wf && blk.proj_out.wf &&
-         T % 64 == 0 && c->precision != GN_PREC_F32 && c->attn_variant >= 1;   // needs the attention kernel's hm16 output rows (ctx_p)
+         T % 64 == 0 && c->precision != GN_PREC_F32 && c->knobs.attn_variant >= 1;   // needs the attention kernel's hm16 output rows (ctx_p)
 }
 
 // The block tail's form on this call, predicted from the same sub-batch group's previous call (k_tile_lists leaves (all tiles, valid tiles) in pinned
@@ -677,8 +676,7 @@ inline int ffn_auto_state(const gn_ctx* c) { return (c->auto_level == 1 && proj_
 inline float cert_eps_now(const gn_ctx* c) { return ffn_auto(c) ? (ffn_auto_state(c) == kRung ? c->cert_eps_proj1 : ffn_level_eps(c, c->auto_level)) : c->cert_eps; }
 // the bulk block tail (composed k_ffn128) is what a call of T token rows runs: the grids on which the one-product projections exist
 inline bool tail_is_bulk(const gn_ctx* c, int T) {
-  return c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && c->ffn_fold && c->ffn_compose && T % 128 == 0 &&
-         (gn::g_ffn_shape == 128 || (gn::g_ffn_shape == 0 && T / 128 >= 256));
+  return c->planes_mode && c->x_planes_only && c->ffn_fused == 3 && c->ffn_fold && c->ffn_compose && ffn_bulk_shape(c->knobs.ffn_shape, T);
 }
 // the two levels whose certificates a call on level lvl evaluates beside its own (HeadArgs::uncert_alt, uncert_alt2): the other of {2, 3} and 1; on level 1: 2 and 3
 inline int ffn_alt_level(int lvl, int k) { return lvl == 1 ? 2 + k : (k == 0 ? 5 - lvl : 1); }
@@ -689,7 +687,7 @@ inline void ffn_window_reset(gn_ctx* c, int level) { c->auto_level = level; c->a
 // projection is a k_qkv<., true, 2> launch, it is computed inside the tail instead; returns true when it was (the caller then skips the projection)
 bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool keep_f32, const Block* next = nullptr, bool next_cross = false, int np = 0, int vt_perm = 0) {
   if (skinny_applies(c, T, np) && !(c->skinny & 8) && c->ffn_fused == 3 && c->ffn_compose && tail_folds_out_proj(c, blk, T) && blk.wfc && blk.b1c && !blk.comp_dirty && blk.ffn3.wfn &&
-      w.h && w.ctx_p && gn::g_ffn_stamps == 0 && gn::g_ffn_shape == 0) {
+      w.h && w.ctx_p && c->knobs.ffn_stamps == 0 && c->knobs.ffn_shape == 0) {
     // small grid: the weight stream split across CUs -- two launches (gn_skinny.hip)
     SkinnyTailArgs a;
     a.xp = w.x_p; a.cp = w.ctx_p; a.w1 = blk.wfc; a.w1_scale = blk.wfc_scale; a.b1 = blk.b1c; a.h = w.h; a.ln_g = blk.ln_g; a.ln_b = blk.ln_b;
@@ -708,13 +706,13 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
     const bool comp = fold && c->ffn_compose && blk.wfc && blk.b1c && !blk.comp_dirty;
     if (comp) { f.composed = 1; f.w1s = blk.wfc; f.w1_scale = blk.wfc_scale; f.b1 = blk.b1c; }
     f.ovf = c->guard ? w.ovf : nullptr;
-    f.tiles = (c->use_lists && w.lists && gn::g_ffn_stamps == 0) ? w.lists : nullptr;
+    f.tiles = (c->use_lists && w.lists && c->knobs.ffn_stamps == 0) ? w.lists : nullptr;
     f.walk = c->use_lists == 2 || (c->use_lists == 1 && tail_should_walk(c, w.g));
     f.ncu = c->ncu;
     f.composed = comp ? 1 : 0;
     f.products = (comp && ffn_level(c) <= 2) ? ffn_level(c) : 3;
-    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f) && gn::g_ffn_stamps == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
-                          c->precision != GN_PREC_F32 && c->attn_variant >= 1 && qkv_projection_applies(c, w, *next, T, np, vt_perm) && !(vt_perm & 2);
+    const bool fuse_qkv = next != nullptr && c->qkv_in_tail && !c->fused_proj_off && comp && ffn_selects_128(f, c->knobs) && c->knobs.ffn_stamps == 0 && c->attn_f16 && c->qkv_products != 3 && !c->qkv_stamps &&
+                          c->precision != GN_PREC_F32 && c->knobs.attn_variant >= 1 && qkv_projection_applies(c, w, *next, T, np, vt_perm) && !(vt_perm & 2);
     if (fuse_qkv) {
       f.qkv = next_cross ? 2 : 1;
       if (f.products == 1 && proj_one(c)) f.qkv += 2;      // 3 / 4: the projection on one product as well (what qkv_projection launches on this grid)
@@ -724,7 +722,7 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
       f.npad = np;
     }
     if (c->use_lists) { f.nvalid = w.nvalid; f.npad = c->npad_run; }
-    f.dbg_ts = gn::g_ffn_stamps ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
+    f.dbg_ts = c->knobs.ffn_stamps ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer: phase stamps land in the (idle) sim buffer
     double flops = 2.0 * T * (512.0 * 512.0 + 256.0 * 512.0 + ((fold && !comp) ? 256.0 * 256.0 : 0.0));   // composed: the flops the kernel's own formulation needs (algorithmic: whatever the number of partial products)
     double bytes = 4.0 * T * (256.0 + 256.0 + 256.0 + 256.0) + 4.0 * (512.0 * 512.0 + 256.0 * 512.0);   // x, msg, residual rows in; x out; weights once
     if (fuse_qkv) {     // + the projection (k_qkv's figures without its read of the rows)
@@ -732,7 +730,7 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
       flops += 2.0 * T * N * kDim;
       bytes += 2.0 * T * N + 4.0 * N * kDim + (next_cross ? 0.0 : 2.0 * 4.0 * T * kFreq);
     }
-    return timed_launch(c, s, 0, flops, bytes, nullptr, [&] { launch_ffn_fused(f, s); }) && fuse_qkv;
+    return timed_launch(c, s, 0, flops, bytes, nullptr, [&] { launch_ffn_fused(f, s, c->knobs); }) && fuse_qkv;
   }
   GemmArgs g = gemm_args(w.x, kDim, blk.ffn0, w.h, 2 * kDim, T);
   g.A2 = w.msg; g.lda2 = kDim; g.K1 = kDim;
@@ -757,9 +755,8 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
 
 int run_matcher(gn_ctx* c, const View& w, const Call& v, hipStream_t s) {
   const int B = v.B, np = c->npad_run, T = B * 2 * np, BS = B * 2;
-  const bool bf16v2 = c->precision != GN_PREC_F32 && c->attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
-  gn::g_attn_variant = c->attn_variant;
-  gn::g_attn_stamps = (c->attn_variant == 73 && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;
+  const bool bf16v2 = c->precision != GN_PREC_F32 && c->knobs.attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
+  c->knobs.attn_stamps = (c->knobs.attn_variant == 73 && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // (the idle sim buffer of THIS view)
   const int vt_perm = (bf16v2 ? 1 : 0) | (c->dbg_vt_skip ? 2 : 0);   // k_attn_bf16_v5 reads V^T with keys permuted inside 16-groups   // k_attn_bf16_v4 reads permuted V^T
   const bool attn_planes = c->planes_mode && (bf16v2 || c->attn_f16 == 2);   // k_attn_bf16_v5 / k_attn_f16x2 write the hm16 rows themselves
   c->launch_count = 0;
@@ -1001,7 +998,7 @@ int selfcheck_fused_projection(gn_ctx* c) {
   const int np = c->npad;
   GN_HIP(hipDeviceSynchronize());        // (nothing of an earlier call may still be using the workspaces)
   if (!c->planes_mode || !c->qkv_in_tail || !c->attn_f16 || c->attn_f16 == 2 || c->qkv_products == 3 || !c->ffn_compose || c->ffn_fused != 3 || !c->x_planes_only || c->n_layers < 1 ||
-      !c->qkv_fused || !w.rot4 || !w.lists || !w.msg_p || !w.h_p || c->feature < 0 || gn::g_ffn_stamps != 0 || (gn::g_ffn_shape != 0 && gn::g_ffn_shape != 128)) return GN_OK;      // (shape 128 = k_ffn128 forced: the grid below selects it either way)
+      !c->qkv_fused || !w.rot4 || !w.lists || !w.msg_p || !w.h_p || c->feature < 0 || c->knobs.ffn_stamps != 0 || (c->knobs.ffn_shape != 0 && c->knobs.ffn_shape != 128)) return GN_OK;      // (shape 128 = k_ffn128 forced: the grid below selects it either way)
   int B = (256 * 128 + 2 * np - 1) / (2 * np);          // the smallest batch whose grid selects k_ffn128 (>= 256 tiles of 128 tokens)
   if (B > c->max_batch) return GN_OK;                   // this context never runs the bulk kernels
   const int T = B * 2 * np;
@@ -1136,8 +1133,8 @@ void ffn_level_update(gn_ctx* c, int B, const int32_t* flags, const int32_t* alt
 //   accuracy) on the f32 workspaces.  The weights stay as hm16 planes: f32x3 splits the f32 weights on the fly; the attention operands go back to
 //   bf16 (f32's exponent range).
 struct ExactF32 : Restore<int, int, int, int, int> {
-  explicit ExactF32(gn_ctx* c) : Restore(c->precision, c->planes_mode, c->gemm_variant, c->no_planes, c->attn_f16) {
-    c->precision = GN_PREC_F32; c->planes_mode = 0; c->gemm_variant = 3; c->no_planes = 1; c->attn_f16 = 0;
+  explicit ExactF32(gn_ctx* c) : Restore(c->precision, c->planes_mode, c->knobs.gemm_variant, c->no_planes, c->attn_f16) {
+    c->precision = GN_PREC_F32; c->planes_mode = 0; c->knobs.gemm_variant = 3; c->no_planes = 1; c->attn_f16 = 0;
   }
 };
 struct MidLevel : Restore<int, int, int, float> {
@@ -1146,8 +1143,8 @@ struct MidLevel : Restore<int, int, int, float> {
   }
 };
 struct F32x3 : Restore<int, int, int, int> {
-  explicit F32x3(gn_ctx* c) : Restore(c->planes_mode, c->gemm_variant, c->no_planes, c->attn_f16) {
-    c->planes_mode = 0; c->gemm_variant = 5; c->no_planes = 1; c->attn_f16 = 0;
+  explicit F32x3(gn_ctx* c) : Restore(c->planes_mode, c->knobs.gemm_variant, c->no_planes, c->attn_f16) {
+    c->planes_mode = 0; c->knobs.gemm_variant = 5; c->no_planes = 1; c->attn_f16 = 0;
   }
 };
 inline bool ladder_active(const gn_ctx* c) { return c->ladder && c->cert_eps_mid >= 0.f && c->precision != GN_PREC_F32 && c->planes_mode && c->attn_f16 != 2; }
@@ -1444,7 +1441,7 @@ int gn_create_ex(int device, int max_batch, int max_kpts, int precision, int fea
   if (feature != GN_FEATURE_SIFT && feature != GN_FEATURE_SUPERPOINT) { delete ctx; return fail(nullptr, GN_ERR_ARG, "bad feature type"); }
   ctx->device = device; ctx->max_batch = max_batch; ctx->precision = precision; ctx->feature = feature;
   ctx->precision_api = precision_api; ctx->attn_f16 = precision_api == GN_PREC_F16X2_F16_ATTN ? 1 : precision_api == GN_PREC_F16X2_F16X2_ATTN ? 2 : 0;
-  ctx->gemm_variant = precision == GN_PREC_F16X2_BF16_ATTN ? 6 : precision == GN_PREC_F32X3_BF16_ATTN ? 5 : 3;
+  ctx->knobs.gemm_variant = precision == GN_PREC_F16X2_BF16_ATTN ? 6 : precision == GN_PREC_F32X3_BF16_ATTN ? 5 : 3;
   { const int rc_ws = alloc_workspace(ctx, max_kpts); if (rc_ws != GN_OK) { gn_destroy(ctx); return rc_ws; } }
   // pinned host words: [0, 16) guard words, [16, 16 + 4096) the per-image counters the SIFT / SuperPoint calls read back (up to 1024 images per call)
   if (hipHostMalloc((void**)&ctx->ovf_host, (16 + 4096 + 16) * sizeof(unsigned int), hipHostMallocDefault) != hipSuccess) { gn_destroy(ctx); return fail(nullptr, GN_ERR_HIP, "hipHostMalloc failed"); }
@@ -2556,10 +2553,9 @@ int gn_vo_match(gn_ctx* ctx, int B, const float* desc_q, const int32_t* n_q, int
   gs.A = ctx->ws.desc; gs.lda = kInDim; gs.K1 = kInDim; gs.W = ctx->ws.desc + (size_t)np * kInDim; gs.ldw = kInDim;
   gs.Y = ctx->ws.sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kInDim; gs.acc_scale = 1.f;
   gs.strideA = gs.strideW = 2LL * np * kInDim; gs.strideY = (long long)np * np;
-  const int saved = gn::g_gemm_variant;
-  gn::g_gemm_variant = 3;
-  launch_gemm_f32(EPI_PLAIN, gs, B, s);
-  gn::g_gemm_variant = saved;
+  gn::LaunchKnobs exact = ctx->knobs;
+  exact.gemm_variant = 3;
+  launch_gemm_f32(EPI_PLAIN, gs, B, s, exact);
   launch_vo_knn2(v, s);
   if (nn_idx) GN_HIP(hipMemcpyAsync(nn_idx, ctx->vo_nn_idx, (size_t)B * np * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   if (nn_dist) GN_HIP(hipMemcpyAsync(nn_dist, ctx->vo_nn_dist, (size_t)B * np * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -2776,15 +2772,15 @@ int gn_sift_detect_and_compute_batch(gn_ctx* ctx, const uint8_t* gray, int B, in
   SiftPyramid& py = ctx->sift_py;
   auto blur = [&](int o_in, const float* in, int o_out, float* out, int ki, float* dog = nullptr, int in_step = 1, float* half_scratch = nullptr) {
     sift_blur(B, py.oct[o_in].stride, py.oct[o_out].stride, in, ctx->sift_tmp, out, py.oct[o_out].w, py.oct[o_out].h, ctx->sift_dk + ctx->sift_koff[ki],
-              (int)ctx->sift_kernels[ki].size(), s, dog, in_step, py.oct[o_in].w, half_scratch);
+              (int)ctx->sift_kernels[ki].size(), ctx->knobs.sift_general_blur, s, dog, in_step, py.oct[o_in].w, half_scratch);
   };
   // createInitialImage: 2x bilinear, blur to sigma; then the Gaussian and DoG pyramids
   const int nl = py.n_layers, n_g = nl + 3;
   sift_base_blur(gray, B, H, W, py.oct[0].gauss[n_g - 1], ctx->sift_tmp, py.oct[0].gauss[0], py.oct[0].stride, ctx->sift_dk + ctx->sift_koff[0],
-                 (int)ctx->sift_kernels[0].size(), ctx->sift_counts, s);   // (scratch = the last level, overwritten later); also zeroes the counters
+                 (int)ctx->sift_kernels[0].size(), ctx->knobs.sift_general_blur, ctx->sift_counts, s);   // (scratch = the last level, overwritten later); also zeroes the counters
   int ksize[kSiftMaxLayers + 3] = {};
   for (int i = 0; i < n_g; ++i) ksize[i] = (int)ctx->sift_kernels[i].size();
-  const int o_tail = sift_tail_first(py, ksize);                     // octaves from here on: one single-workgroup launch per image
+  const int o_tail = sift_tail_first(py, ksize, ctx->knobs.sift_general_blur);                     // octaves from here on: one single-workgroup launch per image
   for (int o = 0; o < o_tail; ++o) {
     const SiftOctave& oc = py.oct[o];
     // level 1 of octave o > 0 samples level nOctaveLayers of the octave above directly (its level 0 is never stored)
@@ -2959,13 +2955,13 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     if (split) GN_HIP(hipMemsetAsync(ctx->ovf_base + 8, 0, sizeof(unsigned int), s));
     // (k_sp_conv_s addresses a frame's activations with 32-bit buffer offsets, 0x80000000 marking a pixel outside the image: frames whose
     // full-resolution 64-channel map reaches 2 GB -- beyond 8 Mpixel -- stay on the round-2 kernels)
-    hm16_io = split && ctx->sp_split == 1 && gn::g_sp_conv_s != 0 && (size_t)H * W * 256 < 0x7fffffffull;
+    hm16_io = split && ctx->sp_split == 1 && ctx->knobs.sp_conv_s != 0 && (size_t)H * W * 256 < 0x7fffffffull;
     for (int i = 1; i < 12; ++i) hm16_io = hm16_io && ctx->sp[i].wfh != nullptr;
     ctx->sp_enc_hm16 = hm16_io;
     ctx->sp_enc_fp16 = !hm16_io && split && ctx->sp_split == 2 && ctx->sp[7].wfh != nullptr;
     // round 6: in the split-fp16 mode the first convolution is evaluated inside the second one's halo staging (k_sp_conv_s16<., ., true>): its
     // full-resolution 64-channel map -- 0.53 GB of records per 1080p frame -- is neither written nor read; same bits (knob 46 = 0: two launches)
-    const bool fuse1 = hm16_io && gn::g_sp_fuse1 && gn::g_sp_conv_s == 2 && ctx->sp[1].cin == 64 && ctx->sp[1].cout_pad == 64 && ctx->sp[1].taps == 9 && ctx->sp_stop != 1 &&
+    const bool fuse1 = hm16_io && ctx->knobs.sp_fuse1 && ctx->knobs.sp_conv_s == 2 && ctx->sp[1].cin == 64 && ctx->sp[1].cout_pad == 64 && ctx->sp[1].taps == 9 && ctx->sp_stop != 1 &&
                        !(ctx->sp_ts_layer == 1 && ctx->sp_ts != nullptr);
     if (fuse1) {
       sp_conv_fused1(gray01 + (size_t)b0 * H * W, ctx->sp[0].wf, ctx->sp[0].b, n, H, W, ctx->sp[1].b, Y, ctx->sp[1].cout_pad, s, ctx->sp[1].wfh, ctx->sp[1].acc_scale, ctx->ovf_base + 8);
@@ -2987,7 +2983,7 @@ int gn_sp_detect_and_describe(gn_ctx* ctx, const float* gray01, int B, int H, in
     sp_scores(Z, ctx->sp[9].cout_pad, ctx->sp_maps[0], n, h, w, s);
     sp_nms(ctx->sp_maps[0], n, H, W, ctx->sp_maps[1], s);
     sp_select(ctx->sp_maps[1], n, H, W, 0.005f, 4, ctx->sp_cand, ctx->sp_counts, ctx->sp_cap, max_kpts,
-              kpt_xysa + (size_t)b0 * max_kpts * 4, score ? score + (size_t)b0 * max_kpts : ctx->sp_maps[2], ctx->sp_index, max_kpts, s);
+              kpt_xysa + (size_t)b0 * max_kpts * 4, score ? score + (size_t)b0 * max_kpts : ctx->sp_maps[2], ctx->sp_index, max_kpts, ctx->knobs.sp_select_stream, s);
     }
     conv(10, Y, X, n, h, w, 1);            conv(11, X, Z, n, h, w, 0);                          // descriptor head: Z = raw descriptor map [h][w][256]
     if (tail_desc) sp_describe(Z, n, h, w, kpt_xysa + (size_t)b0 * max_kpts * 4, ctx->sp_counts, max_kpts, max_kpts, desc + (size_t)b0 * max_kpts * 256, s);
@@ -3074,8 +3070,7 @@ int gn_debug_gemm(gn_ctx* ctx, int M, int N, int K, const float* A, const float*
   memset(&g, 0, sizeof g);
   g.A = A; g.lda = K; g.K1 = K; g.W = W; g.ldw = K; g.bias = bias; g.Y = Y; g.ldy = N; g.M = M; g.N = N; g.K = K;
   g.acc_scale = 1.f;
-  if (ctx->gemm_variant >= 0) gn::g_gemm_variant = ctx->gemm_variant;   // the kernel family of THIS context (the selector is a process-wide developer knob: another context's last launch may have left its own)
-  if (ctx->gemm_variant == 7) {   // k_gemm_p2: both operands as fp16 planes (W scaled by 2^(dbg_planes - 1) if dbg_planes > 0)
+  if (ctx->knobs.gemm_variant == 7) {   // k_gemm_p2: both operands as fp16 planes (W scaled by 2^(dbg_planes - 1) if dbg_planes > 0)
     
     const size_t na = (size_t)M * K, nw = (size_t)N * K;
     if (ctx->dbg_ap_n < na) { ctx->dbg_ap = nullptr; int rc = dalloc(ctx, &ctx->dbg_ap, 2 * na); if (rc != GN_OK) return rc; ctx->dbg_ap_n = na; }
@@ -3092,14 +3087,14 @@ int gn_debug_gemm(gn_ctx* ctx, int M, int N, int K, const float* A, const float*
       g.Yp = ctx->dbg_yp; g.ldyp = N;
       if (ctx->dbg_out == 1) g.Y = nullptr;
     }
-    launch_gemm_p2(bias ? EPI_BIAS : EPI_PLAIN, g, 1, (hipStream_t)stream);
+    launch_gemm_p2(bias ? EPI_BIAS : EPI_PLAIN, g, 1, (hipStream_t)stream, ctx->knobs);
     GN_HIP(hipGetLastError());
     return GN_OK;
   }
   if (ctx->dbg_planes) {
     const size_t n = (size_t)N * K;
     if (ctx->dbg_wp_n < n) { ctx->dbg_wp = nullptr; int rc = dalloc(ctx, &ctx->dbg_wp, 3 * n); if (rc != GN_OK) return rc; ctx->dbg_wp_n = n; }
-    if (ctx->gemm_variant == 6 || ctx->gemm_variant >= 60) {   // fp16 planes of W * 2^(dbg_planes - 1)
+    if (ctx->knobs.gemm_variant == 6 || ctx->knobs.gemm_variant >= 60) {   // fp16 planes of W * 2^(dbg_planes - 1)
       launch_split2_f16(W, ctx->dbg_wp, (long long)n, ldexpf(1.0f, ctx->dbg_planes - 1), (hipStream_t)stream);
       g.acc_scale = ldexpf(1.0f, 1 - ctx->dbg_planes);
     } else {
@@ -3107,7 +3102,7 @@ int gn_debug_gemm(gn_ctx* ctx, int M, int N, int K, const float* A, const float*
     }
     g.Wp = ctx->dbg_wp; g.wp_plane = (long long)n;
   }
-  launch_gemm_f32(bias ? EPI_BIAS : EPI_PLAIN, g, 1, (hipStream_t)stream);
+  launch_gemm_f32(bias ? EPI_BIAS : EPI_PLAIN, g, 1, (hipStream_t)stream, ctx->knobs);
   GN_HIP(hipGetLastError());
   return GN_OK;
 }
@@ -3122,14 +3117,13 @@ int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale, c
   a.nvalid = nkv; a.npad = npad; a.cross = cross; a.qscale = qscale; a.BS = BS;
   a.qb = a.kb = a.vt = nullptr; a.ldqb = a.ldkb = 0; a.outp = nullptr; a.half_fmt = ctx->attn_f16; a.ncu = ctx->ncu;
   const long long cap = (long long)ctx->max_batch * 2 * ctx->npad;
-  if (ctx->precision != GN_PREC_F32 && ctx->attn_f16 != 2 && ctx->attn_variant >= 1 && ctx->ws.qkb && ctx->ws.vtb && (long long)BS * npad <= cap) {
+  if (ctx->precision != GN_PREC_F32 && ctx->attn_f16 != 2 && ctx->knobs.attn_variant >= 1 && ctx->ws.qkb && ctx->ws.vtb && (long long)BS * npad <= cap) {
     // the production kernel (k_attn_bf16_v5) on the layouts the projection epilogues would have written
     launch_pack_attn_bf16(a, ctx->ws.qkb, ctx->ws.vtb, (hipStream_t)stream);
     a.qb = ctx->ws.qkb; a.kb = ctx->ws.qkb + kDim; a.ldqb = a.ldkb = 2 * kDim; a.vt = ctx->ws.vtb;
-    gn::g_attn_variant = ctx->attn_variant;
-    gn::g_attn_stamps = (ctx->attn_variant == 73 && ctx->ws.sim) ? reinterpret_cast<long long*>(ctx->ws.sim) : nullptr;
+    ctx->knobs.attn_stamps = (ctx->knobs.attn_variant == 73 && ctx->ws.sim) ? reinterpret_cast<long long*>(ctx->ws.sim) : nullptr;
     attn_split(ctx, a);
-    launch_attention_bf16_v2(a, (hipStream_t)stream);
+    launch_attention_bf16_v2(a, (hipStream_t)stream, ctx->knobs);
   } else {
     attention(ctx, a, (hipStream_t)stream);
   }
@@ -3155,7 +3149,7 @@ static bool retired_variant(int which, int value) {
     case 12: return value != 0 && value != 8 && value != 136;
     case 24: case 36: return true;            // SuperPoint's older single-product kernels and the 16-launch simple_nms
     case 34: return value != 0 && value != 2; // ... and its 3 x 3 k_sp_conv_s (1): the round-2 kernels (0) and the shipped form (2) live on
-    case 42: return (value & 0xff) != 0;      // LoFTR's forms of rounds 3-4; bits 8.. (lf_conv's cost model) live on
+    case 42: return true;                     // lf_conv's cost model: it reaches nothing on a matcher context (gn_loftr_debug_set_variant)
     default: return false;
   }
 }
@@ -3166,8 +3160,8 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
     GN_HIP(hipSetDevice(ctx->device));
     const int rc = ensure_sim(ctx); if (rc != GN_OK) return rc;
   }
-  if (which == 0) { gn::g_gemm_variant = value; ctx->gemm_variant = value; }
-  else if (which == 1) ctx->attn_variant = value;
+  if (which == 0) ctx->knobs.gemm_variant = value;
+  else if (which == 1) ctx->knobs.attn_variant = value;
   else if (which == 2) ctx->dbg_planes = value;
   else if (which == 3) ctx->no_planes = value;
   else if (which == 4) ctx->stop_after = value;
@@ -3176,24 +3170,23 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 7) ctx->dbg_out = value;
   else if (which == 10) ctx->ffn_fused = value;
   else if (which == 11) ctx->x_planes_only = value;
-  else if (which == 8) gn::g_p2_wide = value;
+  else if (which == 8) ctx->knobs.p2_wide = value;
   else if (which == 9) ctx->dbg_vt_skip = value;
-  else if (which == 12) gn::g_ffn_stamps = value;
+  else if (which == 12) ctx->knobs.ffn_stamps = value;
   else if (which == 13) ctx->ffn_fold = value;
-  else if (which == 14) gn::g_ffn_shape = value;
+  else if (which == 14) ctx->knobs.ffn_shape = value;
   else if (which == 15) ctx->pnp_stamps = value;
   else if (which == 16) ctx->head_fused = value;
   else if (which == 17) ctx->head_stamps = value;
   else if (which == 19) ctx->qkv_fused = value;
   else if (which == 20) ctx->qkv_stamps = value;
   else if (which == 21) ctx->sp_split = value;
-  else if (which == 34) gn::g_sp_conv_s = value;
-  else if (which == 40) gn::g_sp_select_stream = value;
-  else if (which == 41) gn::g_gemm_m64 = value;
-  else if (which == 42) gn::g_lf_conv_knob = value;
-  else if (which == 43) gn::g_attn_f32_ks = value;
-  else if (which == 44) gn::g_gemm_r64 = value;
-  else if (which == 46) gn::g_sp_fuse1 = value;
+  else if (which == 34) ctx->knobs.sp_conv_s = value;
+  else if (which == 40) ctx->knobs.sp_select_stream = value;
+  else if (which == 41) ctx->knobs.gemm_m64 = value;
+  else if (which == 43) ctx->knobs.attn_f32_ks = value;
+  else if (which == 44) ctx->knobs.gemm_r64 = value;
+  else if (which == 46) ctx->knobs.sp_fuse1 = value;
   else if (which == 47) { ctx->fused_proj_pending = value == 0; }   // 1: skip the fused-projection self-check of the next forward call (profiling passes: its launches are set-up, not steps)
   else if (which == 39) ctx->sp_stop = value;
   else if (which == 35) {
@@ -3211,7 +3204,7 @@ int gn_debug_set_variant(gn_ctx* ctx, int which, int value) {
   else if (which == 33) ctx->skinny = value;
   else if (which == 48) ctx->prep_fused = value ? 1 : 0;
   else if (which == 49) ctx->pnp_rounds = value ? 1 : 0;
-  else if (which == 50) gn::g_sift_general_blur = value ? 1 : 0;   // SIFT scale space through k_blur_row + k_blur_col only (the cost table of DESIGN.md 18)
+  else if (which == 50) ctx->knobs.sift_general_blur = value ? 1 : 0;   // SIFT scale space through k_blur_row + k_blur_col only (the cost table of DESIGN.md 18)
   else if (which == 29) {   // CU shares for the sub-batch streams: takes effect for streams created afterwards
     GN_HIP(hipSetDevice(ctx->device));
     for (int i = 0; i < 8; ++i) if (ctx->sub_s[i]) { hipStreamSynchronize(ctx->sub_s[i]); hipEventDestroy(ctx->ev_join[i]); hipStreamDestroy(ctx->sub_s[i]); ctx->sub_s[i] = nullptr; ctx->ev_join[i] = nullptr; }

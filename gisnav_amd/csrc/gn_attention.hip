@@ -995,12 +995,11 @@ __global__ __launch_bounds__(64 * NW) void k_attn_ks(AttnArgs a) {
 }
 }  // namespace
 
-int g_attn_f32_ks = 0;       // developer knob 43: bits 0-1: 0 = k_attn_f32_ks for one or two pairs per call, 1 = never, 2 = always; bit 2: its eight-wave form
-void launch_attention_f32(const AttnArgs& a, hipStream_t s) {
+void launch_attention_f32(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k) {
   // (the choice depends on the number of pairs only, like k_attn_ks': padding does not change the kernel family)
-  if ((g_attn_f32_ks & 3) == 2 || ((g_attn_f32_ks & 3) == 0 && a.BS <= 4)) {
+  if ((k.attn_f32_ks & 3) == 2 || ((k.attn_f32_ks & 3) == 0 && a.BS <= 4)) {
     // (knob 43 bit 2: eight waves per workgroup instead of four -- measured: 34.9 against 35.8 us at one pair, 62.6 against 58.0 at two: not shipped)
-    if (g_attn_f32_ks & 4) hipLaunchKernelGGL(k_attn_f32_ks<8>, dim3(a.npad / 32, kHeads, a.BS), dim3(512), 0, s, a);
+    if (k.attn_f32_ks & 4) hipLaunchKernelGGL(k_attn_f32_ks<8>, dim3(a.npad / 32, kHeads, a.BS), dim3(512), 0, s, a);
     else hipLaunchKernelGGL(k_attn_f32_ks<4>, dim3(a.npad / 32, kHeads, a.BS), dim3(256), 0, s, a);
     g_last_kernel = "k_attn_f32_ks(";
     return;
@@ -1044,24 +1043,22 @@ void launch_pack_attn_bf16(const AttnArgs& a, uint16_t* qkb, uint16_t* vtb, hipS
   hipLaunchKernelGGL(k_pack_attn_bf16, dim3((unsigned)((ntok * 32 + 255) / 256)), dim3(256), 0, s, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.qscale,
                      qkb, qkb + kDim, 2 * kDim, vtb, ntok, a.npad, a.half_fmt);
 }
-thread_local long long* g_attn_stamps = nullptr;
-thread_local int g_attn_variant = 4;  // developer knob 1 (include/gisnav_amd.h): 4 = the automatic choice below
-void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s) {
+void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k) {
   // fp16 mode, grids of at least one 256-query workgroup per CU: k_attn_pw (one wave per SIMD, pinned instruction stream; 31 vs 36 us at 8 pairs x
   // 1024 keypoints, 112 vs 125 us at 32, 224 vs 244 us at 64; below that k_attn16_v5's two workgroups per CU and its key splits win: 27 vs 24 us at 4
   // pairs).  Knob 1: 4 = this choice, 5 = k_attn16_v5 always, 70 = k_attn_pw whenever npad % 256 == 0, 73 = the same with phase stamps.
-  const bool pw_auto = g_attn_variant == 4 && a.half_fmt && a.npad % 256 == 0 && (long long)(a.npad / 256) * kHeads * a.BS >= 256;
-  if ((pw_auto || g_attn_variant == 70 || g_attn_variant == 73) && !(a.nsplit > 1 && a.part != nullptr) &&
-      launch_attention_pw(a, g_attn_variant == 73, s)) return;
+  const bool pw_auto = k.attn_variant == 4 && a.half_fmt && a.npad % 256 == 0 && (long long)(a.npad / 256) * kHeads * a.BS >= 256;
+  if ((pw_auto || k.attn_variant == 70 || k.attn_variant == 73) && !(a.nsplit > 1 && a.part != nullptr) &&
+      launch_attention_pw(a, s, k)) return;
   // ONE pair (k_attn16_v5's grid leaves three quarters of the CUs idle; measured 14.4 vs 21.1 us per launch at 1024 keypoints; at two pairs the
   // two kernels tie): the four waves of a workgroup split the KEYS of 32 queries (k_attn_ks).  The choice depends on the number of pairs only,
   // never on the padded length: gn_set_active_kpts must not change a result bit (test_active_kpts_padding_does_not_change_results).
   // Knob 1: 80 = always, 81 = always in the four-wave form, 5 = never.
   {
-    const bool ks_auto = g_attn_variant == 4 && a.BS <= 2;
-    if ((ks_auto || g_attn_variant == 80 || g_attn_variant == 81) && !(a.nsplit > 1 && a.part != nullptr) && a.npad % 64 == 0) {
+    const bool ks_auto = k.attn_variant == 4 && a.BS <= 2;
+    if ((ks_auto || k.attn_variant == 80 || k.attn_variant == 81) && !(a.nsplit > 1 && a.part != nullptr) && a.npad % 64 == 0) {
       const dim3 grid(a.npad / 32, kHeads, a.BS);
-      if (g_attn_variant == 81) {
+      if (k.attn_variant == 81) {
         if (a.half_fmt) { hipLaunchKernelGGL((k_attn_ks<true, 4>), grid, dim3(256), 0, s, a); g_last_kernel = "k_attn_ks<true, 4>"; }
         else { hipLaunchKernelGGL((k_attn_ks<false, 4>), grid, dim3(256), 0, s, a); g_last_kernel = "k_attn_ks<false, 4>"; }
       } else {
@@ -1082,17 +1079,17 @@ void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s) {
     // score exceeds it by ~11, which the bench's scenes do often enough that the ALWAYS-exact running maximum is the faster kernel here
     // (measured on one box: 4549 vs 4524 pairs/s; bf16, whose range lets the optimistic pass through, 4590).  It is also exactly what the
     // reference's fp16 SDPA computes: probabilities relative to the running maximum.  Knob 1 = 60 selects the optimistic variant.
-    if (g_attn_variant == 60) { hipLaunchKernelGGL((k_attn16_v5<0, 4, 3, 1, false, true>), dim3(a.npad / 128, kHeads, a.BS), dim3(256), 0, s, a); g_last_kernel = "k_attn16_v5<0, 4, 3, 1, false, true>"; }
+    if (k.attn_variant == 60) { hipLaunchKernelGGL((k_attn16_v5<0, 4, 3, 1, false, true>), dim3(a.npad / 128, kHeads, a.BS), dim3(256), 0, s, a); g_last_kernel = "k_attn16_v5<0, 4, 3, 1, false, true>"; }
     else { hipLaunchKernelGGL((k_attn16_v5<128, 4, 3, 1, false, true>), dim3(a.npad / 128, kHeads, a.BS), dim3(256), 0, s, a); g_last_kernel = "k_attn16_v5<128, 4, 3, 1, false, true>"; }
     return;
   }
-  if (a.nsplit > 1 && a.part != nullptr && a.tickets != nullptr && (g_attn_variant == 4 || g_attn_variant == 59)) {
+  if (a.nsplit > 1 && a.part != nullptr && a.tickets != nullptr && (k.attn_variant == 4 || k.attn_variant == 59)) {
     hipLaunchKernelGGL((k_attn16_v5<0, 4, 3, 1, true>), dim3(a.npad / 128 * a.nsplit, kHeads, a.BS), dim3(256), 0, s, a);
     g_last_kernel = "k_attn16_v5<0, 4, 3, 1, true, false>";
     return;
   }
   dim3 grid(a.npad / 128, kHeads, a.BS), block(256);
-  if (g_attn_variant == 56) hipLaunchKernelGGL((k_attn16_v5<128, 4>), grid, block, 0, s, a);   // the maximum searched in every tile (the exact path a workgroup falls back to)
+  if (k.attn_variant == 56) hipLaunchKernelGGL((k_attn16_v5<128, 4>), grid, block, 0, s, a);   // the maximum searched in every tile (the exact path a workgroup falls back to)
   else hipLaunchKernelGGL((k_attn16_v5<0, 4>), grid, block, 0, s, a);
 }
 }  // namespace gn

@@ -404,8 +404,9 @@ __global__ __launch_bounds__(256) void k_attn_pw(AttnArgs a, int nitems) {
 #undef GN_PIN
 }  // namespace
 
-// grids of whole 256-query blocks; false = not applicable, the caller launches k_attn16_v5.  stamps: the phase-stamp form (developer knob 1 = 73)
-bool launch_attention_pw(const AttnArgs& a, bool stamps, hipStream_t s) {
+// grids of whole 256-query blocks; false = not applicable, the caller launches k_attn16_v5.  Developer knob 1 = 73: the phase-stamp form
+bool launch_attention_pw(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k) {
+  const bool stamps = k.attn_variant == 73;
   if (a.npad % 256 != 0 || a.qb == nullptr) return false;
   const int nitems = a.npad / 256 * kHeads * a.BS;
   if (nitems < 8) return false;
@@ -415,8 +416,8 @@ bool launch_attention_pw(const AttnArgs& a, bool stamps, hipStream_t s) {
   const dim3 grid((unsigned)((stamps || nitems < ncu) ? (nitems & ~7) : (ncu & ~7))), block(256);
   if (a.half_fmt) {
     if (stamps) {
-      if (g_attn_stamps == nullptr) return false;
-      AttnArgs b = a; b.part = reinterpret_cast<float*>(g_attn_stamps); b.tiles = nullptr;
+      if (k.attn_stamps == nullptr) return false;
+      AttnArgs b = a; b.part = reinterpret_cast<float*>(k.attn_stamps); b.tiles = nullptr;
       hipLaunchKernelGGL((k_attn_pw<true, 8>), grid, block, 0, s, b, nitems);
     }
     else hipLaunchKernelGGL((k_attn_pw<true, 0>), grid, block, 0, s, a, nitems);

@@ -67,6 +67,29 @@ template <bool F16> __device__ __forceinline__ unsigned int pack16(float lo, flo
 // the same with the format chosen at run time (GEMM epilogues shared by both attention formats)
 __device__ __forceinline__ unsigned int pack16_rt(float lo, float hi, int f16) { return f16 ? pack16<true>(lo, hi) : pack16<false>(lo, hi); }
 
+// ---- kernel selection ------------------------------------------------------------------------
+// The developer knobs the launch functions below choose their kernel from (numbers: gn_debug_set_variant / gn_loftr_debug_set_variant in
+// include/gisnav_amd.h).  Host side only: a context (gn_ctx, gn_loftr) owns one and hands it to every launch it makes, so nothing a launch path
+// consults is process-wide; a caller that wants another selection for one launch passes a modified copy.  A default-constructed struct selects
+// the shipped kernels.
+struct LaunchKnobs {
+  int gemm_variant = 3;        // knob 0 (launch_gemm_f32): 3 exact-f32 MFMA, 5 f32x3, 6 f16x2; 4 / 50.. / 60..: tools/gemm_bench.py
+  int p2_wide = 1;             // knob 8 (launch_gemm_p2): 1 = the 256x256 kernel when the shape allows, 0 = always the 128x128 kernel
+  int gemm_m64 = 320;          // knob 41: the exact-f32 GEMM runs on 64-row tiles when its 128 x 128 grid has at most this many workgroups (0 = never)
+  int gemm_r64 = 1;            // knob 44 (launch_gemm_f32)
+  int attn_variant = 4;        // knob 1 (launch_attention_bf16_v2): 4 = the automatic attention kernel choice; 0 = k_attn_bf16 (f32 inputs, in-kernel conversion)
+  long long* attn_stamps = nullptr;   // knob 1 = 73: k_attn_pw writes s_memtime phase stamps here (the idle sim buffer of the view being run)
+  int attn_f32_ks = 0;         // knob 43 (launch_attention_f32): bits 0-1: 0 = k_attn_f32_ks for one or two pairs per call, 1 = never, 2 = always; bit 2: its eight-wave form
+  int ffn_stamps = 0;          // knob 12: 8 = phase stamps into FfnArgs::dbg_ts (k_ffn_fused; k_ffn128 also 136), 0 otherwise
+  int ffn_shape = 0;           // knob 14: 0 = automatic, 128 / 64 / 32 = force the 128-token / 64-token / 32-token workgroup shape
+  int lf_conv = 0;             // knob 42 (gn_loftr.hip lf_conv): bits 8.. = the overhead term of the rows-per-wave cost model x 100 (0 = the shipped 0.25); bits 0-7 are retired
+  int sp_conv_s = 2;           // knob 34: 0 = the split-fp16 mode on f32 activations through k_sp_conv<., 1, ...> (the round-2 kernel, also the path of frames beyond
+                               // 8 Mpixel); 2 = hm16 activations: k_sp_conv_s16 for the 3 x 3 layers (another k order: f32 rounding), k_sp_conv_s for the 1 x 1 layers
+  int sp_fuse1 = 1;            // knob 46: 0 = k_sp_conv1 + k_sp_conv_s16 as two launches (the round-5 form; bitwise the same results)
+  int sp_select_stream = 0;    // knob 40: 1 = k_sp_select reads the candidate list from memory in every pass (the path of frames with more than 40 960 candidates)
+  int sift_general_blur = 0;   // knob 50: every SIFT level through k_blur_row + k_blur_col, no fused launch, no tail
+};
+
 // ---- GEMM -----------------------------------------------------------------------------------
 enum GemmEpi { EPI_BIAS = 0, EPI_SCALE_COLS = 1, EPI_ROTARY = 2, EPI_RESIDUAL = 3, EPI_PLAIN = 4,
                EPI_ROTARY_BF16 = 5, EPI_SCALE_BF16 = 6,
@@ -107,17 +130,11 @@ struct GemmArgs {
   // a row tile whose first row r has (mlim_seg ? r % mlim_seg : r) >= mlim[0] * mlim_mul is skipped (its rows of Y keep what they held)
   const int* mlim; int mlim_mul; int mlim_seg;
 };
-void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int sel_m = 0);
-void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s);   // fp16-plane operands (Ap, Wp)
+void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, const LaunchKnobs& k, int sel_m = 0);
+void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s, const LaunchKnobs& k);   // fp16-plane operands (Ap, Wp)
 void launch_mfma_probe(float* out, int blocks, int iters, hipStream_t s);
 void launch_lds_dma_probe(const float* pattern, unsigned int* out, int blocks, int spin, hipStream_t s);
-extern int g_gemm_m64;
-extern int g_gemm_r64;
-extern int g_attn_f32_ks;     // developer knob 43 (gn_attention.hip launch_attention_f32)
-extern int g_lf_conv_knob;   // developer knob 42 (gn_loftr.hip lf_conv)
 extern thread_local const char* g_last_kernel;   // bench facility: rocprof-style name of the kernel the last launch_* call of THIS host thread dispatched
-extern thread_local int g_gemm_variant;  // developer knob: kernel variant selector for A/B benchmarking (per host thread: every API entry sets it from its own context before it launches)
-extern int g_p2_wide;       // developer knob: 1 = k_gemm_p2 uses the 256x256 kernel when the shape allows
 
 // ---- fused block tail (gn_ffn.hip): x <- x + ffn.3(GELU(LayerNorm(ffn.0([x | msg])))) for hm16 rows ----------
 struct FfnArgs {
@@ -151,11 +168,11 @@ struct FfnArgs {
   uint16_t* q_qkb = nullptr; uint16_t* q_vt = nullptr;                                     // fp16 q | k (ld 512) or qk (ld 256) rows; V^T panels [slot][4][64][npad]
   float q_qscale = 1.f, q_scale = 1.f;                                                     // QkvArgs::qscale (self) / scale (cross)
 };
-void launch_ffn_fused(const FfnArgs& a, hipStream_t s);
-bool ffn_selects_128(const FfnArgs& a);   // true when launch_ffn_fused(a) dispatches k_ffn128 (the caller may then ask for the fused projection: a.qkv)
+// the bulk block tail's grid rule: T token rows run on 128-token workgroups (k_ffn128) when there are at least 256 of them; shape = developer knob 14
+inline bool ffn_bulk_shape(int shape, int T) { return T % 128 == 0 && (shape == 128 || (shape == 0 && T / 128 >= 256)); }
+void launch_ffn_fused(const FfnArgs& a, hipStream_t s, const LaunchKnobs& k);
+bool ffn_selects_128(const FfnArgs& a, const LaunchKnobs& k);   // true when launch_ffn_fused(a) dispatches k_ffn128 (the caller may then ask for the fused projection: a.qkv)
 void launch_ffn128(const FfnArgs& a, int stamps, hipStream_t s);   // gn_ffn128.hip: 128 tokens per workgroup (a.cp set, a.T % 128 == 0); stamps: developer knob 12
-extern int g_ffn_stamps;
-extern int g_ffn_shape;
 void build_weight_fragments(const float* w, int N, int K, float scale, int permute_k, uint16_t* out);   // host arrays; out: 2 * N * K halfs
 
 // ---- attention input projections of the f16x2 mode (gn_qkv.hip): hm16 rows in, bf16 q | k rows and bf16 V^T panels out -------
@@ -250,14 +267,12 @@ struct PruneArgs {
 void launch_prune_init(int32_t* ind, int32_t* prune, int32_t* n_in, const int32_t* nvalid, int BS, int npad, hipStream_t s);
 void launch_prune(const PruneArgs& a, hipStream_t s);
 void launch_unprune_idx(int64_t* idx, const int32_t* n_match, const int32_t* ind, int B, int npad, int kmax, hipStream_t s);
-void launch_attention_f32(const AttnArgs& a, hipStream_t s);
+void launch_attention_f32(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k);
 void launch_attention_bf16(const AttnArgs& a, hipStream_t s);
 void launch_attention_f16x2(const AttnArgs& a, hipStream_t s);   // k_attn_f16x2 (gn_attention_f16x2.hip): f32 rows in, split-fp16 operands, f32-accurate
-void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s);
-bool launch_attention_pw(const AttnArgs& a, bool stamps, hipStream_t s);   // k_attn_pw (gn_attention_pw.hip): bulk grids, npad % 256 == 0; false = not applicable
+void launch_attention_bf16_v2(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k);
+bool launch_attention_pw(const AttnArgs& a, hipStream_t s, const LaunchKnobs& k);   // k_attn_pw (gn_attention_pw.hip): bulk grids, npad % 256 == 0; false = not applicable
 void launch_pack_attn_bf16(const AttnArgs& a, uint16_t* qkb, uint16_t* vtb, hipStream_t s);   // (a.half_fmt selects bf16 / fp16)   // f32 rows -> the bf16 layouts k_attn_bf16_v5 reads (test entry)
-extern thread_local long long* g_attn_stamps;   // developer (knob 1 = 73): k_attn_pw writes s_memtime phase stamps here (the idle sim buffer)
-extern thread_local int g_attn_variant;  // developer knob 1: 4 = the automatic attention kernel choice (default)
 
 // ---- elementwise / small kernels ----------------------------------------------------------------
 struct PrepArgs {
@@ -442,12 +457,12 @@ struct SiftKeypoint { float x, y, size, angle, response; int octave; };
 // rounds them to -- edge1 = (float)(edgeThreshold + 1), the sum formed in double as oracle/sift.py writes it
 struct SiftParams { int n_layers; float contrast_thr, edge_thr, edge1, sigma; };
 void sift_gaussian_kernel(double sigma, std::vector<float>& k);
-void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int* counters, hipStream_t s);
+// general (developer knob 50, here and below): every level through k_blur_row + k_blur_col, no fused launch, no tail
+void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int general, int* counters, hipStream_t s);
 // dog = out - in; in_step 2 reads every second pixel of a source image of row stride in_w (half_scratch: only used by the two-launch form)
-void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, hipStream_t s,
+void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, int general, hipStream_t s,
                float* dog = nullptr, int in_step = 1, int in_w = 0, float* half_scratch = nullptr);
-extern int g_sift_general_blur;   // developer switch (gn_debug_set_variant 50): every level through k_blur_row + k_blur_col, no fused launch, no tail
-int sift_tail_first(const SiftPyramid& py, const int* ksize);
+int sift_tail_first(const SiftPyramid& py, const int* ksize, int general);
 void sift_tail(const SiftPyramid& py, int B, int o_first, const float* dk, const int* koff, const int* ksize, hipStream_t s);
 void sift_find(const SiftPyramid& py, int B, float threshold, int4* cand, int* counters, int max_cand, hipStream_t s);
 // counters: int[4] per image = {candidates, raw keypoints, final keypoints, -}; kp: per image [max_raw raw | max_raw sorted | final], kp_stride records apart
@@ -458,11 +473,9 @@ void sift_sort_dedup(int B, SiftKeypoint* kp, long long kp_stride, int* counters
 
 // ---- SuperPoint extractor (gn_superpoint.hip) ------------------------------------------------------------------
 void sp_weight_fragments(const float* w, int Cout, int Cin, int taps, int Cout_pad, float* out);   // host arrays
-void sp_conv1(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, hipStream_t s, int out_half = 0, unsigned int* ovf = nullptr);
+void sp_conv1(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, hipStream_t s, int out_half = 0, unsigned int* ovf = nullptr);   // out_half: 0 f32, 1 fp16, 2 hm16 records (guarded by ovf)
 void sp_conv_fused1(const float* gray, const float* w1, const float* b1, int B, int H, int W, const float* bias, float* out, int Cout_pad, hipStream_t s,
                     const uint16_t* wfh, float acc_scale, unsigned int* ovf);   // layers 0 + 1 in one launch (split-fp16 mode, hm16 records out, 2 x 2 max-pool fused)
-extern int g_sp_fuse1;   // out_half: 0 f32, 1 fp16, 2 hm16 records (guarded by ovf)
-extern int g_sp_conv_s, g_sp_select_stream;
 void sp_weight_fragments_hm16(const float* w, int Cout, int Cin, int taps, int Cout_pad, float scale, uint16_t* out);   // host arrays; out: 2 * Cout_pad * taps * Cin halfs
 void sp_conv(const float* in, int B, int H, int W, int Cin, const float* wf, const float* bias, float* out, int Cout_pad, int taps, int relu, hipStream_t s,
              const uint16_t* wfh = nullptr, float acc_scale = 1.f, unsigned int* ovf = nullptr, int pool = 0,
@@ -472,7 +485,7 @@ void sp_pool(const float* in, float* out, int B, int H, int W, int C, hipStream_
 void sp_scores(const float* logits, int cp, float* scores, int B, int h, int w, hipStream_t s);
 void sp_nms(const float* scores, int B, int H, int W, float* out, hipStream_t s);   // simple_nms(scores, 4)
 void sp_select(const float* nms, int B, int H, int W, float thr, int border, int* cand, int* counts, int cap, int k,
-               float* kpt_xysa, float* score, int* kp_index, long long out_stride, hipStream_t s);
+               float* kpt_xysa, float* score, int* kp_index, long long out_stride, int stream_cand /* developer knob 40 */, hipStream_t s);
 void sp_describe(const float* dmap, int B, int h, int w, const float* kpt_xysa, const int* counts, long long out_stride, int max_k, float* desc, hipStream_t s);
 
 // ---- bf16 helpers -------------------------------------------------------------------------------

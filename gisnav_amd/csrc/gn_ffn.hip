@@ -398,34 +398,30 @@ __global__ __launch_bounds__(NW * 64) void k_ffn_fused(FfnArgs a) {
 }
 }  // namespace
 
-int g_ffn_stamps = 0;   // developer knob 12: 8 = phase stamps into FfnArgs::dbg_ts (k_ffn_fused; k_ffn128 also 136), 0 otherwise
-int g_ffn_shape = 0;    // developer knob 14: 0 = automatic, 64 / 32 = force the 64-token / 32-token workgroup shape
-bool ffn_selects_128(const FfnArgs& a) {
-  return a.cp != nullptr && a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256));
-}
-void launch_ffn_fused(const FfnArgs& a_in, hipStream_t s) {
+bool ffn_selects_128(const FfnArgs& a, const LaunchKnobs& k) { return a.cp != nullptr && ffn_bulk_shape(k.ffn_shape, a.T); }
+void launch_ffn_fused(const FfnArgs& a_in, hipStream_t s, const LaunchKnobs& k) {
   FfnArgs a = a_in;
-  if (a.composed && !(a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256)))) {
+  if (a.composed && !ffn_bulk_shape(k.ffn_shape, a.T)) {
     // composed weights on a small grid: k_ffn_fused's "message rows from memory" form IS ffn.0 over [x | rows] -- the rows are the attention output
     a.mp = a.cp; a.cp = nullptr; a.composed = 0;
   }
   // small grids: 32-token workgroups give twice the workgroups (fewer than one 64-token workgroup per CU leaves CUs idle)
-  const bool small = g_ffn_shape == 32 || (g_ffn_shape == 0 && a.T / 64 < 256);
+  const bool small = k.ffn_shape == 32 || (k.ffn_shape == 0 && a.T / 64 < 256);
   if (a.cp == nullptr) {   // message rows from memory (separate out_proj launch)
     if (small) { hipLaunchKernelGGL((k_ffn_fused<0, false, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a); g_last_kernel = "k_ffn_fused<0, false, 8, 1>"; }
     else { hipLaunchKernelGGL((k_ffn_fused<0, false, 8, 2>), dim3(a.T / 64), dim3(512), 0, s, a); g_last_kernel = "k_ffn_fused<0, false, 8, 2>"; }
     return;
   }
   // bulk grids: 128 tokens per workgroup, one wave per SIMD (gn_ffn128.hip); developer knob 14 = 128 / 64 / 32 forces a shape
-  if (a.T % 128 == 0 && (g_ffn_shape == 128 || (g_ffn_shape == 0 && a.T / 128 >= 256))) { launch_ffn128(a, g_ffn_stamps, s); return; }
+  if (ffn_bulk_shape(k.ffn_shape, a.T)) { launch_ffn128(a, k.ffn_stamps, s); return; }
   if (small) {
-    if (g_ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
+    if (k.ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((k_ffn_fused<0, true, 8, 1>), dim3(a.T / 32), dim3(512), 0, s, a);
     g_last_kernel = "k_ffn_fused<0, true, 8, 1>";
     return;
   }
   const dim3 grid(a.T / 64), block(512);
-  if (g_ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 2>), grid, block, 0, s, a);
+  if (k.ffn_stamps == 8) hipLaunchKernelGGL((k_ffn_fused<8, true, 8, 2>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((k_ffn_fused<0, true, 8, 2>), grid, block, 0, s, a);
   g_last_kernel = "k_ffn_fused<0, true, 8, 2>";
 }

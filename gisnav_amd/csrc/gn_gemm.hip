@@ -1237,11 +1237,6 @@ __global__ __launch_bounds__(256) void k_gemm_f16x2(GemmArgs a) {
 }
 }  // namespace
 
-thread_local int g_gemm_variant = 3;
-int g_lf_conv_knob = 0;  // developer knob 42: bits 8.. = the overhead term of lf_conv's rows-per-wave cost model x 100 (0 = the shipped 0.25); bits 0-7 are retired (gn_debug_set_variant refuses them)
-int g_gemm_r64 = 1;     // developer knob 44 (launch_gemm_f32)
-int g_gemm_m64 = 320;    // developer knob 41: the exact-f32 GEMM runs on 64-row tiles when its 128 x 128 grid has at most this many workgroups (0 = never)
-
 // Pure-MFMA ceiling probe: 4 waves per CU-resident block, 8 independent accumulators, no memory traffic.
 __global__ __launch_bounds__(256) void k_mfma_probe(float* out, int iters) {
   f32x16 acc[8];
@@ -1312,19 +1307,19 @@ void launch_mfma_probe(float* out, int blocks, int iters, hipStream_t s) {
 
 // sel_m > 0: the rows that CHOOSE the tile form below (the grids always cover a.M): a caller whose M stacks several independent problems passes
 // the rows of one, so that each of them runs on the form it would run on alone (batched LoFTR)
-void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int sel_m) {
-  g_last_kernel = g_gemm_variant == 5 || (g_gemm_variant >= 50 && g_gemm_variant < 60) ? "k_gemm_f32x3<" : g_gemm_variant >= 6 ? "k_gemm_f16x2<" : "k_gemm_f32_v3<";
+void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, const LaunchKnobs& k, int sel_m) {
+  g_last_kernel = k.gemm_variant == 5 || (k.gemm_variant >= 50 && k.gemm_variant < 60) ? "k_gemm_f32x3<" : k.gemm_variant >= 6 ? "k_gemm_f16x2<" : "k_gemm_f32_v3<";
   dim3 grid(a.N / BN, a.M / BM, batch), block(256);
-  if (g_gemm_variant == 4 && epi == EPI_BIAS) {
+  if (k.gemm_variant == 4 && epi == EPI_BIAS) {
     hipLaunchKernelGGL((k_gemm_f32_v3<EPI_BIAS, false>), grid, block, 0, s, a);
     return;
   }
-  if (g_gemm_variant >= 50 && epi == EPI_BIAS && a.Wp) {   // 50 / 60: k_gemm_f32x3 / k_gemm_f16x2 on the bias epilogue alone (tools/gemm_bench.py)
-    if (g_gemm_variant >= 60) hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true>), grid, block, 0, s, a);
+  if (k.gemm_variant >= 50 && epi == EPI_BIAS && a.Wp) {   // 50 / 60: k_gemm_f32x3 / k_gemm_f16x2 on the bias epilogue alone (tools/gemm_bench.py)
+    if (k.gemm_variant >= 60) hipLaunchKernelGGL((k_gemm_f16x2<EPI_BIAS, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_gemm_f32x3<EPI_BIAS, true>), grid, block, 0, s, a);
     return;
   }
-  if (g_gemm_variant == 6) {
+  if (k.gemm_variant == 6) {
 #define GN_H2(E)                                                                                   \
   if (a.Wp) hipLaunchKernelGGL((k_gemm_f16x2<E, true>), grid, block, 0, s, a);                     \
   else hipLaunchKernelGGL((k_gemm_f16x2<E, false>), grid, block, 0, s, a);
@@ -1341,7 +1336,7 @@ void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int s
 #undef GN_H2
     return;
   }
-  if (g_gemm_variant == 5) {
+  if (k.gemm_variant == 5) {
 #define GN_X3(E)                                                                                   \
   if (a.Wp) hipLaunchKernelGGL((k_gemm_f32x3<E, true>), grid, block, 0, s, a);                     \
   else hipLaunchKernelGGL((k_gemm_f32x3<E, false>), grid, block, 0, s, a);
@@ -1358,15 +1353,15 @@ void launch_gemm_f32(int epi, const GemmArgs& a, int batch, hipStream_t s, int s
     return;
   }
   // small grids: 64-row tiles when 128 x 128 tiles would leave more than a third of the CUs without a workgroup (same bits: k_gemm_f32_m64)
-  if (g_gemm_m64 && (epi == EPI_BIAS || epi == EPI_PLAIN || epi == EPI_RELU || epi == EPI_SCALE_COLS || epi == EPI_ROTARY || epi == EPI_RESIDUAL) &&
-      (long long)grid.x * ((sel_m > 0 ? sel_m : a.M) / BM) * grid.z <= g_gemm_m64) {
+  if (k.gemm_m64 && (epi == EPI_BIAS || epi == EPI_PLAIN || epi == EPI_RELU || epi == EPI_SCALE_COLS || epi == EPI_ROTARY || epi == EPI_RESIDUAL) &&
+      (long long)grid.x * ((sel_m > 0 ? sel_m : a.M) / BM) * grid.z <= k.gemm_m64) {
     const dim3 g64(a.N / BN, a.M / 64, batch);
     const long long sel64 = (long long)g64.x * ((sel_m > 0 ? sel_m : a.M) / 64) * g64.z;
     // developer knob 44: 0 = k_gemm_f32_m64 always; 1 (default) = k_gemm_f32_r64 on 64 x 64 tiles when 64 x 128 tiles leave half of the CUs idle (at most
     // 128 workgroups: 19.9 -> 14.5 us per GEMM of a one-pair call), k_gemm_f32_m64 otherwise; 2 = the ring kernel on 64 x 128 tiles everywhere (measured:
     // 19.4 against 19.9 us -- it is the tile count, not the ring, that pays; its 96 KB of LDS leave one workgroup per CU)
-    const bool n64 = g_gemm_r64 == 1 && sel64 <= 128 && a.N % 64 == 0;
-    if (n64 || g_gemm_r64 == 2) {
+    const bool n64 = k.gemm_r64 == 1 && sel64 <= 128 && a.N % 64 == 0;
+    if (n64 || k.gemm_r64 == 2) {
       const dim3 gr(n64 ? a.N / 64 : a.N / BN, a.M / 64, batch);
       g_last_kernel = "k_gemm_f32_r64<";
 #define GN_R64(E) do { if (n64) hipLaunchKernelGGL((k_gemm_f32_r64<E, 64>), gr, block, 0, s, a); else hipLaunchKernelGGL((k_gemm_f32_r64<E, 128>), gr, block, 0, s, a); } while (0)

@@ -708,9 +708,8 @@ __global__ __launch_bounds__(512) void k_gemm_p2ln(GemmArgs a) {
 }  // namespace
 
 thread_local const char* g_last_kernel = "";
-int g_p2_wide = 1;   // developer knob 8: 0 = always the 128x128 kernel
 
-void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s) {
+void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s, const LaunchKnobs& k) {
   if (epi == EPI_LN_GELU) {   // ffn.0 + LayerNorm + GELU (caller guarantees N == 512, M % 128 == 0, hm16 output)
     dim3 grid(1, a.M / LBM, batch), block(512);
     hipLaunchKernelGGL((k_gemm_p2ln<0>), grid, block, 0, s, a);
@@ -718,7 +717,7 @@ void launch_gemm_p2(int epi, const GemmArgs& a, int batch, hipStream_t s) {
     return;
   }
   // the 256x256 kernel needs enough tiles to occupy the chip (small batches) and K >= 256 (short-K shapes are faster on 128x128)
-  if (g_p2_wide && a.M % WBM == 0 && a.N % WBN == 0 && a.K >= 256 && (long long)(a.M / WBM) * (a.N / WBN) * batch >= 192) {
+  if (k.p2_wide && a.M % WBM == 0 && a.N % WBN == 0 && a.K >= 256 && (long long)(a.M / WBM) * (a.N / WBN) * batch >= 192) {
     dim3 grid(a.N / WBN, a.M / WBM, batch), block(512);
 #define P2W_CASE(E) case E: hipLaunchKernelGGL((k_gemm_p2w<E>), grid, block, 0, s, a); break;
     switch (epi) {

@@ -1015,6 +1015,7 @@ struct gn_loftr {
   int* n_host = nullptr;
   int use_graph = 1; std::map<int, hipGraphExec_t> graph_exec; std::map<int, bool> graph_failed; hipStream_t cap_stream = nullptr;   // gn_loftr_set_graph; one graph per (arithmetic, certificate, B): key 4 B + 2 certified + arithmetic
   int arith = 0;                        // gn_loftr_set_arithmetic: 0 exact f32, 1 split fp16 (f32-accurate)
+  gn::LaunchKnobs knobs;                // gn_loftr_debug_set_variant: lf_conv's cost model (42) and the exact-f32 GEMM's tile forms (41, 44); lf_gemm sets the GEMM family from arith
   unsigned int* ovf = nullptr; long long ovf_trips = 0;   // split mode: fp16-range guard words (device, one per pair), pairs that fell back to the exact kernels
   // gn_loftr_set_certify: certify 0 off / 1 flags / 2 flags + exact-f32 re-run; cert_fwd: the forward being enqueued evaluates the
   // certificate (off in the re-run); eps_set < 0 = "the calibrated one" (eps_cal, < 0 while there is none: gn_loftr_load_tensor discards it);
@@ -1132,7 +1133,7 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
   // (+ 0.25: the halo rows, the weight stream and the prologue a workgroup pays whatever its height -- without it RPW = 1 wins ties it loses on the GPU;
   // developer knob 42, bits 8..: another overhead, in 1/100 units -- the tile height must not change a bit, tests/test_gpu_fp64_loftr.py)
   const bool fast = c.cout_p % 64 == 0 && c.cin == c.cin_p;      // k_lf_conv<.., FAST>: both 32-channel tiles in every group, every 32-channel slice whole
-  const double ovh = (gn::g_lf_conv_knob >> 8) ? (gn::g_lf_conv_knob >> 8) * 0.01 : 0.25;
+  const double ovh = (ctx->knobs.lf_conv >> 8) ? (ctx->knobs.lf_conv >> 8) * 0.01 : 0.25;
   // (the model counts the workgroups of ONE pair, N = 2, whatever the batch: the kernel form a pair runs on, and with it its bits, must not depend on its neighbours)
   auto units = [&](int rpw) { const long long wg = (long long)((a.Wout + 31) / 32) * ((a.Hout + 4 * rpw - 1) / (4 * rpw)) * 2 * og; return (double)((wg + 255) / 256) * (rpw + ovh); };
   const dim3 blk(256);
@@ -1157,19 +1158,17 @@ void lf_conv(gn_loftr* ctx, const char* name, const float* in, int N, int Hin, i
   }
 }
 
-thread_local int g_lf_gemm_variant = 3;   // set by lf_forward from the context it runs (per host thread)
-thread_local int g_lf_pairs = 1;          // pairs of the forward being launched: a GEMM over the rows of all pairs picks its tile form from the rows of ONE (launch_gemm_f32's sel_m)
 struct LfLimit { const int* n = nullptr; int mul = 0, seg = 0; };     // GemmArgs::mlim
-void lf_gemm(const float* A, int lda, const float* A2, int lda2, int K1, const float* Wt, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K, hipStream_t s, bool relu = false,
+// (a GEMM over the rows of all ctx->B pairs of the forward picks its tile form from the rows of ONE: launch_gemm_f32's sel_m)
+void lf_gemm(gn_loftr* ctx, const float* A, int lda, const float* A2, int lda2, int K1, const float* Wt, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K, hipStream_t s, bool relu = false,
              LfLimit lim = LfLimit(), int pairs = 0 /* pairs whose rows M holds; 0 = all of the forward's */) {
   GemmArgs g;
   memset(&g, 0, sizeof g);
   g.mlim = lim.n; g.mlim_mul = lim.mul; g.mlim_seg = lim.seg;
   g.A = A; g.lda = lda; g.A2 = A2; g.lda2 = lda2; g.K1 = A2 ? K1 : K; g.W = Wt; g.ldw = ldw; g.bias = bias; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.acc_scale = 1.f;
-  const int saved = gn::g_gemm_variant;
-  gn::g_gemm_variant = g_lf_gemm_variant;                   // 3 = the exact-f32 MFMA GEMM, whatever other contexts selected; 6 = every f32 operand split into two fp16 terms on the fly (gn_loftr_set_arithmetic)
-  launch_gemm_f32(relu ? EPI_RELU : bias ? EPI_BIAS : EPI_PLAIN, g, 1, s, M / (pairs > 0 ? pairs : g_lf_pairs));      // (relu: the MLP's first layer, max(x, 0) applied to the value the plain epilogue would store)
-  gn::g_gemm_variant = saved;
+  LaunchKnobs k = ctx->knobs;
+  k.gemm_variant = ctx->arith == 1 ? 6 : 3;                 // 3 = the exact-f32 MFMA GEMM; 6 = every f32 operand split into two fp16 terms on the fly (gn_loftr_set_arithmetic)
+  launch_gemm_f32(relu ? EPI_RELU : bias ? EPI_BIAS : EPI_PLAIN, g, 1, s, k, M / (pairs > 0 ? pairs : ctx->B));      // (relu: the MLP's first layer, max(x, 0) applied to the value the plain epilogue would store)
 }
 
 // One LoFTREncoderLayer over the sequences of buffer x ([rows_pad][d], sequences `seq_rows` rows apart, Lseq valid tokens each):
@@ -1181,7 +1180,7 @@ void lf_gemm(const float* A, int lda, const float* A2, int lda2, int K1, const f
 // d = 256: the coarse level (K^T V per sequence as a two-stage token reduction, its chunk and split chosen from Lseq alone); d = 128: the fine
 // level (windows of Lseq = seq_rows = 25 tokens, k_lf_fine_attn; kvpart / kv unused).  lim (fine level only): the windows behind the match count
 // are skipped (LfLimit with seg = the rows of one side)
-void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pad, int d, int side,
+void lf_encoder(gn_loftr* ctx, const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pad, int d, int side,
                 float* qkv, float* att, float* msg, float* hid, float* kvpart, float* kv, hipStream_t s, LfLimit lim = LfLimit()) {
   const int heads = kLfHeads, per_side = rows_pad / seq_rows / 2;
   const bool cross = side >= 0;
@@ -1193,10 +1192,10 @@ void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pa
   float* qa = qkv + (size_t)a * half * 3 * d; float* kvb = qkv + (size_t)b * half * 3 * d + d;
   float* atta = att + (size_t)a * half * d; float* msga = msg + (size_t)a * half * d; float* hida = hid + (size_t)a * half * 2 * d;
   if (cross) {
-    lf_gemm(xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, rows, d, d, s, false, hl);
-    lf_gemm(xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, rows, 2 * d, d, s, false, hl);
+    lf_gemm(ctx, xa, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qa, 3 * d, rows, d, d, s, false, hl);
+    lf_gemm(ctx, xb, d, nullptr, 0, 0, ly.qkv.w + (size_t)d * d, d, nullptr, kvb, 3 * d, rows, 2 * d, d, s, false, hl);
   } else {
-    lf_gemm(x, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qkv, 3 * d, rows, 3 * d, d, s, false, hl);
+    lf_gemm(ctx, x, d, nullptr, 0, 0, ly.qkv.w, d, nullptr, qkv, 3 * d, rows, 3 * d, d, s, false, hl);
   }
   if (d == kLfDim) {
     const int chunk = 192, nsplit = (Lseq + chunk - 1) / chunk;
@@ -1208,10 +1207,10 @@ void lf_encoder(const LfLayer& ly, float* x, int seq_rows, int Lseq, int rows_pa
   } else {
     hipLaunchKernelGGL(k_lf_fine_attn, dim3(nseq), dim3(128), 0, s, qkv, Lseq, att, a * per_side, (b - a) * per_side, lim.n, per_side);
   }
-  lf_gemm(atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, rows, d, d, s, false, hl);
+  lf_gemm(ctx, atta, d, nullptr, 0, 0, ly.merge.w, d, nullptr, msga, d, rows, d, d, s, false, hl);
   hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, msga, ly.n1g, ly.n1b, (const float*)nullptr, msga, (long long)rows, d, hl.n, hl.mul, hl.seg);
-  lf_gemm(xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, rows, 2 * d, 2 * d, s, true, hl);
-  lf_gemm(hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, rows, d, 2 * d, s, false, hl);
+  lf_gemm(ctx, xa, d, msga, d, d, ly.mlp0.w, 2 * d, nullptr, hida, 2 * d, rows, 2 * d, 2 * d, s, true, hl);
+  lf_gemm(ctx, hida, 2 * d, nullptr, 0, 0, ly.mlp2.w, 2 * d, nullptr, atta, d, rows, d, 2 * d, s, false, hl);
   hipLaunchKernelGGL(k_lf_layernorm, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, atta, ly.n2g, ly.n2b, xa, xa, (long long)rows, d, hl.n, hl.mul, hl.seg);
 }
 }  // namespace
@@ -1382,8 +1381,6 @@ int gn_loftr_missing_tensors(const gn_loftr* ctx) {
 static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   const int H = ctx->H, W = ctx->W, h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4, hc = ctx->hc, wc = ctx->wc, L = ctx->L, Lp = ctx->Lp;
   const int B = ctx->B, N = 2 * B;
-  g_lf_gemm_variant = ctx->arith == 1 ? 6 : 3;
-  g_lf_pairs = B;
   for (int b0 = 0; b0 < B; b0 += 256) hipLaunchKernelGGL(k_lf_clear_words, dim3(1), dim3(256), 0, s, ctx->ovf + b0, std::min(256, B - b0));
   // ---- backbone (the images of both sides as a batch of 2 B)
   {
@@ -1425,10 +1422,10 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   for (int i = 0; i < 8; ++i) {
     const LfLayer& ly = ctx->coarse[i];
     if ((i & 1) == 0) {
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, -1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ctx, ly, ctx->tok, Lp, L, N * Lp, kLfDim, -1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
     } else {   // feat0 <- layer(feat0, feat1); then feat1 <- layer(feat1, feat0 UPDATED): two passes, each updating one side
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
-      lf_encoder(ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ctx, ly, ctx->tok, Lp, L, N * Lp, kLfDim, 0, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
+      lf_encoder(ctx, ly, ctx->tok, Lp, L, N * Lp, kLfDim, 1, ctx->qkv, ctx->att, ctx->msg, ctx->hid, ctx->kvpart, ctx->kv, s);
     }
   }
   if (ctx->arith == 1) hipLaunchKernelGGL(k_lf_check_finite, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->tok, tok4, ctx->ovf, (long long)Lp * 64, B);
@@ -1436,7 +1433,7 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
   const float temp = 0.1f;
   hipLaunchKernelGGL(k_lf_scale, dim3((unsigned)((tok4 + 255) / 256)), dim3(256), 0, s, ctx->tok, ctx->fs, 16.0f, tok4);
   for (int b = 0; b < B; ++b)
-    lf_gemm(ctx->fs + (size_t)b * Lp * 256, 256, nullptr, 0, 0, ctx->fs + (size_t)(B + b) * Lp * 256, 256, nullptr, ctx->sim + (size_t)b * Lp * Lp, Lp, Lp, Lp, 256, s, false, LfLimit(), 1);
+    lf_gemm(ctx, ctx->fs + (size_t)b * Lp * 256, 256, nullptr, 0, 0, ctx->fs + (size_t)(B + b) * Lp * 256, 256, nullptr, ctx->sim + (size_t)b * Lp * Lp, Lp, Lp, Lp, 256, s, false, LfLimit(), 1);
   const int nsplit = 32, rows_per = (L + nsplit - 1) / nsplit;
   hipLaunchKernelGGL(k_lf_row_stats, dim3(L, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->rmax, ctx->rsum);
   hipLaunchKernelGGL(k_lf_col_stats, dim3((L + 255) / 256, nsplit, B), dim3(256), 0, s, ctx->sim, Lp, L, temp, ctx->cpart_a, ctx->cpart_b, rows_per);
@@ -1465,12 +1462,12 @@ static int lf_forward(gn_loftr* ctx, hipStream_t s) {
     // of side 0 pairs with window q + Mp, and a cross half projects, merges and normalises only the side it updates
     LfLimit lim1, lim25;
     lim1.n = ctx->n_tot; lim1.mul = 1; lim1.seg = Mp; lim25.n = ctx->n_tot; lim25.mul = kLfWW; lim25.seg = Mp * kLfWW;
-    lf_gemm(ctx->fc, 256, nullptr, 0, 0, ctx->down_proj.w, 256, ctx->down_proj.b, ctx->fwin, 128, 2 * Mp, 128, 256, s, false, lim1);
+    lf_gemm(ctx, ctx->fc, 256, nullptr, 0, 0, ctx->down_proj.w, 256, ctx->down_proj.b, ctx->fwin, 128, 2 * Mp, 128, 256, s, false, lim1);
     hipLaunchKernelGGL(k_lf_fine_gather, dim3((unsigned)((2LL * Mp * kLfWW * 64 + 255) / 256)), dim3(256), 0, s, ctx->x1_out, h2, w2, wc, ctx->i_ids, ctx->j_ids, ctx->cat, M, B, ctx->n_tot, Mp, ctx->fwin, ctx->frows);
-    lf_gemm(ctx->frows, 256, nullptr, 0, 0, ctx->merge_feat.w, 256, ctx->merge_feat.b, ctx->ftok, 128, R, 128, 256, s, false, lim25);
-    lf_encoder(ctx->finel[0], ctx->ftok, kLfWW, kLfWW, R, kLfFine, -1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
-    lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 0, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
-    lf_encoder(ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
+    lf_gemm(ctx, ctx->frows, 256, nullptr, 0, 0, ctx->merge_feat.w, 256, ctx->merge_feat.b, ctx->ftok, 128, R, 128, 256, s, false, lim25);
+    lf_encoder(ctx, ctx->finel[0], ctx->ftok, kLfWW, kLfWW, R, kLfFine, -1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
+    lf_encoder(ctx, ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 0, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
+    lf_encoder(ctx, ctx->finel[1], ctx->ftok, kLfWW, kLfWW, R, kLfFine, 1, ctx->fqkv, ctx->fatt, ctx->fmsg, ctx->fhid, nullptr, nullptr, s, lim25);
     // (the refined points go into fc, dead since down_proj read it: [B][M][2]; in split arithmetic a result that is not finite raises its pair's guard word)
     hipLaunchKernelGGL(k_lf_fine_match, dim3((unsigned)(((long long)B * M + 3) / 4)), dim3(256), 0, s, ctx->ftok, ctx->ftok + (size_t)Mp * kLfWW * 128, ctx->n_tot, ctx->cat, M, ctx->k1c, ctx->fc,
                        ctx->arith == 1 ? ctx->ovf : (unsigned int*)nullptr);
@@ -1482,6 +1479,20 @@ int gn_loftr_set_arithmetic(gn_loftr* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 1) return GN_ERR_ARG;
   if (mode == 0 && ctx->certify == 2) return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_set_arithmetic: certify mode 2 re-runs flagged pairs in exact f32 and needs arithmetic 1");
   ctx->arith = mode;
+  return GN_OK;
+}
+
+int gn_loftr_debug_set_variant(gn_loftr* ctx, int which, int value) {
+  if (!ctx) return GN_ERR_ARG;
+  if (which == 42 && (value & 0xff) == 0) ctx->knobs.lf_conv = value;      // (bits 0-7: LoFTR's forms of rounds 3-4, retired; bits 8.. -- lf_conv's cost model -- live on)
+  else if (which == 41) ctx->knobs.gemm_m64 = value;
+  else if (which == 44) ctx->knobs.gemm_r64 = value;
+  else return lf_fail(ctx, GN_ERR_ARG, "gn_loftr_debug_set_variant: knobs 41, 42 (bits 8 and up) and 44 are the ones LoFTR's launches read");
+  // the next call captures its graph again, with the knob in force (no replay of the old ones may still be running)
+  LF_HIP(hipSetDevice(ctx->device));
+  LF_HIP(hipDeviceSynchronize());
+  for (auto& g : ctx->graph_exec) if (g.second) hipGraphExecDestroy(g.second);
+  ctx->graph_exec.clear(); ctx->graph_failed.clear();
   return GN_OK;
 }
 

@@ -996,15 +996,14 @@ void sift_gaussian_kernel(double sigma, std::vector<float>& k) {
 
 static inline dim3 grid2d(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
 
-int g_sift_general_blur = 0;
 // tap counts k_sift_tail has a level for: odd, and no wider than its halo (2 kTailPad + 1 = 27)
 static inline bool sift_tail_taps(int n) { return (n & 1) && n >= 7 && n <= 2 * kTailPad + 1; }
-void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, hipStream_t s,
+void sift_blur(int B, long long stride_in, long long stride_out, const float* in, float* tmp, float* out, int w, int h, const float* dk, int n, int general, hipStream_t s,
                float* dog, int in_step, int in_w, float* half_scratch) {
   if (in_w <= 0) in_w = w;
   const dim3 g((w + kFtW - 1) / kFtW, (h + kFtH - 1) / kFtH, B);
 #define GN_FUSED_CASE(N) case N: hipLaunchKernelGGL(k_blur_fused<N>, g, dim3(256), 0, s, in, out, w, h, dk, dog, in_step, in_w, stride_in, stride_out, (int*)nullptr); return;
-  if (!g_sift_general_blur) switch (n) {      // every odd tap count up to kFusedMaxTaps
+  if (!general) switch (n) {      // every odd tap count up to kFusedMaxTaps
     GN_FUSED_CASE(3) GN_FUSED_CASE(5) GN_FUSED_CASE(7) GN_FUSED_CASE(9) GN_FUSED_CASE(11) GN_FUSED_CASE(13) GN_FUSED_CASE(15) GN_FUSED_CASE(17) GN_FUSED_CASE(19)
     GN_FUSED_CASE(21) GN_FUSED_CASE(23) GN_FUSED_CASE(25) GN_FUSED_CASE(27) GN_FUSED_CASE(29) GN_FUSED_CASE(31) GN_FUSED_CASE(33) GN_FUSED_CASE(35) GN_FUSED_CASE(37)
     default: break;
@@ -1027,8 +1026,8 @@ void sift_blur(int B, long long stride_in, long long stride_out, const float* in
 }
 // octaves [o_first, n_oct) in one launch; o_first = sift_tail_first(py) (>= 1; n_oct when a level's kernel is wider than the tail's halo:
 // those pyramids run every octave level by level, through the same expressions)
-int sift_tail_first(const SiftPyramid& py, const int* ksize) {
-  if (g_sift_general_blur) return py.n_oct;
+int sift_tail_first(const SiftPyramid& py, const int* ksize, int general) {
+  if (general) return py.n_oct;
   for (int i = 1; i < py.n_layers + 3; ++i) if (!sift_tail_taps(ksize[i])) return py.n_oct;
   int o = 1;
   while (o < py.n_oct && (py.oct[o].w * py.oct[o].h > kTailPx || py.oct[o].w > kTailSide || py.oct[o].h > kTailSide)) ++o;
@@ -1050,8 +1049,8 @@ void sift_tail(const SiftPyramid& py, int B, int o_first, const float* dk, const
 // createInitialImage for B images: gray [B][h][w] u8 -> level 0 of octave 0 (2h x 2w, blurred to sigma); zeroes counters[4b + 0..2].
 // Stock kernel (11 taps, sigma 1.6): one launch, the doubled image is sampled on the fly; any other sigma: k_sift_base into `scratch` + sift_blur
 // (one fused launch up to kFusedMaxTaps; sigma <= 2.4 needs 19).
-void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int* counters, hipStream_t s) {
-  if (n == 11 && !g_sift_general_blur) {
+void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, float* tmp, float* out, long long out_stride, const float* dk, int n, int general, int* counters, hipStream_t s) {
+  if (n == 11 && !general) {
     const dim3 g((2 * w + kFtW - 1) / kFtW, (2 * h + kFtH - 1) / kFtH, B);
     hipLaunchKernelGGL((k_blur_fused<11, true>), g, dim3(256), 0, s, reinterpret_cast<const float*>(gray), out, 2 * w, 2 * h, dk, (float*)nullptr, 1, 2 * w,
                        (long long)h * w, out_stride, counters);
@@ -1059,7 +1058,7 @@ void sift_base_blur(const uint8_t* gray, int B, int h, int w, float* scratch, fl
   }
   dim3 g = grid2d(2 * w, 2 * h); g.z = B;
   hipLaunchKernelGGL(k_sift_base, g, dim3(256), 0, s, gray, h, w, scratch, out_stride, counters);
-  sift_blur(B, out_stride, out_stride, scratch, tmp, out, 2 * w, 2 * h, dk, n, s);
+  sift_blur(B, out_stride, out_stride, scratch, tmp, out, 2 * w, 2 * h, dk, n, general, s);
 }
 void sift_find(const SiftPyramid& py, int B, float threshold, int4* cand, int* n_cand, int max_cand, hipStream_t s) {
   SiftFindPlan plan;

@@ -1528,8 +1528,6 @@ void sp_weight_fragments_hm16(const float* w, int Cout, int Cin, int taps, int C
           }
 }
 
-int g_sp_conv_s = 2;   // developer knob 34: 0 = the split-fp16 mode on f32 activations through k_sp_conv<., 1, ...> (the round-2 kernel, also the path of frames
-                       // beyond 8 Mpixel); 2 = hm16 activations: k_sp_conv_s16 for the 3 x 3 layers (another k order: f32 rounding), k_sp_conv_s for the 1 x 1 layers
 void sp_conv1(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, hipStream_t s, int out_half, unsigned int* ovf) {
   const long long n = (long long)H * W;      // threads: (quad of pixels, 16-channel group) = H * W / 4 * 4
   const dim3 grid((unsigned)((n + 255) / 256), 1, B);
@@ -1582,7 +1580,6 @@ void sp_conv(const float* in, int B, int H, int W, int Cin, const float* wf, con
   else hipLaunchKernelGGL((k_sp_conv<1, 0, 3, false>), grid, dim3(256), 0, s, a);
 }
 // layers 0 + 1 of the split-fp16 mode in ONE launch (k_sp_conv_s16<true, true, true>): gray image in, pooled hm16 records of layer 1 out
-int g_sp_fuse1 = 1;    // developer knob 46: 0 = k_sp_conv1 + k_sp_conv_s16 as two launches (the round-5 form; bitwise the same results)
 void sp_conv_fused1(const float* gray, const float* w1, const float* b1, int B, int H, int W, const float* bias, float* out, int Cout_pad, hipStream_t s,
                     const uint16_t* wfh, float acc_scale, unsigned int* ovf) {
   ConvArgs a; a.in = nullptr; a.H = H; a.W = W; a.Cin = 64; a.wf = nullptr; a.bias = bias; a.out = out; a.Cout = Cout_pad; a.relu = 1;
@@ -1602,12 +1599,11 @@ void sp_scores(const float* logits, int cp, float* scores, int B, int h, int w, 
 void sp_nms(const float* scores, int B, int H, int W, float* out, hipStream_t s) {
   hipLaunchKernelGGL(k_sp_nms_fused, dim3((W + NMS_TX - 1) / NMS_TX, (H + NMS_TY - 1) / NMS_TY, B), dim3(1024), 0, s, scores, out, H, W);
 }
-int g_sp_select_stream = 0;   // developer knob 40: 1 = k_sp_select reads the candidate list from memory in every pass (the path of frames with more than 40 960 candidates)
 void sp_select(const float* nms, int B, int H, int W, float thr, int border, int* cand, int* counts, int cap, int k,
-               float* kpt_xy, float* score, int* kp_index, long long out_stride, hipStream_t s) {
+               float* kpt_xy, float* score, int* kp_index, long long out_stride, int stream_cand, hipStream_t s) {
   hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(int), s);
   hipLaunchKernelGGL(k_sp_candidates, dim3((unsigned)(((long long)H * W + 2047) / 2048), 1, B), dim3(256), 0, s, nms, H, W, thr, border, reinterpret_cast<int2*>(cand), counts, cap);
-  hipLaunchKernelGGL(k_sp_select, dim3(B), dim3(1024), 0, s, H, W, reinterpret_cast<const int2*>(cand), counts, cap, k, kpt_xy, score, kp_index, out_stride, g_sp_select_stream);
+  hipLaunchKernelGGL(k_sp_select, dim3(B), dim3(1024), 0, s, H, W, reinterpret_cast<const int2*>(cand), counts, cap, k, kpt_xy, score, kp_index, out_stride, stream_cand);
 }
 void sp_describe(const float* dmap, int B, int h, int w, const float* kpt_xy, const int* counts, long long out_stride, int max_k, float* desc, hipStream_t s) {
   hipLaunchKernelGGL(k_sp_describe, dim3((max_k + 3) / 4, B), dim3(256), 0, s, dmap, h, w, kpt_xy, counts, out_stride, desc);

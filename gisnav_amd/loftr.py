@@ -44,6 +44,7 @@ class LoFTR:
             raise _lib.GnError(f"certify_eps must lie in [0, 1), got {certify_eps!r}")
         self._eps_all, self._eps = (None if certify_eps is None else float(certify_eps)), {}
         self._ctx, self._shape, self._device, self._pairs = None, None, None, 0
+        self._knobs = {}                               # debug_variant: developer knobs, re-applied to every context this object creates
         self.lib = None
 
     @staticmethod
@@ -105,6 +106,8 @@ class LoFTR:
         self._ctx, self._shape, self._pairs = ctx, (H, W), pairs
         self.lib.gn_loftr_set_graph(ctx, int(self._graph))
         self.lib.gn_loftr_set_arithmetic(ctx, self._arith)
+        for which, value in self._knobs.items():
+            self._check(self.lib.gn_loftr_debug_set_variant(ctx, which, value), f"gn_loftr_debug_set_variant({which}, {value})")
         for name, arr in self._sd.items():
             if hasattr(arr, "detach"):
                 arr = arr.detach().cpu().numpy()
@@ -227,6 +230,14 @@ class LoFTR:
         return out
 
     forward = __call__
+
+    def debug_variant(self, which: int, value: int) -> None:
+        """Developer knob `which` (41, 42 or 44: gn_loftr_debug_set_variant) of THIS matcher, whatever image shapes it goes on to see; no other
+        context in the process is touched.  A knob the library refuses raises and is not kept (before the first call there is no context to ask:
+        the knob is then checked when one is created)."""
+        if self._ctx is not None:
+            self._check(self.lib.gn_loftr_debug_set_variant(self._ctx, int(which), int(value)), f"gn_loftr_debug_set_variant({which}, {value})")
+        self._knobs[int(which)] = int(value)
 
     def debug_read(self, name: str, count: int) -> np.ndarray:
         buf = np.empty(count, dtype=np.float32)

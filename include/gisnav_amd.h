@@ -35,7 +35,7 @@
  * per GPU; a context is thread-compatible, not thread-safe (PoseNode calls from one executor
  * thread at a time, gisnav/__init__.py:140-154).  DIFFERENT contexts (gn_ctx and gn_loftr alike)
  * may be driven from different host threads at the same time: nothing the launch paths consult
- * is process-wide (the kernel-family selectors and gn_last_error(NULL) are per thread).
+ * is process-wide.  gn_last_error(NULL) reports the calling thread's last error.
  */
 #ifndef GISNAV_AMD_H
 #define GISNAV_AMD_H
@@ -751,6 +751,11 @@ int gn_loftr_get_certify_stats(gn_loftr* ctx, int64_t* out4);
  * runner-ups) and "unc" (the certificate's words, raw).  Returns the element count or a negative status.
  * After a call with B pairs the buffers are side-major over the pairs: [2][B]... maps and tokens, [B]... "sim" / "crow" / "ccol". */
 int64_t gn_loftr_debug_read(gn_loftr* ctx, const char* name, void* host_out, int64_t max_bytes, void* stream);
+/* Developer knobs of THIS LoFTR context: the selectors its launches read, with the numbers and values gn_debug_set_variant documents below --
+ * 41 and 44 (the exact-f32 GEMM's 64-row and 64 x 64 tile forms) and 42 (bits 8 and up: the overhead term of the convolutions' rows-per-wave cost
+ * model x 100; any of bits 0-7 is refused).  Every other knob returns GN_ERR_ARG.  Synchronises the device and drops the context's captured
+ * graphs: the next call captures again with the knob in force.  All three select between forms with identical results. */
+int gn_loftr_debug_set_variant(gn_loftr* ctx, int which, int value);
 
 /* ---- test / profiling hooks (not part of the drop-in surface) --------------------------- */
 /* Copy an internal workspace tensor to HOST memory after synchronising `stream`.
@@ -777,6 +782,9 @@ int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);
  * out3 = {launches recorded, total milliseconds, total algorithmic flops (2 M N K)}. */
 /* Developer knobs: select a kernel variant (which = 0: GEMM) for A/B benchmarking; run a pure
  * v_mfma_f32_32x32x2_f32 issue-rate probe (blocks x 256 threads x iters x 8 MFMAs per wave).
+ * Every knob belongs to the context it is set on and to nothing else: a gn_ctx keeps the matcher's and the pose stage's (0-33, 41, 43, 44, 47-49), the SuperPoint
+ * extractor's (21, 34, 35, 39, 40, 46) and the SIFT extractor's (50) for the calls made on it; a gn_loftr keeps its own 41, 42 and 44
+ * (gn_loftr_debug_set_variant).  Another context, of either type, in the same process is not affected.
  * Knobs added in round 2 (value 0 restores the round-1 path unless noted): 10 block-tail fusion level, 12 block-tail phase stamps
  * (8; k_ffn128 also 136), 13 out_proj folded into the tail, 14 k_ffn_fused workgroup shape (64 / 32 tokens), 15 PnP phase stamps,
  * 16 fused match head (0 = similarity GEMM + five passes), 17 k_head_fused phase stamps, 19 k_qkv projections
@@ -786,13 +794,13 @@ int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);
  * optimistic fp16 form, 70 / 73 k_attn_pw whenever it applies (73 with phase stamps), 80 / 81 k_attn_ks always (eight / four waves).  Knob 8: 0 / 1
  * (the 256 x 256 GEMM k_gemm_p2w off / automatic).  Retired timing ablations and rejected experiments (knob 0 = 51-57, 61-67; knob 1 = 41-46,
  * 48, 51-55, 57, 58, 71, 72, >= 1000; knob 8 >= 2; knob 12 other than 0 / 8 / 136; knob 18; knob 24 and knob 36 with any value, knob 34 other than 0 / 2: SuperPoint's superseded
- * convolution and simple_nms forms; knob 42 with any of bits 0-7) return GN_ERR_ARG.  A bench line run with any knob set records it in `debug_variant`.
- * Process-wide knobs of late round 5 (every context; the shipped value is 0 unless noted): 41 largest 128 x 128 grid the exact-f32 GEMM leaves to 64-row
- * tiles (320; 0 = never), 42 bits 8 and up: the overhead term of the rows-per-wave cost model of LoFTR's convolutions x 100 (0 = the shipped 0.25; bits
- * 0-7 selected LoFTR's forms of rounds 3-4 and are retired), 43 exact-f32 attention of one or two pairs (bits 0-1: 0 = k_attn_f32_ks, 1 = k_attn_f32 always, 2 = k_attn_f32_ks
- * always; bit 2 its eight-wave form), 44 exact-f32 GEMM on 64 x 64 tiles (1 = for grids of at most 128 workgroups on 64 x 128 tiles, 0 = never,
+ * convolution and simple_nms forms; knob 42 with any value: it is a gn_loftr knob and reaches nothing here) return GN_ERR_ARG.  A bench line run with any knob set records it in `debug_variant`.
+ * Knobs of late round 5 (the shipped value is 0 unless noted): 41 (gn_ctx and gn_loftr) largest 128 x 128 grid the exact-f32 GEMM leaves to 64-row
+ * tiles (320; 0 = never), 42 (gn_loftr only) bits 8 and up: the overhead term of the rows-per-wave cost model of LoFTR's convolutions x 100 (0 = the shipped 0.25; bits
+ * 0-7 selected LoFTR's forms of rounds 3-4 and are retired), 43 (gn_ctx) exact-f32 attention of one or two pairs (bits 0-1: 0 = k_attn_f32_ks, 1 = k_attn_f32 always, 2 = k_attn_f32_ks
+ * always; bit 2 its eight-wave form), 44 (gn_ctx and gn_loftr) exact-f32 GEMM on 64 x 64 tiles (1 = for grids of at most 128 workgroups on 64 x 128 tiles, 0 = never,
  * 2 = the four-slot-ring kernel on 64 x 128 tiles everywhere).  All of them select between forms with identical results except 43 (f32 rounding).
- * Knob 49 (per context): 1 sends iterations_count <= 16 through the round path of the PnP stage as well (same bits; tests). */
+ * Knob 49: 1 sends iterations_count <= 16 through the round path of the PnP stage as well (same bits; tests). */
 int gn_debug_set_variant(gn_ctx* ctx, int which, int value);
 int gn_debug_mfma_probe(gn_ctx* ctx, int blocks, int iters, void* stream);
 /* LDS-DMA addressing probe (80 KB of LDS per block filled by global_load_lds, verified by ds_read):

@@ -97,7 +97,7 @@ def runs():
         assert eng.lib.gn_debug_set_variant(eng.ctx, 31, 2) == 0          # one workgroup per CU walking the list of tiles
         out["two_walk"] = _run(eng, inp)
     finally:
-        for k, v in DEFAULTS:          # (knob 14 is process-wide)
+        for k, v in DEFAULTS:
             eng.lib.gn_debug_set_variant(eng.ctx, k, v)
         del eng
     return out

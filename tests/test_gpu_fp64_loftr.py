@@ -228,21 +228,16 @@ def test_loftr_conv_tilings_are_bitwise_equal(arith):
     Every output's sum does not depend on RPW: each lane accumulates its own pixel in one accumulator over channel slices -> taps -> channel
     steps in the same order whatever the tile height, from the same halo values, through the same epilogue (k_lf_conv, k_lf_conv_h).  So a large
     overhead (RPW 4 at stride 1, 2 at stride 2) and a small one (RPW 1 on small grids) give the default's bits, every tap and output."""
-    from gisnav_amd.engine import PoseEngine
     from gisnav_amd.loftr import LoFTR
     sd, _ = _weights(0)
     h, w = 136, 200
     i0, i1 = _images(h, w, "synthetic")
-    eng = PoseEngine(0, max_batch=1, max_kpts=128, precision="f32")      # a gn_ctx to reach the process-wide developer knob
     res = {}
-    try:
-        for knob in (0, 100000 << 8, 1 << 8):
-            eng.lib.gn_debug_set_variant(eng.ctx, 42, knob)
-            m = LoFTR(state_dict=sd, arithmetic=arith).to("cuda:0").eval()        # (a new context per knob: the graph is captured with it in force)
-            res[knob] = _gpu_run(m, i0, i1, h, w)
-            del m
-    finally:
-        eng.lib.gn_debug_set_variant(eng.ctx, 42, 0)
+    for knob in (0, 100000 << 8, 1 << 8):
+        m = LoFTR(state_dict=sd, arithmetic=arith).to("cuda:0").eval()        # (a new matcher per knob; the knob is its own, nothing to restore)
+        m.debug_variant(42, knob)
+        res[knob] = _gpu_run(m, i0, i1, h, w)
+        del m
     base_out, base_taps = res[0]
     assert base_out["keypoints0"].shape[0] > 100
     for knob in (100000 << 8, 1 << 8):

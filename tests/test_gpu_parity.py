@@ -337,13 +337,20 @@ def test_c_abi_rejects_bad_arguments(eng256, dev):
 def test_retired_developer_knob_values_are_refused(eng256_h2, state_dict_t, dev):
     """Knob values of retired timing ablations and rejected experiments return an error instead of timing the default kernel under
     their label; the context still matches the oracle afterwards."""
-    for which, value in ((1, 41), (1, 48), (1, 1000), (0, 51), (8, 2), (12, 1), (18, 1), (42, 1), (42, 2), (42, 4), (42, 8), (42, 16), (42, 15),
+    from gisnav_amd.loftr import LoFTR
+    from oracle import loftr as olf
+    for which, value in ((1, 41), (1, 48), (1, 1000), (0, 51), (8, 2), (12, 1), (18, 1),
                          (24, 0), (24, 1), (24, 2), (36, 0), (36, 1), (34, 1)):      # SuperPoint's superseded convolution and simple_nms forms
         assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, which, value) != 0, (which, value)
-    try:     # knob 42 keeps its bits 8 and up: the overhead term of the cost model of LoFTR's convolutions
-        assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 42, 50 << 8) == 0
-    finally:
-        eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 42, 0)
+    # knob 42 belongs to LoFTR contexts (gn_loftr_debug_set_variant): bits 0-7 are retired, bits 8 and up -- the overhead term of the cost model of
+    # LoFTR's convolutions -- live on; a matcher context, which it never reached, refuses it altogether
+    m = LoFTR(state_dict=olf.synthetic_state_dict(0)).to("cuda:0").eval()
+    m._ensure(32, 32)                                    # (the smallest image LoFTR's tests use; the knob belongs to this context alone)
+    for value in (1, 2, 4, 8, 16, 15):
+        assert m.lib.gn_loftr_debug_set_variant(m._ctx, 42, value) != 0, (42, value)
+    assert m.lib.gn_loftr_debug_set_variant(m._ctx, 42, 50 << 8) == 0
+    assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 42, 50 << 8) != 0
+    del m
     try:     # knob 34 keeps the round-2 kernels on f32 activations (0, also the path of frames beyond 8 Mpixel) and the shipped form (2)
         assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 34, 0) == 0
         assert eng256_h2.lib.gn_debug_set_variant(eng256_h2.ctx, 34, 2) == 0

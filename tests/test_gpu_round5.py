@@ -72,7 +72,7 @@ def _assert_headline_family(fam, products=2):
 
 
 class _Knobs:
-    """gn_debug_set_variant settings for the duration of a block (knob 14 is process-wide: always restored)."""
+    """gn_debug_set_variant settings for the duration of a block (the knobs belong to `eng` alone; restored on leaving the block)."""
 
     def __init__(self, eng, **kv):
         self.eng, self.kv = eng, {int(k[1:]): v for k, v in kv.items()}

@@ -65,7 +65,10 @@ def test_tile_counts_are_what_the_dispatch_thresholds_need():
     api, ffn, attn = _src("gn_api.hip"), _src("gn_ffn.hip"), _src("gn_attention.hip")
     # k_qkv from 128 tiles of 128 tokens, k_ffn128 from 256, k_attn_pw from 256 workgroups of 256 queries at P % 256 == 0 (four heads)
     assert re.search(r"bool qkv_projection_applies\([^{]*\{[^}]*T / 128 >= 128", api)
-    assert re.search(r"bool ffn_selects_128\([^{]*\{[^}]*a\.T / 128 >= 256", ffn)
+    # (the block tail's rule is written once, ffn_bulk_shape in gn_common.h; ffn_selects_128, launch_ffn_fused and tail_is_bulk all call it)
+    assert re.search(r"bool ffn_bulk_shape\(int shape, int T\) \{[^}]*T % 128 == 0[^}]*shape == 0 && T / 128 >= 256", _src("gn_common.h"))
+    assert re.search(r"bool ffn_selects_128\([^{]*\{[^}]*ffn_bulk_shape\(k\.ffn_shape, a\.T\)", ffn)
+    assert ffn.count("ffn_bulk_shape(k.ffn_shape, a.T)") == 3 and "ffn_bulk_shape(c->knobs.ffn_shape, T)" in api and "/ 128 >= 256" not in ffn
     assert "a.npad % 256 == 0 && (long long)(a.npad / 256) * kHeads * a.BS >= 256" in attn
     assert "return (c->skinny & 3) && c->planes_mode && c->x_planes_only && T % 32 == 0 && np > 0 && ((c->skinny & 3) == 2 || T / np <= 4);" in api
 

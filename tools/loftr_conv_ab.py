@@ -5,20 +5,17 @@ import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gisnav_amd import loftr_synthetic as olf
 from gisnav_amd.loftr import LoFTR
-from gisnav_amd.engine import PoseEngine
 arith = sys.argv[1] if len(sys.argv) > 1 else "exact_f32"
-eng = PoseEngine(0, max_batch=1, max_kpts=128, precision="f32")      # a gn_ctx to reach the process-wide developer knob
 dev = torch.device("cuda", 0)
 i0, i1 = olf.synthetic_pair(1, 480, 640)
 data = {"image0": i0.to(dev), "image1": i1.to(dev)}
 ref = None
 knobs = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, (25 << 8), (50 << 8), (75 << 8), (100 << 8)] * 2
-extra = [tuple(int(x) for x in a.split(":")) for a in sys.argv[3:]]      # further process-wide knobs, which:value (e.g. 44:0 = the 64-row GEMM without its ring)
-for w, v in extra:
-    eng.lib.gn_debug_set_variant(eng.ctx, w, v)
+extra = [tuple(int(x) for x in a.split(":")) for a in sys.argv[3:]]      # further knobs of the LoFTR context, which:value (e.g. 44:0 = the 64-row GEMM without its ring)
 for knob in knobs:
-    assert eng.lib.gn_debug_set_variant(eng.ctx, 42, knob) == 0, f"knob 42 = {knob} is refused (bits 0-7 are retired)"
-    m2 = LoFTR(state_dict=olf.synthetic_state_dict(0), fine=True, graph=True, arithmetic=arith).to(dev).eval()   # (a new context: the graph is captured with the knob in force)
+    m2 = LoFTR(state_dict=olf.synthetic_state_dict(0), fine=True, graph=True, arithmetic=arith).to(dev).eval()   # (a new matcher per variant; the knobs are its own)
+    for w, v in extra + [(42, knob)]:
+        m2.debug_variant(w, v)       # (a refused knob -- bits 0-7 of 42 are retired -- raises at the first call)
     for _ in range(3): out = m2(data)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(10): out = m2(data)
