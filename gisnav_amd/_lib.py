@@ -134,6 +134,7 @@ SIGNATURES = {
     "gn_debug_gemm": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP, VP]),
     "gn_debug_attention": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_float, VP, C.c_int, VP, C.c_int, VP, C.c_int,
                                      VP, VP, C.c_int, VP]),
+    "gn_debug_match_head": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, VP, VP, VP, VP, VP]),
     "gn_set_stage_timing": (C.c_int, [VP, C.c_int]),
     "gn_get_stage_ms": (C.c_int, [VP, c_f32p, C.c_int]),
     "gn_debug_set_variant": (C.c_int, [VP, C.c_int, C.c_int]),

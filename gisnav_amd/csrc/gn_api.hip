@@ -126,7 +126,7 @@ inline long long lists_stride_of(long long km) { return gn::kTileListBase + 2 * 
   X(int32_t, m1, np, kWsAlways, "m1") X(float, max0b, np, kWsAlways, "max0b") X(float, rpart_c, 8 * np, kWsAlways, nullptr)      \
   X(int32_t, uncert, 1, kWsAlways, "uncert") X(int32_t, uncert_alt, 1, kWsAlways, nullptr) X(int32_t, uncert_alt2, 1, kWsAlways, nullptr) \
   X(int32_t, uncert_alt3, 1, kWsAlways, nullptr)                                                                                 \
-  X(float, colbest, np, kWsAlways, nullptr) X(float, col2, np, kWsAlways, nullptr)                                               \
+  X(float, colbest, np, kWsAlways, "colbest") X(float, col2, np, kWsAlways, "col2")                                                 \
   /* fused head: column partials [np / 32][np], row partials [8][np], two arrival counters (zero between calls) */               \
   X(float, cpart_m, (np / 32) * np, kWsAlways, nullptr) X(float, cpart_s, (np / 32) * np, kWsAlways, nullptr)                    \
   X(int32_t, cpart_i, (np / 32) * np, kWsAlways, nullptr) X(float, rpart_a, 8 * np, kWsAlways, nullptr)                          \
@@ -753,6 +753,48 @@ bool ffn(gn_ctx* c, const View& w, const Block& blk, int T, hipStream_t s, bool 
   return false;
 }
 
+// The match head of a call at the padded size c->npad_run, on projected descriptors (w.md, or w.md_p in the planes mode), matchabilities (w.ls) and
+// counts (w.nvalid) that are already in the view: the fused two-sweep form, or (developer knob 16 = 0) the similarity GEMM + five passes.  Shared by
+// run_matcher and gn_debug_match_head, so the stage-level entry launches what a call launches.
+int run_head(gn_ctx* c, const View& w, int B, int64_t* idx, float* score, int32_t* n_match, bool pruning, hipStream_t s) {
+  const int np = c->npad_run, T = B * 2 * np;
+  HeadArgs hd;
+  hd.n_in = pruning ? w.pr_nin : nullptr;
+  hd.sim = w.sim; hd.ls = w.ls; hd.nvalid = w.nvalid; hd.B = B; hd.npad = np; hd.threshold = c->threshold;
+  hd.rowmax = w.rowmax; hd.rowlog = w.rowlog; hd.colmax = w.colmax; hd.collog = w.collog;
+  hd.m0 = w.m0; hd.max0 = w.max0; hd.m1 = w.m1;
+  hd.ovf = (c->planes_mode && c->guard) ? w.ovf : nullptr;
+  hd.max0b = w.max0b; hd.rpart_c = w.rpart_c; hd.uncert = c->certify ? w.uncert : nullptr;
+  hd.cert_eps = (c->precision == GN_PREC_F32) ? c->cert_eps_f32 : cert_eps_now(c);
+  if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) {
+    hd.uncert_alt = w.uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
+    hd.uncert_alt2 = w.uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
+    // the fourth arithmetic: the rung's eps -- or, on the rung (whose own eps is cert_eps), level 1's
+    hd.uncert_alt3 = w.uncert_alt3; hd.cert_eps_alt3 = ffn_auto_state(c) == kRung ? c->cert_eps_one : (c->qkv_set == 0 ? c->cert_eps_proj1 : -1.f);
+  }
+  hd.idx = idx; hd.score = score; hd.n_match = n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
+  hd.md = c->planes_mode ? (const void*)w.md_p : (const void*)w.md; hd.md_f32 = c->planes_mode ? 0 : 1;
+  hd.cpart_m = w.cpart_m; hd.cpart_s = w.cpart_s; hd.cpart_i = w.cpart_i; hd.rpart_a = w.rpart_a; hd.rpart_b = w.rpart_b; hd.tickets = w.tickets;
+  hd.dbg_ts = (c->head_stamps && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 17
+  if (c->cal_cols) { hd.colbest = w.colbest; hd.col2 = w.col2; }
+  if (c->head_fused || !w.sim) {   // both sweeps as one entry
+    timed_launch(c, s, 0, 2.0 * 2.0 * B * (double)np * np * kDim,                         // the similarity tiles are computed twice
+                 2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0,            // descriptors once per sweep, per-row / per-column statistics, matches
+                 "k_head_fused (2 sweeps)", [&] { launch_match_head_fused(hd, s); });
+    if (pruning) launch_unprune_idx(idx, n_match, w.pr_ind, B, np, c->npad, s);
+    return GN_OK;
+  }
+  GemmArgs gs;
+  memset(&gs, 0, sizeof gs);
+  gs.A = w.md; gs.lda = kDim; gs.K1 = kDim; gs.W = w.md + (size_t)np * kDim; gs.ldw = kDim;
+  gs.Y = w.sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kDim; gs.acc_scale = 1.f;
+  gs.strideA = gs.strideW = 2LL * np * kDim; gs.strideY = (long long)np * np;
+  timed_gemm(c, w, EPI_PLAIN, gs, B, s);
+  launch_match_head(hd, s);
+  if (pruning) launch_unprune_idx(idx, n_match, w.pr_ind, B, np, c->npad, s);
+  return GN_OK;
+}
+
 int run_matcher(gn_ctx* c, const View& w, const Call& v, hipStream_t s) {
   const int B = v.B, np = c->npad_run, T = B * 2 * np, BS = B * 2;
   const bool bf16v2 = c->precision != GN_PREC_F32 && c->knobs.attn_variant >= 1 && c->attn_f16 != 2;   // (split attention: f32 projection rows, k_attn_f16x2)
@@ -887,42 +929,8 @@ int run_matcher(gn_ctx* c, const View& w, const Call& v, hipStream_t s) {
     g.scale = 0.25f; g.scale_cols = kDim;  // / d ** 0.25
     gemm(c, w, EPI_SCALE_COLS, g, s);
     launch_matchability(w.x, c->matchability[li].w, c->matchability[li].b, w.ls, T, s);
-    HeadArgs hd;
-    hd.n_in = pruning ? w.pr_nin : nullptr;
-    hd.sim = w.sim; hd.ls = w.ls; hd.nvalid = w.nvalid; hd.B = B; hd.npad = np; hd.threshold = c->threshold;
-    hd.rowmax = w.rowmax; hd.rowlog = w.rowlog; hd.colmax = w.colmax; hd.collog = w.collog;
-    hd.m0 = w.m0; hd.max0 = w.max0; hd.m1 = w.m1;
-    hd.ovf = (c->planes_mode && c->guard) ? w.ovf : nullptr;
-    hd.max0b = w.max0b; hd.rpart_c = w.rpart_c; hd.uncert = c->certify ? w.uncert : nullptr;
-    hd.cert_eps = (c->precision == GN_PREC_F32) ? c->cert_eps_f32 : cert_eps_now(c);
-    if (hd.uncert && c->precision != GN_PREC_F32 && ffn_auto(c)) {
-      hd.uncert_alt = w.uncert_alt; hd.cert_eps_alt = ffn_level_eps(c, ffn_alt_level(c->auto_level, 0));
-      hd.uncert_alt2 = w.uncert_alt2; hd.cert_eps_alt2 = ffn_level_eps(c, ffn_alt_level(c->auto_level, 1));      // (< 0 -- level 1 not calibrated: flags stay 0, never read)
-      // the fourth arithmetic: the rung's eps -- or, on the rung (whose own eps is cert_eps), level 1's
-      hd.uncert_alt3 = w.uncert_alt3; hd.cert_eps_alt3 = ffn_auto_state(c) == kRung ? c->cert_eps_one : (c->qkv_set == 0 ? c->cert_eps_proj1 : -1.f);
-    }
-    hd.idx = v.idx; hd.score = v.score; hd.n_match = v.n_match; hd.kmax = c->npad;   // output stride: gn_kmax(), whatever the active size
-    hd.md = c->planes_mode ? (const void*)w.md_p : (const void*)w.md; hd.md_f32 = c->planes_mode ? 0 : 1;
-    hd.cpart_m = w.cpart_m; hd.cpart_s = w.cpart_s; hd.cpart_i = w.cpart_i; hd.rpart_a = w.rpart_a; hd.rpart_b = w.rpart_b; hd.tickets = w.tickets;
-    hd.dbg_ts = (c->head_stamps && w.sim) ? reinterpret_cast<long long*>(w.sim) : nullptr;   // developer knob 17
-    if (c->cal_cols) { hd.colbest = w.colbest; hd.col2 = w.col2; }
-    if (c->head_fused || !w.sim) {   // both sweeps as one entry
-      timed_launch(c, s, 0, 2.0 * 2.0 * B * (double)np * np * kDim,                         // the similarity tiles are computed twice
-                   2.0 * (4.0 * T * kDim) + 4.0 * T * 4.0 + 8.0 * B * np * 3.0,            // descriptors once per sweep, per-row / per-column statistics, matches
-                   "k_head_fused (2 sweeps)", [&] { launch_match_head_fused(hd, s); });
-      if (pruning) launch_unprune_idx(v.idx, v.n_match, w.pr_ind, B, np, c->npad, s);
-      return GN_OK;
-    }
-    GemmArgs gs;
-    memset(&gs, 0, sizeof gs);
-    gs.A = w.md; gs.lda = kDim; gs.K1 = kDim; gs.W = w.md + (size_t)np * kDim; gs.ldw = kDim;
-    gs.Y = w.sim; gs.ldy = np; gs.M = np; gs.N = np; gs.K = kDim; gs.acc_scale = 1.f;
-    gs.strideA = gs.strideW = 2LL * np * kDim; gs.strideY = (long long)np * np;
-    timed_gemm(c, w, EPI_PLAIN, gs, B, s);
-    launch_match_head(hd, s);
-    if (pruning) launch_unprune_idx(v.idx, v.n_match, w.pr_ind, B, np, c->npad, s);
+    return run_head(c, w, B, v.idx, v.score, v.n_match, pruning, s);
   }
-  return GN_OK;
 }
 
 // The workspaces that exist `when` (a mask of kWs*), at the context's npad: max_batch x (elements per pair)
@@ -3127,6 +3135,31 @@ int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale, c
   } else {
     attention(ctx, a, (hipStream_t)stream);
   }
+  GN_HIP(hipGetLastError());
+  return GN_OK;
+}
+
+int gn_debug_match_head(gn_ctx* ctx, int B, int np, const float* md, const float* ls, const int32_t* nvalid, int64_t* idx, float* score,
+                        int32_t* n_match, void* stream) {
+  if (!ctx || !md || !ls || !nvalid || !idx || !score || !n_match || B < 1 || B > ctx->max_batch || np < 128 || np % 128 || np > ctx->npad)
+    return fail(ctx, GN_ERR_ARG, "gn_debug_match_head needs 1 <= B <= max_batch and np a multiple of 128, at most gn_kmax()");
+  GN_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  // the call's workspaces are laid out at np, and the fused head also writes the column values (gn_debug_read "colbest" / "col2")
+  const Restore keep(ctx->npad_run, ctx->cal_cols);
+  ctx->npad_run = np; ctx->cal_cols = true;
+  const View w = view_of(ctx);
+  const size_t T = (size_t)B * 2 * np;
+  GN_HIP(hipMemcpyAsync(w.md, md, T * kDim * sizeof(float), hipMemcpyDeviceToDevice, s));
+  GN_HIP(hipMemcpyAsync(w.ls, ls, T * sizeof(float), hipMemcpyDeviceToDevice, s));
+  GN_HIP(hipMemcpyAsync(w.nvalid, nvalid, (size_t)B * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (ctx->planes_mode) {   // the hm16 rows the projection's epilogue writes; the guard word starts clear as k_extent leaves it
+    launch_split_hm16(w.md, w.md_p, (long long)T, kDim, 1.0f, s);
+    if (ctx->guard) GN_HIP(hipMemsetAsync(w.ovf, 0, sizeof(unsigned int), s));
+  }
+  ctx->n_ev = 0; ctx->launch_count = 0;
+  const int rc = run_head(ctx, w, B, idx, score, n_match, false, s);
+  if (rc != GN_OK) return rc;
   GN_HIP(hipGetLastError());
   return GN_OK;
 }

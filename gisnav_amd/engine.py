@@ -1117,3 +1117,14 @@ class PoseEngine:
                                          _ptr(nkv), _ptr(out), 256, self._stream())
         _lib.check(self.ctx, rc, "gn_debug_attention")
         return out
+
+    def debug_match_head(self, md: torch.Tensor, ls: torch.Tensor, nvalid: torch.Tensor):
+        """gn_debug_match_head: the match head alone.  md [B, 2, np, 256] f32, ls [B, 2, np] f32, nvalid [B, 2] i32 (device tensors).
+        Returns (idx [B,kmax,2] i64, score [B,kmax] f32, n_match [B] i32) on the device; the per-row / per-column vectors through debug_read."""
+        B, _, npad, _ = md.shape
+        idx = torch.empty((B, self.kmax, 2), dtype=torch.int64, device=self.device)
+        score = torch.empty((B, self.kmax), dtype=torch.float32, device=self.device)
+        n_match = torch.empty((B,), dtype=torch.int32, device=self.device)
+        rc = self.lib.gn_debug_match_head(self.ctx, B, npad, _ptr(md), _ptr(ls), _ptr(nvalid), _ptr(idx), _ptr(score), _ptr(n_match), self._stream())
+        _lib.check(self.ctx, rc, "gn_debug_match_head")
+        return idx, score, n_match

@@ -760,7 +760,8 @@ int gn_loftr_debug_set_variant(gn_loftr* ctx, int which, int value);
 /* ---- test / profiling hooks (not part of the drop-in surface) --------------------------- */
 /* Copy an internal workspace tensor to HOST memory after synchronising `stream`.
  * Names: "desc" "cos" "sin" "x" "qkv" "ctx" "msg" "h" "md" "ls" "sim" "rowmax" "rowlog"
- * "colmax" "collog" "m0" "m1" (ints are returned bit-cast in float slots). Returns the element
+ * "colmax" "collog" "m0" "m1" "max0" "max0b" "colbest" "col2" (ints are returned bit-cast in float slots; the last two exist after a call that
+ * measured columns: gn_calibrate_certify's middle level, gn_debug_match_head). Returns the element
  * count copied, or a negative status.  "sim" exists only after the unfused match head (developer knob 16 = 0), gn_vo_match or a
  * phase-stamp knob allocated it: the matcher itself never materialises the similarity matrix (it returns 0 elements before that).
  * SuperPoint extractor (last pass): "sp_enc" "sp_scores" "sp_nms" "sp_counts" "sp_cand" "sp_x" "sp_y" (raw words of the two activation
@@ -774,6 +775,14 @@ int gn_debug_gemm(gn_ctx* ctx, int M, int N, int K, const float* A, const float*
 int gn_debug_attention(gn_ctx* ctx, int BS, int npad, int cross, float qscale,
                        const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                        const int32_t* nkv, float* out, int ldo, void* stream);
+/* The match head alone, as gn_match runs it behind the last layer (the same launches: the fused two-sweep form, or the similarity GEMM + five passes
+ * under developer knob 16 = 0; gn_set_filter_threshold and gn_set_certify's mode / eps / eps_f32 apply; no weights needed).  md [B][2][np][256] f32
+ * projected descriptors (side 0, then side 1), ls [B][2][np] f32 log-sigmoid matchabilities, nvalid [B][2]; np a multiple of 128, at most gn_kmax().
+ * The inputs are copied into the context's workspaces laid out at np (an f16x2 context splits md into hm16 rows as the projection's epilogue does), so
+ * gn_debug_read serves the first B * np elements of "rowmax" "rowlog" "colmax" "collog" "max0" "max0b" "m0" "m1" -- and, from the fused form, "colbest"
+ * "col2": best score and runner-up of every column -- and gn_get_uncertain the flags.  idx [B][gn_kmax()][2], score [B][gn_kmax()], n_match [B]. */
+int gn_debug_match_head(gn_ctx* ctx, int B, int np, const float* md, const float* ls, const int32_t* nvalid,
+                        int64_t* idx, float* score, int32_t* n_match, void* stream);
 /* Milliseconds spent in each stage of the last gn_estimate/gn_match when timing is enabled. */
 int gn_set_stage_timing(gn_ctx* ctx, int enable);
 int gn_get_stage_ms(gn_ctx* ctx, float* host_ms, int max_stages);

@@ -1,4 +1,5 @@
-"""CPU tests of the margin certificate's LOGIC (the GPU side is tests/test_gpu_round6.py) and of the oracle's half-SDPA mode.
+"""CPU tests of the margin certificate's LOGIC (the GPU side is tests/test_gpu_match_head.py: the head's flags against this rule, entry by entry; the
+certified calls end to end are in tests/test_gpu_round6.py) and of the oracle's half-SDPA mode.
 
 The certificate (include/gisnav_amd.h, gn_set_certify) claims: if two arithmetics' assignment matrices P, Q differ by at most eps on the deciding
 entries, and on P (a) every row whose best score is >= L - eps leads its runner-up by more than 2 eps, (b) the same for every column, (c) no row's
